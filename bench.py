@@ -4,7 +4,7 @@ Headline benchmark (BASELINE.json): agent-steps/s of the GymEnv.step body (examp
     Simulator.step(action) -> render_egocentric(256x256, fov 35 m) -> compute_collision() -> compute_offroad()
 at B = 1024 scenes x A = 64 agents per GPU on the Town01 map (tests/golden/town01_mesh.npz), synthetic agents.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 One process per GPU; the scene batch is sharded (B per GPU is fixed: weak scaling) and there is NO data-path collective.
 N > 1 runs either way:
   * `python bench.py --gpus N ...` by itself: this process never touches a GPU; it starts N children (one per GPU, each with
@@ -551,6 +551,39 @@ def mixed_maps_mode(device, steps, warmup, B, A, overlap, headline_ms, ring):
                 overlap=overlap)
 
 
+DUMP_IMAGES = 32                 # whole images kept by --dump-outputs (768 KiB each at 256 x 256 float32)
+DUMP_BYTES = 64 << 20            # everything --dump-outputs writes, at most
+DUMP_SEED = 0
+
+
+def dump_outputs(path, sim, img, col, off):
+    """--dump-outputs DIR: what the timed loop computed in its last step, one .npy per array, so that two builds can be compared output for output
+    (the inputs of a run depend on its arguments alone: seeded agents, fixed actions):
+      state.npy       B x A x 4 float32   the kinematic state after the step (x, y, psi, v), Simulator.get_state()
+      collision.npy   B x A float32       compute_collision()
+      offroad.npy     B x A float32       compute_offroad()
+      image_sums.npy  B x A x 3 float64   the sum of every image's channel (all B x A images, summed in float64)
+      images.npy      K x 3 x H x W float32   K whole images: the cameras np.random.default_rng(0).choice(B * A, K, replace=False), sorted
+    When B x A is so large that the per-camera arrays would pass the budget, they are cut to the same kind of seeded sample of cameras
+    (flattened to N x ...)."""
+    B, A = col.shape
+    rng = np.random.default_rng(DUMP_SEED)
+    picked = np.sort(rng.choice(B * A, min(DUMP_IMAGES, B * A), replace=False))
+    images = img.reshape(B * A, *img.shape[2:])[torch.from_numpy(picked).to(img.device)].float().cpu().numpy()
+    sums = torch.cat([img[lo:lo + 16].to(torch.float64).sum((-2, -1)) for lo in range(0, B, 16)])      # 16 scenes at a time: no copy of the whole batch
+    out = dict(state=sim.get_state().float(), collision=col.float(), offroad=off.float(), image_sums=sums)
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    per_camera = sum(v[0, 0].nbytes for v in out.values())
+    room = (DUMP_BYTES - images.nbytes) // per_camera
+    if B * A > room:
+        rows = np.sort(rng.choice(B * A, room, replace=False))
+        out = {k: v.reshape(B * A, *v.shape[2:])[rows] for k, v in out.items()}
+    out['images'] = images
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, f'{k}.npy'), np.ascontiguousarray(v))
+
+
 def device_identity(device, reserved_usable=None):
     """Which physical GPU this rank ran on (a SCALE record must be able to show that N ranks sat on N distinct GPUs):
     uuid and PCI address from the device properties, architecture, CU count, and whether the 'reserved' CU layout was usable there."""
@@ -651,8 +684,15 @@ def main():
     ap.add_argument('--ring-candidates', type=int, default=4, help='output allocations probed at most for the two-buffer image ring')
     ap.add_argument('--dry-run', action='store_true', help='no GPU, no kernels: exercises launch, barrier, reduction and the JSON line only')
     ap.add_argument('--launch-timeout', type=float, default=1500.0)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                         "dump_outputs); with N > 1, rank 0's shard")
     ap.add_argument('--worker', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.dry_run:
+        ap.error('--dump-outputs needs the kernels: a dry run computes nothing')
 
     world = int(os.environ.get('WORLD_SIZE', 1))
     if args.gpus > 1 and world == 1 and not args.worker:
@@ -778,6 +818,9 @@ def main():
     if not args.dry_run:
         raster_ms = float(np.mean([a.elapsed_time(b) for a, b in _ops.raster_events])) if _ops.raster_events else None
         _ops.raster_events = None
+        if args.dump_outputs and rank == 0:
+            # before anything else writes into the ring (same_run_write_roofs) or steps the simulator again
+            dump_outputs(args.dump_outputs, sim, sink['img'], sink['col'], sink['off'])
     # every rank's own figures (a rank on slow memory would otherwise show only as a low rate): reporting only, over gloo
     reserved_ok = None
     if not args.dry_run and args.overlap == 'reserved':

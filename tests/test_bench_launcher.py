@@ -21,6 +21,10 @@ def run_bench(*argv, env=None):
     return json.loads(lines[0])
 
 
+# the self-launcher needs as many entries in the inherited device list as ranks: a box may export a list of one (HIP_VISIBLE_DEVICES=0)
+TWO_DEVICES = dict(HIP_VISIBLE_DEVICES='0,1')
+
+
 def check_line(line, n, steps, warmup):
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data',
               'config', 'roofline'):
@@ -38,10 +42,18 @@ def check_line(line, n, steps, warmup):
 
 
 def test_self_launch_two_ranks_dry_run():
-    line = check = run_bench('--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run')
+    line = check = run_bench('--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run', env=TWO_DEVICES)
     check_line(line, 2, 3, 1)
     assert len(line['per_rank_agent_steps_per_s']) == 2 and 'self-launch' in line['launcher']
     assert 'cpu_baseline' not in check                               # rank 0 of N = 1 only
+
+
+def test_bad_arguments_are_refused():
+    for argv, why in ((('--steps', '0', '--dry-run'), '--steps must be at least 1'),
+                      (('--steps', '2', '--dry-run', '--dump-outputs', 'never_written'), 'a dry run computes nothing')):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *argv], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode != 0 and why in r.stderr, r.stderr
+    assert not os.path.exists(os.path.join(ROOT, 'never_written'))
 
 
 def test_device_list_is_narrowed_per_rank():
@@ -71,18 +83,25 @@ def test_single_process_dry_run_and_torchrun_shape():
 
 def test_the_barrier_falls_back_to_gloo_when_rccl_cannot_come_up():
     """The process group only carries the barrier and the timing reductions.  Under an external launcher the worker asks for RCCL; where that
-    fails (here: no GPU at all) both ranks must fall back to gloo and still deliver the line."""
+    fails both ranks must fall back to gloo and still deliver the line.  It fails here on every rank, GPU or not: the ranks name local devices
+    that no box has (on a box with a GPU, one rank in a live RCCL rendezvous would wait for ever for a rank that failed)."""
     import socket
     with socket.socket() as sk:
         sk.bind(('127.0.0.1', 0))
         port = sk.getsockname()[1]
     procs = []
     for r in range(2):
-        e = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), TDS_BENCH_DRY_RUN_TRY_NCCL='1')
+        e = dict(os.environ, RANK=str(r), LOCAL_RANK=str(100 + r), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), TDS_BENCH_DRY_RUN_TRY_NCCL='1')
         e.pop('TDS_BENCH_BACKEND', None)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--dry-run'],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=e))
-    outs = [p.communicate(timeout=300) for p in procs]
+    try:
+        outs = [p.communicate(timeout=300) for p in procs]
+    finally:
+        for p in procs:                     # no rank outlives the test
+            if p.poll() is None:
+                p.kill()
+                p.wait()
     assert all(p.returncode == 0 for p in procs), outs
     assert all('falling back to gloo' in err for _, err in outs), outs
     lines = [ln for ln in outs[0][0].splitlines() if ln.strip()]
@@ -134,10 +153,46 @@ def test_a_dying_worker_ends_the_launch_promptly():
     ends rank 0 instead of waiting for the timeout"""
     import time
     t0 = time.time()
-    e = dict(os.environ, TDS_BENCH_DRY_RUN_FAIL_RANK='1')
+    e = dict(os.environ, TDS_BENCH_DRY_RUN_FAIL_RANK='1', **TWO_DEVICES)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'TDS_BENCH_BACKEND'):
         e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry-run', '--steps', '2', '--warmup', '0'], capture_output=True,
                        text=True, timeout=300, env=e)
     assert r.returncode != 0 and 'worker 1 failed' in (r.stderr + r.stdout) and time.time() - t0 < 120
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith('{')]          # no result line from a failed launch
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: every file float32 / float64; the per-camera arrays whole while they fit, a seeded sample of cameras
+    once they would not (the GPU run: tests/test_gpu_bench_workers.py)"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    B, A = 8, 40
+    g = torch.Generator().manual_seed(0)
+    img = torch.rand(B, A, 3, 4, 4, generator=g) * 255
+    state, col, off = torch.rand(B, A, 4, generator=g), torch.rand(B, A, generator=g), torch.rand(B, A, generator=g)
+    sim = type('Sim', (), {'get_state': lambda self: state})()
+
+    def dump(d):
+        bench.dump_outputs(str(d), sim, img, col, off)
+        return {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    out = dump(tmp_path / 'whole')
+    assert sorted(out) == ['collision', 'image_sums', 'images', 'offroad', 'state']
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values()) and out['image_sums'].dtype == np.float64
+    assert np.array_equal(out['state'], state.numpy()) and np.array_equal(out['collision'], col.numpy()) and np.array_equal(out['offroad'], off.numpy())
+    np.testing.assert_allclose(out['image_sums'], img.double().sum((-2, -1)).numpy(), rtol=1e-12)
+    picked = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(B * A, bench.DUMP_IMAGES, replace=False))
+    assert np.array_equal(out['images'], img.reshape(B * A, 3, 4, 4).numpy()[picked])
+    again = dump(tmp_path / 'again')
+    assert all(np.array_equal(again[k], out[k]) for k in out)
+    # a budget that holds the images and 100 cameras' worth of the rest
+    monkeypatch.setattr(bench, 'DUMP_BYTES', out['images'].nbytes + 100 * (16 + 4 + 4 + 24))
+    cut = dump(tmp_path / 'cut')
+    assert sum(v.nbytes for v in cut.values()) <= bench.DUMP_BYTES
+    assert cut['state'].shape == (100, 4) and cut['collision'].shape == cut['offroad'].shape == (100,) and cut['image_sums'].shape == (100, 3)
+    rows = [int(np.flatnonzero((state.numpy().reshape(-1, 4) == r).all(1))[0]) for r in cut['state']]
+    assert rows == sorted(rows) and np.array_equal(cut['collision'], col.numpy().reshape(-1)[rows])
+    assert np.array_equal(cut['images'], out['images'])

@@ -4,7 +4,8 @@
     gloo barrier on 127.0.0.1;
   * under `python -m torch.distributed.run --nproc-per-node 2`: the worker asks for RCCL; two ranks on one GPU is something RCCL may refuse
     (duplicate device) -- then every rank must agree on gloo -- or serve; either way ONE well-formed line comes out.
-Two ranks share the GPU, so the rates are not a scaling measurement; what is checked is that the sharded path runs kernels and reports."""
+Two ranks share the GPU, so the rates are not a scaling measurement; what is checked is that the sharded path runs kernels and reports.
+Also here: what --dump-outputs writes, from a single-process run."""
 import json
 import os
 import socket
@@ -62,26 +63,69 @@ def test_two_real_workers_under_torch_distributed_run():
     assert 'RCCL barrier' in line['launcher'] or ('gloo' in line['launcher'] and 'falling back to gloo' in r.stderr)
 
 
-def test_eight_real_workers_on_one_gpu():
-    """The largest world the driver launches (BASELINE.json config 4: 8 GPUs), with eight real workers sharing the one GPU of a test box:
-    rendezvous of eight children, eight image rings probed side by side, eight per-rank reports in the one line."""
-    args = ['--gpus', '8', '--batch', '32', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-configs', '--ring-candidates', '2']
+def test_four_real_workers_on_one_gpu():
+    """Many real workers sharing the one GPU of a test box: rendezvous of four children, four image rings probed side by side, four per-rank
+    reports in the one line.  Four, not the eight of the driver's largest world (BASELINE.json config 4): a shared GPU takes
+    at most six processes at once, and the test process already has it open."""
+    args = ['--gpus', '4', '--batch', '64', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-configs', '--ring-candidates', '2']
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *args], capture_output=True, text=True, timeout=1500,
-                       env=clean_env(HIP_VISIBLE_DEVICES='0,0,0,0,0,0,0,0'))
+                       env=clean_env(HIP_VISIBLE_DEVICES='0,0,0,0'))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
     line = json.loads(lines[0])
-    assert line['n_gpus'] == 8 and line['config']['global_batch'] == 256 and 'x8' in line['config']['parallelism']
-    assert len(line['per_rank_agent_steps_per_s']) == 8 and all(v > 0 for v in line['per_rank_agent_steps_per_s'])
+    assert line['n_gpus'] == 4 and line['config']['global_batch'] == 256 and 'x4' in line['config']['parallelism']
+    assert len(line['per_rank_agent_steps_per_s']) == 4 and all(v > 0 for v in line['per_rank_agent_steps_per_s'])
     assert line['value'] <= sum(line['per_rank_agent_steps_per_s']) * 1.0001
     per_rank = line['per_rank']
-    assert [p['rank'] for p in per_rank] == list(range(8))
+    assert [p['rank'] for p in per_rank] == list(range(4))
     for p in per_rank:
         assert p['avg_launch_ms'] > 0 and len(p['ring_probe']['kept']) == 2 and len(set(p['ring_probe']['kept'])) == 2 and not p['ring_probe']['aliased']
         assert len(p['ring_probe']['launch_ms']) >= 2 and p['ring_probe']['fill_ms'] > 0
-    # VERDICT r5 item 6: the record says which physical GPU every rank sat on -- here all eight on the one GPU of the box
+    # VERDICT r5 item 6: the record says which physical GPU every rank sat on -- here all four on the one GPU of the box
     ids = [p['device_identity'] for p in per_rank]
     assert all(i['uuid'] not in (None, 'None') or i['pci'] for i in ids) and all(i['arch'].startswith('gfx950') and i['compute_units'] > 0 for i in ids)
     assert len({(i['uuid'], i['pci']) for i in ids}) == 1 and line['distinct_devices'] == 1
     assert all(i['reserved_usable'] in (True, False) for i in ids)
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs: what the timed loop computed in its LAST step (after --warmup + --steps steps), the same from run to run, within 64 MB;
+    the state is the oracle's after that many steps of the seeded inputs, the metrics the oracle's on that state"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from oracle import oracle as orc
+    B, A, warmup, steps = 32, 16, 2, 3
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', str(B), '--agents', str(A), '--steps', str(steps), '--warmup', str(warmup),
+                            '--no-cpu-baseline', '--no-configs', '--no-default-path', '--ring-candidates', '2', '--dump-outputs', str(d)],
+                           capture_output=True, text=True, timeout=900, env=clean_env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert line['steps'] == steps and line['warmup'] == warmup
+        assert line['roofline']['timed_raster_calls'][1] - line['roofline']['timed_raster_calls'][0] == steps
+        files = sorted(os.listdir(d))
+        assert files == ['collision.npy', 'image_sums.npy', 'images.npy', 'offroad.npy', 'state.npy']
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    for k in dumps[0]:
+        assert dumps[0][k].dtype in (np.float32, np.float64) and np.array_equal(dumps[0][k], dumps[1][k]), k
+    out = dumps[0]
+    assert out['state'].shape == (B, A, 4) and out['collision'].shape == out['offroad'].shape == (B, A)
+    assert out['image_sums'].shape == (B, A, 3) and out['image_sums'].dtype == np.float64
+    assert out['images'].shape == (bench.DUMP_IMAGES, 3, bench.RES, bench.RES)
+    picked = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(B * A, bench.DUMP_IMAGES, replace=False))
+    np.testing.assert_allclose(out['images'].sum((-2, -1), dtype=np.float64), out['image_sums'].reshape(B * A, 3)[picked], rtol=1e-9)
+    verts, faces, vcat, cats = bench.load_town01()
+    state, size, present, actions = bench.synth_agents(B, A, verts[vcat == cats.index('road')], 1234)
+    for i in range(warmup + steps):
+        state = orc.bicycle_step(state, actions[i % actions.shape[0]], np.full((B, A), 1.5, np.float32))
+    np.testing.assert_allclose(out['state'], state, rtol=1e-5, atol=1e-4)
+    s = out['state']
+    sc = np.stack([np.sin(s[..., 2]), np.cos(s[..., 2])], -1).astype(np.float32)
+    boxes = np.concatenate([s[..., :2], size, s[..., 2:3]], -1)
+    np.testing.assert_allclose(out['collision'], orc.collision(boxes, present, metric='iou', sc=sc), rtol=0, atol=1e-5)
+    np.testing.assert_allclose(out['offroad'], orc.offroad(s, size, verts, faces, 0.5, present=present, sc=sc), rtol=0, atol=1e-5)

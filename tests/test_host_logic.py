@@ -308,11 +308,11 @@ def test_reserved_cu_layout_is_judged_from_where_the_streams_really_ran():
 
 def test_reserved_probe_never_raises(monkeypatch):
     """reserved_layout_ok / Simulator._reserved_usable promise "never raises, falls back with ONE warning" -- also when creating or
-    probing the CU-masked streams fails (here: no GPU at all, then a failing tds_stream_create), and a verdict taken under stream capture
-    ('not verified') is not kept for good."""
+    probing the CU-masked streams fails (here: a device that no box has, then a failing tds_stream_create), and a verdict taken under stream
+    capture ('not verified') is not kept for good."""
     from torchdrivesim_amd import _ops
     monkeypatch.setattr(_ops, '_reserved_streams', {})
-    ok, why = _ops.reserved_layout_ok(torch.device('cuda', 0))          # this container has no GPU: whatever fails, fails inside
+    ok, why = _ops.reserved_layout_ok(torch.device('cuda', 100))        # no such device, GPU box or not: whatever fails, fails inside
     assert ok is False and isinstance(why, str) and why
 
     def boom(idx, per_xcd):
