@@ -390,6 +390,32 @@ int tds_lanelet_directions_f64(const tds_laneset_t *set, const int32_t *scene_ma
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */
+/* The flags of tds_raster_set_debug (ablations, work counters and forced launch forms of K3, the scene rasteriser).  Defined in both builds:
+ * the product's kernels name them too, where TDS_DBG() compiles them out. */
+#define TDS_RASTER_DBG_NO_STATIC 1             /* no static map */
+#define TDS_RASTER_DBG_NO_ACTORS 2             /* no actors */
+#define TDS_RASTER_DBG_NO_STORE 4              /* no store of the image */
+#define TDS_RASTER_DBG_NO_EDGES 8              /* no outline edges: no edge classes and no walk */
+#define TDS_RASTER_DBG_NO_SCAN 16              /* no scan conversion */
+#define TDS_RASTER_DBG_NO_BINNED 32            /* never the binned packed-key path */
+#define TDS_RASTER_DBG_NO_BITS 64              /* never the bit planes */
+#define TDS_RASTER_DBG_STATS 128               /* work counters on (tds_raster_get_stats) */
+#define TDS_RASTER_DBG_NO_EDGE_WALK 256        /* the edge classes stay, only the walk of outline edges goes */
+#define TDS_RASTER_DBG_NO_SETUP 512            /* no per-face set-up (nothing is painted) */
+#define TDS_RASTER_DBG_NO_PROJECT 1024         /* walk the grid but project nothing */
+#define TDS_RASTER_DBG_MINWG3 2048             /* the 170-VGPR instantiation everywhere */
+#define TDS_RASTER_DBG_XCD_CLOCKS 4096         /* the work counters hold per-XCD finish [0..7] and ~start [8..15] wall clocks (100 MHz) */
+#define TDS_RASTER_DBG_NO_SPLIT 8192           /* never the split form (K3s + K3r) */
+#define TDS_RASTER_DBG_SPLIT 16384             /* the split form wherever a workspace allows it */
+#define TDS_RASTER_DBG_NO_SHORT_PATH 32768     /* K3r without its short path for small faces */
+#define TDS_RASTER_DBG_GRID8 65536             /* the persistent launch with 8 workgroups per CU (round 3's surplus) instead of the resident number */
+#define TDS_RASTER_DBG_GRID4 131072            /* ... with 4 */
+#define TDS_RASTER_DBG_WHOLE_4WAVES 262144     /* an image whose planes do not fit three workgroups per CU (six and more keys at 256 x 256): whole in
+                                                  4-wave workgroups instead of whole in 8-wave ones */
+#define TDS_RASTER_DBG_NO_8WAVES 524288        /* ... in half-image strips instead */
+#define TDS_RASTER_DBG_WIDEST_STRIPS 1048576   /* strips as wide as the LDS allows instead of equal ones (nine and more keys) */
+#define TDS_RASTER_DBG_NO_EXTRA_STRIP 2097152  /* never one strip more than necessary (nine and more keys) */
+
 #ifdef TDS_TESTING
 /* force the LDS strip width of K3 (0 = automatic, else 8 .. 128 output rows) */
 int tds_raster_set_strip_width(int tw);
@@ -399,16 +425,19 @@ int tds_raster_set_bits_waves(int n);
 int tds_raster_set_list_lds(int lds_kb);
 /* K3r: waves per workgroup (2 or 4; 0 = chosen by the size of a strip) */
 int tds_raster_set_list_waves(int waves);
-/* ablation switches of K3: 1 no static map, 2 no actors, 4 no store, 8 no outline edges, 16 no scan conversion, 32 no binned path,
- * 64 no bit planes, 128 work counters on, 512 no per-face set-up (nothing is painted), 1024 walk the grid but project nothing,
- * 2048 the 170-VGPR instantiation everywhere, 4096 the work counters hold per-XCD finish [0..7] and ~start [8..15] wall clocks (100 MHz),
- * 8192 never the split form (K3s + K3r), 16384 the split form wherever a workspace allows it, 262144 / 524288 an image whose planes do not fit three
- * workgroups per CU (six and more keys at 256 x 256) whole in 4-wave workgroups / in half-image strips instead of whole in 8-wave ones, 1048576 / 2097152
- * strips as wide as the LDS allows instead of equal ones / never one strip more than necessary (nine and more keys), 32768 K3r without its short path for
- * small faces, 65536 / 131072 the persistent launch with 8 / 4 workgroups per CU (round 3's surplus) instead of the resident number */
+/* ablation switches of K3: an OR of the TDS_RASTER_DBG_* flags above */
 int tds_raster_set_debug(int flags);
 /* read and reset the 16 work counters of the bit-plane kernel */
 int tds_raster_get_stats(unsigned long long *out16);
+/* which launches tds_raster_scene makes for a call of this shape (its plan_raster_scene, with explicit knobs: those of the four setters above).
+ * n_keys: distinct keys (-1: more than 15); workspace_bytes: as the caller passes it (0: none).
+ * form: 0 bit planes, 1 split (K3s + K3r + the bit planes over overflowed cameras), 2 packed keys binned, 3 packed keys fused, 4 TDS_ELIMIT */
+typedef struct {
+    int form, tw, strips, twp, nwv, nb, minwg, emit, four_per_cu, persist, tws, lw;
+    int64_t lds, lds_s, grid, caps, off_counts, off_lists, off_lists3;
+} tds_raster_plan_t;
+int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64_t workspace_bytes,
+                    int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug, tds_raster_plan_t *out);
 /* 0: maps created from now on carry no nearest-face candidate lists (K2b then walks grid rings) */
 int tds_testing_set_near_lists(int enabled);
 #endif

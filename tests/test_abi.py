@@ -62,6 +62,12 @@ def test_testing_hooks_are_not_in_the_product():
     assert ' getenv' not in undefined, 'the product library must not read the environment'
 
 
+def test_raster_debug_flags_match_the_header():
+    """_native.RasterDebug names the same bits as include/tdship.h's TDS_RASTER_DBG_* (the flags of tds_raster_set_debug)"""
+    from torchdrivesim_amd import _native
+    defines = dict(re.findall(r'#define TDS_RASTER_DBG_(\w+) (\d+)', open(os.path.join(ROOT, 'include', 'tdship.h')).read()))
+    assert {k: int(v) for k, v in defines.items()} == {f.name: f.value for f in _native.RasterDebug}
+
 def test_errors_are_loud_without_touching_the_gpu():
     from torchdrivesim_amd import _native
     L = _native.lib()

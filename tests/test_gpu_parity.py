@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from torchdrivesim_amd._native import RasterDebug as D
 
 pytestmark = pytest.mark.gpu
 
@@ -555,9 +556,9 @@ def test_k3_golden_scenes_bit_exact(ops, oracle, town, testing_lib):
 def test_k3_split_form_equals_the_fused_kernel_and_the_oracle(ops, oracle, town, testing_lib):
     """Up to 144 x 144 (float32) / 208 x 208 (uint8) the bit-plane path runs as two kernels -- K3s lists every camera's faces, K3r rasterises
     the lists -- with a third launch of the fused kernel over the cameras whose list overflowed.  Every form must paint the same pixels:
-    forced either way (debug flags 8192 / 16384 of the testing build), cut into narrow strips (LDS budget), with a workspace so small that
+    forced either way (debug flags NO_SPLIT / SPLIT of the testing build), cut into narrow strips (LDS budget), with a workspace so small that
     most lists overflow, and with K3r's short path for small faces (the three vertices inside the image and in at most two -- from 112 x 112
-    on: four -- rows, painted by their lane on the spot) switched off (32768): the two set-ups paint the same pixels."""
+    on: four -- rows, painted by their lane on the spot) switched off (NO_SHORT_PATH): the two set-ups paint the same pixels."""
     g = load_golden('g45_mesh_preraster.npz')
     st, sz, pr = g['g5_town01_128_state'], g['g5_town01_128_size'], g['g5_town01_128_present']
     B, A = st.shape[:2]
@@ -570,8 +571,8 @@ def test_k3_split_form_equals_the_fused_kernel_and_the_oracle(ops, oracle, town,
         for res, fov in ((64, 35.0), (108, 120.0), (112, 35.0), (128, 35.0), (192, 60.0), (256, 35.0), (320, 80.0)):
             ref = None
             for dtype in (torch.float32, torch.uint8):
-                for flags, lds_kb, small_ws in ((8192, 40, False), (16384, 40, False), (16384, 16, False), (16384, 52, False), (16384, 40, True),
-                                                (16384 | 32768, 40, False), (16384 | 32768, 16, False)):
+                for flags, lds_kb, small_ws in ((D.NO_SPLIT, 40, False), (D.SPLIT, 40, False), (D.SPLIT, 16, False), (D.SPLIT, 52, False), (D.SPLIT, 40, True),
+                                                (D.SPLIT | D.NO_SHORT_PATH, 40, False), (D.SPLIT | D.NO_SHORT_PATH, 16, False)):
                     testing_lib.tds_raster_set_debug(flags)
                     testing_lib.tds_raster_set_list_lds(lds_kb)
                     ops._workspaces.clear()
@@ -617,7 +618,7 @@ def test_k3_per_camera_triangles_in_every_form(ops, oracle, town, testing_lib):
         for res, fov in ((64, 35.0), (128, 35.0), (256, 35.0)):
             for dtype in (torch.float32, torch.uint8):
                 ref = None
-                for flags, small_ws, bits in ((8192, False, True), (16384, False, True), (16384, True, True), (0, False, True), (0, False, False)):
+                for flags, small_ws, bits in ((D.NO_SPLIT, False, True), (D.SPLIT, False, True), (D.SPLIT, True, True), (0, False, True), (0, False, False)):
                     testing_lib.tds_raster_set_debug(flags)
                     ops._workspaces.clear()
                     if small_ws:
@@ -642,7 +643,7 @@ def test_k3_per_camera_triangles_in_every_form(ops, oracle, town, testing_lib):
 def test_k3_six_to_ten_keys_at_256_in_every_workgroup_shape(ops, oracle, town, testing_lib):
     """Two or three agent types (six / seven distinct keys): at 256 x 256 the bit planes no longer fit three workgroups per CU.  Round 6 renders the
     whole image in 8-wave workgroups, two per CU (raster.hip: raster_scene_impl; profiles/r06_more_keys.log); the alternatives stay reachable in
-    the testing build -- the whole image in 4-wave workgroups (debug flag 262144), two half-image strips (524288).  Same pixels as the oracle in
+    the testing build -- the whole image in 4-wave workgroups (debug flag WHOLE_4WAVES), two half-image strips (NO_8WAVES).  Same pixels as the oracle in
     all three, float32 and uint8."""
     types = dict(vehicle=(4, (32, 74, 135)), bicycle=(5, (255, 150, 40)), pedestrian=(6, (255, 64, 180)), ego=(3, (255, 0, 0)), ground_truth=(9, (196, 188, 165)),
                  prediction=(10, (255, 155, 0)))
@@ -658,7 +659,7 @@ def test_k3_six_to_ten_keys_at_256_in_every_workgroup_shape(ops, oracle, town, t
     B, A, res, fov = 2, 14, 256, 35.0
     try:
         # ... and nine / ten keys (five / six agent types): their planes exceed 64 KiB for a whole image -- strips of equal width (round 6; testing flag
-        # 1048576: the widest that fit, 192 + 64 columns), for ten keys one strip more than necessary (2097152: not)
+        # WIDEST_STRIPS: the widest that fit, 192 + 64 columns), for ten keys one strip more than necessary (NO_EXTRA_STRIP: not)
         for names in (['vehicle', 'pedestrian'], ['vehicle', 'bicycle', 'pedestrian'], ['vehicle', 'bicycle', 'pedestrian', 'ego', 'ground_truth'],
                       ['vehicle', 'bicycle', 'pedestrian', 'ego', 'ground_truth', 'prediction']):
             anchor = road[gen.integers(0, len(road), (B, 1))]
@@ -677,7 +678,7 @@ def test_k3_six_to_ten_keys_at_256_in_every_workgroup_shape(ops, oracle, town, t
             ref = oracle.render_scenes(state, size, mask, state[..., :2].copy(), sc_np(agent_sc), *static, fov, res, agent_sc=sc_np(agent_sc),
                                        actor_levels=lev, actor_colors=col.astype(np.float32))
             assert ref.any()
-            for flags in ((0, 262144, 524288) if len(names) <= 3 else (0, 1048576, 2097152)):
+            for flags in ((0, D.WHOLE_4WAVES, D.NO_8WAVES) if len(names) <= 3 else (0, D.WIDEST_STRIPS, D.NO_EXTRA_STRIP)):
                 testing_lib.tds_raster_set_debug(flags)
                 for dtype in (torch.float32, torch.uint8):
                     img = ops.raster_scene(smap, sd, agent_sc, dev(oracle.actor_template(size)), keys, dev(mask), dev(state[..., :2].copy()), agent_sc, fov, res, dtype)

@@ -6,6 +6,7 @@ There is deliberately NO fallback: if the shared library is missing or a call fa
 """
 import contextlib
 import ctypes
+import enum
 import os
 import subprocess
 
@@ -20,6 +21,32 @@ CSRC = os.path.join(_HERE, 'csrc')
 METRIC_IOU, METRIC_DISCS = 0, 1
 OUT_F32, OUT_U8 = 0, 1
 RASTER_NO_TRIM = 1
+
+
+class RasterDebug(enum.IntFlag):
+    """the flags of tds_raster_set_debug (testing build): TDS_RASTER_DBG_* of include/tdship.h"""
+    NO_STATIC = 1
+    NO_ACTORS = 2
+    NO_STORE = 4
+    NO_EDGES = 8
+    NO_SCAN = 16
+    NO_BINNED = 32
+    NO_BITS = 64
+    STATS = 128
+    NO_EDGE_WALK = 256
+    NO_SETUP = 512
+    NO_PROJECT = 1024
+    MINWG3 = 2048
+    XCD_CLOCKS = 4096
+    NO_SPLIT = 8192
+    SPLIT = 16384
+    NO_SHORT_PATH = 32768
+    GRID8 = 65536
+    GRID4 = 131072
+    WHOLE_4WAVES = 262144
+    NO_8WAVES = 524288
+    WIDEST_STRIPS = 1048576
+    NO_EXTRA_STRIP = 2097152
 
 _lib = None
 
@@ -104,6 +131,7 @@ _TESTING_SIGNATURES = {
     'tds_raster_set_debug': [_i32],
     'tds_raster_get_stats': [ctypes.POINTER(ctypes.c_ulonglong)],
     'tds_testing_set_near_lists': [_i32],
+    'tds_raster_plan': [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
 }
 
 

@@ -86,8 +86,7 @@ struct CommonArgs {
     int no_trim;                // trim_mesh_before_rendering = False (cv2.py:15,32): faces are kept whether or not a vertex is in view
     uint32_t *slices;           // optional: bit-slices of the winning key index per pixel, kept for the backward pass (bit-plane kernel
                                 // only; layout in include/tdship.h, tds_raster_aux_t)
-    int debug;                  // ablation switches for profiling (tds_raster_set_debug): 1 no static, 2 no actors, 4 no store,
-                                // 8 no outline edges, 16 no scan conversion
+    int debug;                  // ablation switches for profiling (tds_raster_set_debug): TDS_RASTER_DBG_* of include/tdship.h
 };
 
 struct Camera {
@@ -436,7 +435,7 @@ __device__ __forceinline__ void process_batch(WaveCtx &w, int n) {
         key = w.q[lane]; v0 = w.q[QCAP + lane]; v1 = w.q[2 * QCAP + lane]; v2 = w.q[3 * QCAP + lane];
         const int px[3] = {unpack_x(v0), unpack_x(v1), unpack_x(v2)}, py[3] = {unpack_y(v0), unpack_y(v1), unpack_y(v2)};
         r = face_rows(px, py, H, W, X0, TW);
-        if (r.nrows > 0 && !(TDS_DBG(w.debug) & 16)) {
+        if (r.nrows > 0 && !(TDS_DBG(w.debug) & TDS_RASTER_DBG_NO_SCAN)) {
             int i1 = r.imin == 2 ? 0 : r.imin + 1, i2 = r.imin == 0 ? 2 : r.imin - 1;
             a = make_chain(px, py, r.imin, i1, i2);
             b = make_chain(px, py, r.imin, i2, i1);
@@ -499,7 +498,7 @@ __device__ __forceinline__ void process_batch(WaveCtx &w, int n) {
         }
     }
     // ---- outline edges: OpenCV draws Line(v2,v0), Line(v0,v1), Line(v1,v2) before the scan conversion
-    if (!(TDS_DBG(w.debug) & 8)) {
+    if (!(TDS_DBG(w.debug) & TDS_RASTER_DBG_NO_EDGES)) {
 #pragma unroll 1
         for (int l = 0; l < 3; ++l) {
             const uint32_t pa = l == 0 ? v2 : (l == 1 ? v0 : v1), pb = l == 0 ? v0 : (l == 1 ? v1 : v2);
@@ -767,13 +766,13 @@ __device__ __forceinline__ void scan_init(ScanState &st, const SA &a, const Comm
     if constexpr (POLY) st.map.cell_start = st.map.qcell_start;
     const MapView &m = st.map;
     const int res = c.res;
-    st.phase = (a.N > 0 && !(TDS_DBG(c.debug) & 2)) ? 0 : 2;      // 0 actors, 1 masked-agent dot, 3 per-camera triangles, 2 static map
+    st.phase = (a.N > 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_ACTORS)) ? 0 : 2;      // 0 actors, 1 masked-agent dot, 3 per-camera triangles, 2 static map
     if constexpr (POLY) {
         // The scan kernel of the split form reads the first phase through the launch's (always zero, in the product) debug word: a phase the
         // compiler knows at compile time makes it restructure the phases so that scan_faces_kernel needs 368 instead of 112 bytes of scratch per
         // lane and takes 0.98 instead of 0.72 ms at B = 1024 x 64.  (Found because the testing build was the faster one; an opaque register
         // in place of the kernel argument does not have the effect.)
-        st.phase = (a.N > 0 && !(c.debug & 2)) ? 0 : 2;
+        st.phase = (a.N > 0 && !(c.debug & TDS_RASTER_DBG_NO_ACTORS)) ? 0 : 2;
     }
     if constexpr (has_extras<SA>::value) { if (st.phase == 2 && a.K > 0) st.phase = 3; }
     st.a0 = 0; st.masked_seen = false;
@@ -781,7 +780,7 @@ __device__ __forceinline__ void scan_init(ScanState &st, const SA &a, const Comm
     st.rw = SCAN_EMPTY_ROW; st.rex = st.rbase = st.rfe = 0; st.rtotal = 0;
     st.have = false; st.cur_i = -1; st.dyn = nullptr; st.done = 0;
     st.pu0 = st.pu1 = st.pu2 = make_uint4(0, 0, 0, 0);
-    if (m.nx > 0 && !(TDS_DBG(c.debug) & 1)) {
+    if (m.nx > 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STATIC)) {
         // world-space bounding box of the window (2 px margin: int truncation moves a vertex by < 1 px) -> grid cell rectangle
         float wx0 = 3.0e38f, wx1 = -3.0e38f, wy0 = 3.0e38f, wy1 = -3.0e38f;
         const float half = (float)res / 2.0f;
@@ -890,7 +889,7 @@ __device__ __forceinline__ void scan_candidate(const ScanState &st, const Common
         const int bx0 = (int)(own & 0x1fffu), bx1 = (int)((own >> 13) & 0x1fffu);
         const bool first_in_row = !(own & (1u << 26)) || (i < first_end);
         const bool none_above = !(own & (1u << 27)) || top || bx1 < plo || bx0 > phi;
-        if (first_in_row && none_above && !(TDS_DBG(c.debug) & 1024)) {      // 1024: ablation, walk the grid but project nothing
+        if (first_in_row && none_above && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_PROJECT)) {      // ablation, walk the grid but project nothing
             unsigned ins = 0;
             float sxv[3] = {__uint_as_float(u0.x) + (-cam.cx), __uint_as_float(u0.z) + (-cam.cx), __uint_as_float(u1.x) + (-cam.cx)};
             float syv[3] = {__uint_as_float(u0.y) + (-cam.cy), __uint_as_float(u0.w) + (-cam.cy), __uint_as_float(u1.y) + (-cam.cy)};
@@ -1082,7 +1081,7 @@ __device__ __forceinline__ void scan_candidate_poly(const ScanState &st, const C
         const int bx0 = (int)(own & 0x1fffu), bx1 = (int)((own >> 13) & 0x1fffu);
         const bool first_in_row = !(own & (1u << 26)) || (i < first_end);
         const bool none_above = !(own & (1u << 27)) || top || bx1 < plo || bx0 > phi;
-        if (first_in_row && none_above && !(TDS_DBG(c.debug) & 1024)) {
+        if (first_in_row && none_above && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_PROJECT)) {
             const float sxv[4] = {__uint_as_float(u0.x) + (-cam.cx), __uint_as_float(u0.z) + (-cam.cx), __uint_as_float(u1.x) + (-cam.cx), __uint_as_float(u1.z) + (-cam.cx)};
             const float syv[4] = {__uint_as_float(u0.y) + (-cam.cy), __uint_as_float(u0.w) + (-cam.cy), __uint_as_float(u1.y) + (-cam.cy), __uint_as_float(u1.w) + (-cam.cy)};
             key = u2.x;
@@ -1196,7 +1195,7 @@ __global__ void __launch_bounds__(RBLOCK, 4) raster_scene_kernel(SceneArgsEx a, 
         if (!more) break;
     }
     __syncthreads();
-    if (!(TDS_DBG(c.debug) & 4)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
+    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
 }
 
 // ---- fast path: two kernels ---------------------------------------------------------------------------------
@@ -1280,7 +1279,7 @@ __global__ void __launch_bounds__(RBLOCK, 4) raster_scene_list_kernel(SceneArgsE
         }
     }
     __syncthreads();
-    if (!(TDS_DBG(c.debug) & 4)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
+    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
 }
 
 // =========================================================================================================
@@ -1533,11 +1532,11 @@ __device__ inline bool clip_line_small(int W, int H, int &x1, int &y1, int &x2, 
 //            c2 = 2 |dy| - dx - (sgn < 0).
 // Both are floor((N0 + tau * 2 dx) / D): stepping tau adds divmod(2 dx, D) = (ia, ib) to (quotient, remainder) with one carry.
 // (checked exhaustively against the iterative walk in tests/test_oracle_fill.py::test_line_rows_closed_form)
-// optional work counters (profiling hook tds_raster_get_stats of the testing build; active with debug flag 128)
+// optional work counters (profiling hook tds_raster_get_stats of the testing build; active with debug flag TDS_RASTER_DBG_STATS)
 #ifdef TDS_TESTING
 __device__ unsigned long long g_stats[16];
-#define TDS_STAT_LANES(W, I, V) do { if ((W).debug & 128) { const unsigned long long v_ = (unsigned long long)(V); if (v_) atomicAdd(&g_stats[I], v_); } } while (0)
-#define TDS_STAT(W, I, V) do { if (((W).debug & 128) && (W).lane == 0) atomicAdd(&g_stats[I], (unsigned long long)(V)); } while (0)
+#define TDS_STAT_LANES(W, I, V) do { if ((W).debug & TDS_RASTER_DBG_STATS) { const unsigned long long v_ = (unsigned long long)(V); if (v_) atomicAdd(&g_stats[I], v_); } } while (0)
+#define TDS_STAT(W, I, V) do { if (((W).debug & TDS_RASTER_DBG_STATS) && (W).lane == 0) atomicAdd(&g_stats[I], (unsigned long long)(V)); } while (0)
 #else
 #define TDS_STAT_LANES(W, I, V) do { } while (0)
 #define TDS_STAT(W, I, V) do { } while (0)
@@ -1620,7 +1619,7 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
     const int lane = w.lane, H = w.H, W = w.W, X0 = w.X0, TWp = w.TWp, wpr = w.wpr;
     const int Xhi = min(W, X0 + TWp) - 1;                              // last column of the strip (X0 = first)
     wave_sync();
-    if (TDS_DBG(w.debug) & 512) return;                       // ablation: no per-face set-up either
+    if (TDS_DBG(w.debug) & TDS_RASTER_DBG_NO_SETUP) return;                       // ablation: no per-face set-up either
     // ---- per-face set-up (lane = face): vertices by row (T, M, B), the three 16.16 slopes, the rows of the vertices painted on the spot,
     //      the rows in between described as two parts (T..M: chains T->M and T->B; M..B: chains M->B and T->B)
     // what a lane keeps of its face: the packed top and middle vertices, the three slopes, the row counts of the two parts (n1 | n2 << 16)
@@ -1641,7 +1640,7 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
         const int xmin = min(xt, min(xm, xb)), xmax = max(xt, max(xm, xb));
         const bool hit = !(xmax < X0 || xmin > Xhi || yb < 0 || yt >= H);
         unsigned cTM = 0, cMB = 0, cTB = 0;
-        if (hit && !(TDS_DBG(w.debug) & 8)) {
+        if (hit && !(TDS_DBG(w.debug) & TDS_RASTER_DBG_NO_EDGES)) {
             const unsigned ocT = vertex_outcode(xt, yt, W, H), ocM = vertex_outcode(xm, ym, W, H), ocB = vertex_outcode(xb, yb, W, H);
             cTM = edge_class(xt, yt, xm, ym, ocT, ocM); cMB = edge_class(xm, ym, xb, yb, ocM, ocB); cTB = edge_class(xt, yt, xb, yb, ocT, ocB);
             // Edges that are not merged and not entirely on one outer side of the image (both outcodes share a bit: cv::clipLine leaves nothing)
@@ -1674,7 +1673,7 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
                 sTB = edge_dx(xt, xb, yb - yt);
                 sTM = ym > yt ? edge_dx(xt, xm, ym - yt) : 0;
                 sMB = yb > ym ? edge_dx(xm, xb, yb - ym) : 0;
-                if (!(TDS_DBG(w.debug) & 16)) {
+                if (!(TDS_DBG(w.debug) & TDS_RASTER_DBG_NO_SCAN)) {
                     // the row of the top vertex (two of them: the span between them): both chains start here
                     {
                         int L = xt, R = xt;
@@ -1753,8 +1752,8 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
     // ---- outline edges that are walked exactly ----
     // They go through a per-wave ring of EQCAP entries (two packed end points + plane index) that lives across batches: 64 of them are
     // taken at a time, so that the per-edge set-up and the row items below run on full waves.
-    // (ablations of the testing build: 8 = no edge classes and no walk -- every edge unmerged, nothing walked --, 256 = the classes stay, only the walk goes)
-    if (!(TDS_DBG(w.debug) & (8 | 256))) {
+    // (ablations of the testing build: NO_EDGES = no edge classes and no walk -- every edge unmerged, nothing walked --, NO_EDGE_WALK = the classes stay, only the walk goes)
+    if (!(TDS_DBG(w.debug) & (TDS_RASTER_DBG_NO_EDGES | TDS_RASTER_DBG_NO_EDGE_WALK))) {
         TDS_STAT_LANES(w, 5, __popc(((unsigned)flags >> 13) & 7u));
 #pragma unroll 1
         for (int l = 0; l < 4; ++l) {
@@ -2335,8 +2334,8 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         if (tid == 0) { lkeys[17] = 0; claim_work(queue, (int)(c.n_img * c.strips), lkeys + 16, only, c.strips); }
     }
 #ifdef TDS_TESTING
-    // debug flag 4096: when does each XCD start and finish its share of the launch?  (wall clock, 100 MHz; blocks are dealt round-robin to the XCDs)
-    if ((c.debug & 4096) && tid == 0) atomicMax(&g_stats[8 + (blockIdx.x & 7)], ~(unsigned long long)wall_clock64());
+    // debug flag TDS_RASTER_DBG_XCD_CLOCKS: when does each XCD start and finish its share of the launch?  (wall clock, 100 MHz; blocks are dealt round-robin to the XCDs)
+    if ((c.debug & TDS_RASTER_DBG_XCD_CLOCKS) && tid == 0) atomicMax(&g_stats[8 + (blockIdx.x & 7)], ~(unsigned long long)wall_clock64());
 #endif
     if (tid < 16) {
         uint32_t kv = 0xffffffffu;
@@ -2417,11 +2416,11 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         if constexpr (PERSIST) { if (tid == 0) claim_work(queue, (int)(c.n_img * c.strips), lkeys + 16, only, c.strips); }
         __syncthreads();
         if constexpr (sizeof(OutT) != 4) __builtin_amdgcn_s_setprio(0);
-        if (!(TDS_DBG(c.debug) & 4)) write_out_bits<BBLOCK, NB, OutT, EMIT>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, c.slices);
+        if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out_bits<BBLOCK, NB, OutT, EMIT>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, c.slices);
         if constexpr (!PERSIST) break;
     }
 #ifdef TDS_TESTING
-    if ((c.debug & 4096) && lane == 0) atomicMax(&g_stats[blockIdx.x & 7], (unsigned long long)wall_clock64());
+    if ((c.debug & TDS_RASTER_DBG_XCD_CLOCKS) && lane == 0) atomicMax(&g_stats[blockIdx.x & 7], (unsigned long long)wall_clock64());
 #endif
 }
 
@@ -2524,7 +2523,7 @@ __global__ void __launch_bounds__(SCAN_WAVES * 64, TDS_SCAN_OCC) scan_faces_kern
     }
     // The static map.  With nothing to rasterise between two chunks of entries the walk would wait for every load (1.2 us each):
     // the entries are taken SCAN_DEPTH chunks at a time, all their loads in flight together.
-    if (!(TDS_DBG(c.debug) & 1)) {
+    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STATIC)) {
         const MapView &m = st.map;
         while (st.row < st.nrows) {
             const int nblk = min(64, st.nrows - st.row);
@@ -2639,7 +2638,7 @@ __global__ void __launch_bounds__(BWAVES * 64) raster_list_bits_kernel(CommonArg
             const int x0 = unpack_x(v0), x1 = unpack_x(v1), x2 = unpack_x(v2), y0 = unpack_y(v0), y1 = unpack_y(v1), y2 = unpack_y(v2);
             const int xmin = min(x0, min(x1, x2)), xmax = max(x0, max(x1, x2)), ymin = min(y0, min(y1, y2)), ymax = max(y0, max(y1, y2));
             if (c.strips > 1) on = on && !(xmax < X0 || xmin > Xhi);       // triangles that miss this strip are not queued
-            small = on && !(TDS_DBG(c.debug) & 32768) && xmin >= 0 && xmax < W && ymin >= 0 && ymax < H && ymax - ymin <= span;
+            small = on && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_SHORT_PATH) && xmin >= 0 && xmax < W && ymin >= 0 && ymax < H && ymax - ymin <= span;
             return on;
         };
         bool small1, small2;
@@ -2655,7 +2654,7 @@ __global__ void __launch_bounds__(BWAVES * 64) raster_list_bits_kernel(CommonArg
         if (!more) break;
     }
     __syncthreads();
-    if (!(TDS_DBG(c.debug) & 4)) write_out_bits<BBLOCK, NB, OutT, false>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, nullptr);
+    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out_bits<BBLOCK, NB, OutT, false>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, nullptr);
 }
 
 inline int bits_index_bits(int K) { return K <= 3 ? 2 : (K <= 7 ? 3 : 4); }
@@ -2665,30 +2664,48 @@ inline size_t bits_lds_bytes(int K, int res, int twp, int nwaves, int out_mode) 
     size_t tab_dw = 3 * P * (out_mode == TDS_OUT_F32 ? 2 : 1);
     return (plane_dw + tab_dw + BITS_FIXED_DW + (size_t)nwaves * BITS_WAVE_LDS_DW) * 4;
 }
-int g_bits_waves = 4;
-int g_list_waves = 0;            // waves per workgroup of K3r (0: by image size; testing hook)
-int g_list_lds_kb = 40;          // K3r picks the widest strip whose workgroup needs at most this much LDS (testing hook)
+// The knobs of K3 that the testing hooks set (include/tdship.h, "testing hooks"), constants in the product: the strip width (0: automatic),
+// waves per workgroup of the bit-plane kernel and of K3r (0: by image size), K3r's LDS budget in KiB (it takes the widest strip that fits), and
+// the TDS_RASTER_DBG_* flags.
+struct RasterKnobs { int force_tw, bits_waves, list_waves, list_lds_kb, debug; };
+#ifndef TDS_TESTING
+constexpr
+#endif
+RasterKnobs g_knobs = {0, 4, 0, 40, 0};
 
 // The work queues of a persistent bit-plane launch: 8 counters (64 bytes) that must be zero when the kernel starts.  They live at the
 // END of the caller's workspace (tds_raster_scene_workspace_bytes provides for them) and are cleared in stream order right before the
-// launch.  Two launches that may overlap in time must not share a
-// workspace; that already holds for the face lists.  The library allocates nothing per call.
+// launch.  Two launches that may overlap in time must not share a workspace; that already holds for the face lists.  The library allocates
+// nothing per call.  (They are cleared by tds::zero_async, a kernel: see there why not hipMemsetAsync.)
 constexpr int64_t QUEUE_BYTES = 64;
-// (cleared by tds::zero_async, a kernel: see there why not hipMemsetAsync)
-// splits the caller's workspace: -> queue (nullptr when there is no room for one), `bytes` is cut to what is left for the lists
-inline uint32_t *workspace_queue(void *workspace, int64_t &bytes) {
-    if (workspace == nullptr || bytes < QUEUE_BYTES + 64) return nullptr;
-    const int64_t off = (bytes - QUEUE_BYTES) & ~(int64_t)63;
-    bytes = off;
-    return (uint32_t *)((char *)workspace + off);
+// where the queues start in a workspace of `bytes` (what lies before is left for the lists); -1: no room for them
+inline int64_t queue_offset(int64_t bytes) { return bytes < QUEUE_BYTES + 64 ? -1 : (bytes - QUEUE_BYTES) & ~(int64_t)63; }
+// the workspace that leaves `lists` bytes for the lists and room for the queues after them
+inline int64_t with_queue_tail(int64_t lists) { return ((lists + 63) & ~(int64_t)63) + QUEUE_BYTES + 64; }
+
+// The workspace of the split form: a marker list (`poisoned`, n_img + 1 words) at 0, a count per camera, then `caps` poly records per camera,
+// each 16 bytes in `lists` (flags, P0, P1, P2) and 4 in `lists3` (P3).  The recommended workspace (tds_raster_scene_workspace_bytes*)
+// counts LIST_CAPS records of 16 bytes while the launch divides what it gets by 20, so LIST_CAPS = 2048 yields about 1636 records per
+// camera.  Kept as it was measured: a change moves which cameras overflow to the fused kernel.
+struct SplitLayout { int64_t counts, lists, lists3, caps; };        // byte offsets; records per camera
+// caps < 0: as many as `bytes` hold (a multiple of 4, at most 8192; 0 when none fit)
+inline SplitLayout split_layout(int64_t n_img, int64_t caps, int64_t bytes = 0) {
+    const int64_t counts = ((n_img + 1) * 4 + 255) & ~(int64_t)255, lists = (counts + n_img * 4 + 255) & ~(int64_t)255;
+    if (caps < 0) caps = bytes > lists ? std::min<int64_t>(((bytes - lists) / (n_img * 20)) & ~(int64_t)3, 8192) : 0;
+    return {counts, lists, lists + n_img * caps * 16, caps};
 }
+
 // workgroups of a persistent launch: exactly as many as are resident at a time -- three per CU (168 VGPRs: three waves per SIMD), fewer when
 // the LDS of one exceeds a third of the CU's 160 KiB.  (A surplus of waiting workgroups costs: DESIGN_HISTORY.md, appendix R6; fewer than the
 // resident number, or head / tail items in strips, do not pay either: profiles/r06_tail_attempts.log.)
-#ifdef TDS_TESTING
-int g_debug = 0;
-#endif
-int persistent_grid(int64_t items, size_t lds_bytes, hipStream_t stream) {
+inline int64_t resident_workgroups(int cus, size_t lds_bytes, const RasterKnobs &k) {
+    const size_t granted = (lds_bytes + 2047) & ~(size_t)2047;                  // LDS is granted in 2 KiB steps
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / std::max<size_t>(granted, 1)));
+    // (testing build, GRID8 / GRID4: 8 / 4 workgroups per CU -- the surplus of round 3)
+    return (int64_t)cus * ((k.debug & TDS_RASTER_DBG_GRID8) ? 8 : ((k.debug & TDS_RASTER_DBG_GRID4) ? 4 : per_cu));
+}
+// the CUs a launch on `stream` may use
+int launch_cus(hipStream_t stream) {
     constexpr int MAX_DEVICES = 64;
     static std::atomic<int> cus_of[MAX_DEVICES];          // per device: a process may drive several (zero-initialised: not looked up yet)
     int dev = 0, cus = 0;
@@ -2706,15 +2723,9 @@ int persistent_grid(int64_t items, size_t lds_bytes, hipStream_t stream) {
             int n = 0;
             for (int i = 0; i < 16; ++i) n += __builtin_popcount(mask[i]);
             if (n > 0 && n < cus) cus = n;
-        } else {
-            (void)hipGetLastError();
-        }
+        } else (void)hipGetLastError();
     }
-    const size_t granted = (lds_bytes + 2047) & ~(size_t)2047;                  // LDS is granted in 2 KiB steps
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / std::max<size_t>(granted, 1)));
-    // (testing build, debug flags 65536 / 131072: 8 / 4 workgroups per CU -- the surplus of round 3)
-    const int64_t cap = (int64_t)cus * ((TDS_DBG(g_debug) & 65536) ? 8 : ((TDS_DBG(g_debug) & 131072) ? 4 : per_cu));
-    return (int)(items < cap ? items : cap);
+    return cus;
 }
 
 // Generic path: arbitrary per-camera RGB mesh, every face is a candidate (no grid).
@@ -2753,7 +2764,7 @@ __global__ void __launch_bounds__(RBLOCK, 4) raster_mesh_kernel(MeshArgs a, Comm
         if (!more) break;
     }
     __syncthreads();
-    if (!(TDS_DBG(c.debug) & 4)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
+    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
 }
 
 inline size_t lds_bytes(int tw, int res) { return ((size_t)tw * res + (size_t)RWAVES * WAVE_LDS_DW) * sizeof(uint32_t); }
@@ -2767,87 +2778,9 @@ inline int pick_tw(int res) {
         if (lds_bytes(tw, res) <= 160 * 1024) return tw;
     return 0;
 }
+// strip width of the packed-key kernels (0: the resolution does not fit)
+inline int strip_width(int res, const RasterKnobs &k) { return (k.force_tw && k.force_tw <= 64) ? k.force_tw : pick_tw(res); }
 
-int g_force_tw = 0;
-
-}  // namespace
-
-#ifdef TDS_TESTING
-// ---- testing build only (include/tdship.h, section "testing hooks"): absent from libtdship.so --------------------------------
-// force the strip width (0 = automatic)
-TDS_EXPORT int tds_raster_set_strip_width(int tw) {
-    TDS_CHECK_ARG(tw == 0 || tw == 8 || tw == 16 || tw == 32 || tw == 64 || tw == 96 || tw == 128, "strip width must be 0, 8, 16, 32, 64, 96 or 128");
-    g_force_tw = tw;
-    return TDS_OK;
-}
-
-// waves per workgroup of the bit-plane kernel (4 or 8)
-TDS_EXPORT int tds_raster_set_bits_waves(int n) {
-    TDS_CHECK_ARG(n == 4 || n == 8, "waves per workgroup must be 4 or 8");
-    g_bits_waves = n;
-    return TDS_OK;
-}
-
-// read and reset the work counters of the bit-plane kernel (debug flag 128)
-TDS_EXPORT int tds_raster_get_stats(unsigned long long *out16) {
-    TDS_CHECK_ARG(out16, "tds_raster_get_stats: null output");
-    unsigned long long zero[16] = {0};
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stats), sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: copy failed"); return TDS_EHIP; }
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: reset failed"); return TDS_EHIP; }
-    return TDS_OK;
-}
-
-// K3r (the list rasteriser of the split bit-plane path): the LDS a workgroup may take in KiB, which sets the strip width
-TDS_EXPORT int tds_raster_set_list_lds(int lds_kb) {
-    TDS_CHECK_ARG(lds_kb >= 16 && lds_kb <= 150, "tds_raster_set_list_lds: 16..150 KiB");
-    g_list_lds_kb = lds_kb;
-    return TDS_OK;
-}
-
-// K3r: waves per workgroup (2 or 4; 0 = chosen by the size of a strip)
-TDS_EXPORT int tds_raster_set_list_waves(int waves) {
-    TDS_CHECK_ARG(waves == 0 || waves == 2 || waves == 4, "tds_raster_set_list_waves: 0, 2 or 4");
-    g_list_waves = waves;
-    return TDS_OK;
-}
-
-// ablation switches, see CommonArgs::debug
-TDS_EXPORT int tds_raster_set_debug(int flags) {
-    g_debug = flags;
-    return TDS_OK;
-}
-
-#endif  // TDS_TESTING
-
-#define TDS_LAUNCH_RASTER(KERNEL, ARGS)                                                                                        \
-    do {                                                                                                                       \
-        size_t lds = lds_bytes(tw, res);                                                                                       \
-        dim3 grid((unsigned)(n_img * cm.strips));                                                                              \
-        auto launch = [&](auto kern) {                                                                                         \
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL(kern, grid, dim3(RBLOCK), lds, (hipStream_t)stream, ARGS, cm);                                  \
-        };                                                                                                                     \
-        if (out_mode == TDS_OUT_F32) {                                                                                         \
-            if (tw == 64) launch(KERNEL<64, float>); else if (tw == 32) launch(KERNEL<32, float>);                             \
-            else if (tw == 16) launch(KERNEL<16, float>); else launch(KERNEL<8, float>);                                       \
-        } else {                                                                                                               \
-            if (tw == 64) launch(KERNEL<64, uint8_t>); else if (tw == 32) launch(KERNEL<32, uint8_t>);                         \
-            else if (tw == 16) launch(KERNEL<16, uint8_t>); else launch(KERNEL<8, uint8_t>);                                   \
-        }                                                                                                                      \
-    } while (0)
-
-static int common_checks(const char *fn, int64_t n_img, int res, int out_mode, const void *out, int &tw) {
-    TDS_CHECK_ARG(n_img >= 0, "%s: negative image count", fn);
-    TDS_CHECK_ARG(res > 0 && res <= 4096, "%s: resolution %d out of range (1..4096)", fn, res);
-    TDS_CHECK_ARG(out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8, "%s: unknown output mode %d", fn, out_mode);
-    TDS_CHECK_ARG(out || n_img == 0, "%s: null output", fn);
-    tw = (g_force_tw && g_force_tw <= 64) ? g_force_tw : pick_tw(res);
-    if (tw == 0 || lds_bytes(tw, res) > 160 * 1024) { tds::set_error("%s: resolution %d does not fit the LDS tile", fn, res); return TDS_ELIMIT; }
-    TDS_CHECK_ARG(n_img * ((res + tw - 1) / tw) < ((int64_t)1 << 31), "%s: too many strips", fn);
-    return TDS_OK;
-}
-
-namespace {
 constexpr int DEFAULT_CAPS = 512;         // faces per strip list that the recommended workspace provides
 constexpr int LIST_CAPS = 2048;           // faces per camera list of the split bit-plane path that the recommended workspace provides
 // The split form (K3s + K3r) serves resolutions up to these; above, the fused launch hides the scan behind its write stream or its row loops.
@@ -2864,10 +2797,204 @@ inline bool split_serves(int res, bool f32) {
     if (!f32) return res <= SPLIT_MAX_RES_U8;
     return res <= SPLIT_ANY_RES_F32 || (res <= SPLIT_MAX_RES_F32 && (res & 15) == 0);
 }
-inline int64_t ws_bytes_for(int64_t n_img, int strips, int caps) {
-    return n_img * strips * ((int64_t)caps * (int64_t)sizeof(uint4) + (int64_t)sizeof(uint32_t));
+
+// Bits: the bit-plane kernel (raster_scene_bits_kernel), the whole image or strips of it; Split: K3s (scan_faces_kernel) + K3r
+// (raster_list_bits_kernel) + the bit-plane kernel over the cameras whose list overflowed; packed keys Binned (K3a bin_faces_kernel + K3b
+// raster_scene_list_kernel) or Fused (raster_scene_kernel); Error: TDS_ELIMIT
+enum class RasterForm { Bits, Split, Binned, Fused, Error };
+
+struct PlanInput {
+    int64_t n_img;
+    int res, out_mode, n_keys;  // n_keys: distinct keys of the scene (its map(s) and the listed actor keys); -1: more than MAX_KEYS
+    bool keys_listed, actors, extra, want_slices;   // the caller listed the actors' keys; N > 0; n_extra > 0; index slices wanted
+    int64_t workspace_bytes;    // what the lists may use, the queue tail cut off; 0: no workspace, or no room for the queues
+    int cus;                    // CUs the launch may use
+};
+
+struct RasterPlan {
+    RasterForm form;
+    const char *error;          // Error: the message (a format that may take MAX_KEYS)
+    int tw, strips;             // strip width of the packed-key kernels; strips per image of the raster launch
+    int twp, nwv, nb;           // bit planes: strip width (32-padded), waves per workgroup, index bits,
+    size_t lds;                 // LDS per workgroup,
+    bool four_per_cu, persist;  // the MINWG = 4 instantiation (one workgroup per item) instead of MINWG = 3, a persistent launch over the queues
+    int64_t grid, caps;         // workgroups of the raster launch; faces per list (Split: per camera, Binned: per strip)
+    SplitLayout ws;             // Split: the workspace layout; Binned: the strip lists at ws.lists, their counts at 0
+    int tws, lw; size_t lds_s;  // Split: strip width, waves and LDS per workgroup of K3r
+};
+
+// A pure function of the call's shape and the knobs: no HIP call, no global.  tests/test_raster_plan.py pins its choices.
+RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
+    RasterPlan p{};
+    const int res = in.res, full = (res + 31) & ~31;
+    p.tw = strip_width(res, k);
+    p.strips = (res + p.tw - 1) / p.tw;
+    p.grid = in.n_img * p.strips;
+    // fastest path: bit planes, when the scene uses at most MAX_KEYS distinct keys and the caller listed the actors' keys
+    if ((in.keys_listed || !(in.actors || in.extra)) && in.n_keys > 0 && !(k.debug & TDS_RASTER_DBG_NO_BITS)) {
+        auto lds_of = [&](int twp, int nwv) { return bits_lds_bytes(in.n_keys, res, twp, nwv, in.out_mode); };
+        // strip width: the whole (32-padded) image if the planes fit 64 KiB, else the widest multiple of 32 that does
+        int twp = full;
+        while (twp > 32 && (size_t)in.n_keys * res * (twp / 8) > 64 * 1024) twp -= 32;
+        // ... in strips of EQUAL width (nine keys at 256 x 256: 192 + 64 columns left the second strip's workgroups a third of the work and the first
+        // one's two per CU -- 10.4 ms; 128 + 128 at three per CU: profiles/r06_more_keys.log)
+        // and, where one more strip lets three workgroups share a CU instead of two, in one more (ten keys: 3 x 96 columns).
+        if (twp < full && !(k.debug & TDS_RASTER_DBG_WIDEST_STRIPS)) {
+            const int n_strips = (res + twp - 1) / twp;
+            auto equal_width = [&](int n) { return (((res + n - 1) / n) + 31) & ~31; };
+            twp = equal_width(n_strips);
+            if (lds_of(twp, k.bits_waves) > 52 * 1024 && equal_width(n_strips + 1) >= 64 && lds_of(equal_width(n_strips + 1), k.bits_waves) <= 52 * 1024 &&
+                !(k.debug & TDS_RASTER_DBG_NO_EXTRA_STRIP))
+                twp = equal_width(n_strips + 1);
+        }
+        int nwv = k.bits_waves;
+        // Three workgroups per CU need at most 52 KiB each (160 KiB of LDS, allocated in 2 KiB steps): five keys at 256 x 256 just fit.
+        // A whole image that does not (six keys and more: two agent types, traffic lights, waypoints) -- measured at B = 1024 x 64, 256 x 256,
+        // six / seven keys, float32 | uint8 ms (profiles/r06_more_keys.log):
+        //     two half-image strips, four 128-VGPR workgroups per CU (each strip scans the grid for itself)   7.79 / 7.86 | 6.88 / 6.98
+        //     the whole image, two 4-wave workgroups per CU (persistent)                                       7.62 / 7.71 | 6.90 / 6.99
+        //     the whole image, two 8-WAVE workgroups per CU (sixteen waves per CU instead of eight)            7.61 / 7.63 | 6.25 / 6.32
+        // so: eight waves on the whole image where two such workgroups fit a CU (80 KiB each: up to seven keys at 256 x 256), else half strips
+        // (eight keys: 7.72 against 7.75 for the whole image in 4-wave workgroups; five keys at 320 x 320: 2.76 against 2.84; and differentiable
+        // calls, whose index slices the 4-wave kernel writes).  Eight waves also rule out the split form below (uint8, 192 - 216 px, 8 - 10 keys).
+        if (twp == full && twp >= 128 && lds_of(twp, nwv) > 52 * 1024 && !(k.debug & TDS_RASTER_DBG_WHOLE_4WAVES)) {
+            const int half = ((twp / 2) + 31) & ~31;
+            if (nwv == 4 && !in.want_slices && lds_of(twp, 8) <= 80 * 1024 && !(k.debug & TDS_RASTER_DBG_NO_8WAVES)) nwv = 8;
+            else if (lds_of(half, nwv) <= 52 * 1024) twp = half;
+        }
+        if (k.force_tw >= 32 && k.force_tw < twp) twp = k.force_tw;     // tuning hook
+        if (lds_of(twp, nwv) <= 150 * 1024) {
+            p.form = RasterForm::Bits; p.twp = twp; p.nwv = nwv; p.nb = bits_index_bits(in.n_keys); p.lds = lds_of(twp, nwv);
+            p.strips = (res + twp - 1) / twp; p.grid = in.n_img * p.strips;
+            // differentiable calls: float32, four waves; the instantiation that also stores the index slices
+            if (in.want_slices && nwv != 4) { p.form = RasterForm::Error; p.error = "tds_raster_scene: index slices need the 4-wave bit-plane kernel"; return p; }
+            // ---- the split form (K3s + K3r) where the launch is not bound by the write stream (where it pays: the sweep beside SPLIT_MAX_RES_*) ----
+            const bool f32 = in.out_mode == TDS_OUT_F32;
+            bool split = !in.want_slices && nwv == 4 && in.workspace_bytes > 0 && split_serves(res, f32);
+            if (k.debug & TDS_RASTER_DBG_NO_SPLIT) split = false;
+            if (k.debug & TDS_RASTER_DBG_SPLIT) split = !in.want_slices && nwv == 4 && in.workspace_bytes > 0;
+            if (split) p.ws = split_layout(in.n_img, -1, in.workspace_bytes);
+            if (split && p.ws.caps >= 128) {
+                // strip width of K3r: the widest multiple of 32 columns whose workgroup stays within the LDS budget (four workgroups per CU);
+                // waves: two up to 104 x 104 float32 / 128 x 128 uint8 pixels of a strip, four above (the sweep is DESIGN_HISTORY.md, appendix R7)
+                int lw = k.list_waves, tws = full;
+                if (lw == 0) lw = (int64_t)res * tws <= (f32 ? 104 * 104 : 128 * 128) ? 2 : 4;
+                while (tws > 32 && lds_of(tws, lw) > (size_t)k.list_lds_kb * 1024) tws -= 32;
+                // (more keys than the sweep's five can push a large image over the LDS budget: K3r in several strips per camera loses to
+                // the fused kernel from about 160 x 160 on -- uint8 224: 7.35 against 4.94 ms -- unless the testing build forces the form)
+                const bool narrowed = tws < full && res >= 160 && !(k.debug & TDS_RASTER_DBG_SPLIT);
+                if (lds_of(tws, lw) <= 150 * 1024 && !narrowed) { p.form = RasterForm::Split; p.tws = tws; p.lw = lw; p.lds_s = lds_of(tws, lw); p.caps = p.ws.caps; }
+            }
+            // the instantiations for three workgroups per CU are persistent launches: their workgroups take (camera, strip) items from per-XCD
+            // queues (see claim_work); the others get one workgroup per item, and so do all without a workspace (there is no queue).  The launch
+            // over the cameras K3s marked (normally none) takes its items from a queue: a persistent instantiation.
+            p.four_per_cu = nwv == 4 && !in.want_slices && p.form != RasterForm::Split && p.lds <= 40 * 1024 && !(k.debug & TDS_RASTER_DBG_MINWG3);
+            p.persist = nwv == 4 && !p.four_per_cu && in.workspace_bytes > 0;
+            if (p.persist) p.grid = std::min(p.form == RasterForm::Split ? 512 : p.grid, resident_workgroups(in.cus, p.lds, k));
+            return p;
+        }
+    }
+    if (in.want_slices) {
+        p.form = RasterForm::Error; p.error = "tds_raster_scene: index slices are produced by the bit-plane kernel only (at most %d distinct keys, listed by the caller)";
+        return p;
+    }
+    // general path: bin once per camera (K3a), then rasterise per strip from the lists (K3b)
+    if (in.workspace_bytes > 0 && !(k.debug & TDS_RASTER_DBG_NO_BINNED) && p.strips <= MAX_STRIPS) {
+        int64_t caps = std::min<int64_t>((in.workspace_bytes / p.grid - (int64_t)sizeof(uint32_t)) / (int64_t)sizeof(uint4), 4096);
+        if (caps >= 64) {
+            p.ws.lists = (p.grid * (int64_t)sizeof(uint32_t) + 255) & ~(int64_t)255;
+            if (p.ws.lists + p.grid * caps * (int64_t)sizeof(uint4) > in.workspace_bytes) --caps;
+            p.form = RasterForm::Binned; p.caps = caps; return p;
+        }
+    }
+    p.form = RasterForm::Fused; return p;
 }
+
+// (auto: instantiated where they are called, so the kernels are instantiated -- and laid out in the code object -- in the order they are named)
+template <int N> using IntC = std::integral_constant<int, N>;
+template <class F> auto with_nb(int nb, F &&f) { if (nb == 2) f(IntC<2>()); else if (nb == 3) f(IntC<3>()); else f(IntC<4>()); }
+template <class F> auto with_tw(int tw, F &&f) { if (tw == 64) f(IntC<64>()); else if (tw == 32) f(IntC<32>()); else if (tw == 16) f(IntC<16>()); else f(IntC<8>()); }
+template <class F> auto with_out(int out_mode, F &&f) { if (out_mode == TDS_OUT_F32) f(float()); else f(uint8_t()); }
+// the scene kernels take SceneArgs where there are no per-camera triangles, else SceneArgsEx
+template <class F> auto with_args(const SceneArgsEx &a, F &&f) { if (a.K == 0) f(static_cast<const SceneArgs &>(a)); else f(a); }
+template <typename... P, typename... A>
+void launch(void (*kern)(P...), int64_t grid, int block, size_t lds, hipStream_t stream, const A &...args) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, stream, args...);
+}
+
 }  // namespace
+
+#ifdef TDS_TESTING
+// ---- testing build only (include/tdship.h, section "testing hooks"): absent from libtdship.so --------------------------------
+// force the strip width (0 = automatic)
+TDS_EXPORT int tds_raster_set_strip_width(int tw) {
+    TDS_CHECK_ARG(tw == 0 || tw == 8 || tw == 16 || tw == 32 || tw == 64 || tw == 96 || tw == 128, "strip width must be 0, 8, 16, 32, 64, 96 or 128");
+    g_knobs.force_tw = tw;
+    return TDS_OK;
+}
+
+// waves per workgroup of the bit-plane kernel (4 or 8)
+TDS_EXPORT int tds_raster_set_bits_waves(int n) {
+    TDS_CHECK_ARG(n == 4 || n == 8, "waves per workgroup must be 4 or 8");
+    g_knobs.bits_waves = n;
+    return TDS_OK;
+}
+
+// read and reset the work counters of the bit-plane kernel (debug flag TDS_RASTER_DBG_STATS)
+TDS_EXPORT int tds_raster_get_stats(unsigned long long *out16) {
+    TDS_CHECK_ARG(out16, "tds_raster_get_stats: null output");
+    unsigned long long zero[16] = {0};
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stats), sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+
+// K3r (the list rasteriser of the split bit-plane path): the LDS a workgroup may take in KiB, which sets the strip width
+TDS_EXPORT int tds_raster_set_list_lds(int lds_kb) {
+    TDS_CHECK_ARG(lds_kb >= 16 && lds_kb <= 150, "tds_raster_set_list_lds: 16..150 KiB");
+    g_knobs.list_lds_kb = lds_kb;
+    return TDS_OK;
+}
+
+// K3r: waves per workgroup (2 or 4; 0 = chosen by the size of a strip)
+TDS_EXPORT int tds_raster_set_list_waves(int waves) {
+    TDS_CHECK_ARG(waves == 0 || waves == 2 || waves == 4, "tds_raster_set_list_waves: 0, 2 or 4");
+    g_knobs.list_waves = waves;
+    return TDS_OK;
+}
+
+// ablation switches, see CommonArgs::debug
+TDS_EXPORT int tds_raster_set_debug(int flags) {
+    g_knobs.debug = flags;
+    return TDS_OK;
+}
+
+// plan_raster_scene with explicit knobs; workspace_bytes as a caller passes it (the queue tail is cut off here, as in the launch)
+TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices,
+                               int64_t workspace_bytes, int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug,
+                               tds_raster_plan_t *out) {
+    TDS_CHECK_ARG(out && n_img > 0 && res > 0 && res <= 4096 && n_keys >= -1 && n_keys <= MAX_KEYS && cus > 0 && (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8), "tds_raster_plan: bad arguments");
+    const int64_t qoff = queue_offset(workspace_bytes);
+    const PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, qoff < 0 ? 0 : qoff, cus};
+    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug});
+    *out = tds_raster_plan_t{(int)p.form, p.tw, p.strips, p.twp, p.nwv, p.nb, p.nwv == 4 ? (p.four_per_cu ? 4 : 3) : 0, want_slices && p.form == RasterForm::Bits,
+                             p.four_per_cu, p.persist, p.tws, p.lw, (int64_t)p.lds, (int64_t)p.lds_s, p.grid, p.caps, p.ws.counts, p.ws.lists, p.ws.lists3};
+    return TDS_OK;
+}
+
+#endif  // TDS_TESTING
+
+static int common_checks(const char *fn, int64_t n_img, int res, int out_mode, const void *out, int &tw) {
+    TDS_CHECK_ARG(n_img >= 0, "%s: negative image count", fn);
+    TDS_CHECK_ARG(res > 0 && res <= 4096, "%s: resolution %d out of range (1..4096)", fn, res);
+    TDS_CHECK_ARG(out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8, "%s: unknown output mode %d", fn, out_mode);
+    TDS_CHECK_ARG(out || n_img == 0, "%s: null output", fn);
+    tw = strip_width(res, g_knobs);
+    if (tw == 0 || lds_bytes(tw, res) > 160 * 1024) { tds::set_error("%s: resolution %d does not fit the LDS tile", fn, res); return TDS_ELIMIT; }
+    TDS_CHECK_ARG(n_img * ((res + tw - 1) / tw) < ((int64_t)1 << 31), "%s: too many strips", fn);
+    return TDS_OK;
+}
 
 TDS_EXPORT int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes) {
     TDS_CHECK_ARG(bytes, "tds_raster_index_slices_bytes: null output");
@@ -2879,17 +3006,15 @@ TDS_EXPORT int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *by
 TDS_EXPORT int tds_raster_scene_workspace_bytes(int64_t n_img, int res, int64_t *bytes) {
     TDS_CHECK_ARG(bytes, "tds_raster_scene_workspace_bytes: null output");
     TDS_CHECK_ARG(res > 0 && res <= 4096 && n_img >= 0, "tds_raster_scene_workspace_bytes: bad arguments");
-    int tw = (g_force_tw && g_force_tw <= 64) ? g_force_tw : pick_tw(res);
-    *bytes = 0;
-    if (tw != 0 && (res + tw - 1) / tw <= MAX_STRIPS) *bytes = ws_bytes_for(n_img, (res + tw - 1) / tw, DEFAULT_CAPS);
-    // the split bit-plane path: a marker list, a count and a list of LIST_CAPS faces (16 bytes each) per camera
-    // (only where the split form can be chosen for either output type; the testing build can force it anywhere)
-    const int64_t lists = (((n_img + 1) * 4 + 255) & ~(int64_t)255) + ((n_img * 4 + 255) & ~(int64_t)255) + n_img * LIST_CAPS * 16;
+    const int tw = strip_width(res, g_knobs);
+    int64_t lists = 0;
+    if (tw != 0 && (res + tw - 1) / tw <= MAX_STRIPS) lists = n_img * ((res + tw - 1) / tw) * (DEFAULT_CAPS * 16 + 4);
+    // the split bit-plane path, LIST_CAPS faces per camera, where the split form can be chosen for either output type (testing: anywhere)
 #ifndef TDS_TESTING
     if (split_serves(res, true) || split_serves(res, false))
 #endif
-    if (lists > *bytes) *bytes = lists;
-    *bytes = ((*bytes + 63) & ~(int64_t)63) + QUEUE_BYTES + 64;          // + the work queues of a persistent launch, at the end (workspace_queue)
+    lists = std::max(lists, split_layout(n_img, LIST_CAPS).lists3);
+    *bytes = with_queue_tail(lists);
     return TDS_OK;
 }
 
@@ -2903,8 +3028,8 @@ TDS_EXPORT int tds_raster_scene_workspace_bytes_for(int64_t n_img, int res, int 
 #ifndef TDS_TESTING
     if (split_serves(res, out_mode == TDS_OUT_F32))
 #endif
-        lists = (((n_img + 1) * 4 + 255) & ~(int64_t)255) + ((n_img * 4 + 255) & ~(int64_t)255) + n_img * LIST_CAPS * 16;
-    *bytes = ((lists + 63) & ~(int64_t)63) + QUEUE_BYTES + 64;
+        lists = split_layout(n_img, LIST_CAPS).lists3;
+    *bytes = with_queue_tail(lists);
     return TDS_OK;
 }
 
@@ -2965,16 +3090,7 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     TDS_CHECK_ARG(scale > 0.0f, "tds_raster_scene: scale must be positive");
     TDS_CHECK_ARG(workspace_bytes >= 0 && (workspace || workspace_bytes == 0), "tds_raster_scene: bad workspace");
     TDS_CHECK_ARG(workspace == nullptr || ((uintptr_t)workspace & 15) == 0, "tds_raster_scene: the workspace must be 16-byte aligned");
-    uint32_t *const ws_queue = workspace_queue(workspace, workspace_bytes);          // the tail of the workspace: work queues of a persistent launch
-    SceneArgsEx a;
-    a.map = ms.one; a.views = ms.views; a.scene_map = ms.scene_map; a.state = (const float4 *)state; a.agent_sc = (const float2 *)agent_sc; a.tmpl = (const float2 *)tmpl;
-    a.actor_key = actor_key; a.mask = mask; a.N = (int)N; a.Nc = (int)Nc; a.key_per_cam = actor_key_per_camera ? 1 : 0;
     TDS_CHECK_ARG(n_extra >= 0 && n_extra < (1 << 20) && (n_extra == 0 || (extra_tri && extra_key)), "tds_raster_scene: bad per-camera triangle arrays");
-    a.extra_tri = extra_tri; a.extra_key = extra_key; a.K = (int)n_extra;
-    CommonArgs cm;
-    cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
-    cm.strips = (res + tw - 1) / tw; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = TDS_DBG(g_debug);
-    cm.no_trim = (aux && (aux->flags & TDS_RASTER_NO_TRIM)) ? 1 : 0;
     const bool want_slices = aux && aux->index_slices;
     if (want_slices) {
         int64_t need = 0;
@@ -2983,190 +3099,85 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
         TDS_CHECK_ARG(aux->index_slices_bytes >= need, "tds_raster_scene: index slices buffer too small (%lld < %lld bytes)",
                       (long long)aux->index_slices_bytes, (long long)need);
     }
-    // fastest path: bit planes, when the scene uses at most MAX_KEYS distinct keys and the caller listed the actors' keys
-    if (((N == 0 && n_extra == 0) || (actor_keys && n_actor_keys > 0)) && ms.n_uniq >= 0 && !(TDS_DBG(g_debug) & 64)) {
-        KeyTable kt;
-        kt.n = 0;
-        bool ok = true;
-        auto add = [&](uint32_t key) {
-            for (int i = 0; i < kt.n; ++i) if (kt.key[i] == key) return;
-            if (kt.n == MAX_KEYS) { ok = false; return; }
-            kt.key[kt.n++] = key;
-        };
-        for (int i = 0; i < ms.n_uniq; ++i) add(ms.uniq_keys[i]);
-        for (int i = 0; i < ((N > 0 || n_extra > 0) ? n_actor_keys : 0); ++i) add(actor_keys[i]);
-        for (int i = kt.n; i < 16; ++i) kt.key[i] = 0xffffffffu;
-        if (ok && kt.n > 0) {
-            for (int i = 1; i < kt.n; ++i)                                   // ascending (insertion sort)
-                for (int j = i; j > 0 && kt.key[j - 1] > kt.key[j]; --j) { uint32_t t = kt.key[j]; kt.key[j] = kt.key[j - 1]; kt.key[j - 1] = t; }
-            // strip width: the whole (32-padded) image if the planes fit 64 KiB, else the widest multiple of 32 that does
-            int twp = (res + 31) & ~31;
-            while (twp > 32 && (size_t)kt.n * res * (twp / 8) > 64 * 1024) twp -= 32;
-            // ... in strips of EQUAL width (nine keys at 256 x 256: 192 + 64 columns left the second strip's workgroups a third of the work and the first
-            // one's two per CU -- 10.4 ms; 128 + 128 at three per CU: profiles/r06_more_keys.log)
-            // and, where one more strip lets three workgroups share a CU instead of two, in one more (ten keys: 3 x 96 columns).
-            if (twp < ((res + 31) & ~31) && !(TDS_DBG(g_debug) & 1048576)) {      // (1048576: testing, the widest strips that fit)
-                int n_strips = (res + twp - 1) / twp;
-                auto equal_width = [&](int n) { return (((res + n - 1) / n) + 31) & ~31; };
-                twp = equal_width(n_strips);
-                if (bits_lds_bytes(kt.n, res, twp, g_bits_waves, out_mode) > 52 * 1024 && equal_width(n_strips + 1) >= 64 &&
-                    bits_lds_bytes(kt.n, res, equal_width(n_strips + 1), g_bits_waves, out_mode) <= 52 * 1024 && !(TDS_DBG(g_debug) & 2097152))      // (2097152: testing, not one more)
-                    twp = equal_width(n_strips + 1);
-            }
-            int nwv = g_bits_waves;
-            // Three workgroups per CU need at most 52 KiB each (160 KiB of LDS, allocated in 2 KiB steps): five keys at 256 x 256 just fit.
-            // A whole image that does not (six keys and more: two agent types, traffic lights, waypoints) -- measured at B = 1024 x 64, 256 x 256,
-            // six / seven keys, float32 | uint8 ms (profiles/r06_more_keys.log):
-            //     two half-image strips, four 128-VGPR workgroups per CU (each strip scans the grid for itself)   7.79 / 7.86 | 6.88 / 6.98
-            //     the whole image, two 4-wave workgroups per CU (persistent)                                       7.62 / 7.71 | 6.90 / 6.99
-            //     the whole image, two 8-WAVE workgroups per CU (sixteen waves per CU instead of eight)            7.61 / 7.63 | 6.25 / 6.32
-            // so: eight waves on the whole image where two such workgroups fit a CU (80 KiB each: up to seven keys at 256 x 256), else half strips
-            // (eight keys: 7.72 against 7.75 for the whole image in 4-wave workgroups; five keys at 320 x 320: 2.76 against 2.84; and differentiable
-            // calls, whose index slices the 4-wave kernel writes).
-            if (twp == ((res + 31) & ~31) && twp >= 128 && bits_lds_bytes(kt.n, res, twp, nwv, out_mode) > 52 * 1024 && !(TDS_DBG(g_debug) & 262144)) {      // (262144: testing, the whole image in 4-wave workgroups, two per CU)
-                const int half = ((twp / 2) + 31) & ~31;
-                if (nwv == 4 && !want_slices && bits_lds_bytes(kt.n, res, twp, 8, out_mode) <= 80 * 1024 && !(TDS_DBG(g_debug) & 524288)) nwv = 8;          // (524288: testing, never eight waves)
-                else if (bits_lds_bytes(kt.n, res, half, nwv, out_mode) <= 52 * 1024) twp = half;
-            }
-            if (g_force_tw >= 32 && g_force_tw < twp) twp = g_force_tw;     // tuning hook
-            size_t lds = bits_lds_bytes(kt.n, res, twp, nwv, out_mode);
-            if (lds <= 150 * 1024) {
-                CommonArgs cb = cm;
-                cb.strips = (res + twp - 1) / twp;
-                cb.slices = want_slices ? aux->index_slices : nullptr;
-                if (aux) { aux->n_keys = kt.n; aux->index_bits = bits_index_bits(kt.n); for (int i = 0; i < 16; ++i) aux->keys[i] = i < kt.n ? kt.key[i] : 0u; }
-                const int nb = bits_index_bits(kt.n);
-                bool four_per_cu = lds <= 40 * 1024 && !(TDS_DBG(g_debug) & 2048);      // see MINWG (2048: ablation, the 170-VGPR kernel)
-                // ---- the split form (K3s + K3r, above) where the launch is not bound by the write stream: uint8 output, resolutions below 256 ----
-                const uint32_t *only = nullptr;
-                {
-                    const bool f32 = out_mode == TDS_OUT_F32;
-                    // (where the split form pays: the sweep beside SPLIT_MAX_RES_*)
-                    bool split = !want_slices && nwv == 4 && workspace != nullptr && split_serves(res, f32);
-                    if (TDS_DBG(g_debug) & 8192) split = false;                              // testing: the fused kernel everywhere
-                    if (TDS_DBG(g_debug) & 16384) split = !want_slices && nwv == 4 && workspace != nullptr;      // testing: the split form everywhere
-                    const size_t off_counts = (((size_t)n_img + 1) * 4 + 255) & ~(size_t)255;
-                    const size_t off_lists = (off_counts + (size_t)n_img * 4 + 255) & ~(size_t)255;
-                    // a poly record is 20 bytes: 16 in `lists` (flags, P0, P1, P2), 4 in `lists3` (P3)
-                    int64_t caps = split && (size_t)workspace_bytes > off_lists ? (((int64_t)workspace_bytes - (int64_t)off_lists) / (n_img * 20)) & ~(int64_t)3 : 0;
-                    if (caps > 8192) caps = 8192;
-                    if (split && caps >= 128) {
-                        uint32_t *poisoned = (uint32_t *)workspace, *counts = (uint32_t *)((char *)workspace + off_counts);
-                        uint4 *lists = (uint4 *)((char *)workspace + off_lists);
-                        uint32_t *lists3 = (uint32_t *)(lists + (size_t)n_img * (size_t)caps);
-                        // strip width of K3r: the widest multiple of 32 columns whose workgroup stays within the LDS budget (four workgroups per CU)
-                        // waves per workgroup of K3r: by the pixels of a strip (testing hook: g_list_waves)
-                        int lw = g_list_waves;
-                        int tws = (res + 31) & ~31;
-                        // (two waves up to 104 x 104 float32 / 128 x 128 uint8 pixels of a strip, four above: the sweep is DESIGN_HISTORY.md, appendix R7)
-                        if (lw == 0) lw = (int64_t)res * tws <= (f32 ? 104 * 104 : 128 * 128) ? 2 : 4;
-                        while (tws > 32 && bits_lds_bytes(kt.n, res, tws, lw, out_mode) > (size_t)g_list_lds_kb * 1024) tws -= 32;
-                        const size_t lds_s = bits_lds_bytes(kt.n, res, tws, lw, out_mode);
-                        // (more keys than the sweep's five can push a large image over the LDS budget: K3r in several strips per camera loses to
-                        // the fused kernel from about 160 x 160 on -- uint8 224: 7.35 against 4.94 ms -- unless the testing build forces the form)
-                        const bool narrowed = tws < ((res + 31) & ~31) && res >= 160 && !(TDS_DBG(g_debug) & 16384);
-                        if (lds_s <= 150 * 1024 && !narrowed) {
-                            if (aux) { aux->n_keys = kt.n; aux->index_bits = nb; for (int i = 0; i < 16; ++i) aux->keys[i] = i < kt.n ? kt.key[i] : 0u; }
-                            if (tds::zero_async(poisoned, 4, (hipStream_t)stream) != hipSuccess) { tds::set_error("tds_raster_scene: clearing the workspace failed"); return TDS_EHIP; }
-                            CommonArgs cs = cm;
-                            cs.strips = 1; cs.slices = nullptr;
-                            const dim3 sgrid((unsigned)((n_img + SCAN_WAVES - 1) / SCAN_WAVES));
-                            const SceneArgs sbase = a;
-                            auto launch_s = [&](auto kern, const auto &args) { hipLaunchKernelGGL(kern, sgrid, dim3(SCAN_WAVES * 64), 0, (hipStream_t)stream, args, cs, kt, counts, lists, lists3, (int)caps, poisoned); };
-                            if (a.K != 0) launch_s(scan_faces_kernel<SceneArgsEx>, a);
-                            else launch_s(scan_faces_kernel<SceneArgs>, sbase);
-                            TDS_LAUNCH_CHECK("scan_faces_kernel");
-                            CommonArgs cr = cm;
-                            cr.strips = (res + tws - 1) / tws; cr.slices = nullptr;
-                            const dim3 rgrid((unsigned)(n_img * cr.strips));
-                            auto launch_r = [&](auto kern) {
-                                if (lds_s > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-                                hipLaunchKernelGGL(kern, rgrid, dim3(lw * 64), lds_s, (hipStream_t)stream, cr, kt, tws, (const uint32_t *)counts, (const uint4 *)lists, (const uint32_t *)lists3, (int)caps);
-                            };
-#define TDS_LIST_DISPATCH_W(T, W) do { if (nb == 2) launch_r(raster_list_bits_kernel<2, T, W>); else if (nb == 3) launch_r(raster_list_bits_kernel<3, T, W>); else launch_r(raster_list_bits_kernel<4, T, W>); } while (0)
-#define TDS_LIST_DISPATCH(T) do { if (lw == 2) TDS_LIST_DISPATCH_W(T, 2); else TDS_LIST_DISPATCH_W(T, 4); } while (0)
-                            if (f32) TDS_LIST_DISPATCH(float); else TDS_LIST_DISPATCH(uint8_t);
-#undef TDS_LIST_DISPATCH
-#undef TDS_LIST_DISPATCH_W
-                            TDS_LAUNCH_CHECK("raster_list_bits_kernel");
-                            only = poisoned;            // what follows: the fused kernel, over the cameras K3s marked (normally none)
-                        }
-                    }
-                }
-                // the instantiations for three workgroups per CU are persistent launches: their workgroups take (camera, strip) items from per-XCD
-                // queues (see claim_work); the others get one workgroup per item
-                if (only != nullptr) four_per_cu = false;          // the launch over the marked cameras takes its items from a queue: a persistent instantiation
-                // (without a workspace there is no queue: the same kernels then run one workgroup per item)
-                const bool persist = nwv == 4 && (!four_per_cu || cb.slices != nullptr) && ws_queue != nullptr;
-                uint32_t *queue = nullptr;
-                if (persist) {
-                    queue = ws_queue;
-                    if (tds::zero_async(queue, (size_t)QUEUE_BYTES, (hipStream_t)stream) != hipSuccess) { tds::set_error("tds_raster_scene: clearing the work queues failed"); return TDS_EHIP; }
-                }
-                dim3 grid((unsigned)(persist ? persistent_grid(only != nullptr ? 512 : n_img * cb.strips, lds, (hipStream_t)stream) : n_img * cb.strips));
-                const SceneArgs base = a;
-                auto launch_b = [&](auto kern) {            // scenes without per-camera triangles
-                    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(nwv * 64), lds, (hipStream_t)stream, base, cb, kt, twp, queue, only);
-                };
-                auto launch = [&](auto kern) {
-                    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(nwv * 64), lds, (hipStream_t)stream, a, cb, kt, twp, queue, only);
-                };
-#define TDS_BITS_DISPATCH(T)                                                                                                   \
-    do {                                                                                                                       \
-        if (nwv == 4 && four_per_cu && a.K == 0) { if (nb == 2) launch_b(raster_scene_bits_kernel<4, 2, T, SceneArgs, false, 4>); else if (nb == 3) launch_b(raster_scene_bits_kernel<4, 3, T, SceneArgs, false, 4>); else launch_b(raster_scene_bits_kernel<4, 4, T, SceneArgs, false, 4>); } \
-        else if (nwv == 4 && four_per_cu) { if (nb == 2) launch(raster_scene_bits_kernel<4, 2, T, SceneArgsEx, false, 4>); else if (nb == 3) launch(raster_scene_bits_kernel<4, 3, T, SceneArgsEx, false, 4>); else launch(raster_scene_bits_kernel<4, 4, T, SceneArgsEx, false, 4>); } \
-        else if (nwv == 4 && a.K == 0) { if (nb == 2) launch_b(raster_scene_bits_kernel<4, 2, T, SceneArgs>); else if (nb == 3) launch_b(raster_scene_bits_kernel<4, 3, T, SceneArgs>); else launch_b(raster_scene_bits_kernel<4, 4, T, SceneArgs>); } \
-        else if (nwv == 4) { if (nb == 2) launch(raster_scene_bits_kernel<4, 2, T, SceneArgsEx>); else if (nb == 3) launch(raster_scene_bits_kernel<4, 3, T, SceneArgsEx>); else launch(raster_scene_bits_kernel<4, 4, T, SceneArgsEx>); } \
-        else { if (nb == 2) launch(raster_scene_bits_kernel<8, 2, T, SceneArgsEx>); else if (nb == 3) launch(raster_scene_bits_kernel<8, 3, T, SceneArgsEx>); else launch(raster_scene_bits_kernel<8, 4, T, SceneArgsEx>); } \
-    } while (0)
-                if (cb.slices != nullptr) {
-                    // differentiable calls: float32, four waves; the instantiation that also stores the index slices
-                    if (nwv != 4) { tds::set_error("tds_raster_scene: index slices need the 4-wave bit-plane kernel"); return TDS_ELIMIT; }
-                    if (a.K == 0) { if (nb == 2) launch_b(raster_scene_bits_kernel<4, 2, float, SceneArgs, true>); else if (nb == 3) launch_b(raster_scene_bits_kernel<4, 3, float, SceneArgs, true>); else launch_b(raster_scene_bits_kernel<4, 4, float, SceneArgs, true>); }
-                    else { if (nb == 2) launch(raster_scene_bits_kernel<4, 2, float, SceneArgsEx, true>); else if (nb == 3) launch(raster_scene_bits_kernel<4, 3, float, SceneArgsEx, true>); else launch(raster_scene_bits_kernel<4, 4, float, SceneArgsEx, true>); }
-                } else if (out_mode == TDS_OUT_F32) TDS_BITS_DISPATCH(float); else TDS_BITS_DISPATCH(uint8_t);
-#undef TDS_BITS_DISPATCH
-                TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
-                return TDS_OK;
-            }
+    // the key table: the distinct keys of the map(s) and, where there are agents or per-camera triangles, the actor keys the caller listed; ascending
+    const bool listed = actor_keys && n_actor_keys > 0;
+    KeyTable kt; kt.n = 0;
+    bool ok = ms.n_uniq >= 0;
+    auto add = [&](uint32_t key) {
+        for (int i = 0; i < kt.n; ++i) if (kt.key[i] == key) return;
+        if (kt.n == MAX_KEYS) ok = false; else kt.key[kt.n++] = key;
+    };
+    for (int i = 0; i < ms.n_uniq; ++i) add(ms.uniq_keys[i]);
+    for (int i = 0; i < (listed && (N > 0 || n_extra > 0) ? n_actor_keys : 0); ++i) add(actor_keys[i]);
+    for (int i = kt.n; i < 16; ++i) kt.key[i] = 0xffffffffu;
+    for (int i = 1; i < kt.n; ++i)                                   // insertion sort
+        for (int j = i; j > 0 && kt.key[j - 1] > kt.key[j]; --j) { uint32_t t = kt.key[j]; kt.key[j] = kt.key[j - 1]; kt.key[j - 1] = t; }
+    // the plan (the work queues of a persistent launch take the tail of the workspace: what the lists may use ends before them)
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t qoff = workspace ? queue_offset(workspace_bytes) : -1;
+    const PlanInput in = {n_img, res, out_mode, ok ? kt.n : -1, listed, N > 0, n_extra > 0, want_slices, qoff < 0 ? 0 : qoff, launch_cus(s)};
+    const RasterPlan p = plan_raster_scene(in, g_knobs);
+    if (aux && p.nb) { aux->n_keys = kt.n; aux->index_bits = p.nb; for (int i = 0; i < 16; ++i) aux->keys[i] = i < kt.n ? kt.key[i] : 0u; }
+    if (p.form == RasterForm::Error) { tds::set_error(p.error, MAX_KEYS); return TDS_ELIMIT; }
+    SceneArgsEx a;
+    a.map = ms.one; a.views = ms.views; a.scene_map = ms.scene_map; a.state = (const float4 *)state; a.agent_sc = (const float2 *)agent_sc; a.tmpl = (const float2 *)tmpl;
+    a.actor_key = actor_key; a.mask = mask; a.N = (int)N; a.Nc = (int)Nc; a.key_per_cam = actor_key_per_camera ? 1 : 0;
+    a.extra_tri = extra_tri; a.extra_key = extra_key; a.K = (int)n_extra;
+    CommonArgs cm;
+    cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
+    cm.strips = p.strips; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = g_knobs.debug;
+    cm.no_trim = (aux && (aux->flags & TDS_RASTER_NO_TRIM)) ? 1 : 0;
+    char *const ws = (char *)workspace;
+    if (p.form == RasterForm::Split || p.form == RasterForm::Bits) {
+        const uint32_t *only = nullptr;              // Split: the bit-plane launch runs over the cameras K3s marked (normally none)
+        if (p.form == RasterForm::Split) {
+            uint32_t *poisoned = (uint32_t *)ws, *counts = (uint32_t *)(ws + p.ws.counts), *lists3 = (uint32_t *)(ws + p.ws.lists3);
+            uint4 *lists = (uint4 *)(ws + p.ws.lists);
+            if (tds::zero_async(poisoned, 4, s) != hipSuccess) { tds::set_error("tds_raster_scene: clearing the workspace failed"); return TDS_EHIP; }
+            CommonArgs cs = cm, cr = cm;
+            cs.strips = 1; cr.strips = (res + p.tws - 1) / p.tws;
+            auto scan = [&](auto kern, const auto &args) { launch(kern, (n_img + SCAN_WAVES - 1) / SCAN_WAVES, SCAN_WAVES * 64, 0, s, args, cs, kt, counts, lists, lists3, (int)p.caps, poisoned); };
+            if (a.K != 0) scan(scan_faces_kernel<SceneArgsEx>, a); else scan(scan_faces_kernel<SceneArgs>, (const SceneArgs &)a);
+            TDS_LAUNCH_CHECK("scan_faces_kernel");
+            auto go = [&](auto kern) { launch(kern, n_img * cr.strips, p.lw * 64, p.lds_s, s, cr, kt, p.tws, (const uint32_t *)counts, (const uint4 *)lists, (const uint32_t *)lists3, (int)p.caps); };
+            with_out(out_mode, [&](auto t) {
+                if (p.lw == 2) with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 2>); });
+                else with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 4>); });
+            });
+            TDS_LAUNCH_CHECK("raster_list_bits_kernel");
+            only = poisoned;
         }
+        uint32_t *const queue = p.persist ? (uint32_t *)(ws + qoff) : nullptr;
+        if (p.persist && tds::zero_async(queue, (size_t)QUEUE_BYTES, s) != hipSuccess) { tds::set_error("tds_raster_scene: clearing the work queues failed"); return TDS_EHIP; }
+        CommonArgs cb = cm;
+        cb.slices = want_slices ? aux->index_slices : nullptr;
+        auto go = [&](auto kern, const auto &args) { launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cb, kt, p.twp, queue, only); };
+        if (want_slices)                // differentiable calls (float32, four waves): the instantiation that also stores the index slices
+            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, float, std::decay_t<decltype(args)>, true>, args); }); });
+        else
+            with_out(out_mode, [&](auto t) {
+                using T = decltype(t);
+                if (p.four_per_cu)
+                    with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>, false, 4>, args); }); });
+                else if (p.nwv == 4)
+                    with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>>, args); }); });
+                else
+                    with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<8, nb, T, SceneArgsEx>, a); });
+            });
+        TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
+        return TDS_OK;
     }
-    if (want_slices) {
-        tds::set_error("tds_raster_scene: index slices are produced by the bit-plane kernel only (at most %d distinct keys, listed by the caller)", MAX_KEYS);
-        return TDS_ELIMIT;
+    if (p.form == RasterForm::Binned) {
+        uint32_t *counts = (uint32_t *)ws; uint4 *lists = (uint4 *)(ws + p.ws.lists);
+        launch(bin_faces_kernel, (n_img + BIN_WAVES - 1) / BIN_WAVES, BIN_WAVES * 64, 0, s, a, cm, p.tw, counts, lists, (int)p.caps);
+        TDS_LAUNCH_CHECK("bin_faces_kernel");
+        with_out(out_mode, [&](auto t) { with_tw(p.tw, [&](auto tw) {
+            launch(raster_scene_list_kernel<tw, decltype(t)>, p.grid, RBLOCK, lds_bytes(tw, res), s, a, cm, (const uint32_t *)counts, (const uint4 *)lists, (int)p.caps);
+        }); });
+        TDS_LAUNCH_CHECK("raster_scene_list_kernel");
+        return TDS_OK;
     }
-    // general path: bin once per camera (K3a), then rasterise per strip from the lists (K3b)
-    if (workspace && !(TDS_DBG(g_debug) & 32) && cm.strips <= MAX_STRIPS) {
-        int64_t caps = (workspace_bytes / (n_img * cm.strips) - (int64_t)sizeof(uint32_t)) / (int64_t)sizeof(uint4);
-        if (caps > 4096) caps = 4096;
-        if (caps >= 64) {
-            uint32_t *counts = (uint32_t *)workspace;
-            size_t off = ((size_t)n_img * cm.strips * sizeof(uint32_t) + 255) & ~(size_t)255;
-            if ((int64_t)(off + (size_t)n_img * cm.strips * caps * sizeof(uint4)) > workspace_bytes) --caps;
-            uint4 *lists = (uint4 *)((char *)workspace + off);
-            hipLaunchKernelGGL(bin_faces_kernel, dim3((unsigned)((n_img + BIN_WAVES - 1) / BIN_WAVES)), dim3(BIN_WAVES * 64), 0,
-                               (hipStream_t)stream, a, cm, tw, counts, lists, (int)caps);
-            TDS_LAUNCH_CHECK("bin_faces_kernel");
-            size_t lds = lds_bytes(tw, res);
-            dim3 grid((unsigned)(n_img * cm.strips));
-            auto launch = [&](auto kern) {
-                if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(kern, grid, dim3(RBLOCK), lds, (hipStream_t)stream, a, cm, (const uint32_t *)counts, (const uint4 *)lists, (int)caps);
-            };
-            if (out_mode == TDS_OUT_F32) {
-                if (tw == 64) launch(raster_scene_list_kernel<64, float>); else if (tw == 32) launch(raster_scene_list_kernel<32, float>);
-                else if (tw == 16) launch(raster_scene_list_kernel<16, float>); else launch(raster_scene_list_kernel<8, float>);
-            } else {
-                if (tw == 64) launch(raster_scene_list_kernel<64, uint8_t>); else if (tw == 32) launch(raster_scene_list_kernel<32, uint8_t>);
-                else if (tw == 16) launch(raster_scene_list_kernel<16, uint8_t>); else launch(raster_scene_list_kernel<8, uint8_t>);
-            }
-            TDS_LAUNCH_CHECK("raster_scene_list_kernel");
-            return TDS_OK;
-        }
-    }
-    TDS_LAUNCH_RASTER(raster_scene_kernel, a);
+    with_out(out_mode, [&](auto t) { with_tw(p.tw, [&](auto tw) { launch(raster_scene_kernel<tw, decltype(t)>, p.grid, RBLOCK, lds_bytes(tw, res), s, a, cm); }); });
     TDS_LAUNCH_CHECK("raster_scene_kernel");
     return TDS_OK;
 }
@@ -3190,9 +3201,11 @@ TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int
     for (int i = 1; i < n_levels; ++i) TDS_CHECK_ARG(levels[i] < levels[i - 1], "tds_raster_mesh: levels must be strictly descending");
     CommonArgs cm;
     cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
-    cm.strips = (res + tw - 1) / tw; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = TDS_DBG(g_debug);
+    cm.strips = (res + tw - 1) / tw; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (flags & TDS_RASTER_NO_TRIM) ? 1 : 0;
-    TDS_LAUNCH_RASTER(raster_mesh_kernel, a);
+    with_out(out_mode, [&](auto t) { with_tw(tw, [&](auto w) {
+        launch(raster_mesh_kernel<w, decltype(t)>, n_img * cm.strips, RBLOCK, lds_bytes(w, res), (hipStream_t)stream, a, cm);
+    }); });
     TDS_LAUNCH_CHECK("raster_mesh_kernel");
     return TDS_OK;
 }
