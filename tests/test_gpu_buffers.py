@@ -93,7 +93,7 @@ def test_the_workspace_is_sized_for_the_kernels_that_run():
     from torchdrivesim_amd import _ops
     from torchdrivesim_amd.utils import Resolution
     sim, actions, _ = bench.build_simulator(4, 16, torch.device(DEV), seed=2)
-    keys = sim._scene()['maps'][0][0].face_keys()
+    keys = sim._scene()['map'].face_keys()
     assert keys is not None and 1 <= len(keys) <= 8 and len(set(keys)) == len(keys)
     _ops._workspaces.clear()
     img = sim.render_egocentric(res=Resolution(256, 256), fov=35.0)

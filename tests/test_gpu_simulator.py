@@ -322,7 +322,7 @@ def test_mixed_maps_batch_builds_one_map_per_distinct_mesh(oracle):
     n0 = _ops.map_creations
     img = sim.render_egocentric(res=Resolution(res, res), fov=fov)
     assert _ops.map_creations == n0 + 2, 'one rendering map per DISTINCT mesh'
-    smap = sim._scene()['maps'][0][0]
+    smap = sim._scene()['map']
     assert isinstance(smap, _ops.StaticMapSet) and len(smap.maps) == 2
     np.testing.assert_array_equal(smap.scene_map.cpu().numpy(), order if order[0] == 0 else 1 - order)       # groups are numbered by first occurrence
     off = sim.compute_offroad()

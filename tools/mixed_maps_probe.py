@@ -40,11 +40,11 @@ def main():
     out['town01'] = time_render(sim, buf)
     # the same scenes through a set of two maps with identical content
     scene = sim._scene()
-    one = scene['maps'][0][0]
+    one = scene['map']
     gen = sim.birdview_mesh_generator
     lv = one.levels
     twin = sim.renderer.make_static_map(gen.background_mesh[0:1], lv, device=dev)
-    scene['maps'][0] = (_ops.StaticMapSet([one, twin], torch.arange(B, dtype=torch.int32) % 2), None)
+    scene['map'] = _ops.StaticMapSet([one, twin], torch.arange(B, dtype=torch.int32) % 2)
     out['town01_as_set'] = time_render(sim, buf)
     del sim, scene
     sim, _, _ = bench.build_simulator(B, A, dev, seed=4321, mixed=True)

@@ -24,6 +24,11 @@ def _c(t, dtype=f32):
     return t.contiguous()
 
 
+def _u8(mask):
+    """a mask as the uint8 bytes the kernels read (a dense bool tensor is reinterpreted, not copied)"""
+    return mask.contiguous().view(u8) if mask.dtype == torch.bool else _c(mask, u8)
+
+
 def heading_sc(psi):
     """[sin, cos] of headings with torch on the tensor's device -- exactly where the reference calls torch.sin/cos
     (simulator.py:940, utils.py:40-53, _iou_utils.py:290-291).  psi: (...,) -> (..., 2); differentiable."""
@@ -222,7 +227,7 @@ def metric_sc(boxes, metric):
 
 def collision_forward(boxes, sc, present, n_exposed, metric, want_overlap=False, want_partner=False):
     boxes, sc = _c(boxes), _c(sc)
-    present = _c(present, u8) if present.dtype != torch.bool else present.contiguous().view(u8)
+    present = _u8(present)
     B, N = boxes.shape[:2]
     A = N if n_exposed is None else int(n_exposed)
     out = torch.empty((B, A), dtype=f32, device=boxes.device)
@@ -239,7 +244,7 @@ def overlap_count(boxes, present, sc=None):
     the number of other present agents whose rectangle shares area with the agent's.  NaNs are scrubbed to 0 first."""
     boxes = torch.nan_to_num(_c(boxes.detach()), nan=0.0)
     sc = heading_sc(boxes[..., 4]) if sc is None else _c(sc)
-    present = _c(present, u8) if present.dtype != torch.bool else present.contiguous().view(u8)
+    present = _u8(present)
     B, A = boxes.shape[:2]
     out = torch.empty((B, A), dtype=torch.float64, device=boxes.device)
     nat.call('tds_overlap_count_f32', boxes.device, nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(present, u8, 'present'),
@@ -263,7 +268,7 @@ class _Collision(torch.autograd.Function):
         B, N = boxes.shape[:2]
         A = N if n_exposed is None else int(n_exposed)
         gout = _c(gout)
-        pres = _c(present, u8) if present.dtype != torch.bool else present.contiguous().view(u8)
+        pres = _u8(present)
         gb, gsc = torch.empty_like(boxes), torch.empty_like(sc)
         nat.call('tds_collision_bwd_f32', boxes.device, nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'),
                  nat.dev_ptr(pres, u8, 'present'), nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gb, f32, 'gb'), nat.dev_ptr(gsc, f32, 'gsc'),
@@ -316,7 +321,7 @@ def occlusion_mask(state, size, present, n_exposed):
     present (B,E) -> (B,A,E) bool, True = present and in line of sight of ego a"""
     B, E = present.shape
     state, size = _c(state.detach()), _c(size.detach())
-    p8 = present.contiguous().view(u8) if present.dtype == torch.bool else _c(present, u8)
+    p8 = _u8(present)
     out = torch.empty((B, int(n_exposed), E), dtype=u8, device=state.device)
     nat.call('tds_occlusion_mask_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(size, f32, 'size'), nat.dev_ptr(p8, u8, 'present'),
              nat.dev_ptr(out, u8, 'out'), B, int(n_exposed), E, nat.stream_ptr(state.device))
@@ -329,8 +334,35 @@ def quantise_colors(attrs):
     return (q[..., 0] << 16) | (q[..., 1] << 8) | q[..., 2]
 
 
-class StaticMap:
+class _Handle:
+    """A native object of the library (`_h`, on `self.device`) that the entry point named by `_destroy_call` destroys: at close(), or when
+    the wrapper goes."""
+    _destroy_call = None
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise RuntimeError(f'{type(self).__name__} was destroyed')
+        return self._h
+
+    def _destroy(self):
+        if getattr(self, '_h', None) is not None:
+            h, self._h = self._h, None
+            nat.call(self._destroy_call, self.device, h)
+
+    def close(self):
+        self._destroy()
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+
+class StaticMap(_Handle):
     """Device-resident static mesh + uniform grid (tds_map_t).  Built once per map and per device from HOST arrays."""
+    _destroy_call, _keys_call = 'tds_map_destroy', 'tds_map_keys'
 
     def __init__(self, verts, faces, face_z=None, face_rgb=None, levels=None, device='cuda', cell_size=0.0):
         verts = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype=np.float32).reshape(-1, 2)
@@ -351,17 +383,12 @@ class StaticMap:
                  0 if lv is None else len(lv), float(cell_size), ctypes.byref(handle))
         self._h = handle
 
-    @property
-    def handle(self):
-        if self._h is None:
-            raise RuntimeError('StaticMap was destroyed')
-        return self._h
-
     def face_keys(self):
-        """distinct face keys of the map (None: more than 64) -- with the actors' keys they decide which rasteriser serves a launch"""
+        """distinct face keys of the map, or over the maps of a set (None: more than 64) -- with the actors' keys they decide which
+        rasteriser serves a launch"""
         if not hasattr(self, '_face_keys'):
             buf, n = (ctypes.c_uint32 * 64)(), ctypes.c_int(0)
-            nat.call('tds_map_keys', self.device, self.handle, ctypes.cast(buf, ctypes.c_void_p), 64, ctypes.byref(n))
+            nat.call(self._keys_call, self.device, self.handle, ctypes.cast(buf, ctypes.c_void_p), 64, ctypes.byref(n))
             self._face_keys = None if n.value < 0 else [int(buf[i]) for i in range(n.value)]
         return self._face_keys
 
@@ -375,22 +402,11 @@ class StaticMap:
         """1-based painter rank of a rendering level (larger = drawn later = on top)"""
         return self.levels.index(float(level)) + 1
 
-    def _destroy(self):
-        if getattr(self, '_h', None) is not None:
-            h, self._h = self._h, None
-            nat.call('tds_map_destroy', self.device, h)
-
     def close(self):
         """destroy the device map now -- unless the process-wide cache handed it out (`shared`): other simulators may hold it, and it is
         destroyed when the last holder drops it"""
         if not getattr(self, 'shared', False):
             self._destroy()
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
 
 
 #: how many tds_map_create calls this process has made (tests count them: one per DISTINCT mesh, none for a batch operation)
@@ -516,9 +532,26 @@ map_cache = MapCache()
 atexit.register(map_cache.clear)
 
 
-class StaticMapSet:
+def map_per_distinct_row(tensors, prepare):
+    """The device map of a batch of meshes: ONE StaticMap per distinct batch element of the (device) `tensors` (`group_rows`), each taken
+    from the process-wide `map_cache` or built once.  prepare(reps) -> (key, build), called once per batch with the representatives:
+    key(h, rows) is the cache key of the map of the representative whose content hashes are `h` and whose rows are `rows`, build(r) builds
+    the map of batch element r.  Returns a StaticMap when the whole batch shares one mesh, else a StaticMapSet whose `scene_map` says
+    which map scene b uses."""
+    scene_map, reps, hashes = group_rows(tensors)
+    key, build = prepare(reps)
+    maps = []
+    for r, h in zip(reps, hashes):
+        rows = [t[r] for t in tensors]
+        maps.append(map_cache.get(key(h, rows), rows, lambda r=r: build(r)))
+    return maps[0] if len(maps) == 1 else StaticMapSet(maps, torch.from_numpy(scene_map))
+
+
+class StaticMapSet(_Handle):
     """Several StaticMaps of one device (created with the same level table) + which of them every scene of a batch uses: lets one
     launch serve a batch whose scenes have different meshes (tds_mapset_t).  `scene_map`: (B,) int32 device tensor of indices."""
+    _destroy_call, _keys_call = 'tds_mapset_destroy', 'tds_mapset_keys'
+    face_keys = StaticMap.face_keys
 
     def __init__(self, maps, scene_map):
         assert len(maps) > 0
@@ -532,37 +565,8 @@ class StaticMapSet:
         nat.call('tds_mapset_create', self.device, arr, len(self.maps), ctypes.byref(handle))
         self._h = handle
 
-    @property
-    def handle(self):
-        if self._h is None:
-            raise RuntimeError('StaticMapSet was destroyed')
-        return self._h
-
     def rank_of(self, level):
         return self.maps[0].rank_of(level)
-
-    def face_keys(self):
-        """distinct face keys over the maps of the set (None: more than 64)"""
-        if not hasattr(self, '_face_keys'):
-            buf, n = (ctypes.c_uint32 * 64)(), ctypes.c_int(0)
-            nat.call('tds_mapset_keys', self.device, self.handle, ctypes.cast(buf, ctypes.c_void_p), 64, ctypes.byref(n))
-            self._face_keys = None if n.value < 0 else [int(buf[i]) for i in range(n.value)]
-        return self._face_keys
-
-    def select(self, idx):
-        """the same maps for a sub-batch / re-ordered batch"""
-        return StaticMapSet(self.maps, self.scene_map[idx])
-
-    def close(self):
-        if getattr(self, '_h', None) is not None:
-            h, self._h = self._h, None
-            nat.call('tds_mapset_destroy', self.device, h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _agents_per_scene(smap, state):
@@ -577,9 +581,7 @@ def offroad_forward(smap, state, lenwid, sc, present, threshold):
     state, lenwid, sc = _c(state), _c(lenwid), _c(sc)
     n = state.numel() // 4
     out = torch.empty(state.shape[:-1], dtype=f32, device=state.device)
-    pres = None
-    if present is not None:
-        pres = _c(present, u8) if present.dtype != torch.bool else present.contiguous().view(u8)
+    pres = None if present is None else _u8(present)
     if isinstance(smap, StaticMapSet):
         nat.call('tds_offroad_multi_f32', state.device, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map'), _agents_per_scene(smap, state),
                  nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(lenwid, f32, 'lenwid'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(pres, u8, 'present'),
@@ -605,9 +607,7 @@ class _Offroad(torch.autograd.Function):
         state, lenwid, sc = ctx.saved_tensors
         smap, present, threshold = ctx.cfg
         gout = _c(gout)
-        pres = None
-        if present is not None:
-            pres = _c(present, u8) if present.dtype != torch.bool else present.contiguous().view(u8)
+        pres = None if present is None else _u8(present)
         gs, gl, gsc = torch.empty_like(state), torch.empty_like(lenwid), torch.empty_like(sc)
         if isinstance(smap, StaticMapSet):
             nat.call('tds_offroad_multi_bwd_f32', state.device, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map'), _agents_per_scene(smap, state),
@@ -885,7 +885,7 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
         state, agent_sc, tmpl = _c(state), _c(agent_sc), _c(tmpl)
         actor_key = _c(actor_key, i32)
         assert tuple(actor_key.shape) in ((B, N, 2), (B, Nc, N, 2)), 'actor_key must be (B,N,2) or (B,Nc,N,2)'
-        mask = mask.contiguous().view(u8) if mask.dtype == torch.bool else _c(mask, u8)
+        mask = _u8(mask)
     assert out_dtype in (torch.float32, torch.uint8)
     if out is None:
         out = empty_image((B, Nc, 3, res, res), out_dtype, dev)
@@ -1014,7 +1014,7 @@ class _RasterScene(torch.autograd.Function):
             gout = _c(gout)
         g_agent = torch.empty((B, Nc, max(N, 1), 4), dtype=f32, device=dev)
         g_cam = torch.empty((B, Nc, 4), dtype=f32, device=dev)
-        m8 = mask.contiguous().view(u8) if mask.dtype == torch.bool else _c(mask, u8)
+        m8 = _u8(mask)
         p = lambda t, d, nme: nat.dev_ptr(_c(t, d), d, nme) if N > 0 else None
         ev = None
         if raster_bwd_events is not None:
@@ -1087,8 +1087,9 @@ def raster_mesh(verts, attrs, faces, cam_xy, cam_sc, levels, scale, res, out_dty
 # ---------------------------------------------------------------------------------------------------------------
 # lane tables and the wrong-way query (csrc/lanes.hip)
 # ---------------------------------------------------------------------------------------------------------------
-class LaneTableHandle:
+class LaneTableHandle(_Handle):
     """Device-resident lane table of one map (tds_lanes_t), built from the HOST arrays of `lanelet2.lane_table`."""
+    _destroy_call = 'tds_lanes_destroy'
 
     def __init__(self, table, device='cuda', max_tolerance=1.0, cell_size=0.0):
         self.device = torch.device(device)
@@ -1106,32 +1107,16 @@ class LaneTableHandle:
                  self.max_tolerance, ctypes.byref(handle))
         self._h = handle
 
-    @property
-    def handle(self):
-        if self._h is None:
-            raise RuntimeError('LaneTableHandle was destroyed')
-        return self._h
-
     def info(self):
         buf = (ctypes.c_int64 * 4)()
         nat.call('tds_lanes_info', self.device, self.handle, buf)
         return dict(lanelets=buf[0], nx=buf[1], ny=buf[2], bytes=buf[3])
 
-    def close(self):
-        if getattr(self, '_h', None) is not None:
-            h, self._h = self._h, None
-            nat.call('tds_lanes_destroy', self.device, h)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LaneTableSet:
+class LaneTableSet(_Handle):
     """The lane tables of a batch (tds_laneset_t) + which of them every scene uses (`scene_map`, (B,) int32 on the device, -1 = the
     scene has no lane map; None = every scene uses table 0)."""
+    _destroy_call = 'tds_laneset_destroy'
 
     def __init__(self, tables, scene_map=None):
         assert len(tables) > 0
@@ -1142,23 +1127,6 @@ class LaneTableSet:
         handle = ctypes.c_void_p()
         nat.call('tds_laneset_create', self.device, arr, len(self.tables), ctypes.byref(handle))
         self._h = handle
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise RuntimeError('LaneTableSet was destroyed')
-        return self._h
-
-    def close(self):
-        if getattr(self, '_h', None) is not None:
-            h, self._h = self._h, None
-            nat.call('tds_laneset_destroy', self.device, h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def wrong_way(lane_set, state, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance):
@@ -1174,9 +1142,7 @@ def wrong_way(lane_set, state, recenter_offset, present, direction_angle_thresho
     if lane_set.scene_map is not None and lane_set.scene_map.shape[0] != B:
         raise RuntimeError(f'wrong_way: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, the state has {B}')
     off = None if recenter_offset is None else _c(recenter_offset.detach())
-    pres = None
-    if present is not None:
-        pres = present.contiguous().view(u8) if present.dtype == torch.bool else _c(present, u8)
+    pres = None if present is None else _u8(present)
     nat.call('tds_wrong_way_f32', state.device, lane_set.handle, None if lane_set.scene_map is None else nat.dev_ptr(lane_set.scene_map, i32, 'scene_map'),
              A, nat.dev_ptr(state, f32, 'state'), None if off is None else nat.dev_ptr(off, f32, 'recenter_offset'),
              None if pres is None else nat.dev_ptr(pres, u8, 'present'), nat.dev_ptr(out, f32, 'out'), B * A,

@@ -2,7 +2,7 @@
 Infraction metrics with the reference's names and signatures (torchdrivesim/infractions.py), computed by the K2 HIP
 kernels: oriented-box IoU, 5-disc overlap, and off-road distance to the driving-surface mesh.
 """
-from typing import List, Optional, Union
+from typing import Optional, Union
 
 import os
 import numpy as np
@@ -40,30 +40,23 @@ def box2corners_th(box: Tensor) -> Tensor:
 OFFROAD_CELL_SIZE = float(os.environ.get('TDS_OFFROAD_CELL', 3.0))
 
 
-def _static_maps_for(mesh: BaseMesh, device) -> List:
-    """The geometry-only device map(s) of a batch of meshes -- ONE per distinct batch element (`_ops.group_rows`), taken from the process-wide
-    content cache or built once -- remembered on the mesh object: [(StaticMap or StaticMapSet, None)]."""
+def _static_maps_for(mesh: BaseMesh, device) -> Union[_ops.StaticMap, _ops.StaticMapSet]:
+    """The geometry-only device map of a batch of meshes (`_ops.map_per_distinct_row`: a StaticMap, or a StaticMapSet served in one launch
+    when the batch holds several meshes), remembered on the mesh object."""
     key = (mesh.verts.data_ptr(), mesh.faces.data_ptr(), tuple(mesh.verts.shape), tuple(mesh.faces.shape), str(device))
     cache = getattr(mesh, '_tds_offroad_maps', None)
     if cache is not None and cache[0] == key:
         return cache[1]
     dev = torch.device(device)
     tensors = [t.detach() if t.is_cuda else t.detach().to(dev) for t in (mesh.verts, mesh.faces)]
-    scene_map, reps, hashes = _ops.group_rows(tensors)
-    per_group = []
-    for r, h in zip(reps, hashes):
-        rows = [t[r] for t in tensors]
-        ckey = ('offroad', str(dev), h, tuple(tuple(x.shape) for x in rows), OFFROAD_CELL_SIZE)
-        per_group.append(_ops.map_cache.get(ckey, rows, lambda rows=rows: _ops.StaticMap(rows[0][..., :2], rows[1], device=dev, cell_size=OFFROAD_CELL_SIZE)))
-    if len(per_group) == 1:
-        maps = [(per_group[0], None)]
-    else:
-        maps = [(_ops.StaticMapSet(per_group, torch.from_numpy(scene_map)), None)]           # one launch for the batch
+    smap = _ops.map_per_distinct_row(tensors, lambda reps: (
+        lambda h, rows: ('offroad', str(dev), h, tuple(tuple(x.shape) for x in rows), OFFROAD_CELL_SIZE),
+        lambda r: _ops.StaticMap(tensors[0][r][..., :2], tensors[1][r], device=dev, cell_size=OFFROAD_CELL_SIZE)))
     try:
-        object.__setattr__(mesh, '_tds_offroad_maps', (key, maps))
+        object.__setattr__(mesh, '_tds_offroad_maps', (key, smap))
     except Exception:
         pass
-    return maps
+    return smap
 
 
 def offroad_infraction_loss(agent_states: Tensor, lenwid: Tensor, driving_surface_mesh: Union[BaseMesh, _ops.StaticMap],
@@ -74,20 +67,16 @@ def offroad_infraction_loss(agent_states: Tensor, lenwid: Tensor, driving_surfac
         raise NotImplementedError('pytorch3d is not part of this framework; the HIP kernel follows the pure-torch path')
     B, A = agent_states.shape[:2]
     if isinstance(driving_surface_mesh, _ops.StaticMap):
-        maps = [(driving_surface_mesh, None)]
-        n_faces = driving_surface_mesh.n_faces
+        smap, n_faces = driving_surface_mesh, driving_surface_mesh.n_faces
     else:
-        n_faces = driving_surface_mesh.faces_count
-        maps = None
+        smap, n_faces = None, driving_surface_mesh.faces_count
     if A == 0 or n_faces == 0:
         return torch.zeros_like(agent_states[..., 0])
     if lenwid.dim() == 2:
         lenwid = lenwid.unsqueeze(-2).expand((lenwid.shape[0], A, lenwid.shape[1]))
-    if maps is None:
-        maps = _static_maps_for(driving_surface_mesh, agent_states.device)
-    if maps[0][1] is None:
-        return _ops.offroad(maps[0][0], agent_states, lenwid, threshold=threshold)
-    return torch.cat([_ops.offroad(m, agent_states[b:b + 1], lenwid[b:b + 1], threshold=threshold) for m, b in maps], dim=0)
+    if smap is None:
+        smap = _static_maps_for(driving_surface_mesh, agent_states.device)
+    return _ops.offroad(smap, agent_states, lenwid, threshold=threshold)
 
 
 LANELET_TAGS_TO_EXCLUDE = ['parking']          # infractions.py:21

@@ -761,21 +761,17 @@ class Simulator:
             actor_levels += [float(lv[c]) for c in cats]
         # one device map per DISTINCT mesh of the batch (a collated batch of 512 x Town01 + 512 x Town02 builds two), shared through the
         # process-wide content cache: `copy`, `select_batch_elements`, `extend`, `to` and `shard_simulator` end up here again and find the handles
-        maps = [(self.renderer.scene_maps(bg, actor_levels, device=dev), None)]
+        smap = self.renderer.scene_maps(bg, actor_levels, device=dev)
         tmpl = actor_template(sizes.detach()).contiguous()          # B x N x 7 x 2 (a render that differentiates the sizes builds its own)
-        keys, key_tables, wp_keys = [], [], []
-        for smap, _ in maps:
-            body = torch.tensor([(smap.rank_of(lv[n]) << 24) | int(_ops.quantise_colors(torch.tensor(cm[n], dtype=torch.float32) / 255.0)) for n in names],
-                                dtype=torch.int64, device=dev)
-            dkey = (smap.rank_of(lv['direction']) << 24) | int(_ops.quantise_colors(torch.tensor(cm['direction'], dtype=torch.float32) / 255.0))
-            k = torch.stack([body[types.long()], torch.full_like(types.long(), dkey)], dim=-1)
-            keys.append(k.to(torch.int32).contiguous())             # bit pattern of the uint32 key
-            key_tables.append(sorted(set(body.tolist()) | {dkey}))   # distinct actor keys, known on the host (bit-plane kernel)
-            wp_keys.append((smap.rank_of(lv['goal_waypoint']) << 24) | int(_ops.quantise_colors(torch.tensor(cm['goal_waypoint'], dtype=torch.float32) / 255.0)))
+        key_of = lambda name: (smap.rank_of(lv[name]) << 24) | int(_ops.quantise_colors(torch.tensor(cm[name], dtype=torch.float32) / 255.0))  # noqa: E731
+        body = torch.tensor([key_of(n) for n in names], dtype=torch.int64, device=dev)
+        dkey = key_of('direction')
+        keys = torch.stack([body[types.long()], torch.full_like(types.long(), dkey)], dim=-1).to(torch.int32).contiguous()     # bit pattern of the uint32 key
+        key_table = sorted(set(body.tolist()) | {dkey})            # distinct actor keys, known on the host (bit-plane kernel)
+        wp_key = key_of('goal_waypoint')
         ctrl = None
         if ctrl_kinds:
-            q = lambda name: int(_ops.quantise_colors(torch.tensor(cm[name], dtype=torch.float32) / 255.0))
-            st_q, tm_q, static_keys, light_tables = [], [], [], []
+            st_q, tm_q, static_keys = [], [], []
             for kind in ctrl_kinds:
                 c = controls[kind]
                 pos, m = c.pos.to(dev).to(sizes.dtype), c.mask.to(dev)[..., None]
@@ -786,18 +782,13 @@ class Simulator:
                 sy = torch.tensor([0.5, 0.5, -0.5, -0.5], dtype=pos.dtype, device=dev) * pos[..., 3:4]
                 quad = torch.stack([sx, sy], dim=-1) * m[..., None].to(pos.dtype)
                 tm_q.append(torch.cat([quad, torch.zeros(quad.shape[:2] + (3, 2), dtype=pos.dtype, device=dev)], dim=-2))
-                per_map = []
-                for smap, _ in maps:
-                    if kind == 'traffic_light':
-                        per_map.append(torch.tensor([(smap.rank_of(lv[f'{kind}_{s_}']) << 24) | q(f'{kind}_{s_}') for s_ in c.allowed_states],
-                                                    dtype=torch.int64, device=dev))
-                    else:
-                        per_map.append(torch.full((1,), (smap.rank_of(lv[kind]) << 24) | q(kind), dtype=torch.int64, device=dev))
-                static_keys.append(per_map)
+                if kind == 'traffic_light':
+                    static_keys.append(torch.tensor([key_of(f'{kind}_{s_}') for s_ in c.allowed_states], dtype=torch.int64, device=dev))
+                else:
+                    static_keys.append(torch.full((1,), key_of(kind), dtype=torch.int64, device=dev))
             ctrl = dict(kinds=ctrl_kinds, state=torch.cat(st_q, dim=1).contiguous(), tmpl=torch.cat(tm_q, dim=1).contiguous(), key_lut=static_keys)
-            for i in range(len(maps)):
-                key_tables[i] = sorted(set(key_tables[i]) | {int(v) for per_map in static_keys for v in per_map[i].tolist()})
-        self._scene_cache = dict(sources=sources, versions=[t._version for t in sources], extra=extra, maps=maps, tmpl=tmpl, keys=keys, key_tables=key_tables, ctrl=ctrl, wp_keys=wp_keys)
+            key_table = sorted(set(key_table) | {int(v) for lut in static_keys for v in lut.tolist()})
+        self._scene_cache = dict(sources=sources, versions=[t._version for t in sources], extra=extra, map=smap, tmpl=tmpl, keys=keys, key_table=key_table, ctrl=ctrl, wp_key=wp_key)
         return self._scene_cache
 
     def _waypoint_triangles(self, waypoints: Tensor, rendering_mask: Optional[Tensor]):
@@ -814,13 +805,12 @@ class Simulator:
             tri = torch.where(rendering_mask.to(torch.bool)[..., None, None, None], tri, first.expand_as(tri))
         return tri.reshape(B, Nc, M * corner.shape[1], 3, 2).contiguous(), None
 
-    def _control_keys(self, scene, i_map: int, sl) -> Tensor:
-        """(b, Nq, 2) int32 keys of the control quads of the scenes in `sl`: (colour of the current state, 0 = no direction part)"""
+    def _control_keys(self, scene) -> Tensor:
+        """(B, Nq, 2) int32 keys of the control quads: (colour of the current state, 0 = no direction part)"""
         out = []
-        for kind, per_map in zip(scene['ctrl']['kinds'], scene['ctrl']['key_lut']):
+        for kind, lut in zip(scene['ctrl']['kinds'], scene['ctrl']['key_lut']):
             c = self.traffic_controls[kind]
-            lut = per_map[i_map]
-            idx = c.state[sl].to(lut.device).long() if kind == 'traffic_light' else torch.zeros_like(c.state[sl].to(lut.device).long())
+            idx = c.state.to(lut.device).long() if kind == 'traffic_light' else torch.zeros_like(c.state.to(lut.device).long())
             out.append(lut[idx])
         body = torch.cat(out, dim=1)
         return torch.stack([body, torch.zeros_like(body)], dim=-1).to(torch.int32)
@@ -900,9 +890,6 @@ class Simulator:
             wp_tri = wp_on = None
             if waypoints is not None and waypoints.shape[2] > 0:
                 wp_tri, wp_on = self._waypoint_triangles(waypoints.to(state.dtype), waypoints_rendering_mask)
-            if out is not None and len(scene['maps']) != 1:
-                raise RuntimeError('`out=` needs a batch that is served by one launch')
-            out_arg, out = ({} if out is None else dict(out=out)), []
             # the metrics run beside the launch; a differentiable render forks too when the launch stays on the caller's stream (the plain second
             # stream, or 'reserved' with the loop on sim.raster_stream()): the metric nodes are then autograd nodes of the side stream, and the
             # engine runs their backward there as well -- beside the rasteriser's backward
@@ -913,52 +900,46 @@ class Simulator:
                 self._mark_fork(write_bound=self.renderer.out_dtype == torch.float32 and (r is None or min(r.height, r.width) > 208))
             # render_egocentric with gradients: the cameras are the exposed agents themselves -- one autograd node takes state and headings and
             # folds the cameras' gradient into the agents' (no slice nodes for camera_xy / camera_sc in the graph)
-            ego_n = n_cam if (_ego and diff and ctrl is None and len(scene['maps']) == 1 and n_cam <= state.shape[1]) else 0
-            for i_map, ((smap, b), keys, ktab) in enumerate(zip(scene['maps'], scene['keys'], scene['key_tables'])):
-                sl = slice(None) if b is None else slice(b, b + 1)
-                cut = (lambda t: t) if b is None else (lambda t: t[sl])       # (a full slice would still be a node of the autograd graph)
-                k = keys[sl]
-                if custom_agent_colors is not None:
-                    # generate() paints the four body vertices of agent a with custom_agent_colors[b, c, a] for camera c
-                    # (mesh.py:1092-1099); the direction triangle keeps its colour.  Same rendering level, so only the colour
-                    # bits of the body key change -- per camera.
-                    rgb = _ops.quantise_colors(custom_agent_colors[sl].to(state.device)).to(torch.int32)          # (b,Nc,A,)
-                    kc = k[:, None].expand(-1, n_cam, -1, -1).clone()
-                    kc[..., 0] = (kc[..., 0] & ~0xFFFFFF) | rgb
-                    k, ktab = kc.contiguous(), None
-                if ctrl is not None:
-                    kq = self._control_keys(scene, i_map, sl)
-                    k = torch.cat([k, kq[:, None].expand(-1, n_cam, -1, -1) if k.dim() == 4 else kq], dim=-2).contiguous()
-                extra = dict()
-                if wp_tri is not None:
-                    wk = scene['wp_keys'][i_map]
-                    extra = dict(extra_tri=wp_tri[sl], extra_key=torch.full(wp_tri[sl].shape[:3], wk, dtype=torch.int32, device=state.device))
-                    ktab = None if ktab is None else sorted(set(ktab) | {wk})
-                launch = lambda: self.renderer.render_scene(smap, cut(state), cut(agent_sc), cut(tmpl_all), k, cut(mask).contiguous(),     # noqa: E731
-                                                            cut(camera_xy), cut(camera_sc), res=res, fov=fov, key_table=ktab, differentiable=diff, **extra,
-                                                            **out_arg, **(dict(ego_cameras=ego_n) if ego_n else {}))
-                if self.overlap_infractions == 'reserved' and not diff and self._fork is not None and state.is_cuda and \
-                        self._fork[2] != _ops.reserved_streams(state.device, Simulator._reserved_per_xcd)[0]:
-                    # the launch goes to the stream that is kept off the reserved CUs: it waits for what the caller's stream has enqueued so far
-                    # (the fork event) and the caller's stream waits for it -- beside it, on the reserved CUs, the foreseen metrics are running.
-                    # (A loop that makes that stream its current one -- `with torch.cuda.stream(sim.raster_stream()):` -- saves these two waits.)
-                    main = self._fork[2]
-                    rs = _ops.reserved_streams(state.device, Simulator._reserved_per_xcd)[0]
-                    # NOT the fork event: the per-launch inputs (per-camera colour keys, traffic-control keys, waypoint triangles and their
-                    # keys) were built on the caller's stream AFTER it -- the launch waits for an event recorded here, behind all of them
-                    built = torch.cuda.Event()
-                    built.record(main)
-                    rs.wait_event(built)
-                    with torch.cuda.stream(rs):
-                        img = launch()
-                    img.record_stream(main)
-                    done = torch.cuda.Event()
-                    done.record(rs)
-                    main.wait_event(done)
-                    out.append(img)
-                else:
-                    out.append(launch())
-            return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+            ego_n = n_cam if (_ego and diff and ctrl is None and n_cam <= state.shape[1]) else 0
+            k, ktab = scene['keys'], scene['key_table']
+            if custom_agent_colors is not None:
+                # generate() paints the four body vertices of agent a with custom_agent_colors[b, c, a] for camera c
+                # (mesh.py:1092-1099); the direction triangle keeps its colour.  Same rendering level, so only the colour
+                # bits of the body key change -- per camera.
+                rgb = _ops.quantise_colors(custom_agent_colors.to(state.device)).to(torch.int32)          # (B,Nc,A,)
+                kc = k[:, None].expand(-1, n_cam, -1, -1).clone()
+                kc[..., 0] = (kc[..., 0] & ~0xFFFFFF) | rgb
+                k, ktab = kc.contiguous(), None
+            if ctrl is not None:
+                kq = self._control_keys(scene)
+                k = torch.cat([k, kq[:, None].expand(-1, n_cam, -1, -1) if k.dim() == 4 else kq], dim=-2).contiguous()
+            extra = dict()
+            if wp_tri is not None:
+                wk = scene['wp_key']
+                extra = dict(extra_tri=wp_tri, extra_key=torch.full(wp_tri.shape[:3], wk, dtype=torch.int32, device=state.device))
+                ktab = None if ktab is None else sorted(set(ktab) | {wk})
+            launch = lambda: self.renderer.render_scene(scene['map'], state, agent_sc, tmpl_all, k, mask.contiguous(), camera_xy, camera_sc,     # noqa: E731
+                                                        res=res, fov=fov, key_table=ktab, differentiable=diff, **extra, out=out, ego_cameras=ego_n)
+            if self.overlap_infractions == 'reserved' and not diff and self._fork is not None and state.is_cuda and \
+                    self._fork[2] != _ops.reserved_streams(state.device, Simulator._reserved_per_xcd)[0]:
+                # the launch goes to the stream that is kept off the reserved CUs: it waits for what the caller's stream has enqueued so far
+                # (the fork event) and the caller's stream waits for it -- beside it, on the reserved CUs, the foreseen metrics are running.
+                # (A loop that makes that stream its current one -- `with torch.cuda.stream(sim.raster_stream()):` -- saves these two waits.)
+                main = self._fork[2]
+                rs = _ops.reserved_streams(state.device, Simulator._reserved_per_xcd)[0]
+                # NOT the fork event: the per-launch inputs (per-camera colour keys, traffic-control keys, waypoint triangles and their
+                # keys) were built on the caller's stream AFTER it -- the launch waits for an event recorded here, behind all of them
+                built = torch.cuda.Event()
+                built.record(main)
+                rs.wait_event(built)
+                with torch.cuda.stream(rs):
+                    img = launch()
+                img.record_stream(main)
+                done = torch.cuda.Event()
+                done.record(rs)
+                main.wait_event(done)
+                return img
+            return launch()
         if out is not None:
             raise RuntimeError(f'`out=` is served by HipRenderer only, not by {type(self.renderer).__name__}')
         # any other BirdviewRenderer: the reference's generic dataflow (explicit per-camera mesh)
@@ -1005,18 +986,12 @@ class Simulator:
         if self.agent_count == 0 or self.road_mesh.faces_count == 0:
             return torch.zeros_like(state[..., 0])
         from torchdrivesim_amd.infractions import _static_maps_for
-        maps = _static_maps_for(self.road_mesh, state.device)      # geometry-only device map(s), cached on the mesh
+        smap = _static_maps_for(self.road_mesh, state.device)      # geometry-only device map, cached on the mesh
         size, present = self.get_agent_size(), self.get_present_mask()
-        sc_all = self._heading_sc()
-        if sc_all.shape[-2] != self.agent_count:
-            sc_all = sc_all[..., :self.agent_count, :]
-        out = []
-        for smap, b in maps:
-            sl = slice(None) if b is None else slice(b, b + 1)
-            cut = (lambda t: t) if b is None else (lambda t: t[sl])           # (a full slice would still be a node of the autograd graph)
-            out.append(_ops.offroad(smap, cut(state), cut(size), threshold=self.cfg.offroad_threshold, present=cut(present),
-                                    sc=None if sc_all is None else cut(sc_all)))
-        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+        sc = self._heading_sc()
+        if sc.shape[-2] != self.agent_count:
+            sc = sc[..., :self.agent_count, :]
+        return _ops.offroad(smap, state, size, threshold=self.cfg.offroad_threshold, present=present, sc=sc)
 
     def compute_wrong_way(self) -> Tensor:
         """Wrong-way metric per agent, -cos of the angle between the agent and the lane it is on where that angle exceeds
