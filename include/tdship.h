@@ -189,6 +189,8 @@ int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t *scene_map,
  * ---------------------------------------------------------------------------------------------------------- */
 #define TDS_OUT_F32 0      /* reference-faithful float32 image with values 0..255 */
 #define TDS_OUT_U8 1       /* same values as uint8 (separate mode, 4x fewer bytes) */
+#define TDS_OUT_MASK_U8 2    /* semantic masks, one 0 / 1 byte per pixel and channel (tds_raster_scene_masks) */
+#define TDS_OUT_MASK_BITS 3  /* semantic masks, one bit per pixel and channel (tds_raster_scene_masks) */
 
 /* Fused scene path used by Simulator.render / render_egocentric: the static map comes from the handle, the actor
  * mesh is generated on the fly from agent state (never materialised per camera).
@@ -257,11 +259,36 @@ int tds_raster_scene_multi(const tds_mapset_t *set, const int32_t *scene_map, co
                            int64_t N, float scale, int res, int out_mode, void *out, void *workspace, int64_t workspace_bytes,
                            const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera,
                            const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream);
+/* Semantic bird's-eye masks: the same scene and arguments as tds_raster_scene / _multi (without actor_key_per_camera: the actors' keys are
+ * those of their types), but instead of an image a stack of C = n_channels binary channels.  Channel c is set at pixel (x, y) exactly when
+ * the colour image would paint there a face whose key has bit c set in its key_channels word -- the same fill, trim rule (TDS_RASTER_NO_TRIM
+ * in aux->flags), mask, masked-agent dot, per-camera triangles as the colour call, but WITHOUT occlusion: a road channel stays set under a car.
+ *   key_channels  HOST array, one uint32 channel set per entry of the launch's key table: the distinct values of the map's keys (tds_map_keys,
+ *                 over the set for _multi) and of actor_keys, in ascending order.  1 <= n_channels <= 32.
+ *   out_mode      TDS_OUT_MASK_U8:   out = B x Nc x C x H x W bytes, 0 or 1, in the memory order of the colour image (x, y = the last two axes)
+ *                 TDS_OUT_MASK_BITS: out = B x Nc x C x ceil(W / 32) x H uint32 words: bit i of word (xw, y) is pixel (32 xw + i, y);
+ *                                    padding bits are 0.  16-byte aligned.
+ *   workspace     required: tds_raster_scene_workspace_bytes_for(B * Nc, res, out_mode, n_keys) bytes.  The call writes its channel table there
+ *                 in stream order (nothing is allocated: the call can be captured into a HIP graph).
+ * The masks are streamed out of the bit-plane kernels, with the plan of the uint8 image of the same shape: a scene with more than 15 distinct
+ * keys is TDS_ELIMIT.  actor_keys must be listed when N > 0 or n_extra > 0; aux->index_slices must be NULL (TDS_EINVAL otherwise). */
+int tds_raster_scene_masks(const tds_map_t *map, const float *state, const float *agent_sc, const float *tmpl,
+                           const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc,
+                           int64_t B, int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out, void *workspace,
+                           int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys,
+                           const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, const uint32_t *key_channels, int n_channels,
+                           tds_raster_aux_t *aux, void *stream);
+int tds_raster_scene_masks_multi(const tds_mapset_t *set, const int32_t *scene_map, const float *state, const float *agent_sc, const float *tmpl,
+                                 const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc, int64_t B, int64_t Nc,
+                                 int64_t N, float scale, int res, int out_mode, void *out, void *workspace, int64_t workspace_bytes,
+                                 const uint32_t *actor_keys, int n_actor_keys, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra,
+                                 const uint32_t *key_channels, int n_channels, tds_raster_aux_t *aux, void *stream);
 /* recommended scratch size for n_img = B * Nc cameras at this resolution (0 if the fast path cannot be used): enough for every path */
 int tds_raster_scene_workspace_bytes(int64_t n_img, int res, int64_t *bytes);
 /* the same for a launch of which the caller knows the number of distinct keys (map keys + actor keys, tds_map_keys): with at most 15 the
  * bit-plane kernels run, which use the face lists up to 160 x 160 (float32; above 116 x 116 only multiples of 16) / 216 x 216 (uint8) only and above nothing but the 64 bytes of
  * work queues -- 128 bytes instead of 32 KB per camera at 256 x 256.  n_keys < 0 or > 15: as tds_raster_scene_workspace_bytes. */
+/* The mask modes: the uint8 image's size and 256 bytes for the channel table. */
 int tds_raster_scene_workspace_bytes_for(int64_t n_img, int res, int out_mode, int n_keys, int64_t *bytes);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -431,7 +458,8 @@ int tds_raster_set_debug(int flags);
 int tds_raster_get_stats(unsigned long long *out16);
 /* which launches tds_raster_scene makes for a call of this shape (its plan_raster_scene, with explicit knobs: those of the four setters above).
  * n_keys: distinct keys (-1: more than 15); workspace_bytes: as the caller passes it (0: none).
- * form: 0 bit planes, 1 split (K3s + K3r + the bit planes over overflowed cameras), 2 packed keys binned, 3 packed keys fused, 4 TDS_ELIMIT */
+ * form: 0 bit planes, 1 split (K3s + K3r + the bit planes over overflowed cameras), 2 packed keys binned, 3 packed keys fused, 4 TDS_ELIMIT.
+ * The mask modes (tds_raster_scene_masks): the uint8 plan with the pair table taken off lds / lds_s; 4 where that plan takes packed keys. */
 typedef struct {
     int form, tw, strips, twp, nwv, nb, minwg, emit, four_per_cu, persist, tws, lw;
     int64_t lds, lds_s, grid, caps, off_counts, off_lists, off_lists3;

@@ -20,6 +20,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 
 METRIC_IOU, METRIC_DISCS = 0, 1
 OUT_F32, OUT_U8 = 0, 1
+OUT_MASK_U8, OUT_MASK_BITS = 2, 3     # semantic masks (tds_raster_scene_masks): 0 / 1 bytes, packed bits
 RASTER_NO_TRIM = 1
 
 
@@ -93,6 +94,8 @@ _SIGNATURES = {
     'tds_raster_index_slices_bytes': [_i64, _i32, ctypes.POINTER(_i64)],
     'tds_raster_scene_bwd_idx_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
     'tds_raster_scene_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp],
+    'tds_raster_scene_masks': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp],
+    'tds_raster_scene_masks_multi': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp],
     'tds_raster_scene_workspace_bytes': [_i64, _i32, ctypes.POINTER(_i64)],
     'tds_raster_scene_workspace_bytes_for': [_i64, _i32, _i32, _i32, ctypes.POINTER(_i64)],
     'tds_map_keys': [_vp, _vp, _i32, ctypes.POINTER(_i32)],

@@ -967,6 +967,68 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     return out
 
 
+def mask_table(smap, actor_keys, key_channels):
+    """The key table of a mask launch -- the distinct keys of the map (over the set) and of `actor_keys`, ascending -- and, aligned with it, the
+    channel set of every key: key_channels.get(key, 0).  Raises when the map has more than 64 distinct keys (the masks need at most 15)."""
+    face = smap.face_keys()
+    if face is None:
+        raise RuntimeError('semantic masks: the map has more than 64 distinct face keys (the bit-plane kernels take at most 15 keys)')
+    table = sorted(set(int(k) & 0xffffffff for k in face) | set(int(k) & 0xffffffff for k in actor_keys))
+    return table, [int(key_channels.get(k, 0)) & 0xffffffff for k in table]
+
+
+def raster_scene_masks(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, key_table, key_channels, n_channels, packed=False,
+                       out=None, extra_tri=None, extra_key=None, trim=True):
+    """Semantic bird's-eye masks of the scene raster_scene would draw (same arguments; actor_key (B,N,2) only): `n_channels` binary channels,
+    channel c set wherever the image would paint a face whose key k has bit c in key_channels[k] (dict key -> channel set), occlusion ignored.
+    key_table: the actors' (and per-camera triangles') distinct keys.  -> (B,Nc,C,res,res) torch.bool (memory order of the image: the last two
+    axes are x, y), or with packed=True (B,Nc,C,ceil(res/32),res) int32 words holding bit i of pixel (32 xw + i, y) (rendering.unpack_mask_bits).
+    `out`: a caller-owned contiguous tensor of that shape and dtype.  Never differentiable."""
+    B, Nc = cam_xy.shape[:2]
+    N = state.shape[1]
+    dev = cam_xy.device
+    cam_xy, cam_sc = _c(cam_xy.detach()), _c(cam_sc.detach())
+    if N > 0:
+        state, agent_sc, tmpl = _c(state.detach()), _c(agent_sc.detach()), _c(tmpl.detach())
+        actor_key = _c(actor_key, i32)
+        if tuple(actor_key.shape) != (B, N, 2):
+            raise RuntimeError(f'actor_key must be ({B}, {N}, 2), got {tuple(actor_key.shape)}')
+        mask = _u8(mask)
+    C = int(n_channels)
+    if not 1 <= C <= 32:
+        raise ValueError(f'semantic masks take 1 to 32 channels, got {C}')
+    shape, dtype = ((B, Nc, C, (res + 31) // 32, res), i32) if packed else ((B, Nc, C, res, res), torch.bool)
+    if out is None:
+        out = empty_image(shape, dtype, dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != dev or out.data_ptr() % 16 != 0:
+        raise RuntimeError(f'`out` must be a contiguous, 16-byte aligned {dtype} tensor of shape {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}')
+    K = 0
+    if extra_tri is not None and extra_tri.shape[2] > 0:
+        K = extra_tri.shape[2]
+        assert tuple(extra_tri.shape) == (B, Nc, K, 3, 2) and tuple(extra_key.shape) == (B, Nc, K), 'extra_tri must be (B,Nc,K,3,2), extra_key (B,Nc,K)'
+        extra_tri, extra_key = _c(extra_tri.detach()), _c(extra_key, i32)
+    actors = [int(v) & 0xffffffff for v in key_table]
+    table, chans = mask_table(smap, actors, key_channels)
+    kt = (ctypes.c_uint32 * max(len(actors), 1))(*actors)
+    kc = (ctypes.c_uint32 * max(len(chans), 1))(*chans)
+    mode = nat.OUT_MASK_BITS if packed else nat.OUT_MASK_U8
+    # (more than 15 keys: the call reports TDS_ELIMIT; the workspace is sized as for 15 rather than for the packed-key kernels' lists)
+    ws = _raster_workspace(dev, B * Nc, int(res), mode, min(len(table), 15))
+    multi = isinstance(smap, StaticMapSet)
+    if multi and smap.scene_map.shape[0] != B:
+        raise RuntimeError(f'the StaticMapSet is for {smap.scene_map.shape[0]} scenes, the cameras for {B}')
+    aux = None if trim else nat.RasterAux(flags=nat.RASTER_NO_TRIM)
+    p = lambda t, d, nme: nat.dev_ptr(t, d, nme) if N > 0 else None      # noqa: E731
+    head = ('tds_raster_scene_masks_multi', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map')) if multi else \
+        ('tds_raster_scene_masks', dev, smap.handle)
+    nat.call(*head, p(state, f32, 'state'), p(agent_sc, f32, 'agent_sc'), p(tmpl, f32, 'tmpl'), p(actor_key, i32, 'actor_key'), p(mask, u8, 'mask'),
+             nat.dev_ptr(cam_xy, f32, 'cam_xy'), nat.dev_ptr(cam_sc, f32, 'cam_sc'), B, Nc, N, float(2.0 / fov), int(res), mode,
+             nat.dev_ptr(out, dtype, 'out'), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.cast(kt, ctypes.c_void_p), len(actors),
+             nat.dev_ptr(extra_tri, f32, 'extra_tri') if K > 0 else None, nat.dev_ptr(extra_key, i32, 'extra_key') if K > 0 else None, K,
+             ctypes.cast(kc, ctypes.c_void_p), C, None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev))
+    return out
+
+
 class _RasterScene(torch.autograd.Function):
     """Differentiable wrapper of the fused scene rasteriser.  Forward: tds_raster_scene (CV2 pixel semantics).  Backward: the build-defined
     edge-sampling gradient with respect to actor position / heading / template vertices (sizes) and camera position / heading (DESIGN.md "K3 backward"); the

@@ -2264,8 +2264,115 @@ __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typ
     }
 }
 
+// Output tags of the semantic masks (TDS_OUT_MASK_U8 / TDS_OUT_MASK_BITS): the bit-plane kernels instantiated with one of them stream the
+// planes out as channels (write_out_masks) instead of resolving them to colours.  Separate tags, so that every colour instantiation keeps its name
+// and its code.
+struct MaskU8 {};
+struct MaskBits {};
+template <typename OutT> struct is_mask : std::integral_constant<bool, std::is_same<OutT, MaskU8>::value || std::is_same<OutT, MaskBits>::value> {};
+template <int NB> struct PairTab<NB, MaskU8> { using E = uint32_t; };
+template <int NB> struct PairTab<NB, MaskBits> { using E = uint32_t; };
+
+// LDS of the pair table; the masks need no colour lookup and have none
 template <int NB, typename OutT>
-constexpr int pair_tab_dw() { return 3 * (1 << (2 * NB)) * (int)sizeof(typename PairTab<NB, OutT>::E) / 4; }
+constexpr int pair_tab_dw() { return is_mask<OutT>::value ? 0 : 3 * (1 << (2 * NB)) * (int)sizeof(typename PairTab<NB, OutT>::E) / 4; }
+
+// The channel table of a mask launch, in the caller's workspace (written by the call, in stream order): [0] = C channels, [1 + c] = the planes
+// (bit k: key k of the launch's ascending key table) whose union is channel c.  The mask instantiations find it in CommonArgs::slices.
+constexpr int MASK_TABLE_DW = 64;
+constexpr int64_t MASK_TABLE_BYTES = MASK_TABLE_DW * 4;
+struct MaskTable { uint32_t w[MASK_TABLE_DW]; };
+
+// Mask stream-out of one (camera, strip): channel c of a pixel is set iff one of the planes of chan[1 + c] holds it -- coverage, no occlusion.
+//   MaskU8    out = n_img x C x W x H bytes (0 / 1), the RGB image's order: byte (x, y) of channel c at c * W * H + x * H + y;
+//   MaskBits  out = n_img x C x ceil(W / 32) x H words, the planes' own layout: bit i of word (xw, y) is pixel (32 xw + i, y), padding bits 0.
+// Items of 4 rows x 32 columns (uint8: 8 rows where that still gives every thread an item) in consecutive lanes along y, the output's fastest
+// axis: the planes are read with ds_read_b128, a lane stores 16 bytes (bits) or 4 / 8 bytes per column (uint8), non-temporal.  Odd
+// resolutions: one pixel (uint8) or one word (bits) per thread.
+template <int BBLOCK, typename OutT>
+__device__ __noinline__ void write_out_masks(const uint32_t *planes, const uint32_t *chan, void *out, int64_t img, int res, int X0, int TWp, int wpr,
+                                                int tid) {
+    constexpr bool BITS = std::is_same<OutT, MaskBits>::value;
+    const int H = res, W = res, wpw = (W + 31) >> 5;
+    const int C = (int)chan[0];
+    const int cols = min(TWp, W - X0);
+    // per channel: bytes of a uint8 channel, words of a packed one (offsets from the image's base fit 32 bits: 32 x 4096^2 bytes at most)
+    const uint32_t ch_elems = BITS ? (uint32_t)(wpw * H) : (uint32_t)(W * H);
+    char *const ob = (char *)out + (size_t)img * (size_t)C * ch_elems * (BITS ? 4u : 1u);
+    if ((H & 3) == 0) {
+        auto run = [&](auto rows_tag) {
+            constexpr int ROWS = decltype(rows_tag)::value, HALVES = ROWS / 4;
+            const int groups = H / ROWS;
+            for (int item = tid; item < groups * wpr; item += BBLOCK) {
+                const int rg = item % groups, xw = item / groups, y0 = rg * ROWS;
+                if (xw * 32 >= cols) continue;
+                const int ncol = min(32, cols - xw * 32);
+                const uint32_t keep = ncol == 32 ? 0xffffffffu : (1u << ncol) - 1u;
+                for (int ch = 0; ch < C; ++ch) {                         // wave-uniform
+                    uint32_t wd[ROWS];
+#pragma unroll
+                    for (int j = 0; j < ROWS; ++j) wd[j] = 0;
+                    for (uint32_t m = chan[1 + ch]; m != 0u; m &= m - 1u) {
+                        const int k = __builtin_ctz(m);
+                        const uint4 *pw = (const uint4 *)(planes + ((size_t)k * wpr + xw) * H + y0);
+#pragma unroll
+                        for (int h = 0; h < HALVES; ++h) { const uint4 q = pw[h]; wd[4 * h] |= q.x; wd[4 * h + 1] |= q.y; wd[4 * h + 2] |= q.z; wd[4 * h + 3] |= q.w; }
+                    }
+                    if constexpr (BITS) {
+                        typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
+                        const vu4 v = {wd[0] & keep, wd[1] & keep, wd[2] & keep, wd[3] & keep};
+                        const uint32_t off = (uint32_t)ch * ch_elems + (uint32_t)(((X0 >> 5) + xw) * H + y0);
+                        __builtin_nontemporal_store(v, (vu4 *)(ob + 4 * (size_t)off));
+                    } else {
+                        char *const base = ob + (size_t)ch * ch_elems + (size_t)((X0 + xw * 32) * H + y0);
+                        // one dword per column and 4 rows: byte r = bit p of row r
+                        auto quad = [&](int h, int p) {
+                            return ((wd[4 * h] >> p) & 1u) | (((wd[4 * h + 1] >> p) & 1u) << 8) | (((wd[4 * h + 2] >> p) & 1u) << 16) | (((wd[4 * h + 3] >> p) & 1u) << 24);
+                        };
+                        auto emit = [&](auto check) {
+#pragma unroll 4
+                            for (int p = 0; p < 32; ++p) {
+                                if (decltype(check)::value && p >= ncol) continue;
+                                if constexpr (ROWS == 8) {
+                                    typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
+                                    const vu2 v = {quad(0, p), quad(1, p)};
+                                    __builtin_nontemporal_store(v, (vu2 *)(base + (size_t)p * H));
+                                } else {
+                                    __builtin_nontemporal_store(quad(0, p), (uint32_t *)(base + (size_t)p * H));
+                                }
+                            }
+                        };
+                        if (ncol == 32) emit(std::false_type{}); else emit(std::true_type{});
+                    }
+                }
+            }
+        };
+        if (!BITS && (H & 7) == 0 && (H >> 3) * wpr >= BBLOCK) run(std::integral_constant<int, 8>{}); else run(std::integral_constant<int, 4>{});
+        return;
+    }
+    if constexpr (BITS) {
+        const int wcols = (cols + 31) >> 5;
+        for (int i = tid; i < H * wcols; i += BBLOCK) {                  // odd resolutions: one word per thread
+            const int xw = i / H, y = i - xw * H;
+            const int ncol = min(32, cols - xw * 32);
+            const uint32_t keep = ncol == 32 ? 0xffffffffu : (1u << ncol) - 1u;
+            for (int ch = 0; ch < C; ++ch) {
+                uint32_t v = 0;
+                for (uint32_t m = chan[1 + ch]; m != 0u; m &= m - 1u) v |= planes[((size_t)__builtin_ctz(m) * wpr + xw) * H + y];
+                ((uint32_t *)ob)[(size_t)ch * ch_elems + (size_t)((X0 >> 5) + xw) * H + y] = v & keep;
+            }
+        }
+    } else {
+        for (int i = tid; i < H * cols; i += BBLOCK) {                   // odd resolutions: one pixel per thread
+            const int lx = i / H, y = i - lx * H;
+            for (int ch = 0; ch < C; ++ch) {
+                uint32_t v = 0;
+                for (uint32_t m = chan[1 + ch]; m != 0u; m &= m - 1u) v |= planes[((size_t)__builtin_ctz(m) * wpr + (lx >> 5)) * H + y];
+                ob[(size_t)ch * ch_elems + (size_t)(X0 + lx) * H + y] = (char)((v >> (lx & 31)) & 1u);
+            }
+        }
+    }
+}
 
 // Work distribution of the bit-plane kernel.  The launch is PERSISTENT: a fixed number of workgroups (a few per CU), each of which takes
 // one (camera, strip) after the other from a queue until none is left.  There is one queue per XCD -- a contiguous eighth of the launch, so
@@ -2344,13 +2451,15 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         lkeys[tid] = kv;                                                   // entry 15 is no key (K <= 15): the next chunk of the grid scan, set per item
     }
     __syncthreads();
-    for (int e = tid; e < 3 * P; e += BBLOCK) {
-        const int ch = e / P, pr = e - ch * P, ilo = pr & ((1 << NB) - 1), ihi = pr >> NB;
-        const uint32_t klo = (ilo >= 1 && ilo <= K) ? lkeys[ilo - 1] : 0u, khi = (ihi >= 1 && ihi <= K) ? lkeys[ihi - 1] : 0u;
-        const int sh = 16 - 8 * ch;
-        const uint32_t vlo = (klo >> sh) & 255u, vhi = (khi >> sh) & 255u;
-        if constexpr (sizeof(OutT) == 4) tab[e] = make_float2((float)vlo, (float)vhi);
-        else tab[e] = vlo | (vhi << 8);
+    if constexpr (!is_mask<OutT>::value) {
+        for (int e = tid; e < 3 * P; e += BBLOCK) {
+            const int ch = e / P, pr = e - ch * P, ilo = pr & ((1 << NB) - 1), ihi = pr >> NB;
+            const uint32_t klo = (ilo >= 1 && ilo <= K) ? lkeys[ilo - 1] : 0u, khi = (ihi >= 1 && ihi <= K) ? lkeys[ihi - 1] : 0u;
+            const int sh = 16 - 8 * ch;
+            const uint32_t vlo = (klo >> sh) & 255u, vhi = (khi >> sh) & 255u;
+            if constexpr (sizeof(OutT) == 4) tab[e] = make_float2((float)vlo, (float)vhi);
+            else tab[e] = vlo | (vhi << 8);
+        }
     }
     BitCtx w;
     w.planes = planes;
@@ -2416,7 +2525,10 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         if constexpr (PERSIST) { if (tid == 0) claim_work(queue, (int)(c.n_img * c.strips), lkeys + 16, only, c.strips); }
         __syncthreads();
         if constexpr (sizeof(OutT) != 4) __builtin_amdgcn_s_setprio(0);
-        if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out_bits<BBLOCK, NB, OutT, EMIT>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, c.slices);
+        if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) {
+            if constexpr (is_mask<OutT>::value) write_out_masks<BBLOCK, OutT>(planes, c.slices, c.out, img, res, X0, TWp, wpr, tid);
+            else write_out_bits<BBLOCK, NB, OutT, EMIT>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, c.slices);
+        }
         if constexpr (!PERSIST) break;
     }
 #ifdef TDS_TESTING
@@ -2592,13 +2704,15 @@ __global__ void __launch_bounds__(BWAVES * 64) raster_list_bits_kernel(CommonArg
         lkeys[tid] = tid == 15 ? (uint32_t)BWAVES : kv;                    // entry 15: the next chunk of the lists
     }
     __syncthreads();
-    for (int e = tid; e < 3 * P; e += BBLOCK) {
-        const int ch = e / P, pr = e - ch * P, ilo = pr & ((1 << NB) - 1), ihi = pr >> NB;
-        const uint32_t klo = (ilo >= 1 && ilo <= K) ? lkeys[ilo - 1] : 0u, khi = (ihi >= 1 && ihi <= K) ? lkeys[ihi - 1] : 0u;
-        const int sh = 16 - 8 * ch;
-        const uint32_t vlo = (klo >> sh) & 255u, vhi = (khi >> sh) & 255u;
-        if constexpr (sizeof(OutT) == 4) tab[e] = make_float2((float)vlo, (float)vhi);
-        else tab[e] = vlo | (vhi << 8);
+    if constexpr (!is_mask<OutT>::value) {
+        for (int e = tid; e < 3 * P; e += BBLOCK) {
+            const int ch = e / P, pr = e - ch * P, ilo = pr & ((1 << NB) - 1), ihi = pr >> NB;
+            const uint32_t klo = (ilo >= 1 && ilo <= K) ? lkeys[ilo - 1] : 0u, khi = (ihi >= 1 && ihi <= K) ? lkeys[ihi - 1] : 0u;
+            const int sh = 16 - 8 * ch;
+            const uint32_t vlo = (klo >> sh) & 255u, vhi = (khi >> sh) & 255u;
+            if constexpr (sizeof(OutT) == 4) tab[e] = make_float2((float)vlo, (float)vhi);
+            else tab[e] = vlo | (vhi << 8);
+        }
     }
     BitCtx w;
     w.planes = planes;
@@ -2654,7 +2768,10 @@ __global__ void __launch_bounds__(BWAVES * 64) raster_list_bits_kernel(CommonArg
         if (!more) break;
     }
     __syncthreads();
-    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out_bits<BBLOCK, NB, OutT, false>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, nullptr);
+    if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) {
+        if constexpr (is_mask<OutT>::value) write_out_masks<BBLOCK, OutT>(planes, c.slices, c.out, img, res, X0, TWp, wpr, tid);
+        else write_out_bits<BBLOCK, NB, OutT, false>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, nullptr);
+    }
 }
 
 inline int bits_index_bits(int K) { return K <= 3 ? 2 : (K <= 7 ? 3 : 4); }
@@ -2682,6 +2799,12 @@ constexpr int64_t QUEUE_BYTES = 64;
 inline int64_t queue_offset(int64_t bytes) { return bytes < QUEUE_BYTES + 64 ? -1 : (bytes - QUEUE_BYTES) & ~(int64_t)63; }
 // the workspace that leaves `lists` bytes for the lists and room for the queues after them
 inline int64_t with_queue_tail(int64_t lists) { return ((lists + 63) & ~(int64_t)63) + QUEUE_BYTES + 64; }
+// what the lists may use of a workspace of `bytes` (0: none): all that lies before the queues -- and, in a mask call, before the channel table
+// (MASK_TABLE_BYTES right in front of the queues)
+inline int64_t lists_room(int64_t bytes, bool masks) {
+    const int64_t q = queue_offset(bytes);
+    return q < 0 ? 0 : (masks ? std::max<int64_t>(q - MASK_TABLE_BYTES, 0) : q);
+}
 
 // The workspace of the split form: a marker list (`poisoned`, n_img + 1 words) at 0, a count per camera, then `caps` poly records per camera,
 // each 16 bytes in `lists` (flags, P0, P1, P2) and 4 in `lists3` (P3).  The recommended workspace (tds_raster_scene_workspace_bytes*)
@@ -2824,7 +2947,25 @@ struct RasterPlan {
 };
 
 // A pure function of the call's shape and the knobs: no HIP call, no global.  tests/test_raster_plan.py pins its choices.
+inline bool is_mask_mode(int out_mode) { return out_mode == TDS_OUT_MASK_U8 || out_mode == TDS_OUT_MASK_BITS; }
+
 RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
+    // the masks take the plan of the uint8 image of the same shape; only their LDS is smaller (no pair table).  They are streamed out of the
+    // bit-plane kernels only.
+    if (is_mask_mode(in.out_mode)) {
+        PlanInput u8 = in;
+        u8.out_mode = TDS_OUT_U8;
+        RasterPlan p = plan_raster_scene(u8, k);
+        if (p.form == RasterForm::Bits || p.form == RasterForm::Split) {
+            const size_t tab = (size_t)3 * ((size_t)1 << (2 * p.nb)) * 4;
+            p.lds -= tab;
+            if (p.form == RasterForm::Split) p.lds_s -= tab;
+        } else if (p.form != RasterForm::Error) {
+            p.form = RasterForm::Error;
+            p.error = "tds_raster_scene_masks: the masks come from the bit-plane kernels only (at most %d distinct keys, listed by the caller)";
+        }
+        return p;
+    }
     RasterPlan p{};
     const int res = in.res, full = (res + 31) & ~31;
     p.tw = strip_width(res, k);
@@ -2925,7 +3066,7 @@ void launch(void (*kern)(P...), int64_t grid, int block, size_t lds, hipStream_t
 
 }  // namespace
 
-#ifdef TDS_TESTING
+#if defined(TDS_TESTING) && !defined(TDS_RASTER_MASKS_TU)
 // ---- testing build only (include/tdship.h, section "testing hooks"): absent from libtdship.so --------------------------------
 // force the strip width (0 = automatic)
 TDS_EXPORT int tds_raster_set_strip_width(int tw) {
@@ -2974,9 +3115,9 @@ TDS_EXPORT int tds_raster_set_debug(int flags) {
 TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices,
                                int64_t workspace_bytes, int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug,
                                tds_raster_plan_t *out) {
-    TDS_CHECK_ARG(out && n_img > 0 && res > 0 && res <= 4096 && n_keys >= -1 && n_keys <= MAX_KEYS && cus > 0 && (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8), "tds_raster_plan: bad arguments");
-    const int64_t qoff = queue_offset(workspace_bytes);
-    const PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, qoff < 0 ? 0 : qoff, cus};
+    TDS_CHECK_ARG(out && n_img > 0 && res > 0 && res <= 4096 && n_keys >= -1 && n_keys <= MAX_KEYS && cus > 0 &&
+                  (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode)), "tds_raster_plan: bad arguments");
+    const PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, lists_room(workspace_bytes, is_mask_mode(out_mode)), cus};
     const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug});
     *out = tds_raster_plan_t{(int)p.form, p.tw, p.strips, p.twp, p.nwv, p.nb, p.nwv == 4 ? (p.four_per_cu ? 4 : 3) : 0, want_slices && p.form == RasterForm::Bits,
                              p.four_per_cu, p.persist, p.tws, p.lw, (int64_t)p.lds, (int64_t)p.lds_s, p.grid, p.caps, p.ws.counts, p.ws.lists, p.ws.lists3};
@@ -2996,6 +3137,7 @@ static int common_checks(const char *fn, int64_t n_img, int res, int out_mode, c
     return TDS_OK;
 }
 
+#ifndef TDS_RASTER_MASKS_TU
 TDS_EXPORT int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes) {
     TDS_CHECK_ARG(bytes, "tds_raster_index_slices_bytes: null output");
     TDS_CHECK_ARG(n_img >= 0 && res > 0 && res <= 4096, "tds_raster_index_slices_bytes: bad sizes");
@@ -3021,6 +3163,11 @@ TDS_EXPORT int tds_raster_scene_workspace_bytes(int64_t n_img, int res, int64_t 
 TDS_EXPORT int tds_raster_scene_workspace_bytes_for(int64_t n_img, int res, int out_mode, int n_keys, int64_t *bytes) {
     TDS_CHECK_ARG(bytes, "tds_raster_scene_workspace_bytes_for: null output");
     TDS_CHECK_ARG(res > 0 && res <= 4096 && n_img >= 0, "tds_raster_scene_workspace_bytes_for: bad arguments");
+    if (is_mask_mode(out_mode)) {                // the uint8 image's workspace and the channel table in front of the queues
+        const int rc = tds_raster_scene_workspace_bytes_for(n_img, res, TDS_OUT_U8, n_keys, bytes);
+        if (rc == TDS_OK) *bytes += MASK_TABLE_BYTES;
+        return rc;
+    }
     TDS_CHECK_ARG(out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8, "tds_raster_scene_workspace_bytes_for: unknown output mode %d", out_mode);
     if (n_keys < 0 || n_keys > MAX_KEYS) return tds_raster_scene_workspace_bytes(n_img, res, bytes);
     // the bit-plane kernels: face lists where the split form can run for this output type, the work queues of the persistent launch always
@@ -3032,6 +3179,7 @@ TDS_EXPORT int tds_raster_scene_workspace_bytes_for(int64_t n_img, int res, int 
     *bytes = with_queue_tail(lists);
     return TDS_OK;
 }
+#endif  // !TDS_RASTER_MASKS_TU
 
 namespace {
 // what the scene kernels need to know about the static map(s) of a launch
@@ -3045,14 +3193,21 @@ struct MapSource {
 };
 int raster_scene_impl(const MapSource &ms, const float *state, const float *agent_sc, const float *tmpl, const uint32_t *actor_key, const uint8_t *mask,
                       const float *cam_xy, const float *cam_sc, int64_t B, int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out,
-                      void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream);
+                      void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream,
+                      const uint32_t *key_channels = nullptr, int n_channels = 0);
+#ifdef TDS_RASTER_MASKS_TU
+int launch_masks(const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff, int out_mode, hipStream_t s);
+__global__ void put_mask_table_kernel(uint32_t *dst, MaskTable t);
+#endif
 }  // namespace
 
+#ifndef TDS_RASTER_MASKS_TU
 TDS_EXPORT int tds_raster_scene(const tds_map_t *map, const float *state, const float *agent_sc, const float *tmpl,
                                 const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc, int64_t B,
                                 int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out, void *workspace,
                                 int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream) {
     TDS_CHECK_ARG(map, "tds_raster_scene: null map");
+    TDS_CHECK_ARG(!is_mask_mode(out_mode), "tds_raster_scene: the mask modes are served by tds_raster_scene_masks");
     MapSource ms;
     ms.one = map->view; ms.views = nullptr; ms.scene_map = nullptr; ms.uniq_keys = map->uniq_keys; ms.n_uniq = map->n_uniq;
     ms.renders = map->n_levels > 0 || map->view.nx == 0;
@@ -3066,23 +3221,61 @@ TDS_EXPORT int tds_raster_scene_multi(const tds_mapset_t *set, const int32_t *sc
                                       int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream) {
     TDS_CHECK_ARG(set && set->n > 0, "tds_raster_scene_multi: null or empty map set");
     TDS_CHECK_ARG(scene_map || B == 0, "tds_raster_scene_multi: null scene -> map index array");
+    TDS_CHECK_ARG(!is_mask_mode(out_mode), "tds_raster_scene_multi: the mask modes are served by tds_raster_scene_masks_multi");
     MapSource ms;
     ms.one = tds::MapView{}; ms.views = set->d_views; ms.scene_map = scene_map; ms.uniq_keys = set->uniq_keys; ms.n_uniq = set->n_uniq;
     ms.renders = set->n_levels > 0;
     return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
                              actor_keys, n_actor_keys, actor_key_per_camera, extra_tri, extra_key, n_extra, aux, stream);
 }
+#else
+TDS_EXPORT int tds_raster_scene_masks(const tds_map_t *map, const float *state, const float *agent_sc, const float *tmpl,
+                                      const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc, int64_t B,
+                                      int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out, void *workspace,
+                                      int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, const float *extra_tri, const uint32_t *extra_key,
+                                      int64_t n_extra, const uint32_t *key_channels, int n_channels, tds_raster_aux_t *aux, void *stream) {
+    TDS_CHECK_ARG(map, "tds_raster_scene_masks: null map");
+    TDS_CHECK_ARG(is_mask_mode(out_mode), "tds_raster_scene_masks: unknown output mode %d (TDS_OUT_MASK_U8 or TDS_OUT_MASK_BITS)", out_mode);
+    MapSource ms;
+    ms.one = map->view; ms.views = nullptr; ms.scene_map = nullptr; ms.uniq_keys = map->uniq_keys; ms.n_uniq = map->n_uniq;
+    ms.renders = map->n_levels > 0 || map->view.nx == 0;
+    return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
+                             actor_keys, n_actor_keys, 0, extra_tri, extra_key, n_extra, aux, stream, key_channels, n_channels);
+}
+
+TDS_EXPORT int tds_raster_scene_masks_multi(const tds_mapset_t *set, const int32_t *scene_map, const float *state, const float *agent_sc, const float *tmpl,
+                                            const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc, int64_t B,
+                                            int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out, void *workspace,
+                                            int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, const float *extra_tri, const uint32_t *extra_key,
+                                            int64_t n_extra, const uint32_t *key_channels, int n_channels, tds_raster_aux_t *aux, void *stream) {
+    TDS_CHECK_ARG(set && set->n > 0, "tds_raster_scene_masks_multi: null or empty map set");
+    TDS_CHECK_ARG(scene_map || B == 0, "tds_raster_scene_masks_multi: null scene -> map index array");
+    TDS_CHECK_ARG(is_mask_mode(out_mode), "tds_raster_scene_masks_multi: unknown output mode %d (TDS_OUT_MASK_U8 or TDS_OUT_MASK_BITS)", out_mode);
+    MapSource ms;
+    ms.one = tds::MapView{}; ms.views = set->d_views; ms.scene_map = scene_map; ms.uniq_keys = set->uniq_keys; ms.n_uniq = set->n_uniq;
+    ms.renders = set->n_levels > 0;
+    return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
+                             actor_keys, n_actor_keys, 0, extra_tri, extra_key, n_extra, aux, stream, key_channels, n_channels);
+}
+#endif  // TDS_RASTER_MASKS_TU
 
 namespace {
 int raster_scene_impl(const MapSource &ms, const float *state, const float *agent_sc, const float *tmpl, const uint32_t *actor_key, const uint8_t *mask,
                       const float *cam_xy, const float *cam_sc, int64_t B, int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out,
-                      void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream) {
+                      void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream,
+                      const uint32_t *key_channels, int n_channels) {
     TDS_CHECK_ARG(B >= 0 && Nc >= 0 && N >= 0 && N < (1 << 20), "tds_raster_scene: bad sizes");
     if (aux) { aux->n_keys = 0; aux->index_bits = 0; }
     TDS_CHECK_ARG(ms.renders, "tds_raster_scene: the map was created without rendering data");
+    const bool masks = is_mask_mode(out_mode);
+    if (masks) {
+        TDS_CHECK_ARG(n_channels >= 1 && n_channels <= 32 && key_channels, "tds_raster_scene_masks: 1 to 32 channels and their key_channels array");
+        TDS_CHECK_ARG(!(aux && aux->index_slices), "tds_raster_scene_masks: index slices belong to the colour image");
+        TDS_CHECK_ARG((N == 0 && n_extra == 0) || (actor_keys && n_actor_keys > 0), "tds_raster_scene_masks: the actors' keys must be listed");
+    }
     int64_t n_img = B * Nc;
     int tw = 0;
-    int rc = common_checks("tds_raster_scene", n_img, res, out_mode, out, tw);
+    int rc = common_checks("tds_raster_scene", n_img, res, masks ? TDS_OUT_U8 : out_mode, out, tw);
     if (rc != TDS_OK) return rc;
     if (n_img == 0) return TDS_OK;
     TDS_CHECK_ARG(cam_xy && cam_sc, "tds_raster_scene: null camera arrays");
@@ -3108,14 +3301,14 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
         if (kt.n == MAX_KEYS) ok = false; else kt.key[kt.n++] = key;
     };
     for (int i = 0; i < ms.n_uniq; ++i) add(ms.uniq_keys[i]);
-    for (int i = 0; i < (listed && (N > 0 || n_extra > 0) ? n_actor_keys : 0); ++i) add(actor_keys[i]);
+    for (int i = 0; i < (listed && (N > 0 || n_extra > 0 || masks) ? n_actor_keys : 0); ++i) add(actor_keys[i]);
     for (int i = kt.n; i < 16; ++i) kt.key[i] = 0xffffffffu;
     for (int i = 1; i < kt.n; ++i)                                   // insertion sort
         for (int j = i; j > 0 && kt.key[j - 1] > kt.key[j]; --j) { uint32_t t = kt.key[j]; kt.key[j] = kt.key[j - 1]; kt.key[j - 1] = t; }
     // the plan (the work queues of a persistent launch take the tail of the workspace: what the lists may use ends before them)
     const hipStream_t s = (hipStream_t)stream;
     const int64_t qoff = workspace ? queue_offset(workspace_bytes) : -1;
-    const PlanInput in = {n_img, res, out_mode, ok ? kt.n : -1, listed, N > 0, n_extra > 0, want_slices, qoff < 0 ? 0 : qoff, launch_cus(s)};
+    const PlanInput in = {n_img, res, out_mode, ok ? kt.n : -1, listed, N > 0, n_extra > 0, want_slices, workspace ? lists_room(workspace_bytes, masks) : 0, launch_cus(s)};
     const RasterPlan p = plan_raster_scene(in, g_knobs);
     if (aux && p.nb) { aux->n_keys = kt.n; aux->index_bits = p.nb; for (int i = 0; i < 16; ++i) aux->keys[i] = i < kt.n ? kt.key[i] : 0u; }
     if (p.form == RasterForm::Error) { tds::set_error(p.error, MAX_KEYS); return TDS_ELIMIT; }
@@ -3128,6 +3321,20 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     cm.strips = p.strips; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (aux && (aux->flags & TDS_RASTER_NO_TRIM)) ? 1 : 0;
     char *const ws = (char *)workspace;
+#ifdef TDS_RASTER_MASKS_TU
+    // (this translation unit serves the mask entry points only: raster_masks.hip)
+    TDS_CHECK_ARG(masks && qoff >= MASK_TABLE_BYTES, "tds_raster_scene_masks: needs a workspace (tds_raster_scene_workspace_bytes_for with the mask mode)");
+    // channel c = the union of the planes of the keys whose key_channels word has bit c (key_channels is aligned with the key table)
+    MaskTable mt{};
+    mt.w[0] = (uint32_t)n_channels;
+    for (int k = 0; k < kt.n; ++k)
+        for (int ch = 0; ch < n_channels; ++ch)
+            if ((key_channels[k] >> ch) & 1u) mt.w[1 + ch] |= 1u << k;
+    cm.slices = (uint32_t *)(ws + qoff - MASK_TABLE_BYTES);
+    hipLaunchKernelGGL(put_mask_table_kernel, dim3(1), dim3(MASK_TABLE_DW), 0, s, cm.slices, mt);
+    TDS_LAUNCH_CHECK("put_mask_table_kernel");
+    return launch_masks(p, a, cm, kt, ws, qoff, out_mode, s);
+#else
     if (p.form == RasterForm::Split || p.form == RasterForm::Bits) {
         const uint32_t *only = nullptr;              // Split: the bit-plane launch runs over the cameras K3s marked (normally none)
         if (p.form == RasterForm::Split) {
@@ -3180,9 +3387,11 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     with_out(out_mode, [&](auto t) { with_tw(p.tw, [&](auto tw) { launch(raster_scene_kernel<tw, decltype(t)>, p.grid, RBLOCK, lds_bytes(tw, res), s, a, cm); }); });
     TDS_LAUNCH_CHECK("raster_scene_kernel");
     return TDS_OK;
+#endif  // TDS_RASTER_MASKS_TU
 }
 }  // namespace
 
+#ifndef TDS_RASTER_MASKS_TU
 TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int32_t *faces, int64_t n_img, int64_t V, int64_t F,
                                const float *cam_xy, const float *cam_sc, const float *levels, int n_levels, float scale, int res,
                                int out_mode, void *out, int flags, void *stream) {
@@ -3209,3 +3418,49 @@ TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int
     TDS_LAUNCH_CHECK("raster_mesh_kernel");
     return TDS_OK;
 }
+#else
+// ---- semantic masks: the launches of tds_raster_scene_masks(_multi) (raster_masks.hip) ------------------------------------------------
+namespace {
+__global__ void put_mask_table_kernel(uint32_t *dst, MaskTable t) {
+    if (threadIdx.x < (unsigned)MASK_TABLE_DW) dst[threadIdx.x] = t.w[threadIdx.x];
+}
+
+// the launches of raster_scene_impl's bit-plane branch, with the mask tags for the output type (the plan is the uint8 image's)
+int launch_masks(const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff, int out_mode, hipStream_t s) {
+    auto with_mask = [&](auto f) { if (out_mode == TDS_OUT_MASK_BITS) f(MaskBits()); else f(MaskU8()); };
+    const int64_t n_img = cm.n_img;
+    const uint32_t *only = nullptr;
+    if (p.form == RasterForm::Split) {
+        uint32_t *poisoned = (uint32_t *)ws, *counts = (uint32_t *)(ws + p.ws.counts), *lists3 = (uint32_t *)(ws + p.ws.lists3);
+        uint4 *lists = (uint4 *)(ws + p.ws.lists);
+        if (tds::zero_async(poisoned, 4, s) != hipSuccess) { tds::set_error("tds_raster_scene_masks: clearing the workspace failed"); return TDS_EHIP; }
+        CommonArgs cs = cm, cr = cm;
+        cs.strips = 1; cr.strips = (cm.res + p.tws - 1) / p.tws;
+        auto scan = [&](auto kern, const auto &args) { launch(kern, (n_img + SCAN_WAVES - 1) / SCAN_WAVES, SCAN_WAVES * 64, 0, s, args, cs, kt, counts, lists, lists3, (int)p.caps, poisoned); };
+        if (a.K != 0) scan(scan_faces_kernel<SceneArgsEx>, a); else scan(scan_faces_kernel<SceneArgs>, (const SceneArgs &)a);
+        TDS_LAUNCH_CHECK("scan_faces_kernel");
+        auto go = [&](auto kern) { launch(kern, n_img * cr.strips, p.lw * 64, p.lds_s, s, cr, kt, p.tws, (const uint32_t *)counts, (const uint4 *)lists, (const uint32_t *)lists3, (int)p.caps); };
+        with_mask([&](auto t) {
+            if (p.lw == 2) with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 2>); });
+            else with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 4>); });
+        });
+        TDS_LAUNCH_CHECK("raster_list_bits_kernel");
+        only = poisoned;
+    }
+    uint32_t *const queue = p.persist ? (uint32_t *)(ws + qoff) : nullptr;
+    if (p.persist && tds::zero_async(queue, (size_t)QUEUE_BYTES, s) != hipSuccess) { tds::set_error("tds_raster_scene_masks: clearing the work queues failed"); return TDS_EHIP; }
+    auto go = [&](auto kern, const auto &args) { launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cm, kt, p.twp, queue, only); };
+    with_mask([&](auto t) {
+        using T = decltype(t);
+        if (p.four_per_cu)
+            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>, false, 4>, args); }); });
+        else if (p.nwv == 4)
+            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>>, args); }); });
+        else
+            with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<8, nb, T, SceneArgsEx>, a); });
+    });
+    TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
+    return TDS_OK;
+}
+}  // namespace
+#endif  // TDS_RASTER_MASKS_TU

@@ -126,6 +126,32 @@ class HipRenderer(BirdviewRenderer):
         return _ops.raster_scene(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, res.height, out_dtype=self.out_dtype,
                                  key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out)
 
+    def render_scene_masks(self, static_map, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor, camera_xy: Tensor,
+                           camera_sc: Tensor, key_channels: Dict[int, int], n_channels: int, res: Optional[Resolution] = None,
+                           fov: Optional[float] = None, key_table=(), extra_tri: Optional[Tensor] = None, extra_key: Optional[Tensor] = None,
+                           packed: bool = False, out: Optional[Tensor] = None) -> Tensor:
+        """Semantic masks of the scene `render_scene` draws: B x Nc x C x H x W bool (packed: B x Nc x C x ceil(W/32) x H int32 words, see
+        `unpack_mask_bits`).  Channel c is set wherever the image would paint a face whose key k has bit c in key_channels[k], whatever is drawn
+        over it.  `key_table`: the actors' distinct keys.  Never differentiable; `out`: a caller-owned tensor of that shape and dtype."""
+        res = self.res if res is None else res
+        if res.width != res.height:
+            raise RuntimeError('only square resolutions are supported')
+        fov = fov if fov is not None else 2.0 / self.scale
+        return _ops.raster_scene_masks(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, res.height, key_table,
+                                       key_channels, n_channels, packed=packed, out=out, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim)
+
+
+def unpack_mask_bits(words: Tensor, res: int) -> Tensor:
+    """The packed masks (..., ceil(res/32), res) of 32-bit words -> (..., res, res) bool: element [..., x, y] is bit x % 32 of word
+    [..., x // 32, y] (the memory order of the unpacked masks and of the RGB images)."""
+    res = int(res)
+    wpw = (res + 31) // 32
+    if words.shape[-2:] != (wpw, res):
+        raise ValueError(f'packed masks of {res} x {res} pixels end in ({wpw}, {res}), got {tuple(words.shape)}')
+    shifts = torch.arange(32, device=words.device, dtype=torch.int64)
+    bits = (words.to(torch.int64).unsqueeze(-2) >> shifts[:, None]) & 1            # (..., wpw, 32, res)
+    return bits.reshape(words.shape[:-2] + (wpw * 32, res))[..., :res, :].to(torch.bool)
+
 
 class _DeviceTimer:
     """what allocate_image_ring measures, on the device (tests inject their own timer with the same three methods)"""

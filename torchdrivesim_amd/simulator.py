@@ -975,6 +975,117 @@ class Simulator:
                            waypoints=waypoints, waypoints_rendering_mask=waypoints_mask, noisy_perception=noisy_perception, _camera_sc=cam_sc,
                            out=out, _ego=ego_rotate)
 
+    # ------------------------------------------------------------------------------------------------- semantic masks
+    def _category_keys(self, scene) -> Dict[str, int]:
+        """category -> its key in this scene's launches (rank of its rendering level << 24 | its colour, as _scene() builds them), for every
+        category with a level and a colour whose level the map's level table holds"""
+        lv, cm, smap = self.renderer.rendering_levels, self.renderer.color_map, scene['map']
+        out = {}
+        for n in lv:
+            if n not in cm:
+                continue
+            try:
+                rank = smap.rank_of(lv[n])
+            except ValueError:                                       # a level this scene never draws at
+                continue
+            out[n] = (rank << 24) | int(_ops.quantise_colors(torch.tensor(cm[n], dtype=torch.float32) / 255.0))
+        return out
+
+    def semantic_channels(self) -> List[str]:
+        """The default channels of `render_semantic`: one per category that has a key in this scene (map faces, agent types and their
+        direction triangle, traffic controls, waypoint goals), from the lowest-priority rendering level (road) to the highest (direction),
+        ties broken by name."""
+        if not isinstance(self.renderer, HipRenderer):
+            raise NotImplementedError(f'semantic masks are rendered by HipRenderer only, not by {type(self.renderer).__name__}')
+        scene = self._scene()
+        present = set(scene['map'].face_keys() or ()) | set(scene['key_table'])
+        if self.waypoint_goals is not None:
+            present.add(scene['wp_key'])
+        lv = self.renderer.rendering_levels
+        return sorted((n for n, k in self._category_keys(scene).items() if k in present), key=lambda n: (-float(lv[n]), n))
+
+    def _semantic_spec(self, scene, channels):
+        """channels (names or collections of names) -> (the channels as tuples, key -> channel set)"""
+        chans = [(c,) if isinstance(c, str) else tuple(c) for c in (self.semantic_channels() if channels is None else channels)]
+        if not 1 <= len(chans) <= 32:
+            raise ValueError(f'semantic masks take 1 to 32 channels, got {len(chans)}')
+        lv, cm = self.renderer.rendering_levels, self.renderer.color_map
+        keys = self._category_keys(scene)
+        key_channels = {}
+        for i, cats in enumerate(chans):
+            for name in cats:
+                if name not in lv or name not in cm:
+                    raise ValueError(f'unknown category {name!r} in channel {i} (categories: {sorted(n for n in lv if n in cm)})')
+            for name in cats:
+                k = keys.get(name)
+                if k is None:
+                    continue                                         # valid, but never drawn with this map: an all-zero contribution
+                for other, ko in keys.items():
+                    if ko == k and other not in cats:
+                        raise ValueError(f'channel {i} names {name!r}, which shares its key (colour and rendering level) with {other!r}, '
+                                         f'which the channel does not name')
+                key_channels[k] = key_channels.get(k, 0) | (1 << i)
+        return chans, key_channels
+
+    def render_semantic(self, camera_xy: Tensor, camera_psi: Tensor, channels=None, res: Optional[Resolution] = None, fov: Optional[float] = None,
+                        rendering_mask: Optional[Tensor] = None, waypoints: Optional[Tensor] = None, waypoints_rendering_mask: Optional[Tensor] = None,
+                        packed: bool = False, out: Optional[Tensor] = None, _camera_sc: Optional[Tensor] = None) -> Tensor:
+        """Semantic bird's-eye masks for the cameras of `render` -> BxNcxCxHxW bool (packed: BxNcxCxceil(W/32)xH int32 words,
+        `rendering.unpack_mask_bits`).  `channels`: a list of C <= 32 entries, each a category name or a collection of names (their union);
+        default `semantic_channels()`.  Channel c is set at a pixel exactly where `render` would paint a face of one of its categories -- the
+        same faces, masks, stop lines, light states and waypoint discs -- whatever is drawn over it (a road channel stays set under a car).
+        Categories map to keys through the renderer's colour map and rendering levels; agents take the colour of their type.  A category that
+        this scene never draws gives an all-zero channel; an unknown name, or a category that shares its colour and level with one the channel
+        does not name, is a ValueError.  A plain launch on the current stream, never differentiable; `out`: a caller-owned tensor of the result's
+        shape and dtype.  HipRenderer only."""
+        if not isinstance(self.renderer, HipRenderer):
+            raise NotImplementedError(f'semantic masks are rendered by HipRenderer only, not by {type(self.renderer).__name__}')
+        scene = self._scene()
+        chans, key_channels = self._semantic_spec(scene, channels)
+        camera_sc = _camera_sc if _camera_sc is not None else torch.cat([torch.sin(camera_psi), torch.cos(camera_psi)], dim=-1)
+        if camera_xy.dim() == 2:
+            camera_xy, camera_sc = camera_xy.unsqueeze(1), camera_sc.unsqueeze(1)
+        n_cam = camera_xy.shape[-2]
+        present = self.get_all_agent_present_mask()
+        mask = present.unsqueeze(-2).expand(present.shape[:-1] + (n_cam,) + present.shape[-1:])
+        if rendering_mask is not None:
+            mask = mask.logical_and(rendering_mask.to(torch.bool))
+        state, tmpl, ctrl = self.get_all_agent_state().detach(), scene['tmpl'], scene['ctrl']
+        keys, ktab = scene['keys'], scene['key_table']
+        if ctrl is not None:                                        # stop lines and lights ride along as extra quads, as in render()
+            state = torch.cat([state, ctrl['state'].to(state.dtype)], dim=1)
+            tmpl = torch.cat([tmpl, ctrl['tmpl'].to(tmpl.dtype)], dim=1)
+            mask = torch.cat([mask, torch.ones(mask.shape[:-1] + (ctrl['state'].shape[1],), dtype=torch.bool, device=mask.device)], dim=-1)
+            keys = torch.cat([keys, self._control_keys(scene)], dim=-2).contiguous()
+        agent_sc = self._heading_sc() if ctrl is None else _ops.heading_sc(state[..., 2])
+        extra = dict()
+        if waypoints is not None and waypoints.shape[2] > 0:
+            wp_tri, _ = self._waypoint_triangles(waypoints.to(state.dtype), waypoints_rendering_mask)
+            extra = dict(extra_tri=wp_tri, extra_key=torch.full(wp_tri.shape[:3], scene['wp_key'], dtype=torch.int32, device=state.device))
+            ktab = sorted(set(ktab) | {scene['wp_key']})
+        return self.renderer.render_scene_masks(scene['map'], state, agent_sc, tmpl, keys, mask.contiguous(), camera_xy, camera_sc, key_channels,
+                                                len(chans), res=res, fov=fov, key_table=ktab, packed=packed, out=out, **extra)
+
+    def render_egocentric_semantic(self, ego_rotate: bool = True, channels=None, res: Optional[Resolution] = None, fov: Optional[float] = None,
+                                   visibility_matrix: Optional[Tensor] = None, n_subsequent_waypoints: int = 1, packed: bool = False,
+                                   out: Optional[Tensor] = None) -> Tensor:
+        """`render_semantic` with one camera per exposed agent, the cameras, masks and waypoint goals of `render_egocentric` -> BxAxCxHxW."""
+        state = self.get_state()
+        camera_xy, camera_psi = state[..., :2], state[..., 2:3]
+        if not ego_rotate:
+            camera_psi = torch.ones_like(camera_psi) * (np.pi / 2)
+        rendering_mask = visibility_matrix
+        if self.cfg.single_agent_rendering:
+            A, total = self.agent_count, self.agent_count + self.npc_count
+            rendering_mask = torch.eye(A, total, dtype=torch.bool, device=state.device).unsqueeze(0).expand(self.batch_size, -1, -1)
+        cam_sc = None
+        if ego_rotate:
+            cam_sc = self._heading_sc()[..., :self.agent_count, :]
+        waypoints = self.get_waypoints(count=n_subsequent_waypoints)
+        waypoints_mask = self.get_waypoints_mask(count=n_subsequent_waypoints) if waypoints is not None else None
+        return self.render_semantic(camera_xy, camera_psi, channels=channels, rendering_mask=rendering_mask, res=res, fov=fov, waypoints=waypoints,
+                                    waypoints_rendering_mask=waypoints_mask, packed=packed, out=out, _camera_sc=cam_sc)
+
     # ------------------------------------------------------------------------------------------------- infractions
     def compute_offroad(self) -> Tensor:
         """BxA off-road loss = thresholded squared corner-to-mesh distance x present (simulator.py:1035-1044).
