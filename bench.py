@@ -4,7 +4,12 @@ Headline benchmark (BASELINE.json): agent-steps/s of the GymEnv.step body (examp
     Simulator.step(action) -> render_egocentric(256x256, fov 35 m) -> compute_collision() -> compute_offroad()
 at B = 1024 scenes x A = 64 agents per GPU on the Town01 map (tests/golden/town01_mesh.npz), synthetic agents.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does what the headline needs and nothing else: it sets up (simulator, image ring), warms up, times the K steps, writes its
+outputs if asked and prints the line, whose `roofline` holds only what the timed launches and the set-up measured anyway.  `--full` adds
+everything that takes runs of its own: the same-run write rates of the output buffer (`roofline.measured_*`) and, with N = 1, `mixed_maps`,
+`default_path`, `roofline_u8 / _128 / _64`, `configs` and `cpu_baseline` (`--no-configs`, `--no-default-path`, `--no-cpu-baseline` leave
+entries out of a full run).
 One process per GPU; the scene batch is sharded (B per GPU is fixed: weak scaling) and there is NO data-path collective.
 N > 1 runs either way:
   * `python bench.py --gpus N ...` by itself: this process never touches a GPU; it starts N children (one per GPU, each with
@@ -673,14 +678,19 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=1024, help='scenes per GPU')
     ap.add_argument('--agents', type=int, default=64)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-configs', action='store_true', help="skip the extra `configs` / `roofline_u8` entries (BASELINE.json's configs 2, 3, 5; N = 1 only)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure everything else the line can carry: the same-run write rates of the output buffer and, '
+                         'with N = 1, mixed_maps, default_path, roofline_u8 / _128 / _64, configs and cpu_baseline (a plain run does none of them)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the `cpu_baseline` entry')
+    ap.add_argument('--no-configs', action='store_true',
+                    help="with --full: skip the extra `mixed_maps` / `roofline_u8` / `roofline_128` / `roofline_64` / `configs` entries (BASELINE.json's "
+                         "configs 2, 3, 5; N = 1 only)")
     ap.add_argument('--cpu-scenes', type=int, default=768, help='scenes of the CPU-baseline sample (all usable cores, about 10 s at 16 of them); the single-thread run uses 16')
     ap.add_argument('--overlap', choices=('reserved', 'stream', 'off'), default='reserved',
                     help="where compute_collision / compute_offroad run: 'reserved' (default) -- the loop runs on a stream that is kept off 4 CUs per XCD and the "
                          "metrics on a stream confined to those 32 CUs, beside the raster launch (Simulator.overlap_infractions = 'reserved'); 'stream' -- a plain "
                          "second stream (slower: nothing fits beside the persistent launch); 'off' -- behind the launch on the caller's stream")
-    ap.add_argument('--no-default-path', action='store_true', help='skip the `default_path` entry (the loop without out=; N = 1 only)')
+    ap.add_argument('--no-default-path', action='store_true', help='with --full: skip the `default_path` entry (the loop without out=; N = 1 only)')
     ap.add_argument('--ring-candidates', type=int, default=4, help='output allocations probed at most for the two-buffer image ring')
     ap.add_argument('--dry-run', action='store_true', help='no GPU, no kernels: exercises launch, barrier, reduction and the JSON line only')
     ap.add_argument('--launch-timeout', type=float, default=1500.0)
@@ -777,7 +787,7 @@ def main():
         # at 7/8 of the rate for as long as it lives; DESIGN_HISTORY.md section 4): the buffers come from the library's allocator, which spreads the
         # pages out (csrc/alloc.hip), and allocate_image_ring still measures every candidate against the fill_ rate of the same run; what
         # it saw is reported per rank (`roofline.ring_probe`, `per_rank`).  The reference-shaped call without `out=` is measured after the
-        # timed region and reported beside (`default_path`).
+        # timed region and reported beside (`default_path`, --full).
         from torchdrivesim_amd.rendering import allocate_image_ring
         # The metrics run BESIDE the raster launch: the loop's stream (sim.raster_stream()) is kept off four CUs per XCD -- the write-bound launch loses
         # nothing on 224 of 256 CUs -- and the metric kernels, foreseen from the previous step, are enqueued on a stream confined to those 32 CUs
@@ -836,7 +846,8 @@ def main():
         traffic, traffic_note = stamped_traffic(B, A)
         same_run = {}
         if not args.dry_run:
-            same_run = same_run_write_roofs(sim, bufs[0], res, device)
+            if args.full:
+                same_run = same_run_write_roofs(sim, bufs[0], res, device)
             same_run['first_touch_ms'] = first_touch_ms
             same_run['ring_probe'] = ring_probe
             same_run['timed_raster_calls'] = [first_call, first_call + args.steps]     # [first, end) among this process's raster launches
@@ -852,12 +863,13 @@ def main():
                           kernel='raster_scene_bits_kernel', avg_launch_ms=raster_ms, algorithmic_bytes_per_launch=B * A * ALGO_BYTES_PER_IMAGE,
                           **same_run))
         line['methodology'] = ('images are rendered into a two-buffer ring the loop owns (rendering.allocate_image_ring: buffers from the library\'s '
-                               'allocator, each measured against the fill_ rate of the same run; `roofline.ring_probe`); `default_path` is the same '
-                               'loop with the reference-shaped call render_egocentric() without out= (a fresh tensor per step from the image pool); '
+                               'allocator, each measured against the fill_ rate of the same run; `roofline.ring_probe`); `default_path` (--full) is the '
+                               'same loop with the reference-shaped call render_egocentric() without out= (a fresh tensor per step from the image pool); '
                                + {'reserved': 'the loop runs on a stream kept off 4 CUs per XCD (224 of 256 CUs for the raster launch) and the metric kernels on a '
                                               'stream confined to those 32 CUs, beside the launch (Simulator.overlap_infractions = \'reserved\'; --overlap off: behind it)',
                                   'stream': 'the metric kernels on a plain second stream', 'off': 'the metric kernels behind the raster launch on the same stream'}[args.overlap])
         line['overlap'] = args.overlap
+        line['full'] = args.full                                          # False: the entries of a full run are absent, not failed
         line['distinct_devices'] = distinct_devices(all_reports)          # N ranks on N GPUs <=> distinct_devices == n_gpus
         if world == 1:
             line['device_identity'] = all_reports[0]['device_identity']
@@ -869,7 +881,7 @@ def main():
         if args.dry_run:
             line['dry_run'] = True
             line['data'] = 'none (dry run: no kernels were launched, the value is meaningless)'
-        if world == 1 and not args.dry_run:
+        if world == 1 and not args.dry_run and args.full:
             if not args.no_configs:
                 line['mixed_maps'] = mixed_maps_mode(device, args.steps, args.warmup, B, A, args.overlap, line['ms_per_step'], bufs)
                 torch.cuda.set_stream(loop_stream)

@@ -81,6 +81,18 @@ def test_single_process_dry_run_and_torchrun_shape():
     check_line(line, 1, 2, 1)
 
 
+def test_the_line_says_whether_the_run_was_full():
+    """a plain run and a --full one give the same headline fields; the line records which it was (the GPU side: tests/test_gpu_bench_workers.py)"""
+    plain = run_bench('--steps', '2', '--warmup', '1', '--dry-run')
+    full = run_bench('--steps', '2', '--warmup', '1', '--dry-run', '--full')
+    for line in (plain, full):
+        check_line(line, 1, 2, 1)
+    assert plain['full'] is False and full['full'] is True
+    line = run_bench('--gpus', '2', '--steps', '1', '--warmup', '0', '--dry-run', '--full', env=TWO_DEVICES)
+    check_line(line, 2, 1, 0)
+    assert line['full'] is True
+
+
 def test_the_barrier_falls_back_to_gloo_when_rccl_cannot_come_up():
     """The process group only carries the barrier and the timing reductions.  Under an external launcher the worker asks for RCCL; where that
     fails both ranks must fall back to gloo and still deliver the line.  It fails here on every rank, GPU or not: the ranks name local devices

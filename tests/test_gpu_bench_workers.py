@@ -5,7 +5,7 @@
   * under `python -m torch.distributed.run --nproc-per-node 2`: the worker asks for RCCL; two ranks on one GPU is something RCCL may refuse
     (duplicate device) -- then every rank must agree on gloo -- or serve; either way ONE well-formed line comes out.
 Two ranks share the GPU, so the rates are not a scaling measurement; what is checked is that the sharded path runs kernels and reports.
-Also here: what --dump-outputs writes, from a single-process run."""
+Also here, from single-process runs: what --dump-outputs writes, and which entries a plain run and a --full one carry."""
 import json
 import os
 import socket
@@ -87,6 +87,31 @@ def test_four_real_workers_on_one_gpu():
     assert all(i['uuid'] not in (None, 'None') or i['pci'] for i in ids) and all(i['arch'].startswith('gfx950') and i['compute_units'] > 0 for i in ids)
     assert len({(i['uuid'], i['pci']) for i in ids}) == 1 and line['distinct_devices'] == 1
     assert all(i['reserved_usable'] in (True, False) for i in ids)
+
+
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest():
+    """A plain run sets up, warms up, times its steps and reports what those measured (the roofline from the timed launches, the image ring's
+    probe); the entries that take runs of their own come with --full, and --no-default-path / --no-configs / --no-cpu-baseline still thin it"""
+    base = ['--batch', '32', '--agents', '16', '--steps', '2', '--warmup', '1', '--ring-candidates', '2']
+    extras = ('mixed_maps', 'default_path', 'roofline_u8', 'roofline_128', 'roofline_64', 'configs', 'cpu_baseline')
+    same_run = ('measured_fill_gbs', 'measured_stream_gbs', 'measured_stream_ms')
+    lines = []
+    for more in ([], ['--full', '--no-configs', '--no-cpu-baseline']):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *base, *more], capture_output=True, text=True, timeout=900, env=clean_env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, r.stdout
+        lines.append(json.loads(out[0]))
+    plain, full = lines
+    for line in (plain, full):
+        assert line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+        roof = line['roofline']
+        assert roof['avg_launch_ms'] > 0 and roof['frac'] > 0 and roof['first_touch_ms'] > 0 and len(roof['ring_probe']['kept']) == 2
+        assert roof['timed_raster_calls'][1] - roof['timed_raster_calls'][0] == 2
+    assert plain['full'] is False and not any(k in plain for k in extras) and not any(k in plain['roofline'] for k in same_run)
+    assert full['full'] is True and all(full['roofline'][k] > 0 for k in same_run)
+    assert full['default_path']['ms_per_step'] > 0 and full['default_path']['avg_launch_ms'] > 0
+    assert not any(k in full for k in extras if k != 'default_path')
 
 
 def test_dump_outputs_are_the_last_timed_step(tmp_path):

@@ -10,16 +10,16 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # the same command without the profiler, before and after the traced run: rocprofv3's tracing slows this kernel by 1 % on some boxes and by 7 - 16 % on
 # others (DESIGN_HISTORY.md section 4), so the committed trace comes with the plain figures of the same box and minute
-python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-configs > $OUT/bench_plain_before.log 2>/dev/null
+python3 $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-configs > $OUT/bench_plain_before.log 2>/dev/null
 for try in 1 2; do          # two traced runs: the launch time of this kernel differs from process to process on one box (7.2 - 7.9 ms); both are kept
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-configs > $OUT/bench_under_rocprof_$try.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-configs > $OUT/bench_under_rocprof_$try.log 2>&1
   cp $(find $OUT/kt -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats_$try.csv
   # the per-dispatch rows of the raster kernel (header + its launches): tools/make_profiles.py cuts them to the launches of the timed region
   T=$(find $OUT/kt -name "*kernel_trace.csv" | head -1)
   (head -1 $T; grep raster_scene_bits_kernel $T) > $OUT/bench_raster_trace_$try.csv
   rm -rf $OUT/kt
 done
-python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-configs > $OUT/bench_plain_after.log 2>/dev/null
+python3 $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-configs > $OUT/bench_plain_after.log 2>/dev/null
 # the committed trace is the run whose raster kernel averaged less; the other run's figures go into the log beside it
 python3 - "$OUT" <<'PY'
 import csv, shutil, sys

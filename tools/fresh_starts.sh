@@ -4,7 +4,7 @@
 N=${1:-20}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for i in $(seq 1 $N); do
-  python3 $R/bench.py --no-configs --no-cpu-baseline 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --no-configs --no-cpu-baseline 2>/dev/null | python3 -c "
 import json, sys
 l = json.loads(sys.stdin.read()); r = l['roofline']; d = l.get('default_path', {})
 print('start $i: ms/step %.3f raster %.3f | ring probe launch_ms %s fill %.2f fast %s kept %s | without out=: ms/step %.3f raster avg %.3f min %.3f max %.3f' % (

@@ -19,7 +19,7 @@ src, dst = os.path.join(ROOT, 'gpurun_out', 'profiles'), os.path.join(ROOT, 'pro
 B, A, RES = 1024, 64, 256
 stamp = bench.kernel_source_stamp()
 
-commands = dict(bench='python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-configs',
+commands = dict(bench='python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-configs',
                 config2='python3 tools/bench_configs.py --only config2 --steps 20 --warmup 3',
                 config3='python3 tools/bench_configs.py --only config3 --steps 20 --warmup 3',
                 config5='python3 tools/bench_configs.py --only config5 --steps 20 --warmup 3')
