@@ -868,15 +868,12 @@ raster_bwd_events = None
 raster_calls = 0
 
 
-def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, out_dtype=torch.float32, out=None, key_table=None,
-                 extra_tri=None, extra_key=None, index_slices=False, trim=True):
-    """Fused Simulator.render: state (B,N,4), agent_sc (B,N,2), tmpl (B,N,7,2), actor_key (B,N,2) int32 bit patterns -- or (B,Nc,N,2)
-    when every camera sees its own colours (custom_agent_colors) --, mask (B,Nc,N) bool/uint8, cam_xy / cam_sc (B,Nc,2)
-    -> (B,Nc,3,res,res) float32 [0,255] or uint8.  extra_tri (B,Nc,K,3,2) world-space triangles with keys extra_key (B,Nc,K) int32
-    (0 = none) are drawn per camera (waypoint discs); their keys belong into `key_table` too.
-    index_slices=True: returns (image, slices, keys) -- the per-pixel key index as bit-slices (int32 tensor, layout in include/tdship.h)
-    and the ascending key table of the launch, what the backward pass reads instead of the image; (image, None, None) when the call
-    cannot be served by the bit-plane kernel."""
+def _scene_call(fn, smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, extra_tri, extra_key, fov, res, mode, out, out_tail, out_dtype):
+    """What raster_scene and raster_scene_masks prepare alike: the sizes, the dense inputs, the per-camera triangles, the map set's scene count and
+    `out` (checked, or allocated: B x Nc x out_tail of out_dtype).  -> (B, Nc, N, K, actor_key, extra_key, out, call): the dense keys and
+    call(middle, tail), the C call of entry point `fn` (`fn`_multi for a StaticMapSet) with `middle` (workspace, key table ...) between the
+    arguments both entry points take first and the per-camera triangles, `tail` after them.  `call` holds the dense inputs: their pointers
+    are taken when it runs."""
     B, Nc = cam_xy.shape[:2]
     N = state.shape[1]
     dev = cam_xy.device
@@ -886,27 +883,53 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
         actor_key = _c(actor_key, i32)
         assert tuple(actor_key.shape) in ((B, N, 2), (B, Nc, N, 2)), 'actor_key must be (B,N,2) or (B,Nc,N,2)'
         mask = _u8(mask)
-    assert out_dtype in (torch.float32, torch.uint8)
+    shape = (B, Nc) + tuple(out_tail)
     if out is None:
-        out = empty_image((B, Nc, 3, res, res), out_dtype, dev)
+        out = empty_image(shape, out_dtype, dev)
     else:
         # a real error, not an assert (python -O strips those), on anything the kernel's 16-byte non-temporal stores cannot take
-        if tuple(out.shape) != (B, Nc, 3, res, res) or out.dtype != out_dtype or not out.is_contiguous():
-            raise RuntimeError(f'`out` must be a contiguous {out_dtype} tensor of shape {(B, Nc, 3, res, res)}, got {out.dtype} {tuple(out.shape)}'
+        if tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous():
+            raise RuntimeError(f'`out` must be a contiguous {out_dtype} tensor of shape {shape}, got {out.dtype} {tuple(out.shape)}'
                                f'{"" if out.is_contiguous() else " (not contiguous)"}')
         if out.device != dev:
             raise RuntimeError(f'`out` is on {out.device}, the cameras on {dev}')
         if out.data_ptr() % 16 != 0:
             raise RuntimeError('`out` must be 16-byte aligned (a view with an odd storage offset is not)')
-    p = lambda t, d, nme: nat.dev_ptr(t, d, nme) if N > 0 else None
-    mode = nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8
-    # distinct actor keys (host side): enables the bit-plane kernel.  Callers that know them (Simulator) pass `key_table`;
-    # otherwise they are read back from the device tensor (a synchronisation -- fine for tests and one-off calls)
     K = 0
     if extra_tri is not None and extra_tri.shape[2] > 0:
         K = extra_tri.shape[2]
         assert tuple(extra_tri.shape) == (B, Nc, K, 3, 2) and tuple(extra_key.shape) == (B, Nc, K), 'extra_tri must be (B,Nc,K,3,2), extra_key (B,Nc,K)'
         extra_tri, extra_key = _c(extra_tri), _c(extra_key, i32)
+    multi = isinstance(smap, StaticMapSet)
+    if multi and smap.scene_map.shape[0] != B:
+        raise RuntimeError(f'the StaticMapSet is for {smap.scene_map.shape[0]} scenes, the cameras for {B}')
+    p = lambda t, d, nme: nat.dev_ptr(t, d, nme) if N > 0 else None      # noqa: E731
+
+    def call(middle, tail):
+        head = (fn + '_multi', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map')) if multi else (fn, dev, smap.handle)
+        nat.call(*head, p(state, f32, 'state'), p(agent_sc, f32, 'agent_sc'), p(tmpl, f32, 'tmpl'), p(actor_key, i32, 'actor_key'),
+                 p(mask, u8, 'mask'), nat.dev_ptr(cam_xy, f32, 'cam_xy'), nat.dev_ptr(cam_sc, f32, 'cam_sc'), B, Nc, N, float(2.0 / fov), int(res),
+                 mode, nat.dev_ptr(out, out_dtype, 'out'), *middle, nat.dev_ptr(extra_tri, f32, 'extra_tri') if K > 0 else None,
+                 nat.dev_ptr(extra_key, i32, 'extra_key') if K > 0 else None, K, *tail)
+    return B, Nc, N, K, actor_key, extra_key, out, call
+
+
+def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, out_dtype=torch.float32, out=None, key_table=None,
+                 extra_tri=None, extra_key=None, index_slices=False, trim=True):
+    """Fused Simulator.render: state (B,N,4), agent_sc (B,N,2), tmpl (B,N,7,2), actor_key (B,N,2) int32 bit patterns -- or (B,Nc,N,2)
+    when every camera sees its own colours (custom_agent_colors) --, mask (B,Nc,N) bool/uint8, cam_xy / cam_sc (B,Nc,2)
+    -> (B,Nc,3,res,res) float32 [0,255] or uint8.  extra_tri (B,Nc,K,3,2) world-space triangles with keys extra_key (B,Nc,K) int32
+    (0 = none) are drawn per camera (waypoint discs); their keys belong into `key_table` too.
+    index_slices=True: returns (image, slices, keys) -- the per-pixel key index as bit-slices (int32 tensor, layout in include/tdship.h)
+    and the ascending key table of the launch, what the backward pass reads instead of the image; (image, None, None) when the call
+    cannot be served by the bit-plane kernel."""
+    assert out_dtype in (torch.float32, torch.uint8)
+    dev = cam_xy.device
+    mode = nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8
+    B, Nc, N, K, actor_key, extra_key, out, call = _scene_call('tds_raster_scene', smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc,
+                                                               extra_tri, extra_key, fov, res, mode, out, (3, res, res), out_dtype)
+    # distinct actor keys (host side): enables the bit-plane kernel.  Callers that know them (Simulator) pass `key_table`;
+    # otherwise they are read back from the device tensor (a synchronisation -- fine for tests and one-off calls)
     if key_table is None and (N > 0 or K > 0) and use_bitplanes:
         parts = ([actor_key.flatten()] if N > 0 else []) + ([extra_key.flatten()] if K > 0 else [])
         key_table = [v for v in torch.unique(torch.cat(parts)).cpu().tolist() if v != 0]
@@ -922,9 +945,6 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     if raster_events is not None:          # bench.py: HIP events on the launch stream, right around the kernel
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record(torch.cuda.current_stream(dev))
-    multi = isinstance(smap, StaticMapSet)
-    if multi and smap.scene_map.shape[0] != B:
-        raise RuntimeError(f'the StaticMapSet is for {smap.scene_map.shape[0]} scenes, the cameras for {B}')
     aux = slices = None
     if index_slices and kt is not None and out_dtype == torch.float32 and res % 4 == 0 and B * Nc > 0:
         nbytes = ctypes.c_int64(0)
@@ -934,16 +954,10 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     if not trim:
         aux = aux if aux is not None else nat.RasterAux()
         aux.flags = nat.RASTER_NO_TRIM
-    head = ('tds_raster_scene_multi', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map')) if multi else ('tds_raster_scene', dev, smap.handle)
     def launch(aux):
-        nat.call(*head, p(state, f32, 'state'), p(agent_sc, f32, 'agent_sc'), p(tmpl, f32, 'tmpl'),
-             p(actor_key, i32, 'actor_key'), p(mask, u8, 'mask'), nat.dev_ptr(cam_xy, f32, 'cam_xy'), nat.dev_ptr(cam_sc, f32, 'cam_sc'),
-             B, Nc, N, float(2.0 / fov), int(res), mode, nat.dev_ptr(out, out_dtype, 'out'),
-             None if ws is None else ctypes.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(),
-             None if kt is None else ctypes.cast(kt, ctypes.c_void_p), 0 if kt is None else len(key_table),
-             1 if (N > 0 and actor_key.dim() == 4) else 0,
-             nat.dev_ptr(extra_tri, f32, 'extra_tri') if K > 0 else None, nat.dev_ptr(extra_key, i32, 'extra_key') if K > 0 else None, K,
-             None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev))
+        call((None if ws is None else ctypes.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(),
+              None if kt is None else ctypes.cast(kt, ctypes.c_void_p), 0 if kt is None else len(key_table), 1 if (N > 0 and actor_key.dim() == 4) else 0),
+             (None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev)))
 
     global raster_calls
     raster_calls += 1
@@ -977,55 +991,34 @@ def mask_table(smap, actor_keys, key_channels):
     return table, [int(key_channels.get(k, 0)) & 0xffffffff for k in table]
 
 
+@torch.no_grad()
 def raster_scene_masks(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, key_table, key_channels, n_channels, packed=False,
                        out=None, extra_tri=None, extra_key=None, trim=True):
     """Semantic bird's-eye masks of the scene raster_scene would draw (same arguments; actor_key (B,N,2) only): `n_channels` binary channels,
     channel c set wherever the image would paint a face whose key k has bit c in key_channels[k] (dict key -> channel set), occlusion ignored.
     key_table: the actors' (and per-camera triangles') distinct keys.  -> (B,Nc,C,res,res) torch.bool (memory order of the image: the last two
     axes are x, y), or with packed=True (B,Nc,C,ceil(res/32),res) int32 words holding bit i of pixel (32 xw + i, y) (rendering.unpack_mask_bits).
-    `out`: a caller-owned contiguous tensor of that shape and dtype.  Never differentiable."""
-    B, Nc = cam_xy.shape[:2]
-    N = state.shape[1]
-    dev = cam_xy.device
-    cam_xy, cam_sc = _c(cam_xy.detach()), _c(cam_sc.detach())
-    if N > 0:
-        state, agent_sc, tmpl = _c(state.detach()), _c(agent_sc.detach()), _c(tmpl.detach())
-        actor_key = _c(actor_key, i32)
-        if tuple(actor_key.shape) != (B, N, 2):
-            raise RuntimeError(f'actor_key must be ({B}, {N}, 2), got {tuple(actor_key.shape)}')
-        mask = _u8(mask)
+    `out`: a caller-owned contiguous tensor of that shape and dtype.  Never differentiable (no autograd graph is recorded here)."""
+    B, N = cam_xy.shape[0], state.shape[1]
+    if N > 0 and tuple(actor_key.shape) != (B, N, 2):
+        raise RuntimeError(f'actor_key must be ({B}, {N}, 2), got {tuple(actor_key.shape)}')
     C = int(n_channels)
     if not 1 <= C <= 32:
         raise ValueError(f'semantic masks take 1 to 32 channels, got {C}')
-    shape, dtype = ((B, Nc, C, (res + 31) // 32, res), i32) if packed else ((B, Nc, C, res, res), torch.bool)
-    if out is None:
-        out = empty_image(shape, dtype, dev)
-    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != dev or out.data_ptr() % 16 != 0:
-        raise RuntimeError(f'`out` must be a contiguous, 16-byte aligned {dtype} tensor of shape {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}')
-    K = 0
-    if extra_tri is not None and extra_tri.shape[2] > 0:
-        K = extra_tri.shape[2]
-        assert tuple(extra_tri.shape) == (B, Nc, K, 3, 2) and tuple(extra_key.shape) == (B, Nc, K), 'extra_tri must be (B,Nc,K,3,2), extra_key (B,Nc,K)'
-        extra_tri, extra_key = _c(extra_tri.detach()), _c(extra_key, i32)
+    dev = cam_xy.device
+    mode = nat.OUT_MASK_BITS if packed else nat.OUT_MASK_U8
+    tail, dtype = ((C, (res + 31) // 32, res), i32) if packed else ((C, res, res), torch.bool)
+    B, Nc, _, _, _, _, out, call = _scene_call('tds_raster_scene_masks', smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, extra_tri,
+                                               extra_key, fov, res, mode, out, tail, dtype)
     actors = [int(v) & 0xffffffff for v in key_table]
     table, chans = mask_table(smap, actors, key_channels)
     kt = (ctypes.c_uint32 * max(len(actors), 1))(*actors)
     kc = (ctypes.c_uint32 * max(len(chans), 1))(*chans)
-    mode = nat.OUT_MASK_BITS if packed else nat.OUT_MASK_U8
     # (more than 15 keys: the call reports TDS_ELIMIT; the workspace is sized as for 15 rather than for the packed-key kernels' lists)
     ws = _raster_workspace(dev, B * Nc, int(res), mode, min(len(table), 15))
-    multi = isinstance(smap, StaticMapSet)
-    if multi and smap.scene_map.shape[0] != B:
-        raise RuntimeError(f'the StaticMapSet is for {smap.scene_map.shape[0]} scenes, the cameras for {B}')
     aux = None if trim else nat.RasterAux(flags=nat.RASTER_NO_TRIM)
-    p = lambda t, d, nme: nat.dev_ptr(t, d, nme) if N > 0 else None      # noqa: E731
-    head = ('tds_raster_scene_masks_multi', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map')) if multi else \
-        ('tds_raster_scene_masks', dev, smap.handle)
-    nat.call(*head, p(state, f32, 'state'), p(agent_sc, f32, 'agent_sc'), p(tmpl, f32, 'tmpl'), p(actor_key, i32, 'actor_key'), p(mask, u8, 'mask'),
-             nat.dev_ptr(cam_xy, f32, 'cam_xy'), nat.dev_ptr(cam_sc, f32, 'cam_sc'), B, Nc, N, float(2.0 / fov), int(res), mode,
-             nat.dev_ptr(out, dtype, 'out'), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.cast(kt, ctypes.c_void_p), len(actors),
-             nat.dev_ptr(extra_tri, f32, 'extra_tri') if K > 0 else None, nat.dev_ptr(extra_key, i32, 'extra_key') if K > 0 else None, K,
-             ctypes.cast(kc, ctypes.c_void_p), C, None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev))
+    call((ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.cast(kt, ctypes.c_void_p), len(actors)),
+         (ctypes.cast(kc, ctypes.c_void_p), C, None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev)))
     return out
 
 

@@ -3191,14 +3191,16 @@ struct MapSource {
     int n_uniq;                     // -1: too many for the bit-plane path
     bool renders;                   // created with rendering data
 };
+MapSource map_source(const tds_map_t *map) {
+    return MapSource{map->view, nullptr, nullptr, map->uniq_keys, map->n_uniq, map->n_levels > 0 || map->view.nx == 0};
+}
+MapSource map_source(const tds_mapset_t *set, const int32_t *scene_map) {
+    return MapSource{tds::MapView{}, set->d_views, scene_map, set->uniq_keys, set->n_uniq, set->n_levels > 0};
+}
 int raster_scene_impl(const MapSource &ms, const float *state, const float *agent_sc, const float *tmpl, const uint32_t *actor_key, const uint8_t *mask,
                       const float *cam_xy, const float *cam_sc, int64_t B, int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out,
                       void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream,
                       const uint32_t *key_channels = nullptr, int n_channels = 0);
-#ifdef TDS_RASTER_MASKS_TU
-int launch_masks(const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff, int out_mode, hipStream_t s);
-__global__ void put_mask_table_kernel(uint32_t *dst, MaskTable t);
-#endif
 }  // namespace
 
 #ifndef TDS_RASTER_MASKS_TU
@@ -3208,11 +3210,8 @@ TDS_EXPORT int tds_raster_scene(const tds_map_t *map, const float *state, const 
                                 int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream) {
     TDS_CHECK_ARG(map, "tds_raster_scene: null map");
     TDS_CHECK_ARG(!is_mask_mode(out_mode), "tds_raster_scene: the mask modes are served by tds_raster_scene_masks");
-    MapSource ms;
-    ms.one = map->view; ms.views = nullptr; ms.scene_map = nullptr; ms.uniq_keys = map->uniq_keys; ms.n_uniq = map->n_uniq;
-    ms.renders = map->n_levels > 0 || map->view.nx == 0;
-    return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
-                             actor_keys, n_actor_keys, actor_key_per_camera, extra_tri, extra_key, n_extra, aux, stream);
+    return raster_scene_impl(map_source(map), state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace,
+                             workspace_bytes, actor_keys, n_actor_keys, actor_key_per_camera, extra_tri, extra_key, n_extra, aux, stream);
 }
 
 TDS_EXPORT int tds_raster_scene_multi(const tds_mapset_t *set, const int32_t *scene_map, const float *state, const float *agent_sc, const float *tmpl,
@@ -3222,11 +3221,8 @@ TDS_EXPORT int tds_raster_scene_multi(const tds_mapset_t *set, const int32_t *sc
     TDS_CHECK_ARG(set && set->n > 0, "tds_raster_scene_multi: null or empty map set");
     TDS_CHECK_ARG(scene_map || B == 0, "tds_raster_scene_multi: null scene -> map index array");
     TDS_CHECK_ARG(!is_mask_mode(out_mode), "tds_raster_scene_multi: the mask modes are served by tds_raster_scene_masks_multi");
-    MapSource ms;
-    ms.one = tds::MapView{}; ms.views = set->d_views; ms.scene_map = scene_map; ms.uniq_keys = set->uniq_keys; ms.n_uniq = set->n_uniq;
-    ms.renders = set->n_levels > 0;
-    return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
-                             actor_keys, n_actor_keys, actor_key_per_camera, extra_tri, extra_key, n_extra, aux, stream);
+    return raster_scene_impl(map_source(set, scene_map), state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out,
+                             workspace, workspace_bytes, actor_keys, n_actor_keys, actor_key_per_camera, extra_tri, extra_key, n_extra, aux, stream);
 }
 #else
 TDS_EXPORT int tds_raster_scene_masks(const tds_map_t *map, const float *state, const float *agent_sc, const float *tmpl,
@@ -3236,11 +3232,8 @@ TDS_EXPORT int tds_raster_scene_masks(const tds_map_t *map, const float *state, 
                                       int64_t n_extra, const uint32_t *key_channels, int n_channels, tds_raster_aux_t *aux, void *stream) {
     TDS_CHECK_ARG(map, "tds_raster_scene_masks: null map");
     TDS_CHECK_ARG(is_mask_mode(out_mode), "tds_raster_scene_masks: unknown output mode %d (TDS_OUT_MASK_U8 or TDS_OUT_MASK_BITS)", out_mode);
-    MapSource ms;
-    ms.one = map->view; ms.views = nullptr; ms.scene_map = nullptr; ms.uniq_keys = map->uniq_keys; ms.n_uniq = map->n_uniq;
-    ms.renders = map->n_levels > 0 || map->view.nx == 0;
-    return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
-                             actor_keys, n_actor_keys, 0, extra_tri, extra_key, n_extra, aux, stream, key_channels, n_channels);
+    return raster_scene_impl(map_source(map), state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace,
+                             workspace_bytes, actor_keys, n_actor_keys, 0, extra_tri, extra_key, n_extra, aux, stream, key_channels, n_channels);
 }
 
 TDS_EXPORT int tds_raster_scene_masks_multi(const tds_mapset_t *set, const int32_t *scene_map, const float *state, const float *agent_sc, const float *tmpl,
@@ -3251,15 +3244,68 @@ TDS_EXPORT int tds_raster_scene_masks_multi(const tds_mapset_t *set, const int32
     TDS_CHECK_ARG(set && set->n > 0, "tds_raster_scene_masks_multi: null or empty map set");
     TDS_CHECK_ARG(scene_map || B == 0, "tds_raster_scene_masks_multi: null scene -> map index array");
     TDS_CHECK_ARG(is_mask_mode(out_mode), "tds_raster_scene_masks_multi: unknown output mode %d (TDS_OUT_MASK_U8 or TDS_OUT_MASK_BITS)", out_mode);
-    MapSource ms;
-    ms.one = tds::MapView{}; ms.views = set->d_views; ms.scene_map = scene_map; ms.uniq_keys = set->uniq_keys; ms.n_uniq = set->n_uniq;
-    ms.renders = set->n_levels > 0;
-    return raster_scene_impl(ms, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out, workspace, workspace_bytes,
-                             actor_keys, n_actor_keys, 0, extra_tri, extra_key, n_extra, aux, stream, key_channels, n_channels);
+    return raster_scene_impl(map_source(set, scene_map), state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, B, Nc, N, scale, res, out_mode, out,
+                             workspace, workspace_bytes, actor_keys, n_actor_keys, 0, extra_tri, extra_key, n_extra, aux, stream, key_channels, n_channels);
 }
+
+namespace {
+// the channel table of a mask launch, written in stream order in front of the work queues
+__global__ void put_mask_table_kernel(uint32_t *dst, MaskTable t) {
+    if (threadIdx.x < (unsigned)MASK_TABLE_DW) dst[threadIdx.x] = t.w[threadIdx.x];
+}
+}  // namespace
 #endif  // TDS_RASTER_MASKS_TU
 
 namespace {
+// The launches of a Bits or Split plan, the output tag F where `first`, else S: float / uint8_t for the image, MaskBits / MaskU8 for the masks.
+// Split: K3s lists each camera's faces, K3r rasterises the lists, and the bit-plane launch runs over the cameras whose list overflowed (normally
+// none).  cm.slices: where a float32 image's differentiable call stores its index slices (the 4-wave instantiation that does), or the masks'
+// channel table.  fn: the entry point, for the errors.
+template <typename F, typename S>
+auto launch_bit_planes(const char *fn, const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff,
+                       bool first, hipStream_t s) {
+    auto with_tag = [&](auto f) { if (first) f(F()); else f(S()); };
+    const int64_t n_img = cm.n_img;
+    const uint32_t *only = nullptr;
+    if (p.form == RasterForm::Split) {
+        uint32_t *poisoned = (uint32_t *)ws, *counts = (uint32_t *)(ws + p.ws.counts), *lists3 = (uint32_t *)(ws + p.ws.lists3);
+        uint4 *lists = (uint4 *)(ws + p.ws.lists);
+        if (tds::zero_async(poisoned, 4, s) != hipSuccess) { tds::set_error("%s: clearing the workspace failed", fn); return TDS_EHIP; }
+        CommonArgs cs = cm, cr = cm;
+        cs.strips = 1; cr.strips = (cm.res + p.tws - 1) / p.tws;
+        auto scan = [&](auto kern, const auto &args) { launch(kern, (n_img + SCAN_WAVES - 1) / SCAN_WAVES, SCAN_WAVES * 64, 0, s, args, cs, kt, counts, lists, lists3, (int)p.caps, poisoned); };
+        if (a.K != 0) scan(scan_faces_kernel<SceneArgsEx>, a); else scan(scan_faces_kernel<SceneArgs>, (const SceneArgs &)a);
+        TDS_LAUNCH_CHECK("scan_faces_kernel");
+        auto go = [&](auto kern) { launch(kern, n_img * cr.strips, p.lw * 64, p.lds_s, s, cr, kt, p.tws, (const uint32_t *)counts, (const uint4 *)lists, (const uint32_t *)lists3, (int)p.caps); };
+        with_tag([&](auto t) {
+            if (p.lw == 2) with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 2>); });
+            else with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 4>); });
+        });
+        TDS_LAUNCH_CHECK("raster_list_bits_kernel");
+        only = poisoned;
+    }
+    uint32_t *const queue = p.persist ? (uint32_t *)(ws + qoff) : nullptr;
+    if (p.persist && tds::zero_async(queue, (size_t)QUEUE_BYTES, s) != hipSuccess) { tds::set_error("%s: clearing the work queues failed", fn); return TDS_EHIP; }
+    auto go = [&](auto kern, const auto &args) { launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cm, kt, p.twp, queue, only); };
+    with_tag([&](auto t) {
+        using T = decltype(t);
+        if constexpr (std::is_same<T, float>::value) {
+            if (cm.slices) {            // differentiable calls (float32, four waves): the instantiation that also stores the index slices
+                with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, float, std::decay_t<decltype(args)>, true>, args); }); });
+                return;
+            }
+        }
+        if (p.four_per_cu)
+            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>, false, 4>, args); }); });
+        else if (p.nwv == 4)
+            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>>, args); }); });
+        else
+            with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<8, nb, T, SceneArgsEx>, a); });
+    });
+    TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
+    return TDS_OK;
+}
+
 int raster_scene_impl(const MapSource &ms, const float *state, const float *agent_sc, const float *tmpl, const uint32_t *actor_key, const uint8_t *mask,
                       const float *cam_xy, const float *cam_sc, int64_t B, int64_t Nc, int64_t N, float scale, int res, int out_mode, void *out,
                       void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream,
@@ -3318,11 +3364,11 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     a.extra_tri = extra_tri; a.extra_key = extra_key; a.K = (int)n_extra;
     CommonArgs cm;
     cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
-    cm.strips = p.strips; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = g_knobs.debug;
+    cm.strips = p.strips; cm.n_img = n_img; cm.out = out; cm.slices = want_slices ? aux->index_slices : nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (aux && (aux->flags & TDS_RASTER_NO_TRIM)) ? 1 : 0;
     char *const ws = (char *)workspace;
 #ifdef TDS_RASTER_MASKS_TU
-    // (this translation unit serves the mask entry points only: raster_masks.hip)
+    // (this translation unit serves the mask entry points only: raster_masks.hip; their plan is the uint8 image's, Bits or Split)
     TDS_CHECK_ARG(masks && qoff >= MASK_TABLE_BYTES, "tds_raster_scene_masks: needs a workspace (tds_raster_scene_workspace_bytes_for with the mask mode)");
     // channel c = the union of the planes of the keys whose key_channels word has bit c (key_channels is aligned with the key table)
     MaskTable mt{};
@@ -3333,47 +3379,10 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     cm.slices = (uint32_t *)(ws + qoff - MASK_TABLE_BYTES);
     hipLaunchKernelGGL(put_mask_table_kernel, dim3(1), dim3(MASK_TABLE_DW), 0, s, cm.slices, mt);
     TDS_LAUNCH_CHECK("put_mask_table_kernel");
-    return launch_masks(p, a, cm, kt, ws, qoff, out_mode, s);
+    return launch_bit_planes<MaskBits, MaskU8>("tds_raster_scene_masks", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_MASK_BITS, s);
 #else
-    if (p.form == RasterForm::Split || p.form == RasterForm::Bits) {
-        const uint32_t *only = nullptr;              // Split: the bit-plane launch runs over the cameras K3s marked (normally none)
-        if (p.form == RasterForm::Split) {
-            uint32_t *poisoned = (uint32_t *)ws, *counts = (uint32_t *)(ws + p.ws.counts), *lists3 = (uint32_t *)(ws + p.ws.lists3);
-            uint4 *lists = (uint4 *)(ws + p.ws.lists);
-            if (tds::zero_async(poisoned, 4, s) != hipSuccess) { tds::set_error("tds_raster_scene: clearing the workspace failed"); return TDS_EHIP; }
-            CommonArgs cs = cm, cr = cm;
-            cs.strips = 1; cr.strips = (res + p.tws - 1) / p.tws;
-            auto scan = [&](auto kern, const auto &args) { launch(kern, (n_img + SCAN_WAVES - 1) / SCAN_WAVES, SCAN_WAVES * 64, 0, s, args, cs, kt, counts, lists, lists3, (int)p.caps, poisoned); };
-            if (a.K != 0) scan(scan_faces_kernel<SceneArgsEx>, a); else scan(scan_faces_kernel<SceneArgs>, (const SceneArgs &)a);
-            TDS_LAUNCH_CHECK("scan_faces_kernel");
-            auto go = [&](auto kern) { launch(kern, n_img * cr.strips, p.lw * 64, p.lds_s, s, cr, kt, p.tws, (const uint32_t *)counts, (const uint4 *)lists, (const uint32_t *)lists3, (int)p.caps); };
-            with_out(out_mode, [&](auto t) {
-                if (p.lw == 2) with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 2>); });
-                else with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 4>); });
-            });
-            TDS_LAUNCH_CHECK("raster_list_bits_kernel");
-            only = poisoned;
-        }
-        uint32_t *const queue = p.persist ? (uint32_t *)(ws + qoff) : nullptr;
-        if (p.persist && tds::zero_async(queue, (size_t)QUEUE_BYTES, s) != hipSuccess) { tds::set_error("tds_raster_scene: clearing the work queues failed"); return TDS_EHIP; }
-        CommonArgs cb = cm;
-        cb.slices = want_slices ? aux->index_slices : nullptr;
-        auto go = [&](auto kern, const auto &args) { launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cb, kt, p.twp, queue, only); };
-        if (want_slices)                // differentiable calls (float32, four waves): the instantiation that also stores the index slices
-            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, float, std::decay_t<decltype(args)>, true>, args); }); });
-        else
-            with_out(out_mode, [&](auto t) {
-                using T = decltype(t);
-                if (p.four_per_cu)
-                    with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>, false, 4>, args); }); });
-                else if (p.nwv == 4)
-                    with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>>, args); }); });
-                else
-                    with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<8, nb, T, SceneArgsEx>, a); });
-            });
-        TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
-        return TDS_OK;
-    }
+    if (p.form == RasterForm::Split || p.form == RasterForm::Bits)
+        return launch_bit_planes<float, uint8_t>("tds_raster_scene", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_F32, s);
     if (p.form == RasterForm::Binned) {
         uint32_t *counts = (uint32_t *)ws; uint4 *lists = (uint4 *)(ws + p.ws.lists);
         launch(bin_faces_kernel, (n_img + BIN_WAVES - 1) / BIN_WAVES, BIN_WAVES * 64, 0, s, a, cm, p.tw, counts, lists, (int)p.caps);
@@ -3418,49 +3427,4 @@ TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int
     TDS_LAUNCH_CHECK("raster_mesh_kernel");
     return TDS_OK;
 }
-#else
-// ---- semantic masks: the launches of tds_raster_scene_masks(_multi) (raster_masks.hip) ------------------------------------------------
-namespace {
-__global__ void put_mask_table_kernel(uint32_t *dst, MaskTable t) {
-    if (threadIdx.x < (unsigned)MASK_TABLE_DW) dst[threadIdx.x] = t.w[threadIdx.x];
-}
-
-// the launches of raster_scene_impl's bit-plane branch, with the mask tags for the output type (the plan is the uint8 image's)
-int launch_masks(const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff, int out_mode, hipStream_t s) {
-    auto with_mask = [&](auto f) { if (out_mode == TDS_OUT_MASK_BITS) f(MaskBits()); else f(MaskU8()); };
-    const int64_t n_img = cm.n_img;
-    const uint32_t *only = nullptr;
-    if (p.form == RasterForm::Split) {
-        uint32_t *poisoned = (uint32_t *)ws, *counts = (uint32_t *)(ws + p.ws.counts), *lists3 = (uint32_t *)(ws + p.ws.lists3);
-        uint4 *lists = (uint4 *)(ws + p.ws.lists);
-        if (tds::zero_async(poisoned, 4, s) != hipSuccess) { tds::set_error("tds_raster_scene_masks: clearing the workspace failed"); return TDS_EHIP; }
-        CommonArgs cs = cm, cr = cm;
-        cs.strips = 1; cr.strips = (cm.res + p.tws - 1) / p.tws;
-        auto scan = [&](auto kern, const auto &args) { launch(kern, (n_img + SCAN_WAVES - 1) / SCAN_WAVES, SCAN_WAVES * 64, 0, s, args, cs, kt, counts, lists, lists3, (int)p.caps, poisoned); };
-        if (a.K != 0) scan(scan_faces_kernel<SceneArgsEx>, a); else scan(scan_faces_kernel<SceneArgs>, (const SceneArgs &)a);
-        TDS_LAUNCH_CHECK("scan_faces_kernel");
-        auto go = [&](auto kern) { launch(kern, n_img * cr.strips, p.lw * 64, p.lds_s, s, cr, kt, p.tws, (const uint32_t *)counts, (const uint4 *)lists, (const uint32_t *)lists3, (int)p.caps); };
-        with_mask([&](auto t) {
-            if (p.lw == 2) with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 2>); });
-            else with_nb(p.nb, [&](auto nb) { go(raster_list_bits_kernel<nb, decltype(t), 4>); });
-        });
-        TDS_LAUNCH_CHECK("raster_list_bits_kernel");
-        only = poisoned;
-    }
-    uint32_t *const queue = p.persist ? (uint32_t *)(ws + qoff) : nullptr;
-    if (p.persist && tds::zero_async(queue, (size_t)QUEUE_BYTES, s) != hipSuccess) { tds::set_error("tds_raster_scene_masks: clearing the work queues failed"); return TDS_EHIP; }
-    auto go = [&](auto kern, const auto &args) { launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cm, kt, p.twp, queue, only); };
-    with_mask([&](auto t) {
-        using T = decltype(t);
-        if (p.four_per_cu)
-            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>, false, 4>, args); }); });
-        else if (p.nwv == 4)
-            with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, T, std::decay_t<decltype(args)>>, args); }); });
-        else
-            with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<8, nb, T, SceneArgsEx>, a); });
-    });
-    TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
-    return TDS_OK;
-}
-}  // namespace
-#endif  // TDS_RASTER_MASKS_TU
+#endif  // !TDS_RASTER_MASKS_TU

@@ -101,6 +101,13 @@ class HipRenderer(BirdviewRenderer):
                     lambda r: self.make_static_map(rgb_mesh[r:r + 1], extra, device=dev))
         return _ops.map_per_distinct_row(tensors, prepare)
 
+    def _side_and_fov(self, res: Optional[Resolution], fov: Optional[float]):
+        """(side of the square image, fov) of a scene launch, the renderer's own where not given"""
+        res = self.res if res is None else res
+        if res.width != res.height:
+            raise RuntimeError('only square resolutions are supported')
+        return res.height, (fov if fov is not None else 2.0 / self.scale)
+
     def render_scene(self, static_map: _ops.StaticMap, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor,
                      camera_xy: Tensor, camera_sc: Tensor, res: Optional[Resolution] = None, fov: Optional[float] = None,
                      key_table=None, differentiable: bool = False, extra_tri: Optional[Tensor] = None,
@@ -111,19 +118,16 @@ class HipRenderer(BirdviewRenderer):
         camera_sc; float32 output only).  `extra_tri` (B,Nc,K,3,2) / `extra_key` (B,Nc,K): per-camera world-space triangles.
         `key_colors` (K,3) / `color_keys` (K packed keys): colour-gradient handle, see _ops.raster_scene_diff.
         `ego_cameras` = Nc (differentiable calls): the cameras are the first Nc agents of `state` / `agent_sc` -- their gradient is folded into the agents'."""
-        res = self.res if res is None else res
-        if res.width != res.height:
-            raise RuntimeError('only square resolutions are supported')
-        fov = fov if fov is not None else 2.0 / self.scale
+        side, fov = self._side_and_fov(res, fov)
         if differentiable:
             if self.out_dtype != torch.float32:
                 raise RuntimeError('the differentiable path renders float32 images')
             if out is not None:
                 raise RuntimeError('`out=` cannot be combined with a differentiable render (autograd owns the image)')
-            return _ops.raster_scene_diff(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, res.height, key_table=key_table,
+            return _ops.raster_scene_diff(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, side, key_table=key_table,
                                           extra_tri=extra_tri, extra_key=extra_key, key_colors=key_colors, color_keys=color_keys, trim=self.trim,
                                           ego_cameras=ego_cameras)
-        return _ops.raster_scene(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, res.height, out_dtype=self.out_dtype,
+        return _ops.raster_scene(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, side, out_dtype=self.out_dtype,
                                  key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out)
 
     def render_scene_masks(self, static_map, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor, camera_xy: Tensor,
@@ -133,11 +137,8 @@ class HipRenderer(BirdviewRenderer):
         """Semantic masks of the scene `render_scene` draws: B x Nc x C x H x W bool (packed: B x Nc x C x ceil(W/32) x H int32 words, see
         `unpack_mask_bits`).  Channel c is set wherever the image would paint a face whose key k has bit c in key_channels[k], whatever is drawn
         over it.  `key_table`: the actors' distinct keys.  Never differentiable; `out`: a caller-owned tensor of that shape and dtype."""
-        res = self.res if res is None else res
-        if res.width != res.height:
-            raise RuntimeError('only square resolutions are supported')
-        fov = fov if fov is not None else 2.0 / self.scale
-        return _ops.raster_scene_masks(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, res.height, key_table,
+        side, fov = self._side_and_fov(res, fov)
+        return _ops.raster_scene_masks(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, side, key_table,
                                        key_channels, n_channels, packed=packed, out=out, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim)
 
 

@@ -750,7 +750,7 @@ class Simulator:
         dev = sizes.device
         bg = gen.background_mesh                                   # RGBMesh, batch B, (x, y, z) + colour per vertex
         names = list(self.agent_types)
-        lv, cm = self.renderer.rendering_levels, self.renderer.color_map
+        lv = self.renderer.rendering_levels
         actor_levels = [float(lv[n]) for n in names] + [float(lv['direction']), float(lv['goal_waypoint'])]
         B = self.batch_size
         # traffic controls are drawn like actors without a direction triangle: one quad per stop line (mesh.py:1007-1035)
@@ -763,7 +763,7 @@ class Simulator:
         # process-wide content cache: `copy`, `select_batch_elements`, `extend`, `to` and `shard_simulator` end up here again and find the handles
         smap = self.renderer.scene_maps(bg, actor_levels, device=dev)
         tmpl = actor_template(sizes.detach()).contiguous()          # B x N x 7 x 2 (a render that differentiates the sizes builds its own)
-        key_of = lambda name: (smap.rank_of(lv[name]) << 24) | int(_ops.quantise_colors(torch.tensor(cm[name], dtype=torch.float32) / 255.0))  # noqa: E731
+        key_of = lambda name: self._category_key(smap, name)      # noqa: E731
         body = torch.tensor([key_of(n) for n in names], dtype=torch.int64, device=dev)
         dkey = key_of('direction')
         keys = torch.stack([body[types.long()], torch.full_like(types.long(), dkey)], dim=-1).to(torch.int32).contiguous()     # bit pattern of the uint32 key
@@ -791,6 +791,12 @@ class Simulator:
         self._scene_cache = dict(sources=sources, versions=[t._version for t in sources], extra=extra, map=smap, tmpl=tmpl, keys=keys, key_table=key_table, ctrl=ctrl, wp_key=wp_key)
         return self._scene_cache
 
+    def _category_key(self, smap, name: str) -> int:
+        """the key of category `name` in the launches over `smap`: the rank of its rendering level << 24 | its quantised colour
+        (ValueError: a level the map does not draw at)"""
+        lv, cm = self.renderer.rendering_levels, self.renderer.color_map
+        return (smap.rank_of(lv[name]) << 24) | int(_ops.quantise_colors(torch.tensor(cm[name], dtype=torch.float32) / 255.0))
+
     def _waypoint_triangles(self, waypoints: Tensor, rendering_mask: Optional[Tensor]):
         """B x Nc x M waypoints -> the world-space triangles generate() would add per camera (mesh.py:1120-1145): B x Nc x M*T x 3 x 2.
         The faces of a masked waypoint are zeroed there and so alias the first waypoint vertex of the camera -- a dot at the centre of
@@ -814,6 +820,55 @@ class Simulator:
             out.append(lut[idx])
         body = torch.cat(out, dim=1)
         return torch.stack([body, torch.zeros_like(body)], dim=-1).to(torch.int32)
+
+    def _cameras(self, camera_xy: Tensor, camera_psi: Tensor, camera_sc: Optional[Tensor], rendering_mask: Optional[Tensor]):
+        """-> (camera_xy, camera_sc, mask): B x Nc cameras (B x 2 ones become B x 1), their [sin, cos] (`camera_sc`, or of `camera_psi`) and
+        the agents each of them sees (present x rendering_mask)"""
+        camera_sc = camera_sc if camera_sc is not None else torch.cat([torch.sin(camera_psi), torch.cos(camera_psi)], dim=-1)
+        if camera_xy.dim() == 2:
+            camera_xy, camera_sc = camera_xy.unsqueeze(1), camera_sc.unsqueeze(1)
+        present = self.get_all_agent_present_mask()
+        mask = present.unsqueeze(-2).expand(present.shape[:-1] + (camera_xy.shape[-2],) + present.shape[-1:])
+        if rendering_mask is not None:
+            mask = mask.logical_and(rendering_mask.to(torch.bool))
+        return camera_xy, camera_sc, mask
+
+    def _scene_inputs(self, scene, state: Tensor, tmpl: Tensor, mask: Tensor, waypoints: Optional[Tensor], waypoints_rendering_mask: Optional[Tensor]):
+        """The agents of a scene launch, from the caller's `state` and templates and the cameras' `mask` -> (state, tmpl, mask, agent_sc, wp_tri):
+        the scene's traffic controls appended as quads without a direction triangle, the [sin, cos] of every agent and quad, and the per-camera
+        waypoint triangles (None without waypoints)"""
+        ctrl = scene['ctrl']
+        if ctrl is not None:
+            state = torch.cat([state, ctrl['state'].to(state.dtype)], dim=1)
+            tmpl = torch.cat([tmpl, ctrl['tmpl'].to(tmpl.dtype)], dim=1)
+            mask = torch.cat([mask, torch.ones(mask.shape[:-1] + (ctrl['state'].shape[1],), dtype=torch.bool, device=mask.device)], dim=-1)
+        agent_sc = self._heading_sc() if ctrl is None else _ops.heading_sc(state[..., 2])
+        wp_tri = None
+        if waypoints is not None and waypoints.shape[2] > 0:
+            wp_tri, _ = self._waypoint_triangles(waypoints.to(state.dtype), waypoints_rendering_mask)
+        return state, tmpl, mask, agent_sc, wp_tri
+
+    def _launch_keys(self, scene, n_cam: int, custom_agent_colors: Optional[Tensor], wp_tri: Optional[Tensor]):
+        """-> (keys, key table, per-camera triangles) of a launch: the scene's keys, per camera where `custom_agent_colors` are given (the key
+        table is then left to the launch), the control quads' keys appended, and the waypoint key for the triangles `wp_tri`"""
+        k, ktab = scene['keys'], scene['key_table']
+        if custom_agent_colors is not None:
+            # generate() paints the four body vertices of agent a with custom_agent_colors[b, c, a] for camera c
+            # (mesh.py:1092-1099); the direction triangle keeps its colour.  Same rendering level, so only the colour
+            # bits of the body key change -- per camera.
+            rgb = _ops.quantise_colors(custom_agent_colors.to(k.device)).to(torch.int32)          # (B,Nc,A,)
+            kc = k[:, None].expand(-1, n_cam, -1, -1).clone()
+            kc[..., 0] = (kc[..., 0] & ~0xFFFFFF) | rgb
+            k, ktab = kc.contiguous(), None
+        if scene['ctrl'] is not None:
+            kq = self._control_keys(scene)
+            k = torch.cat([k, kq[:, None].expand(-1, n_cam, -1, -1) if k.dim() == 4 else kq], dim=-2).contiguous()
+        extra = dict()
+        if wp_tri is not None:
+            wk = scene['wp_key']
+            extra = dict(extra_tri=wp_tri, extra_key=torch.full(wp_tri.shape[:3], wk, dtype=torch.int32, device=wp_tri.device))
+            ktab = None if ktab is None else sorted(set(ktab) | {wk})
+        return k, ktab, extra
 
     # ------------------------------------------------------------------------------------------------- rendering
     def _noisy_scene_sources(self):
@@ -861,14 +916,8 @@ class Simulator:
                                    noisy_perception=False, _camera_sc=_camera_sc, out=out, _ego=_ego)
             finally:
                 self.birdview_mesh_generator, self.traffic_controls, self._scene_cache = saved
-        camera_sc = _camera_sc if _camera_sc is not None else torch.cat([torch.sin(camera_psi), torch.cos(camera_psi)], dim=-1)
-        if camera_xy.dim() == 2:
-            camera_xy, camera_sc = camera_xy.unsqueeze(1), camera_sc.unsqueeze(1)
+        camera_xy, camera_sc, mask = self._cameras(camera_xy, camera_psi, _camera_sc, rendering_mask)
         n_cam = camera_xy.shape[-2]
-        present = self.get_all_agent_present_mask()
-        mask = present.unsqueeze(-2).expand(present.shape[:-1] + (n_cam,) + present.shape[-1:])
-        if rendering_mask is not None:
-            mask = mask.logical_and(rendering_mask.to(torch.bool))
         if isinstance(self.renderer, HipRenderer):
             scene = self._scene()
             state = self.get_all_agent_state()
@@ -881,15 +930,7 @@ class Simulator:
                 state, camera_xy, camera_sc = state.detach(), camera_xy.detach(), camera_sc.detach()
             # gradients with respect to the agents' length and width flow through the template vertices (actor_template is plain torch)
             tmpl_all = actor_template(sizes).contiguous() if size_grad else scene['tmpl']
-            ctrl = scene['ctrl']
-            if ctrl is not None:                                    # stop lines ride along as extra quads
-                state = torch.cat([state, ctrl['state'].to(state.dtype)], dim=1)
-                tmpl_all = torch.cat([tmpl_all, ctrl['tmpl'].to(tmpl_all.dtype)], dim=1)
-                mask = torch.cat([mask, torch.ones(mask.shape[:-1] + (ctrl['state'].shape[1],), dtype=torch.bool, device=mask.device)], dim=-1)
-            agent_sc = self._heading_sc() if ctrl is None else _ops.heading_sc(state[..., 2])
-            wp_tri = wp_on = None
-            if waypoints is not None and waypoints.shape[2] > 0:
-                wp_tri, wp_on = self._waypoint_triangles(waypoints.to(state.dtype), waypoints_rendering_mask)
+            state, tmpl_all, mask, agent_sc, wp_tri = self._scene_inputs(scene, state, tmpl_all, mask, waypoints, waypoints_rendering_mask)
             # the metrics run beside the launch; a differentiable render forks too when the launch stays on the caller's stream (the plain second
             # stream, or 'reserved' with the loop on sim.raster_stream()): the metric nodes are then autograd nodes of the side stream, and the
             # engine runs their backward there as well -- beside the rasteriser's backward
@@ -900,24 +941,8 @@ class Simulator:
                 self._mark_fork(write_bound=self.renderer.out_dtype == torch.float32 and (r is None or min(r.height, r.width) > 208))
             # render_egocentric with gradients: the cameras are the exposed agents themselves -- one autograd node takes state and headings and
             # folds the cameras' gradient into the agents' (no slice nodes for camera_xy / camera_sc in the graph)
-            ego_n = n_cam if (_ego and diff and ctrl is None and n_cam <= state.shape[1]) else 0
-            k, ktab = scene['keys'], scene['key_table']
-            if custom_agent_colors is not None:
-                # generate() paints the four body vertices of agent a with custom_agent_colors[b, c, a] for camera c
-                # (mesh.py:1092-1099); the direction triangle keeps its colour.  Same rendering level, so only the colour
-                # bits of the body key change -- per camera.
-                rgb = _ops.quantise_colors(custom_agent_colors.to(state.device)).to(torch.int32)          # (B,Nc,A,)
-                kc = k[:, None].expand(-1, n_cam, -1, -1).clone()
-                kc[..., 0] = (kc[..., 0] & ~0xFFFFFF) | rgb
-                k, ktab = kc.contiguous(), None
-            if ctrl is not None:
-                kq = self._control_keys(scene)
-                k = torch.cat([k, kq[:, None].expand(-1, n_cam, -1, -1) if k.dim() == 4 else kq], dim=-2).contiguous()
-            extra = dict()
-            if wp_tri is not None:
-                wk = scene['wp_key']
-                extra = dict(extra_tri=wp_tri, extra_key=torch.full(wp_tri.shape[:3], wk, dtype=torch.int32, device=state.device))
-                ktab = None if ktab is None else sorted(set(ktab) | {wk})
+            ego_n = n_cam if (_ego and diff and scene['ctrl'] is None and n_cam <= state.shape[1]) else 0
+            k, ktab, extra = self._launch_keys(scene, n_cam, custom_agent_colors, wp_tri)
             launch = lambda: self.renderer.render_scene(scene['map'], state, agent_sc, tmpl_all, k, mask.contiguous(), camera_xy, camera_sc,     # noqa: E731
                                                         res=res, fov=fov, key_table=ktab, differentiable=diff, **extra, out=out, ego_cameras=ego_n)
             if self.overlap_infractions == 'reserved' and not diff and self._fork is not None and state.is_cuda and \
@@ -955,6 +980,11 @@ class Simulator:
                           visibility_matrix: Optional[Tensor] = None, custom_agent_colors: Optional[Tensor] = None,
                           n_subsequent_waypoints: int = 1, noisy_perception: bool = False, out: Optional[Tensor] = None) -> Tensor:
         """One camera per exposed agent -> BxAx3xHxW (simulator.py:994-1033).  `out`: see `render`."""
+        return self.render(**self._egocentric_cameras(ego_rotate, visibility_matrix, n_subsequent_waypoints), res=res, fov=fov,
+                           custom_agent_colors=custom_agent_colors, noisy_perception=noisy_perception, out=out, _ego=ego_rotate)
+
+    def _egocentric_cameras(self, ego_rotate: bool, visibility_matrix: Optional[Tensor], n_subsequent_waypoints: int):
+        """the cameras of `render_egocentric`, one per exposed agent, as keyword arguments of `render` / `render_semantic`"""
         state = self.get_state()
         camera_xy, camera_psi = state[..., :2], state[..., 2:3]
         if not ego_rotate:
@@ -971,24 +1001,21 @@ class Simulator:
                 cam_sc = cam_sc[..., :self.agent_count, :]
         waypoints = self.get_waypoints(count=n_subsequent_waypoints)                  # simulator.py:1013-1017
         waypoints_mask = self.get_waypoints_mask(count=n_subsequent_waypoints) if waypoints is not None else None
-        return self.render(camera_xy, camera_psi, rendering_mask=rendering_mask, res=res, fov=fov, custom_agent_colors=custom_agent_colors,
-                           waypoints=waypoints, waypoints_rendering_mask=waypoints_mask, noisy_perception=noisy_perception, _camera_sc=cam_sc,
-                           out=out, _ego=ego_rotate)
+        return dict(camera_xy=camera_xy, camera_psi=camera_psi, rendering_mask=rendering_mask, waypoints=waypoints,
+                    waypoints_rendering_mask=waypoints_mask, _camera_sc=cam_sc)
 
     # ------------------------------------------------------------------------------------------------- semantic masks
     def _category_keys(self, scene) -> Dict[str, int]:
         """category -> its key in this scene's launches (rank of its rendering level << 24 | its colour, as _scene() builds them), for every
         category with a level and a colour whose level the map's level table holds"""
-        lv, cm, smap = self.renderer.rendering_levels, self.renderer.color_map, scene['map']
         out = {}
-        for n in lv:
-            if n not in cm:
+        for n in self.renderer.rendering_levels:
+            if n not in self.renderer.color_map:
                 continue
             try:
-                rank = smap.rank_of(lv[n])
+                out[n] = self._category_key(scene['map'], n)
             except ValueError:                                       # a level this scene never draws at
                 continue
-            out[n] = (rank << 24) | int(_ops.quantise_colors(torch.tensor(cm[n], dtype=torch.float32) / 255.0))
         return out
 
     def semantic_channels(self) -> List[str]:
@@ -1042,27 +1069,10 @@ class Simulator:
             raise NotImplementedError(f'semantic masks are rendered by HipRenderer only, not by {type(self.renderer).__name__}')
         scene = self._scene()
         chans, key_channels = self._semantic_spec(scene, channels)
-        camera_sc = _camera_sc if _camera_sc is not None else torch.cat([torch.sin(camera_psi), torch.cos(camera_psi)], dim=-1)
-        if camera_xy.dim() == 2:
-            camera_xy, camera_sc = camera_xy.unsqueeze(1), camera_sc.unsqueeze(1)
-        n_cam = camera_xy.shape[-2]
-        present = self.get_all_agent_present_mask()
-        mask = present.unsqueeze(-2).expand(present.shape[:-1] + (n_cam,) + present.shape[-1:])
-        if rendering_mask is not None:
-            mask = mask.logical_and(rendering_mask.to(torch.bool))
-        state, tmpl, ctrl = self.get_all_agent_state().detach(), scene['tmpl'], scene['ctrl']
-        keys, ktab = scene['keys'], scene['key_table']
-        if ctrl is not None:                                        # stop lines and lights ride along as extra quads, as in render()
-            state = torch.cat([state, ctrl['state'].to(state.dtype)], dim=1)
-            tmpl = torch.cat([tmpl, ctrl['tmpl'].to(tmpl.dtype)], dim=1)
-            mask = torch.cat([mask, torch.ones(mask.shape[:-1] + (ctrl['state'].shape[1],), dtype=torch.bool, device=mask.device)], dim=-1)
-            keys = torch.cat([keys, self._control_keys(scene)], dim=-2).contiguous()
-        agent_sc = self._heading_sc() if ctrl is None else _ops.heading_sc(state[..., 2])
-        extra = dict()
-        if waypoints is not None and waypoints.shape[2] > 0:
-            wp_tri, _ = self._waypoint_triangles(waypoints.to(state.dtype), waypoints_rendering_mask)
-            extra = dict(extra_tri=wp_tri, extra_key=torch.full(wp_tri.shape[:3], scene['wp_key'], dtype=torch.int32, device=state.device))
-            ktab = sorted(set(ktab) | {scene['wp_key']})
+        camera_xy, camera_sc, mask = self._cameras(camera_xy, camera_psi, _camera_sc, rendering_mask)
+        state, tmpl, mask, agent_sc, wp_tri = self._scene_inputs(scene, self.get_all_agent_state().detach(), scene['tmpl'], mask, waypoints,
+                                                                 waypoints_rendering_mask)
+        keys, ktab, extra = self._launch_keys(scene, camera_xy.shape[-2], None, wp_tri)
         return self.renderer.render_scene_masks(scene['map'], state, agent_sc, tmpl, keys, mask.contiguous(), camera_xy, camera_sc, key_channels,
                                                 len(chans), res=res, fov=fov, key_table=ktab, packed=packed, out=out, **extra)
 
@@ -1070,21 +1080,8 @@ class Simulator:
                                    visibility_matrix: Optional[Tensor] = None, n_subsequent_waypoints: int = 1, packed: bool = False,
                                    out: Optional[Tensor] = None) -> Tensor:
         """`render_semantic` with one camera per exposed agent, the cameras, masks and waypoint goals of `render_egocentric` -> BxAxCxHxW."""
-        state = self.get_state()
-        camera_xy, camera_psi = state[..., :2], state[..., 2:3]
-        if not ego_rotate:
-            camera_psi = torch.ones_like(camera_psi) * (np.pi / 2)
-        rendering_mask = visibility_matrix
-        if self.cfg.single_agent_rendering:
-            A, total = self.agent_count, self.agent_count + self.npc_count
-            rendering_mask = torch.eye(A, total, dtype=torch.bool, device=state.device).unsqueeze(0).expand(self.batch_size, -1, -1)
-        cam_sc = None
-        if ego_rotate:
-            cam_sc = self._heading_sc()[..., :self.agent_count, :]
-        waypoints = self.get_waypoints(count=n_subsequent_waypoints)
-        waypoints_mask = self.get_waypoints_mask(count=n_subsequent_waypoints) if waypoints is not None else None
-        return self.render_semantic(camera_xy, camera_psi, channels=channels, rendering_mask=rendering_mask, res=res, fov=fov, waypoints=waypoints,
-                                    waypoints_rendering_mask=waypoints_mask, packed=packed, out=out, _camera_sc=cam_sc)
+        return self.render_semantic(**self._egocentric_cameras(ego_rotate, visibility_matrix, n_subsequent_waypoints), channels=channels, res=res,
+                                    fov=fov, packed=packed, out=out)
 
     # ------------------------------------------------------------------------------------------------- infractions
     def compute_offroad(self) -> Tensor:
