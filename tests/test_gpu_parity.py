@@ -179,6 +179,33 @@ def test_k1_unicycle_closed_form(ops):
 
 
 # ---------------------------------------------------------------------------------------------------- K2a
+#: Pairs whose overlap FLAG (value > 0) on the device may differ from the reference's recorded one: (set, metric, index, golden value).
+#: The device's sin / cos differ from torch-CPU's by an ulp in a minority of headings, so a golden value inside the value tolerance of the same
+#: test can land on the other side of zero.  An entry is legal only if its golden value lies in (0, atol] of its set -- asserted for every
+#: entry, so the table cannot wave a real error through -- and it must really flip on the device, so the table stays true.
+FLAG_EXCEPTIONS = [
+]
+
+
+def assert_flags_equal_golden(tag, metric, out, gold, atol, box1, box2):
+    """`out > 0` equals `gold > 0` on every pair with a finite golden value, except the pairs FLAG_EXCEPTIONS names for (tag, metric), which must
+    differ.  The message lists every pair that is out of line: index, golden value, device value, the two boxes."""
+    excepted = {i: v for t, m, i, v in FLAG_EXCEPTIONS if (t, m) == (tag, metric)}
+    out, gold = np.asarray(out).reshape(-1), np.asarray(gold).reshape(-1)
+    box1, box2 = np.asarray(box1).reshape(-1, 5), np.asarray(box2).reshape(-1, 5)
+    for i, v in excepted.items():
+        assert np.float32(gold[i]) == np.float32(v), f'{tag} {metric} pair {i}: the table says {v!r}, the golden file {gold[i]!r}'
+        assert 0 < gold[i] <= atol, f'{tag} {metric} pair {i}: golden value {gold[i]!r} is outside (0, {atol}]: a flip there is an error, not an exception'
+    fin = np.isfinite(gold)
+    differs = fin & ((out > 0) != (gold > 0))
+    expected = np.zeros_like(differs)
+    expected[list(excepted)] = True
+    wrong = np.nonzero(differs != expected)[0]
+    lines = [f'  pair {i}: golden {gold[i]!r} device {out[i]!r} box1 {box1[i].tolist()} box2 {box2[i].tolist()}'
+             + (' (in FLAG_EXCEPTIONS, but did not flip)' if expected[i] else '') for i in wrong]
+    assert not len(wrong), f'{tag} {metric}: {len(wrong)} of {int(fin.sum())} overlap flags out of line with the reference\n' + '\n'.join(lines)
+
+
 @pytest.mark.parametrize('metric', ['iou', 'discs'])
 @pytest.mark.parametrize('tag', ['cur', 'rnd0', 'rnd400'])
 def test_k2_pairwise_bit_exact(ops, oracle, metric, tag):
@@ -191,12 +218,11 @@ def test_k2_pairwise_bit_exact(ops, oracle, metric, tag):
     same = (out == ref) | (np.isnan(out) & np.isnan(ref))
     assert same.all(), f'{(~same).sum()} of {same.size} pairs differ, max {np.nanmax(np.abs(out - ref))}'
     # and against the reference's own numbers (its sin/cos come from torch-CPU): values to 2e-3 abs far from the origin
-    # (SURVEY Q3), overlap flags exact away from the touching configurations of the curated set
+    # (SURVEY Q3), overlap flags exact on every set, the curated touching configurations included (FLAG_EXCEPTIONS names what may flip)
     gold = g[tag + ('_iou' if metric == 'iou' else '_discs')]
     fin = np.isfinite(gold)
     np.testing.assert_allclose(out[fin], gold[fin], atol=2e-3 if tag == 'rnd400' else 2e-6, rtol=0)
-    if tag != 'cur':
-        assert ((out > 0) == (gold > 0)).mean() > 0.999
+    assert_flags_equal_golden(tag, metric, out, gold, 2e-3 if tag == 'rnd400' else 2e-6, g[tag + '_box1'], g[tag + '_box2'])
 
 
 @pytest.mark.parametrize('num_discs', [3, 5, 7, 9, 25])
@@ -211,7 +237,7 @@ def test_k2_discs_with_other_disc_counts(ops, oracle, num_discs):
     if num_discs != 5:
         gold = g[f'discs_{num_discs}']                           # the reference's numbers (its sin / cos come from torch-CPU)
         np.testing.assert_allclose(out, gold, atol=2e-6, rtol=0)
-        assert ((out > 0) == (gold > 0)).mean() > 0.995
+        assert_flags_equal_golden(f'discs_{num_discs}', 'discs', out, gold, 2e-6, g['box1'], g['box2'])
     with pytest.raises(AssertionError):
         collision_detection_with_discs(b1, b2, num_discs=4)
     with pytest.raises(RuntimeError):
@@ -686,6 +712,52 @@ def test_k3_six_to_ten_keys_at_256_in_every_workgroup_shape(ops, oracle, town, t
                     assert not bad.any(), f'{len(names)} agent types, debug {flags}, {dtype}: {bad.sum()} values differ'
     finally:
         testing_lib.tds_raster_set_debug(0)
+
+
+@pytest.mark.parametrize('res', [192, 208, 216])
+def test_k3_eight_to_ten_keys_between_192_and_216_pixels(ops, oracle, town, res):
+    """Four to six agent types (eight to ten distinct keys) at 192 / 208 / 216 pixels: the planes of a whole image exceed 52 KiB there, so the launch takes
+    8-wave workgroups and with them leaves the split form (K3s + K3r) that these resolutions otherwise use when a workspace exists (raster.hip:
+    raster_scene_impl).  Whichever form serves the launch, with a workspace and without one: the oracle's pixels, uint8 and float32."""
+    types = dict(vehicle=(4, (32, 74, 135)), bicycle=(5, (255, 150, 40)), pedestrian=(6, (255, 64, 180)), ego=(3, (255, 0, 0)), ground_truth=(9, (196, 188, 165)),
+                 prediction=(10, (255, 155, 0)))
+    levels = sorted(set(LEVEL_TABLE) | {float(z) for z, _ in types.values()}, reverse=True)
+    cats = town['categories']
+    cat = np.asarray(town['vert_category'])[town['faces'][:, 0]]
+    smap = ops.StaticMap(town['verts'], town['faces'], np.array([LEVELS[cats[c]] for c in cat], np.float32),
+                         np.array([pack(COLORS[cats[c]]) for c in cat], np.uint32), levels, device=DEV)
+    static = oracle.static_mesh_arrays(town['verts'], town['faces'], town['vert_category'], cats, colors={**oracle.DEFAULT_COLORS, **COLORS},
+                                       levels={**oracle.DEFAULT_LEVELS, **LEVELS})
+    road = town['verts'][np.asarray(town['vert_category']) == cats.index('road')]
+    gen = np.random.default_rng(res)
+    B, A, fov = 2, 14, 35.0
+    for n_types in (4, 5, 6):                                                 # 8, 9, 10 keys
+        names = list(types)[:n_types]
+        anchor = road[gen.integers(0, len(road), (B, 1))]
+        state = np.concatenate([anchor + gen.uniform(-20, 20, (B, A, 2)), gen.uniform(-np.pi, np.pi, (B, A, 1)), np.zeros((B, A, 1))], -1).astype(np.float32)
+        size = np.concatenate([gen.uniform(1.0, 8, (B, A, 1)), gen.uniform(0.6, 2.8, (B, A, 1))], -1).astype(np.float32)
+        kind = gen.integers(0, n_types, (B, A))
+        kind[:, :n_types] = np.arange(n_types)                                # every type occurs
+        mask = np.ascontiguousarray((gen.uniform(size=(B, 1, A)) < 0.9) & (gen.uniform(size=(B, A, A)) < 0.95))
+        body = np.array([(smap.rank_of(types[n][0]) << 24) | pack(types[n][1]) for n in names], np.int64)
+        dkey = (smap.rank_of(LEVELS['direction']) << 24) | pack(COLORS['direction'])
+        keys = torch.from_numpy(np.stack([body[kind], np.full_like(kind, dkey)], -1)).to(torch.int32).to(DEV)
+        lev = np.stack([np.array([types[n][0] for n in names], np.float32)[kind], np.full(kind.shape, LEVELS['direction'], np.float32)], -1)
+        col = np.stack([np.array([types[n][1] for n in names], np.float32)[kind], np.broadcast_to(np.array(COLORS['direction'], np.float32), kind.shape + (3,))], -2) / np.float32(255.0)
+        sd = dev(state)
+        agent_sc = ops.heading_sc(sd[..., 2])
+        ref = oracle.render_scenes(state, size, mask, state[..., :2].copy(), sc_np(agent_sc), *static, fov, res, agent_sc=sc_np(agent_sc),
+                                   actor_levels=lev, actor_colors=col.astype(np.float32))
+        assert (ref > 0).mean() > 0.05
+        for ws in (True, False):
+            ops.use_workspace = ws
+            try:
+                for dtype in (torch.uint8, torch.float32):
+                    img = ops.raster_scene(smap, sd, agent_sc, dev(oracle.actor_template(size)), keys, dev(mask), dev(state[..., :2].copy()), agent_sc, fov, res, dtype)
+                    bad = img.cpu().numpy().astype(np.float32) != ref
+                    assert not bad.any(), f'{res} pixels, {n_types} agent types, workspace={ws}, {dtype}: {bad.sum()} values differ'
+            finally:
+                ops.use_workspace = True
 
 
 def test_k3_u8_mode_equals_f32(ops, oracle, town):

@@ -209,7 +209,17 @@ def test_traffic_controls_are_rendered_like_the_reference_mesh(oracle):
         ref2 = oracle.render_rgb_mesh(rgb.verts.cpu().numpy(), rgb.attrs.cpu().numpy(), rgb.faces.cpu().numpy().astype(np.int32),
                                       s[..., :2].reshape(-1, 2).cpu().numpy(), cam_sc.reshape(-1, 2).cpu().numpy(), 2.0 / fov, res)
         np.testing.assert_array_equal(img2.cpu().numpy(), np.transpose(ref2, (0, 3, 1, 2)).reshape(img.shape))
-        assert (img2.cpu().numpy() != ref).mean() < 1e-3
+        # img2 comes from a mesh built with the device's sin / cos, ref from the reference's mesh: counted, and held to what the oracle shows when the
+        # golden mesh's positions move by the 2e-5 allowed for rgb.verts above (every x and y, random sign, three seeds) -- and to the earlier 1e-3 at most
+        n_diff = int((img2.cpu().numpy() != ref).sum())
+        moved = []
+        for seed in range(3):
+            v = g['rgb_verts'].copy()
+            v[..., :2] += np.float32(2e-5) * (np.random.default_rng(seed).integers(0, 2, v[..., :2].shape) * 2 - 1).astype(np.float32)
+            o = oracle.render_rgb_mesh(v, g['rgb_attrs'], g['rgb_faces'], s[..., :2].reshape(-1, 2).cpu().numpy(), cam_sc.reshape(-1, 2).cpu().numpy(), 2.0 / fov, res)
+            moved.append(int((np.transpose(o, (0, 3, 1, 2)).reshape(B, A, 3, res, res) != ref).sum()))
+        print(f'\ntraffic-control mesh at {res} pixels: {n_diff} of {ref.size} values differ from the reference mesh\'s image; golden vertices moved 2e-5: {moved}')
+        assert n_diff <= max(moved) and n_diff < 1e-3 * ref.size, f'{n_diff} of {ref.size} values differ, the moved golden mesh gives {moved}'
     # a light that changes state changes colour
     before = sim.render_egocentric(res=Resolution(96, 96), fov=60.0)
     tl.set_state((tl.state + 1) % 3)
@@ -391,6 +401,34 @@ def test_group_rows_confirms_hash_groups_exactly():
             for j in range(6):
                 if sm[i] == sm[j]:
                     assert order[i] == order[j]
+    finally:
+        _ops.row_hashes = saved
+    # rows narrower than a word are grouped by their BITS: two half-precision meshes that differ only in fractional parts (0.3 against 0.9, both 0 once
+    # converted to an integer) are two maps; narrow integers and masks that differ in one element too; equal rows still share a group
+    for dtype in (torch.float16, torch.bfloat16):
+        x = torch.full((4, 50, 3), 0.3, dtype=dtype)
+        x[1, 49, 2] = 0.9
+        x[3, 0, 0] = -0.3                                     # the sign alone
+        sm, reps, _ = _ops.group_rows([x.to(DEV)])
+        assert sm.tolist() == [0, 1, 0, 2] and reps == [0, 1, 3], f'{dtype}: {sm.tolist()}'
+        y = (torch.randn(3, 64, 3, generator=g) * 0.4).to(dtype)[order].to(DEV)       # random rows, mostly inside (-1, 1)
+        assert _ops.group_rows([y])[0].tolist() == [0, 1, 0, 2, 1, 0], dtype
+        assert _ops.group_rows([y, x[:1].expand(6, -1, -1).to(DEV)])[0].tolist() == [0, 1, 0, 2, 1, 0], dtype
+    for dtype, lo, hi in ((torch.int8, -128, 127), (torch.int16, -32768, 32767), (torch.uint8, 0, 255)):
+        x = torch.full((4, 33), lo, dtype=dtype)
+        x[1, 32] = hi
+        x[3, 0] = lo + 1
+        assert _ops.group_rows([x.to(DEV)])[0].tolist() == [0, 1, 0, 2], dtype
+    m = torch.zeros(4, 37, dtype=torch.bool)
+    m[2, 36] = True
+    assert _ops.group_rows([m.to(DEV)])[0].tolist() == [0, 0, 1, 0]
+    # with the exact confirmation alone (hashes forced equal): the comparison reads the same bits
+    try:
+        _ops.row_hashes = lambda tensors: torch.zeros(tensors[0].shape[0], 2, dtype=torch.int64, device=tensors[0].device)
+        for dtype in (torch.float16, torch.bfloat16):
+            x = torch.full((3, 50, 3), 0.3, dtype=dtype)
+            x[1, 49, 2] = 0.9
+            assert _ops.group_rows([x.to(DEV)])[0].tolist() == [0, 1, 0], dtype
     finally:
         _ops.row_hashes = saved
 
@@ -698,6 +736,122 @@ def test_differentiable_step_with_metrics_beside_the_rasteriser(mode):
         for x, y in zip(a, b):
             assert torch.isfinite(x).all() and torch.equal(x, y)
     assert serial[0][2].abs().sum() > 0 and serial[0][1].abs().sum() > 0
+
+
+@pytest.mark.parametrize('mode', [True, 'reserved'])
+def test_metric_gradients_do_not_depend_on_the_grad_mode_of_the_render(mode):
+    """A foreseen metric is computed inside render(), ahead of the raster launch -- in render()'s grad mode, not in that of the compute_* call that hands
+    it out.  A state that requires grad, an observation rendered under torch.no_grad() and the infraction losses under grad: on every step (the second and
+    third take the foreseen path) the metrics carry a graph, and values and gradients of state and action equal the serial run bit for bit.  And the
+    mirror: render under grad, metrics under no_grad -- the results carry no graph."""
+    import bench
+    from torchdrivesim_amd.utils import Resolution
+    dev = torch.device(DEV)
+    sim, actions, _ = bench.build_simulator(8, 32, dev, seed=13)
+    res = Resolution(256, 256)
+    state0 = sim.get_state().clone()
+
+    def run(overlap, metrics_under_grad):
+        sim.overlap_infractions = overlap
+        stream = sim.raster_stream() if mode == 'reserved' else torch.cuda.current_stream(dev)
+        torch.cuda.synchronize(dev)
+        out, forked = [], 0
+        with torch.cuda.stream(stream):
+            for i in range(3):
+                s0 = state0.clone().requires_grad_(True)
+                act = actions[i].clone().requires_grad_(True)
+                sim.kinematic_model.set_state(s0)
+                sim.step(act)
+                with torch.set_grad_enabled(not metrics_under_grad):
+                    sim.render_egocentric(res=res, fov=35.0)
+                forked += sim._fork is not None
+                with torch.set_grad_enabled(metrics_under_grad):
+                    col, off = sim.compute_collision(), sim.compute_offroad()
+                if metrics_under_grad:
+                    assert col.requires_grad and off.requires_grad, f'step {i}: the metrics of a state that requires grad carry no graph'
+                    (col.sum() + (off * off).sum()).backward()
+                    out.append((col.detach().clone(), off.detach().clone(), s0.grad.clone(), act.grad.clone()))
+                else:
+                    assert col.grad_fn is None and off.grad_fn is None and not col.requires_grad and not off.requires_grad, f'step {i}: computed under no_grad'
+                    out.append((col.clone(), off.clone()))
+            torch.cuda.synchronize(dev)
+        sim.overlap_infractions = False
+        return out, forked
+
+    for metrics_under_grad in (True, False):
+        serial, n0 = run(False, metrics_under_grad)
+        beside, n1 = run(mode, metrics_under_grad)
+        assert n0 == 0 and n1 == 3, 'the render did not fork'
+        for i, (a, b) in enumerate(zip(serial, beside)):
+            for x, y in zip(a, b):
+                assert torch.isfinite(x).all() and torch.equal(x, y), f'step {i}, metrics under grad: {metrics_under_grad}'
+        if metrics_under_grad:
+            assert all(a[2].abs().sum() > 0 and a[3].abs().sum() > 0 for a in serial)
+
+
+def test_a_metric_beside_the_render_is_differentiable_twice_and_pins_no_graph():
+    """Asked for twice between two renders, a metric that carries a graph is two graphs, as in the serial order: backward() through each succeeds and gives
+    the serial gradient, beside a differentiable render and beside an observation rendered under no_grad (first such render: computed beside the launch;
+    from the second: foreseen).  The state is a leaf set directly -- through step() the serial order could not walk the kinematic node twice either.  And what render() computed ahead does not outlive the state it was computed for: after step() or
+    set_state() nothing with a grad_fn can be reached from the fork."""
+    import bench
+    from torchdrivesim_amd.utils import Resolution
+    dev = torch.device(DEV)
+    sim, actions, _ = bench.build_simulator(4, 32, dev, seed=14)
+    res = Resolution(256, 256)
+    state0 = sim.get_state().clone()
+
+    def with_grad_fn(x, seen=None):
+        seen = set() if seen is None else seen
+        if id(x) in seen:
+            return []
+        seen.add(id(x))
+        if isinstance(x, torch.Tensor):
+            return [x] if x.grad_fn is not None else []
+        if isinstance(x, dict):
+            x = list(x.values())
+        return [t for y in x for t in with_grad_fn(y, seen)] if isinstance(x, (list, tuple)) else []
+
+    for i in range(6):
+        render_grad = i < 3                                                   # a differentiable render, then an observation rendered under no_grad
+        s0 = (state0 + 0.01 * i).requires_grad_(True)
+        sim.kinematic_model.set_state(s0)
+        sim.overlap_infractions = False
+        want_col, = torch.autograd.grad(sim.compute_collision().sum(), s0)
+        want_off, = torch.autograd.grad((sim.compute_offroad() ** 2).sum(), s0)
+        assert want_col.abs().sum() > 0 and want_off.abs().sum() > 0
+        sim.overlap_infractions = True
+        with torch.set_grad_enabled(render_grad):
+            sim.render_egocentric(res=res, fov=35.0)
+        assert sim._fork is not None
+        if i > 3:                                                             # asked for after the last observation render: foreseen at this one
+            assert set(sim._fork[3]) == {('collision', None), ('offroad',)}
+        for _ in range(2):
+            col, off = sim.compute_collision(), sim.compute_offroad()
+            s0.grad = None
+            col.sum().backward()
+            assert torch.equal(s0.grad, want_col), f'render {i}'
+            s0.grad = None
+            (off ** 2).sum().backward()
+            assert torch.equal(s0.grad, want_off), f'render {i}'
+    # ... through a step: the metrics of the state that is being left are let go with it
+    for leave in ('set_state', 'step'):
+        s0 = state0.clone().requires_grad_(True)
+        sim.kinematic_model.set_state(s0)
+        sim.step(actions[0].clone().requires_grad_(True))
+        with torch.no_grad():
+            sim.render_egocentric(res=res, fov=35.0)
+        assert sim._fork is not None and set(sim._fork[3]) == {('collision', None), ('offroad',)}
+        assert with_grad_fn(sim._fork)                                       # the state of this step, and the metrics foreseen for the losses
+        if leave == 'set_state':
+            sim.compute_collision(), sim.compute_offroad()
+            sim.set_state(state0.clone())
+        else:
+            sim.compute_collision()                                          # one handed out, one never asked for
+            sim.step(actions[1])
+        held = with_grad_fn(sim._fork)
+        assert not held, f'after {leave}(): {len(held)} tensors with a grad_fn are still reachable from the fork'
+    sim.overlap_infractions = False
 
 
 def test_foreseen_infractions_are_enqueued_ahead_of_the_raster_launch():

@@ -417,11 +417,13 @@ _ROW_SEEDS = (0x9e3779b97f4a7c15, 0xc2b2ae3d27d4eb4f)
 
 def _rows_view(t):
     """(tensor to read, number of rows, bytes per row, bytes between rows) for the row kernels: whole 4-byte words, dense inside a row;
-    a batch that is ONE row expanded (stride 0) is one row."""
+    a batch that is ONE row expanded (stride 0) is one row.  Rows are compared by their bits."""
     if t.dim() == 0:
         raise RuntimeError('group_rows needs tensors with a leading batch axis')
     if t.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.float16, torch.bfloat16):
-        t = t.to(torch.int32)
+        # narrower than a word: every element widened to one word of its own.  The BITS are widened, not the values -- a value conversion
+        # of half-precision numbers truncates them (0.3 and 0.9 are both 0), and rows that differ only in fractional parts would share a map
+        t = t.view(torch.int16 if t.element_size() == 2 else torch.uint8).to(torch.int32)
     n = t.shape[0]
     if n > 1 and t.stride(0) == 0:
         t, n = t[:1], 1

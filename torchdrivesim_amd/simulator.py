@@ -279,7 +279,7 @@ class Simulator:
             self.birdview_mesh_generator.initialize_traffic_controls_mesh(self.traffic_controls)      # simulator.py:373-374
         self._scene_cache = None        # device-resident static maps + actor templates/keys, rebuilt lazily
         self._fork = None               # (event, stamp, stream, results) recorded right before the last raster launch, see _beside_render
-        self._fork_used = []            # metrics asked for since then: enqueued ahead of the next raster launch
+        self._fork_used = {}            # metrics asked for since then -> the grad mode they were asked in: enqueued ahead of the next raster launch
 
     # ------------------------------------------------------------------------------------------------- properties
     @property
@@ -563,6 +563,7 @@ class Simulator:
         assert_equal(agent_action.shape[-2], self.agent_count)
         self.npc_controller.advance_npcs(self)
         self._sc_cache_grad = None               # the shared [sin, cos] node of the state that is being left: do not pin its graph
+        self._drop_fork()                        # nor do the metrics computed for it
         self.kinematic_model.step(agent_action)
         if self.traffic_controls is not None:                       # simulator.py:857-859
             for control in self.traffic_controls.values():
@@ -582,6 +583,7 @@ class Simulator:
         assert k <= full
         state = agent_state if k == full else torch.cat([agent_state, current[..., (k - full):]], dim=-1)
         self._sc_cache_grad = None
+        self._drop_fork()
         self.kinematic_model.set_state(state.where(mask.unsqueeze(-1).expand_as(state), current))
 
     def update_present_mask(self, present_mask: Tensor) -> None:
@@ -603,7 +605,9 @@ class Simulator:
     #: after its previous render are enqueued on the side stream right BEFORE the next raster launch, from inside `render` (`_mark_fork`):
     #: they take the CUs they need first, the surplus workgroups of the persistent launch start a few microseconds late and still find work,
     #: and `compute_*` hands the finished result out.  A metric that was not foreseen runs on the side stream after the launch, as in round 3,
-    #: and is foreseen from then on; one that is no longer asked for is dropped after one step.
+    #: and is foreseen from then on; one that is no longer asked for is dropped after one step.  A metric is foreseen in the grad mode it was last
+    #: ASKED FOR in (render() under no_grad for an observation, the infraction losses under grad: the foreseen result carries its graph), and what
+    #: was computed for a state is let go when `step` / `set_state` leave that state.
     overlap_infractions = False
     _side_streams: Dict[int, Any] = {}
     _side_priority = -1          # HIP stream priority of the side stream (-1: high)
@@ -661,20 +665,16 @@ class Simulator:
         float32 launch between 160 and 208 pixels is still limited by instruction issue -- 192 x 192: 4.97 ms for 29 GB = 0.73 of the roof.)
         Only then does 'reserved' pay -- a compute-bound launch (uint8, low resolutions) would give an eighth of its CUs away for nothing, so
         the mode is skipped for it (the metrics run behind the launch)."""
-        prev, self._fork = self._fork, None
-        wanted, self._fork_used = getattr(self, '_fork_used', None) or [], []
+        self._drop_fork()
+        wanted, self._fork_used = getattr(self, '_fork_used', None) or {}, {}
         state = self.kinematic_model.get_state()
-        if prev is not None:
-            # a foreseen metric the loop did not ask for again was never joined: its kernels read state / present / [sin, cos] that the
-            # caller's stream is about to overwrite or free.  Join them here -- the launch they ran beside is long over, the wait is free
-            # (and a captured graph has no dangling fork).
-            for _, done in prev[3].values():
-                prev[2].wait_event(done)
         if not self.overlap_infractions or not state.is_cuda or self.npc_count > 0:
             return
         if self.overlap_infractions == 'reserved' and (not write_bound or not self._reserved_usable(state.device)):
             return
-        self._heading_sc()                                        # the shared [sin, cos] exists before the fork
+        for grad_mode in {torch.is_grad_enabled(), *wanted.values()}:
+            with torch.set_grad_enabled(grad_mode):
+                self._heading_sc()                                # the shared [sin, cos] exists before the fork, in every grad mode it will be read in
         srcs = self._fork_sources()
         stream = torch.cuda.current_stream(state.device)
         ev = torch.cuda.Event()
@@ -685,20 +685,35 @@ class Simulator:
             side = self._side_stream(state.device)
             side.wait_event(ev)
             with torch.cuda.stream(side):
-                for key in wanted:
-                    out = self._metric_fn(key)()
+                for key, grad_mode in wanted.items():
+                    with torch.set_grad_enabled(grad_mode):          # the mode compute_* was last called in, not the mode of this render
+                        out = self._metric_fn(key)()
                     out.record_stream(stream)                        # allocated in the side stream's pool, consumed on the caller's stream
                     ready[key] = out
             done = torch.cuda.Event()
             done.record(side)
-            ready = {k: (v, done) for k, v in ready.items()}
+            ready = {k: (v, done, wanted[k]) for k, v in ready.items()}
         self._fork = (ev, [(t, t._version) for t in srcs], stream, ready)
+
+    def _drop_fork(self) -> None:
+        """Lets go of the last fork and of what was computed for it (step / set_state: the state it belongs to is being left, and a result
+        that carries a graph would pin that step's autograd graph until the next render)."""
+        prev, self._fork = self._fork, None
+        if prev is not None:
+            # a foreseen metric the loop did not ask for was never joined: its kernels read state / present / [sin, cos] that the
+            # caller's stream is about to overwrite or free.  Join them here -- the launch they ran beside is long over, the wait is free
+            # (and a captured graph has no dangling fork).
+            for done in {id(entry[1]): entry[1] for entry in prev[3].values()}.values():
+                prev[2].wait_event(done)
 
     def _beside_render(self, fn, key=None):
         """fn() -> Tensor: the result computed ahead of the raster launch when `key` was foreseen, else fn() on the side stream when a
         render of exactly this state is in flight on the current stream, else in place.
         With overlap_infractions on, asking for the same metric twice between two renders returns the SAME tensor object (the result is
-        computed once per state): treat the returned tensors as read-only, or clone them before an in-place edit."""
+        computed once per state) unless it carries a graph: treat the returned tensors as read-only, or clone them before an in-place edit.
+        A result is handed out only in the grad mode it was computed in: one built under no_grad for a caller that records gradients is
+        computed again, one that carries a graph is detached for a caller under no_grad, and a graph is handed out ONCE (asked for again,
+        the metric is computed again -- a second backward() through a shared graph would find it freed), as in the serial order."""
         fork = self._fork
         if fork is None or not self.overlap_infractions:
             return fn()
@@ -709,12 +724,22 @@ class Simulator:
         if len(srcs) != len(stamp) or any(a is not b or a._version != v for a, (b, v) in zip(srcs, stamp)) or self.npc_count > 0 or \
                 torch.cuda.current_stream(state.device) != main or cached is None or cached[0] is not state or cached[1] != state._version:
             return fn()
-        if key is not None and key not in self._fork_used:
-            self._fork_used.append(key)                              # foreseen at the next render
+        grad_mode = torch.is_grad_enabled()
+        if key is not None:
+            self._fork_used[key] = grad_mode                         # foreseen at the next render, in this grad mode
         if key is not None and key in ready:
-            out, done = ready[key]
+            out, done, built_with_grad = ready[key]
             main.wait_event(done)
-            return out
+            if out.requires_grad:
+                if grad_mode:
+                    del ready[key]                                   # a graph is handed out once
+                    return out
+                out = out.detach()
+                ready[key] = (out, done, False)
+                return out
+            if built_with_grad or not grad_mode or not any(t.requires_grad for t in srcs):
+                return out
+            del ready[key]                                           # built under no_grad, wanted with its graph: computed again below
         side = self._side_stream(state.device)
         side.wait_event(ev)
         with torch.cuda.stream(side):
@@ -723,8 +748,8 @@ class Simulator:
         done = torch.cuda.Event()
         done.record(side)
         main.wait_event(done)
-        if key is not None:
-            ready[key] = (out, done)                             # asked for again before the next render: the same tensor
+        if key is not None and not out.requires_grad:
+            ready[key] = (out, done, grad_mode)                  # asked for again before the next render: the same tensor
         return out
 
     # ------------------------------------------------------------------------------------------------- device scene data
