@@ -383,6 +383,8 @@ typedef struct tds_laneset tds_laneset_t;
  * (n_left + n_right + 1) x 3 doubles, *n_out = number of points written (0 when a bound is empty). */
 int tds_lanelet_centerline_f64(const double *left, int n_left, const double *right, int n_right, double *out, int *n_out);
 
+/* tds_lanes_create also keeps, per centre-line point, the cumulative 3-D length of its line (float64, summed front to back) and the list of
+ * lanelets a point can be drawn on, for tds_spawn_on_lanes_f32. */
 /* HOST inputs: poly_xy P x 2 float64 = outline rings (left bound followed by the reversed right bound), lanelet l owns points
  * poly_start[l] .. poly_start[l+1]; cl_xyz C x 3 float64 = centre lines, cl_start likewise; flags (n_lanelets, may be NULL): bit 0 =
  * the lanelet carries one of the tags to exclude (infractions.py:21).  cell_size <= 0 selects the default (8 m).  Queries may use
@@ -413,6 +415,35 @@ int tds_wrong_way_f32(const tds_laneset_t *set, const int32_t *scene_map, int64_
 int tds_lanelet_directions_f64(const tds_laneset_t *set, const int32_t *scene_map, int64_t points_per_scene, const double *xy,
                                double *dirs, double *dists, int32_t *count, uint8_t *status, int max_dirs, int64_t n_points,
                                float lanelet_dist_tolerance, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * On-lane scene initialisation            behavior/heuristic.py:10-53 (heuristic_initialize); lanelet2.py:183-208
+ *                                         (pick_random_point_and_orientation); infractions.py:503-545 (the acceptance test)
+ * The reference places one agent after the other in ONE scene, one torch call and one Lanelet2 query per attempt.  Here a batch of scenes is
+ * one launch: one wavefront per scene, 64 attempts of the current agent at once.
+ *   set, scene_map     lane tables as for tds_wrong_way_f32 (a negative entry, or a table without an eligible lanelet -- at least two
+ *                      centre-line points and a finite positive length --, places nothing)
+ *   scene_ids          n_scenes int64 (device) or NULL = 0 .. n_scenes-1: the identity of each scene in the random stream
+ *   attributes         n_scenes x A x 3  [length, width, lr] (lr is not read)
+ *   occupied           n_scenes x M x 5 boxes [x, y, length, width, psi] that are already there, NOT yet inflated by the gap, or NULL (M = 0);
+ *   occupied_sc        n_scenes x M x 2 [sin, cos] of the angle the disc metric uses for the INFLATED box: psi + pi/2 * (width + gap_lat >
+ *                      length + gap_long); occupied_mask n_scenes x M uint8 or NULL (all present)
+ *   state              n_scenes x A x 4 [x, y, psi, speed];  sc n_scenes x A x 2 [sin, cos] of the heading, taken from the unit vector of
+ *                      the lane's local direction (psi = atan2 of the same vector);  placed n_scenes x A uint8;
+ *   attempts           n_scenes x A int32: candidates drawn for the agent (max_attempts for the one that found no place, 0 = never reached)
+ * Candidate (agent i, attempt a) of scene id s: Philox4x32-10, key = (seed low, seed high), counter = (s low, s high, i, a) -> r0..r3;
+ * eligible lanelet (r0 * n_eligible) >> 32, arc length = length * (r1 + 0.5) * 2^-32 (float64), speed = min_speed + (max_speed - min_speed) *
+ * ((r2 >> 8) * 2^-24) (float32).  Agents are placed in index order; agent i takes the candidate with the LOWEST attempt index whose 5-disc
+ * value (tds_pairwise_overlap_f32, TDS_METRIC_DISCS) against every present occupied box and every agent 0 .. i-1 -- each grown by
+ * [gap_long, gap_lat] -- is not > 0.  In a scene where agent i finds none in max_attempts, agents i .. are not placed (rows of zeros).
+ * agents_per_scene + n_occupied <= TDS_SPAWN_MAX_BOXES (the boxes of a scene live in LDS, 24 bytes each).  Every output is written in
+ * full; nothing is allocated and nothing synchronises. */
+#define TDS_SPAWN_MAX_BOXES 2048
+int tds_spawn_on_lanes_f32(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, int64_t n_scenes,
+                           int agents_per_scene, const float *attributes, const float *occupied, const float *occupied_sc,
+                           const uint8_t *occupied_mask, int n_occupied, uint64_t seed, float min_speed, float max_speed,
+                           float gap_long, float gap_lat, int max_attempts, float *state, float *sc, uint8_t *placed,
+                           int32_t *attempts, void *stream);
 
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with

@@ -119,6 +119,7 @@ _SIGNATURES = {
     'tds_laneset_destroy': [_vp],
     'tds_wrong_way_f32': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp],
     'tds_lanelet_directions_f64': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp],
+    'tds_spawn_on_lanes_f32': [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_uint64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 
 
@@ -201,6 +202,7 @@ def last_error():
 
 E_INVAL, E_HIP, E_NOMEM, E_LIMIT = -1, -2, -3, -4          # TDS_EINVAL, TDS_EHIP, TDS_ENOMEM, TDS_ELIMIT of include/tdship.h
 BUFFER_DENSE = 1
+SPAWN_MAX_BOXES = 2048           # TDS_SPAWN_MAX_BOXES
 
 
 class TdsError(RuntimeError):

@@ -1225,3 +1225,49 @@ def lanelet_directions(tables, scene_map, points, lanelet_dist_tolerance, max_di
              nat.dev_ptr(count, i32, 'count'), nat.dev_ptr(status, u8, 'status'), max_dirs, n, float(lanelet_dist_tolerance),
              nat.stream_ptr(dev))
     return dirs, dists, count, status
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# on-lane scene initialisation (csrc/spawn.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def spawn_on_lanes(lane_set, scene_ids, attributes, seed, min_speed=0.0, max_speed=10.0, gap=(1.0, 0.2), max_attempts=500, occupied=None,
+                   occupied_sc=None, occupied_mask=None):
+    """tds_spawn_on_lanes_f32: attributes (B,A,3) -> (state (B,A,4), sc (B,A,2), placed (B,A) bool, attempts (B,A) int32).
+    lane_set: a LaneTableSet (its scene_map, when there is one, has B entries); scene_ids (B,) int64 or None = arange(B);
+    occupied (B,M,5) boxes not yet inflated, occupied_sc (B,M,2) = metric_sc of the INFLATED boxes ('discs'), occupied_mask (B,M).
+    One launch on the current stream, no allocation besides the outputs, no synchronisation."""
+    attributes = _c(attributes)
+    if attributes.dim() != 3 or attributes.shape[-1] != 3:
+        raise RuntimeError(f'spawn_on_lanes: attributes must be (B,A,3), got {tuple(attributes.shape)}')
+    dev = attributes.device
+    B, A = attributes.shape[:2]
+    attr_p = nat.dev_ptr(attributes, f32, 'attributes')
+    if lane_set.scene_map is not None and lane_set.scene_map.shape[0] != B:
+        raise RuntimeError(f'spawn_on_lanes: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, attributes have {B}')
+    ids_p = None
+    if scene_ids is not None:
+        scene_ids = scene_ids.contiguous()
+        if tuple(scene_ids.shape) != (B,):
+            raise RuntimeError(f'spawn_on_lanes: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
+        ids_p = nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    M, occ_p, occ_sc_p, occ_mask_p = 0, None, None, None
+    if occupied is not None:
+        occupied, occupied_sc = _c(occupied), _c(occupied_sc)
+        M = occupied.shape[1]
+        if tuple(occupied.shape) != (B, M, 5) or tuple(occupied_sc.shape) != (B, M, 2):
+            raise RuntimeError(f'spawn_on_lanes: occupied must be ({B},M,5) with occupied_sc ({B},M,2), got {tuple(occupied.shape)}, {tuple(occupied_sc.shape)}')
+        occ_p, occ_sc_p = nat.dev_ptr(occupied, f32, 'occupied'), nat.dev_ptr(occupied_sc, f32, 'occupied_sc')
+        if occupied_mask is not None:
+            occupied_mask = _u8(occupied_mask)
+            if tuple(occupied_mask.shape) != (B, M):
+                raise RuntimeError(f'spawn_on_lanes: occupied_mask must be ({B},{M}), got {tuple(occupied_mask.shape)}')
+            occ_mask_p = nat.dev_ptr(occupied_mask, u8, 'occupied_mask')
+    state = torch.empty((B, A, 4), dtype=f32, device=dev)
+    sc = torch.empty((B, A, 2), dtype=f32, device=dev)
+    placed = torch.empty((B, A), dtype=torch.bool, device=dev)
+    attempts = torch.empty((B, A), dtype=i32, device=dev)
+    nat.call('tds_spawn_on_lanes_f32', dev, lane_set.handle, None if lane_set.scene_map is None else nat.dev_ptr(lane_set.scene_map, i32, 'scene_map'),
+             ids_p, B, A, attr_p, occ_p, occ_sc_p, occ_mask_p, M, int(seed) & 0xFFFFFFFFFFFFFFFF, float(min_speed), float(max_speed),
+             float(gap[0]), float(gap[1]), int(max_attempts), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
+             ctypes.c_void_p(placed.data_ptr()), nat.dev_ptr(attempts, i32, 'attempts'), nat.stream_ptr(dev))
+    return state, sc, placed, attempts

@@ -1,6 +1,8 @@
-"""NPC behaviours that feed `Simulator.step` (reference torchdrivesim/behavior/): log replay.  The reference's IAI client (an HTTP
-service) and its lanelet-based random initialisation are outside the hot path and not provided."""
+"""NPC behaviours that feed `Simulator.step` and the initial scene (reference torchdrivesim/behavior/): log replay, and the lanelet-based
+random initialisation (`heuristic_initialize`, batched as `heuristic_initialize_batch`: one kernel launch).  The reference's IAI client (an
+HTTP service) is outside the hot path and not provided."""
 from torchdrivesim_amd.behavior.common import InitializationFailedError
+from torchdrivesim_amd.behavior.heuristic import heuristic_initialize, heuristic_initialize_batch
 from torchdrivesim_amd.behavior.replay import ReplayController, interaction_replay
 
-__all__ = ['InitializationFailedError', 'ReplayController', 'interaction_replay']
+__all__ = ['InitializationFailedError', 'ReplayController', 'interaction_replay', 'heuristic_initialize', 'heuristic_initialize_batch']

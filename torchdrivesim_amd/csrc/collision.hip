@@ -3,6 +3,7 @@
 // Reference: simulator.py:1064-1109,1161-1194; _iou_utils.py:42-367; infractions.py:378-426,503-545.
 // Compute bound (~2k VALU ops per surviving pair, 16 IEEE divisions); bytes are negligible (20 B/agent).
 #include "tds_common.h"
+#include "tds_discs.h"
 #include <algorithm>
 
 namespace {
@@ -11,7 +12,8 @@ constexpr int CBLOCK = 256;            // 4 waves
 constexpr int ROWS_PER_WAVE = 4;
 constexpr float PI_F = 3.14159265358979323846f;
 
-struct Box { float x, y, l, w; float s, c; };
+using tds::Box;
+using tds::discs_pair;          // tds_discs.h: shared with spawn.hip
 struct Corners { float x[4], y[4]; };
 
 __device__ __forceinline__ float scrub(float v) {          // torch.nan_to_num(nan=0) simulator.py:1095-1096
@@ -213,31 +215,6 @@ __device__ float iou_pair(const Box &b1, const Corners &c1, const Box &b2, const
     if (!(dx * dx + dy * dy > reach * reach)) inter = intersection_area(c1, c2, scr, lane);
     float u = a1 + a2 - inter;
     return inter / u;                          // iou_differentiable_fast :363-367
-}
-
-// bbox2discs + cdist + relu, infractions.py:378-426,503-545.  b.s/b.c are of yaw + pi/2*(wid>len).
-__device__ float discs_pair(const Box &b1, const Box &b2) {
-    float ra = fminf(b1.l, b1.w) / 2.0f, rb = fminf(b2.l, b2.w) / 2.0f;
-    float ha = fmaxf(b1.l, b1.w) / 2.0f - ra, hb = fmaxf(b2.l, b2.w) / 2.0f - rb;
-    float d = __builtin_inff();
-    bool any_nan = false;
-#pragma unroll
-    for (int i = -2; i <= 2; ++i) {
-        float da = ((float)i * ha) / 2.0f;
-        float ax = (da * b1.c - 0.0f * b1.s) + b1.x, ay = (da * b1.s + 0.0f * b1.c) + b1.y;
-#pragma unroll
-        for (int j = -2; j <= 2; ++j) {
-            float db = ((float)j * hb) / 2.0f;
-            float bx = (db * b2.c - 0.0f * b2.s) + b2.x, by = (db * b2.s + 0.0f * b2.c) + b2.y;
-            float ex = ax - bx, ey = ay - by;
-            float dd = sqrtf(__fmaf_rn(ey, ey, ex * ex));    // torch.cdist accumulates with an FMA (probed)
-            any_nan |= (dd != dd);
-            d = fminf(d, dd);
-        }
-    }
-    if (any_nan) d = __builtin_nanf("");
-    float l = 1.0f - d / (ra + rb);
-    return (l != l) ? l : fmaxf(l, 0.0f);
 }
 
 // the same with 2 * nps + 1 discs per box (`num_discs`, infractions.py:390-400): centres at i * (max/2 - r) / nps

@@ -19,41 +19,7 @@
 #include <vector>
 
 #include "tds_common.h"
-
-namespace tds {
-
-struct LaneRec {
-    int32_t poly_start, poly_n;     // outline ring: left bound, then the right bound reversed (implicitly closed)
-    int32_t cl_start, cl_n;         // centre line points
-    int32_t flags;                  // bit 0: tagged with an excluded attribute ('parking', infractions.py:21)
-    float bx0, by0, bx1, by1;       // bounding box of the outline, rounded outwards
-};
-
-struct LaneView {
-    const double *poly;             // 2 doubles per point
-    const double *cl;               // 3 doubles per point
-    const LaneRec *rec;
-    const int32_t *cell_start;      // nx*ny + 1
-    const int32_t *cell_items;      // lanelet indices
-    double ox, oy, inv_cell;
-    int nx, ny, n;
-    float max_tol;
-};
-
-}  // namespace tds
-
-struct tds_lanes {
-    tds::LaneView view;
-    void *d_poly, *d_cl, *d_rec, *d_cell_start, *d_cell_items;
-    int device;
-    int64_t bytes;
-};
-
-struct tds_laneset {
-    tds::LaneView *d_views;
-    int n, device;
-    float max_tol;
-};
+#include "tds_lanes.h"
 
 using tds::LaneRec;
 using tds::LaneView;
@@ -254,21 +220,41 @@ TDS_EXPORT int tds_lanes_create(const double *poly_xy, const int32_t *poly_start
         v.ox = v.oy = 0, v.nx = v.ny = 0;
     }
     std::vector<double> poly(poly_xy, poly_xy + 2 * (size_t)n_poly), cl(cl_xyz, cl_xyz + 3 * (size_t)n_cl);
+    // for tds_spawn_on_lanes_f32: the cumulative 3-D length at every centre-line point (0 at a lanelet's first point; float64, summed front
+    // to back, each segment sqrt((dx*dx + dy*dy) + dz*dz) -- numpy's `np.sqrt(((c[1:] - c[:-1]) ** 2).sum(1))` and `np.cumsum`) and the
+    // lanelets a point can be drawn on: at least two points and a finite positive length
+    std::vector<double> cum((size_t)n_cl, 0.0);
+    std::vector<int32_t> eligible;
+    for (int l = 0; l < n_lanelets; l++) {
+        const LaneRec &r = rec[l];
+        double acc = 0.0;
+        for (int i = 1; i < r.cl_n; i++) {
+            const double *a = &cl[3 * (size_t)(r.cl_start + i - 1)], *b = a + 3;
+            double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
+            double seg = sqrt((dx * dx + dy * dy) + dz * dz);
+            acc = i == 1 ? seg : acc + seg;
+            cum[(size_t)r.cl_start + i] = acc;
+        }
+        if (r.cl_n >= 2 && acc > 0.0 && isfinite(acc)) eligible.push_back(l);
+    }
+    v.n_eligible = (int)eligible.size();
     int rc;
     if ((rc = upload(&h->d_poly, poly, &h->bytes)) || (rc = upload(&h->d_cl, cl, &h->bytes)) || (rc = upload(&h->d_rec, rec, &h->bytes)) ||
-        (rc = upload(&h->d_cell_start, cell_start, &h->bytes)) || (rc = upload(&h->d_cell_items, cell_items, &h->bytes))) {
+        (rc = upload(&h->d_cell_start, cell_start, &h->bytes)) || (rc = upload(&h->d_cell_items, cell_items, &h->bytes)) ||
+        (rc = upload(&h->d_cum, cum, &h->bytes)) || (rc = upload(&h->d_eligible, eligible, &h->bytes))) {
         tds_lanes_destroy(h);
         return rc;
     }
     v.poly = (const double *)h->d_poly, v.cl = (const double *)h->d_cl, v.rec = (const LaneRec *)h->d_rec;
     v.cell_start = (const int32_t *)h->d_cell_start, v.cell_items = (const int32_t *)h->d_cell_items;
+    v.cum = (const double *)h->d_cum, v.eligible = (const int32_t *)h->d_eligible;
     *out = h;
     return TDS_OK;
 }
 
 TDS_EXPORT int tds_lanes_destroy(tds_lanes_t *h) {
     if (!h) return TDS_OK;
-    for (void *p : {h->d_poly, h->d_cl, h->d_rec, h->d_cell_start, h->d_cell_items}) (void)hipFree(p);
+    for (void *p : {h->d_poly, h->d_cl, h->d_rec, h->d_cell_start, h->d_cell_items, h->d_cum, h->d_eligible}) (void)hipFree(p);
     delete h;
     return TDS_OK;
 }
