@@ -5,6 +5,7 @@ infractions as reward terms.  Runs on one MI355X with the Town01 package shipped
 lane map); the "policy" is random.
 
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
+    python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
 """
 import argparse
 import os
@@ -29,6 +30,8 @@ def main():
     ap.add_argument('--agents', type=int, default=16)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--res', type=int, default=128)
+    ap.add_argument('--scan', type=int, default=0, metavar='RAYS', help='observe RAYS-ray range scans (compute_range_scan) instead of images')
+    ap.add_argument('--scan-range', type=float, default=50.0)
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     gold = os.path.join(ROOT, 'tests', 'golden')
@@ -54,7 +57,11 @@ def main():
         programme.tick(0.1)
         controls['traffic_light'].set_state(current_light_state_tensor_from_controller(programme, light_ids).unsqueeze(0).expand(args.batch, -1).to(dev))
         sim.step(action)
-        obs = sim.render_egocentric(res=res, fov=35.0)                       # (B, A, 3, H, W): what a policy would consume
+        if args.scan:
+            scan = sim.compute_range_scan(n_rays=args.scan, max_range=args.scan_range)
+            obs = torch.stack([scan.agents, scan.road], dim=-1) / args.scan_range        # (B, A, R, 2) in [0, 1]: distance to the nearest other agent, to the road edge
+        else:
+            obs = sim.render_egocentric(res=res, fov=35.0)                   # (B, A, 3, H, W): what a policy would consume
         totals['collision'] += (sim.compute_collision() > 0).float().mean()
         totals['offroad'] += (sim.compute_offroad() > 0).float().mean()
         totals['wrong_way'] += (sim.compute_wrong_way() > 0).float().mean()

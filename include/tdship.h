@@ -445,6 +445,34 @@ int tds_spawn_on_lanes_f32(const tds_laneset_t *set, const int32_t *scene_map, c
                            float gap_long, float gap_lat, int max_attempts, float *state, float *sc, uint8_t *placed,
                            int32_t *attempts, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K5  range scans (no reference counterpart: the definition is this library's own, DESIGN.md "K5"; float64 model: tests/range_scan_model.py)
+ * R rays per exposed agent, from its centre, ray k of agent a along the unit vector [cos, sin] = ray_sc[b, a, k, (1, 0)] -- the caller computes
+ * [sin, cos] of psi_a + off_k with torch, like every other angle of this header.
+ *   boxes       B x E x 5  [x, y, length, width, psi]   all entities = A exposed agents followed by E - A NPCs (psi is not read)
+ *   sc          B x E x 2  [sin, cos] of psi;  present B x E uint8;  ray_sc B x A x R x 2
+ *   agent_range B x A x R  smallest t >= 0 at which the ray enters the rectangle of another present entity (slab test in the rectangle's
+ *                          frame; 0 from inside one); max_range without such a t below max_range
+ *   road_range  B x A x R  length of the ray's initial stretch on the map's faces: the least fixed point of F <- max{b_f : a_f <= F + gap_tolerance}
+ *                          from F = 0, [a_f, b_f] = where the ray meets the closed face f, over the faces of positive area; capped at max_range;
+ *                          ("positive area" is the one test that is NOT binary32: the cross product of two edges in float64 on the float32
+ *                          vertices, so that kernel and model drop the same faces; every range is binary32 + - * /)
+ *                          max_range everywhere without a map (map == NULL)
+ *   hit         B x A x R  int32: the entity that defines agent_range if agent_range < max_range and agent_range <= road_range (lowest index
+ *                          on a tie), -2 if road_range < max_range and road_range < agent_range, -1 if both are max_range
+ * Rows of exposed agents that are not present: max_range, max_range, -1.  Any of the three outputs may be NULL; without agent_range the rectangles
+ * are not tested and hit is computed as if agent_range were max_range.  The map is a geometry-only or a rendering map: only its grid is read.
+ * E <= TDS_SCAN_MAX_ENTITIES (the boxes of a scene live in LDS, 32 bytes each).  Nothing is allocated and nothing synchronises; every loop of the
+ * kernel is bounded whatever the inputs hold. */
+#define TDS_SCAN_MAX_ENTITIES 1024
+int tds_range_scan_f32(const tds_map_t *map, const float *boxes, const float *sc, const uint8_t *present, const float *ray_sc,
+                       float *agent_range, float *road_range, int32_t *hit, int64_t B, int64_t A, int64_t E, int R,
+                       float max_range, float gap_tolerance, void *stream);
+/* the same for scenes with different maps: scene b uses map scene_map[b] of the set (an index outside the set: as without a map) */
+int tds_range_scan_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, const float *boxes, const float *sc, const uint8_t *present,
+                             const float *ray_sc, float *agent_range, float *road_range, int32_t *hit, int64_t B, int64_t A, int64_t E, int R,
+                             float max_range, float gap_tolerance, void *stream);
+
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */

@@ -120,6 +120,8 @@ _SIGNATURES = {
     'tds_wrong_way_f32': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp],
     'tds_lanelet_directions_f64': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp],
     'tds_spawn_on_lanes_f32': [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_uint64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    'tds_range_scan_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
+    'tds_range_scan_multi_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
 }
 
 

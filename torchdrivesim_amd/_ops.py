@@ -631,6 +631,57 @@ def offroad(smap, state, lenwid, threshold=0.5, present=None, sc=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# K5 range scans
+# ---------------------------------------------------------------------------------------------------------------
+def check_range_scan_args(n_rays, max_range, gap_tolerance):
+    """the argument rules of tds_range_scan_f32, on the host: raised before anything is computed or launched"""
+    if int(n_rays) != n_rays or int(n_rays) <= 0 or int(n_rays) > 65536:
+        raise ValueError(f'range scan: the number of rays must be 1 .. 65536 (got {n_rays})')
+    for name, v in (('max_range', max_range), ('gap_tolerance', gap_tolerance)):
+        v = float(v)
+        if not (0.0 <= v <= 3.0e38):                    # (finite as a float32 too; NaN fails both comparisons)
+            raise ValueError(f'range scan: {name} must be finite and not negative (got {v})')
+
+
+def range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents=True):
+    """Range scan of every exposed agent (tds_range_scan_f32 / _multi, include/tdship.h "K5"): boxes (B,E,5) [x,y,length,width,psi], sc (B,E,2)
+    [sin, cos] of psi, present (B,E), ray_sc (B,A,R,2) [sin, cos] of every ray -> (agents, road, hit), each (B,A,R): float32, float32, int32.
+    smap: a StaticMap, a StaticMapSet (scene b on map scene_map[b]) or None (no road part: road = max_range).  want_agents=False skips the
+    rectangles (agents = max_range).  No gradient; CPU tensors raise (there is no CPU fallback)."""
+    if ray_sc.dim() != 4 or ray_sc.shape[-1] != 2:
+        raise ValueError(f'range scan: ray_sc must be (B, A, R, 2), got {tuple(ray_sc.shape)}')
+    B, A, R = (int(d) for d in ray_sc.shape[:3])
+    check_range_scan_args(R, max_range, gap_tolerance)
+    if boxes.dim() != 3 or boxes.shape[-1] != 5 or boxes.shape[0] != B:
+        raise ValueError(f'range scan: boxes must be ({B}, E, 5), got {tuple(boxes.shape)}')
+    E = int(boxes.shape[1])
+    if int(n_exposed) != A or A > E:
+        raise ValueError(f'range scan: {n_exposed} exposed agents, rays for {A}, {E} entities')
+    if tuple(sc.shape) != (B, E, 2) or tuple(present.shape) != (B, E):
+        raise ValueError(f'range scan: sc must be ({B}, {E}, 2) and present ({B}, {E}), got {tuple(sc.shape)} and {tuple(present.shape)}')
+    boxes, sc, ray_sc = _c(boxes.detach()), _c(sc.detach()), _c(ray_sc.detach())
+    present = _u8(present)
+    dev = boxes.device
+    ptrs = [nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(present, u8, 'present'), nat.dev_ptr(ray_sc, f32, 'ray_sc')]
+    if smap is not None and smap.device != dev:
+        raise RuntimeError(f'range scan: the map lives on {smap.device}, the agents on {dev}')
+    if isinstance(smap, StaticMapSet) and smap.scene_map.shape[0] != B:
+        raise RuntimeError(f'range scan: a StaticMapSet for {smap.scene_map.shape[0]} scenes, agents of {B}')
+    agents = torch.empty((B, A, R), dtype=f32, device=dev) if want_agents else None
+    road = torch.empty((B, A, R), dtype=f32, device=dev)
+    hit = torch.empty((B, A, R), dtype=i32, device=dev)
+    tail = [nat.dev_ptr(agents, f32, 'agents'), nat.dev_ptr(road, f32, 'road'), nat.dev_ptr(hit, i32, 'hit'), B, A, E, R, float(max_range),
+            float(gap_tolerance), nat.stream_ptr(dev)]
+    if isinstance(smap, StaticMapSet):
+        nat.call('tds_range_scan_multi_f32', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map'), *ptrs, *tail)
+    else:
+        nat.call('tds_range_scan_f32', dev, None if smap is None else smap.handle, *ptrs, *tail)
+    if agents is None:
+        agents = torch.full((B, A, R), float(max_range), dtype=f32, device=dev)
+    return agents, road, hit
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # K3 rasteriser
 # ---------------------------------------------------------------------------------------------------------------
 #: scratch for the binned fast path of K3, one per (device, stream, cameras, resolution): two renders of one shape on different streams

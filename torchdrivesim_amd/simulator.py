@@ -54,6 +54,14 @@ class TorchDriveConfig:
     waypoint_removal_threshold: float = 2.0
 
 
+@dataclass
+class RangeScan:
+    """What `Simulator.compute_range_scan` returns: three BxAxR tensors (metres, metres, int32 -- see there)."""
+    agents: Tensor
+    road: Tensor
+    hit: Tensor
+
+
 def _enlarge(x: Tensor, n: int) -> Tensor:
     return x.unsqueeze(1).expand((x.shape[0], n) + x.shape[1:]).reshape((n * x.shape[0],) + x.shape[1:])
 
@@ -1125,6 +1133,59 @@ class Simulator:
         if sc.shape[-2] != self.agent_count:
             sc = sc[..., :self.agent_count, :]
         return _ops.offroad(smap, state, size, threshold=self.cfg.offroad_threshold, present=present, sc=sc)
+
+    # ------------------------------------------------------------------------------------------------- range scans
+    @staticmethod
+    def range_scan_angles(n_rays: int, fov: float = 2 * np.pi, device=None) -> Tensor:
+        """(R,) float32 offsets of the rays from the agent's heading, counter-clockwise: off_k = -fov/2 + fov * (k + 0.5) / R, evaluated in
+        float64 on `device` (default: the host) and rounded once.  The division is by a TENSOR: torch divides by a host scalar through its
+        reciprocal on the GPU, and the offsets are the same bits wherever they are computed."""
+        _ops.check_range_scan_args(n_rays, 0.0, 0.0)
+        if not (np.isfinite(fov) and fov > 0):
+            raise ValueError(f'range scan: fov must be finite and positive (got {fov})')
+        k = torch.arange(int(n_rays), dtype=torch.float64, device=device)
+        return (-fov / 2 + (fov * (k + 0.5)) / torch.full((), int(n_rays), dtype=torch.float64, device=device)).to(torch.float32)
+
+    def compute_range_scan(self, n_rays: int = 64, max_range: float = 50.0, fov: float = 2 * np.pi, gap_tolerance: float = 0.02, road: bool = True,
+                           agents: bool = True) -> RangeScan:
+        """A lidar-like observation of every exposed agent: `n_rays` rays from the agent's centre, ray k at the angle psi + off_k
+        (`range_scan_angles`; counter-clockwise in world coordinates, as psi), each reporting in metres
+
+        agents  BxAxR  the smallest t >= 0 at which the ray enters the oriented rectangle of any OTHER present entity (exposed agents and NPCs;
+                       0 from inside one), `max_range` without one below `max_range`;
+        road    BxAxR  the length of the ray's initial stretch that lies on `road_mesh` (the whole of it, lane markings included, as in
+                       `compute_offroad`): with [a_f, b_f] the stretch of the ray inside the closed face f -- faces of positive area only --
+                       the least fixed point of F <- max{b_f : a_f <= F + gap_tolerance} from F = 0, capped at `max_range`; 0 for an agent whose
+                       centre is off the road.  `gap_tolerance` bridges the hairline gaps between separately triangulated lanelets;
+        hit     BxAxR  int32: the index in [0, A + Npc) of the entity that defines `agents` where agents < max_range and agents <= road (the
+                       lowest index on a tie), -2 where road < max_range and road < agents, -1 where both are `max_range`.
+
+        Without a road mesh or with road=False every `road` is `max_range`; with agents=False every `agents` is.  Rows of exposed agents that are not
+        present hold max_range, max_range, -1.  [sin, cos] of the rays come from torch.sin / torch.cos on the device; the rest is one HIP kernel in
+        binary32 (csrc/scan.hip; parity: tests/range_scan_model.py, a float64 model).  No gradient.  Runs on the current stream, allocates its
+        outputs only, and reuses the cached off-road map: once that map exists (one eager call, or `compute_offroad`, on this road mesh) the call
+        can be captured into a graph -- nothing crosses from the host, the ray offsets are built on the device."""
+        _ops.check_range_scan_args(n_rays, max_range, gap_tolerance)
+        if not (np.isfinite(fov) and fov > 0):
+            raise ValueError(f'range scan: fov must be finite and positive (got {fov})')
+        state = self.get_state()
+        if not state.is_cuda:
+            raise RuntimeError(f'compute_range_scan runs on an MI355X; the simulator is on {state.device} (no CPU fallback)')
+        B, A, R = state.shape[0], self.agent_count, int(n_rays)
+        if A == 0:
+            empty = torch.empty((B, 0, R), dtype=torch.float32, device=state.device)
+            return RangeScan(empty, empty.clone(), torch.empty((B, 0, R), dtype=torch.int32, device=state.device))
+        smap = None
+        if road and self.road_mesh.faces_count > 0:
+            from torchdrivesim_amd.infractions import _static_maps_for
+            smap = _static_maps_for(self.road_mesh, state.device)      # the geometry-only device map of compute_offroad, cached on the mesh
+        with torch.no_grad():
+            all_state = self.get_all_agent_state().detach()
+            boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
+            sc = self._heading_sc().detach()
+            ray_sc = _ops.heading_sc(state[..., 2].detach().unsqueeze(-1) + self.range_scan_angles(R, fov, device=state.device))
+            out = _ops.range_scan(smap, boxes, sc, self.get_all_agent_present_mask(), ray_sc, A, max_range, gap_tolerance, want_agents=agents)
+        return RangeScan(*out)
 
     def compute_wrong_way(self) -> Tensor:
         """Wrong-way metric per agent, -cos of the angle between the agent and the lane it is on where that angle exceeds
