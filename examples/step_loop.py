@@ -6,6 +6,7 @@ lane map); the "policy" is random.
 
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
+    python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
 """
 import argparse
 import os
@@ -32,6 +33,7 @@ def main():
     ap.add_argument('--res', type=int, default=128)
     ap.add_argument('--scan', type=int, default=0, metavar='RAYS', help='observe RAYS-ray range scans (compute_range_scan) instead of images')
     ap.add_argument('--scan-range', type=float, default=50.0)
+    ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     gold = os.path.join(ROOT, 'tests', 'golden')
@@ -41,6 +43,15 @@ def main():
     # traffic lights: the programmes run on the host, the device sees one index per light and step
     controls = {k: v.extend(args.batch).to(dev) for k, v in traffic_controls_from_map_config(cfg).items()}
     sim.traffic_controls = controls
+    if args.npcs:
+        # NPC traffic: placed on the lanes clear of the agents (one launch), then on rails along the lane graph, one launch per step.  They drive on
+        # revert_map of the town: the file stores its lanelets against the direction of travel, and the package's stop lines lie at the END of the
+        # reverted lanelets -- ahead of an NPC that approaches a junction, where a red light has to stop it.
+        from torchdrivesim_amd.behavior import LaneFollowingNPCController, heuristic_initialize_batch
+        npc_lanes = lanelet2.revert_map(lanes)
+        agents = torch.cat([sim.get_state()[..., :2], sim.get_agent_size(), sim.get_state()[..., 2:3]], dim=-1)
+        attributes, npc_state, placed = heuristic_initialize_batch(npc_lanes, args.batch, args.npcs, seed=1, occupied=agents, on_failure='mask', device=dev)
+        sim.npc_controller = LaneFollowingNPCController(npc_lanes, attributes[..., :2].contiguous(), npc_state, placed, seed=1)
     programme = cfg.traffic_light_controller
     light_ids = [s.actor_id for s in cfg.stoplines if s.agent_type == 'traffic_light']
     res = Resolution(args.res, args.res)
@@ -70,6 +81,10 @@ def main():
     dt = time.perf_counter() - t0
     print(f'{args.steps} steps of {args.batch} x {args.agents} agents, observations {tuple(obs.shape)}: {1e3 * dt / args.steps:.2f} ms per step, '
           f'{args.batch * args.agents * args.steps / dt / 1e6:.2f} M agent-steps/s')
+    if args.npcs:
+        c = sim.npc_controller
+        print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '
+              f'{float((c.leader != -1).float().mean()):.3f} behind a leader or a red light, {int(c.hops.sum())} lanelet changes')
     print('fraction of agents per step: ' + ', '.join(f'{k} {float(v) / args.steps:.3f}' for k, v in totals.items()))
 
 

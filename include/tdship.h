@@ -446,6 +446,64 @@ int tds_spawn_on_lanes_f32(const tds_laneset_t *set, const int32_t *scene_map, c
                            int32_t *attempts, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Lane-following NPC traffic (no reference counterpart: the definition is this library's own; float64 model:
+ * tests/lane_follow_model.py).
+ *
+ * The lane graph of a table: lanelet l is followed by the lanelets succ_items[succ_start[l] .. succ_start[l + 1]) (HOST arrays, n_lanelets + 1
+ * and succ_start[n_lanelets] int32, indices into the table, ascending per lanelet).  Set once, right after tds_lanes_create and before the
+ * table joins a set; a second call is TDS_EINVAL. */
+int tds_lanes_set_successors(tds_lanes_t *lanes, const int32_t *succ_start, const int32_t *succ_items);
+
+/* A pose onto a lane: xy n x 2 [x, y], sc n x 2 [sin psi, cos psi] (computed by the caller with torch, like every angle of this header).
+ * Candidates are the lanelets whose outline contains the point or lies within `tolerance` of it (the test of tds_wrong_way_f32), that carry
+ * no excluded tag and are eligible in the sense of tds_spawn_on_lanes_f32.  Per candidate: the foot = the closest point of the 2-D centre
+ * line (earliest segment on ties), t = the unit direction of the foot's segment, score = cos psi * t.x + sin psi * t.y.  The candidate with
+ * the largest score wins (lowest index on ties) and must have a score > 0:
+ *   lane n int32     index of the lanelet in the table, -1 without such a candidate
+ *   arc n float64    cum[k] + u * (cum[k + 1] - cum[k]) on the table's cumulative lengths, k the foot's segment, u its parameter in [0, 1]
+ *   lateral n        signed offset from the foot's segment line, left positive
+ * Pose i belongs to scene i / poses_per_scene (the _multi form; scene_map as for tds_wrong_way_f32).  Float64 throughout. */
+int tds_lane_snap(const tds_lanes_t *lanes, const float *xy, const float *sc, int32_t *lane, double *arc, float *lateral, int64_t n_poses,
+                  float tolerance, void *stream);
+int tds_lane_snap_multi(const tds_laneset_t *set, const int32_t *scene_map, int64_t poses_per_scene, const float *xy, const float *sc,
+                        int32_t *lane, double *arc, float *lateral, int64_t n_poses, float tolerance, void *stream);
+
+/* One step of N NPCs per scene that follow the lane graph at the speed the Intelligent Driver Model gives them; one launch, one wavefront per NPC.
+ *   entities      boxes B x E x 5 [x, y, length, width, psi] (psi is not read), ent_sc B x E x 2 [sin, cos], ent_speed B x E, ent_present B x E
+ *                 uint8: everything an NPC may have to brake for, AS IT WAS BEFORE THE STEP (a Jacobi update: the kernel writes none of them)
+ *   self_index    B x N int32 or NULL: the entity row that is the NPC itself (skipped); npc_size B x N x 2 [length, width];
+ *                 desired_speed B x N (v0 > 0); npc_present B x N uint8
+ *   lane, arc, hops   B x N int32 / float64 / int32, IN AND OUT: lanelet, arc length on it, lanelet transitions made so far
+ *   state         B x N x 4 [x, y, psi, speed], in and out (only speed is read); sc B x N x 2 [sin, cos] of the new pose = the unit vector of
+ *                 its segment; leader B x N int32: the entity braked for, -1 none, -2 the end of the lane
+ * Path: from (lane, arc) along the centre line (2-D) to the lanelet's end, then along the successor chosen for hop `hops`, `hops + 1`, ...:
+ * succ[(r0 * n_succ) >> 32], r0 the first word of Philox4x32-10 with key (seed low ^ 0x4C414E45, seed high ^ 0x464F4C57) and counter (scene id
+ * low, scene id high, NPC index, hop).  It ends with the segment in which `horizon` metres are covered, after TDS_FOLLOW_MAX_HOPS successors,
+ * or after 256 segments; a lanelet without a (drivable) successor ends it with a standing obstacle of zero length at its end.
+ * Leader: every other present entity gives five points (centre, corners); each is projected onto the path (closest point over all segments,
+ * earliest on ties) -> path distance d and distance e from the path; it blocks iff d > 0 and e <= width / 2 + lateral_margin.  The leader is
+ * the entity with the smallest d (lowest index on ties), gap = d - length / 2, v_lead = its speed * max(0, cos) of the angle between its heading
+ * and the path's direction at that foot.  IDM with idm = [T, s0, a, b, b_max]: gap = max(gap, 0.1), s* = s0 + max(0, v T + v (v - v_lead) /
+ * (2 sqrt(a b))), acc = max(-b_max, a (1 - (v / v0)^4 - (s* / gap)^2)) (no last term without a leader); v' = max(0, v + acc dt) rounded to
+ * binary32, ds = (v + v') / 2 dt, arc += ds; while arc >= the lanelet's length: arc -= length, lane = successor, hops += 1 (at most
+ * TDS_FOLLOW_MAX_HOPS times); at a dead end arc = length and v' = 0.  Rows with lane < 0, not present, or whose desired_speed is not > 0 (NaN
+ * included): nothing but leader = -1 is written.
+ * Float64 with + - * / sqrt only; psi alone is an atan2.  E > TDS_FOLLOW_MAX_ENTITIES is TDS_ELIMIT; a negative or non-finite dt, horizon,
+ * lateral_margin or IDM parameter is TDS_EINVAL before any launch.  Nothing is allocated, nothing synchronises, every loop is bounded. */
+#define TDS_FOLLOW_MAX_HOPS 8
+#define TDS_FOLLOW_MAX_ENTITIES 1024
+int tds_lane_follow_step(const tds_lanes_t *lanes, const int64_t *scene_ids, int64_t B, int64_t N, int64_t E, const float *boxes,
+                         const float *ent_sc, const float *ent_speed, const uint8_t *ent_present, const int32_t *self_index,
+                         const float *npc_size, const float *desired_speed, const uint8_t *npc_present, int32_t *lane, double *arc,
+                         int32_t *hops, float *state, float *sc, int32_t *leader, uint64_t seed, float dt, float horizon,
+                         float lateral_margin, const float *idm, void *stream);
+int tds_lane_follow_step_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t N, int64_t E,
+                               const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present,
+                               const int32_t *self_index, const float *npc_size, const float *desired_speed, const uint8_t *npc_present,
+                               int32_t *lane, double *arc, int32_t *hops, float *state, float *sc, int32_t *leader, uint64_t seed, float dt,
+                               float horizon, float lateral_margin, const float *idm, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K5  range scans (no reference counterpart: the definition is this library's own, DESIGN.md "K5"; float64 model: tests/range_scan_model.py)
  * R rays per exposed agent, from its centre, ray k of agent a along the unit vector [cos, sin] = ray_sc[b, a, k, (1, 0)] -- the caller computes
  * [sin, cos] of psi_a + off_k with torch, like every other angle of this header.

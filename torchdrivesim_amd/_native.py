@@ -120,6 +120,11 @@ _SIGNATURES = {
     'tds_wrong_way_f32': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp],
     'tds_lanelet_directions_f64': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp],
     'tds_spawn_on_lanes_f32': [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_uint64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    'tds_lanes_set_successors': [_vp, _vp, _vp],
+    'tds_lane_snap': [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
+    'tds_lane_snap_multi': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
+    'tds_lane_follow_step': [_vp, _vp, _i64, _i64, _i64] + [_vp] * 14 + [ctypes.c_uint64, _f32, _f32, _f32, _vp, _vp],
+    'tds_lane_follow_step_multi': [_vp, _vp, _vp, _i64, _i64, _i64] + [_vp] * 14 + [ctypes.c_uint64, _f32, _f32, _f32, _vp, _vp],
     'tds_range_scan_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
     'tds_range_scan_multi_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
 }
@@ -205,6 +210,7 @@ def last_error():
 E_INVAL, E_HIP, E_NOMEM, E_LIMIT = -1, -2, -3, -4          # TDS_EINVAL, TDS_EHIP, TDS_ENOMEM, TDS_ELIMIT of include/tdship.h
 BUFFER_DENSE = 1
 SPAWN_MAX_BOXES = 2048           # TDS_SPAWN_MAX_BOXES
+FOLLOW_MAX_HOPS, FOLLOW_MAX_ENTITIES = 8, 1024       # TDS_FOLLOW_MAX_HOPS, TDS_FOLLOW_MAX_ENTITIES
 
 
 class TdsError(RuntimeError):

@@ -1214,6 +1214,11 @@ class LaneTableHandle(_Handle):
         nat.call('tds_lanes_create', self.device, vp(poly), vp(ps), vp(cl), vp(cs), vp(fl), self.n_lanelets, float(cell_size),
                  self.max_tolerance, ctypes.byref(handle))
         self._h = handle
+        if getattr(table, 'succ_start', None) is not None:          # the lane graph (lanelet2.lane_successors)
+            ss, si = np.ascontiguousarray(table.succ_start, np.int32), np.ascontiguousarray(table.succ_items, np.int32)
+            if ss.shape != (self.n_lanelets + 1,) or int(ss[-1]) != len(si):
+                raise ValueError('lane table: succ_start must have one entry per lanelet plus one and end at len(succ_items)')
+            nat.call('tds_lanes_set_successors', self.device, self.handle, vp(ss), vp(si))
 
     def info(self):
         buf = (ctypes.c_int64 * 4)()
@@ -1322,3 +1327,88 @@ def spawn_on_lanes(lane_set, scene_ids, attributes, seed, min_speed=0.0, max_spe
              float(gap[0]), float(gap[1]), int(max_attempts), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
              ctypes.c_void_p(placed.data_ptr()), nat.dev_ptr(attempts, i32, 'attempts'), nat.stream_ptr(dev))
     return state, sc, placed, attempts
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# lane-following NPC traffic (csrc/lanes.hip: tds_lane_snap; csrc/follow.hip: tds_lane_follow_step)
+# ---------------------------------------------------------------------------------------------------------------
+def _scene_map_ptr(lane_set, B, what):
+    if lane_set.scene_map is None:
+        return None
+    if lane_set.scene_map.shape[0] != B:
+        raise RuntimeError(f'{what}: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, the batch has {B}')
+    return nat.dev_ptr(lane_set.scene_map, i32, 'scene_map')
+
+
+def lane_snap(lane_set, xy, sc, tolerance=1.0):
+    """tds_lane_snap_multi: xy (B,N,2) [x, y], sc (B,N,2) [sin, cos] -> (lane (B,N) int32, arc (B,N) float64, lateral (B,N) float32)."""
+    xy, sc = _c(xy), _c(sc)
+    if xy.dim() != 3 or xy.shape[-1] != 2 or sc.shape != xy.shape:
+        raise RuntimeError(f'lane_snap: xy and sc must be (B,N,2), got {tuple(xy.shape)}, {tuple(sc.shape)}')
+    B, N = xy.shape[:2]
+    xy_p, sc_p = nat.dev_ptr(xy, f32, 'xy'), nat.dev_ptr(sc, f32, 'sc')
+    dev = xy.device
+    lane = torch.empty((B, N), dtype=i32, device=dev)
+    arc = torch.empty((B, N), dtype=torch.float64, device=dev)
+    lateral = torch.empty((B, N), dtype=f32, device=dev)
+    if B * N == 0:
+        return lane, arc, lateral
+    nat.call('tds_lane_snap_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'lane_snap'), N, xy_p, sc_p, nat.dev_ptr(lane, i32, 'lane'),
+             nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(lateral, f32, 'lateral'), B * N, float(tolerance), nat.stream_ptr(dev))
+    return lane, arc, lateral
+
+
+def check_lane_follow_args(n_entities, dt, horizon, lateral_margin, idm):
+    """what tds_lane_follow_step refuses, refused before any tensor is touched: TdsError with the code the entry point would return"""
+    if n_entities > nat.FOLLOW_MAX_ENTITIES:
+        raise nat.TdsError('lane_follow_step', nat.E_LIMIT, f'{n_entities} entities exceed the {nat.FOLLOW_MAX_ENTITIES} a scene\'s LDS holds')
+    values = dict(dt=dt, horizon=horizon, lateral_margin=lateral_margin, **{k: v for k, v in zip(('T', 's0', 'a', 'b', 'b_max'), idm)})
+    for k, x in values.items():
+        if not (0.0 <= float(x) < float('inf')):
+            raise nat.TdsError('lane_follow_step', nat.E_INVAL, f'{k} must be finite and not negative (got {x})')
+    if not (values['a'] > 0 and values['b'] > 0):
+        raise nat.TdsError('lane_follow_step', nat.E_INVAL, 'the IDM accelerations a and b must be positive')
+
+
+def lane_follow_step(lane_set, scene_ids, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size, desired_speed, npc_present, lane, arc,
+                     hops, state, sc, leader, seed, dt, horizon=60.0, lateral_margin=0.2, idm=(1.5, 2.0, 1.5, 2.0, 6.0)):
+    """tds_lane_follow_step_multi (include/tdship.h): entities boxes (B,E,5), ent_sc (B,E,2), ent_speed (B,E), ent_present (B,E); per NPC
+    self_index (B,N) int32, npc_size (B,N,2), desired_speed (B,N), npc_present (B,N); lane / arc / hops / state (B,N,4) / sc (B,N,2) / leader are
+    updated IN PLACE and must be dense tensors of exactly the kernel's types.  One launch on the current stream, no allocation, no
+    synchronisation.  idm = (T, s0, a, b, b_max)."""
+    for name, t in (('boxes', boxes), ('ent_sc', ent_sc), ('ent_speed', ent_speed), ('ent_present', ent_present), ('npc_size', npc_size),
+                    ('desired_speed', desired_speed), ('npc_present', npc_present), ('lane', lane), ('arc', arc), ('hops', hops), ('state', state),
+                    ('sc', sc), ('leader', leader)):
+        if not t.is_cuda:
+            raise RuntimeError(f'{name}: torchdrivesim_amd kernels run on an MI355X; got a {t.device} tensor (no CPU fallback)')
+    if state.dim() != 3 or state.shape[-1] != 4:
+        raise RuntimeError(f'lane_follow_step: state must be (B,N,4), got {tuple(state.shape)}')
+    B, N = state.shape[:2]
+    E = boxes.shape[1]
+    check_lane_follow_args(E, dt, horizon, lateral_margin, idm)
+    shapes = dict(boxes=(B, E, 5), ent_sc=(B, E, 2), ent_speed=(B, E), ent_present=(B, E), npc_size=(B, N, 2), desired_speed=(B, N), npc_present=(B, N),
+                  lane=(B, N), arc=(B, N), hops=(B, N), sc=(B, N, 2), leader=(B, N))
+    given = dict(boxes=boxes, ent_sc=ent_sc, ent_speed=ent_speed, ent_present=ent_present, npc_size=npc_size, desired_speed=desired_speed,
+                 npc_present=npc_present, lane=lane, arc=arc, hops=hops, sc=sc, leader=leader)
+    for k, shp in shapes.items():
+        if tuple(given[k].shape) != shp:
+            raise RuntimeError(f'lane_follow_step: {k} must be {shp}, got {tuple(given[k].shape)}')
+    dev = state.device
+    self_p = None
+    if self_index is not None:
+        if tuple(self_index.shape) != (B, N):
+            raise RuntimeError(f'lane_follow_step: self_index must be ({B},{N}), got {tuple(self_index.shape)}')
+        self_p = nat.dev_ptr(self_index, i32, 'self_index')
+    ids_p = None
+    if scene_ids is not None:
+        if tuple(scene_ids.shape) != (B,):
+            raise RuntimeError(f'lane_follow_step: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
+        ids_p = nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    params = (ctypes.c_float * 5)(*[float(x) for x in idm])
+    nat.call('tds_lane_follow_step_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'lane_follow_step'), ids_p, B, N, E,
+             nat.dev_ptr(_c(boxes), f32, 'boxes'), nat.dev_ptr(_c(ent_sc), f32, 'ent_sc'), nat.dev_ptr(_c(ent_speed), f32, 'ent_speed'),
+             nat.dev_ptr(_u8(ent_present), u8, 'ent_present'), self_p, nat.dev_ptr(_c(npc_size), f32, 'npc_size'),
+             nat.dev_ptr(_c(desired_speed), f32, 'desired_speed'), nat.dev_ptr(_u8(npc_present), u8, 'npc_present'), nat.dev_ptr(lane, i32, 'lane'),
+             nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(hops, i32, 'hops'), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
+             nat.dev_ptr(leader, i32, 'leader'), int(seed) & 0xFFFFFFFFFFFFFFFF, float(dt), float(horizon), float(lateral_margin),
+             ctypes.cast(params, ctypes.c_void_p), nat.stream_ptr(dev))

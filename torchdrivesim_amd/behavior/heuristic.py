@@ -7,7 +7,6 @@ counter-based random stream (Philox4x32-10 keyed by `seed`, counted by scene id,
 `(seed, scene id)` only -- not on the batch it sits in -- and the launch can be captured into a HIP graph.  DESIGN.md, "On-lane
 initialisation", states the build-defined points (eligible lanelets, [sin, cos] from the direction's unit vector, the counter layout).
 """
-import collections
 import random
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -17,33 +16,11 @@ from torch import Tensor
 from torchdrivesim_amd import _native as nat
 from torchdrivesim_amd import _ops
 from torchdrivesim_amd.behavior.common import InitializationFailedError
-from torchdrivesim_amd.lanelet2 import LaneletMap
+from torchdrivesim_amd.lanelet2 import LaneletMap, _lane_set, group_lanelet_maps  # noqa: F401  (group_lanelet_maps is part of this module's surface)
 
 # heuristic.py:11-16
 LENGTH, WIDTH, LR = 4.97, 2.04, 1.96
 LONGITUDINAL_GAP, LATERAL_GAP = 1.0, 0.2
-
-
-def group_lanelet_maps(lanelet_maps: Union[LaneletMap, Sequence[Optional[LaneletMap]]], batch_size: int):
-    """One map for all scenes, or a list of `batch_size` of them (the convention of `Simulator(lanelet_map=...)`) -> (the DISTINCT map
-    objects in order of first appearance, scene_map: for every scene the index of its map, -1 for None; None when one map serves all)."""
-    if isinstance(lanelet_maps, LaneletMap):
-        return [lanelet_maps], None
-    maps = list(lanelet_maps)
-    if len(maps) != batch_size:
-        raise ValueError(f'{len(maps)} lanelet maps for {batch_size} scenes')
-    uniq, index, scene_map = [], {}, []
-    for m in maps:
-        if m is None:
-            scene_map.append(-1)
-            continue
-        if id(m) not in index:
-            index[id(m)] = len(uniq)
-            uniq.append(m)
-        scene_map.append(index[id(m)])
-    if not uniq:
-        raise ValueError('no lanelet map given')
-    return uniq, (None if len(uniq) == 1 and -1 not in scene_map else scene_map)
 
 
 def _device(device) -> torch.device:
@@ -55,25 +32,6 @@ def _device(device) -> torch.device:
     if device.type != 'cuda':
         raise RuntimeError(f'heuristic initialisation runs on an MI355X; got device {device} (no CPU fallback)')
     return device
-
-
-_lane_sets = collections.OrderedDict()          # (tables, scene_map) -> LaneTableSet, the last few: a reset loop asks for the same one every time
-
-
-def _lane_set(uniq, scene_map, device) -> _ops.LaneTableSet:
-    """The device lane tables of the distinct maps and the scenes' indices into them.  Kept between calls: building one allocates and
-    copies, which a call inside a stream capture must not do (the first call with a given map list has to happen outside one)."""
-    from torchdrivesim_amd.infractions import LANELET_TAGS_TO_EXCLUDE
-    tables = [m.table(device, LANELET_TAGS_TO_EXCLUDE) for m in uniq]
-    key = (tuple(id(t) for t in tables), None if scene_map is None else tuple(scene_map))
-    s = _lane_sets.get(key)
-    if s is None or s._h is None or any(a is not b for a, b in zip(s.tables, tables)):
-        s = _lane_sets[key] = _ops.LaneTableSet(tables, scene_map)
-        while len(_lane_sets) > 8:
-            _lane_sets.popitem(last=False)
-    else:
-        _lane_sets.move_to_end(key)
-    return s
 
 
 def heuristic_initialize_batch(lanelet_maps, batch_size: int, agent_num: int, min_speed=0, max_speed=10, num_attempts_per_agent: int = 500, *,

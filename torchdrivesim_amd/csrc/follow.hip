@@ -1,0 +1,382 @@
+// Lane-following NPC traffic: the Intelligent Driver Model on the lane graph, one launch per step.
+//
+// No reference counterpart: the reference's only reactive NPC controller is an HTTP client.  The definition is this library's own; its
+// yardstick is the float64 model tests/lane_follow_model.py, which restates every expression below in the same order.
+//
+// One wavefront per NPC, four NPCs of ONE scene per workgroup (two when a scene has more than 480 entities: the LDS of a workgroup
+// stays within the 64 KiB a launch gets without asking for more).  LDS (dynamic): the scene's entities, eight floats each (x, y, length, width,
+// sin, cos, speed, present), loaded once by the workgroup; then per wave up to FOLLOW_MAX_PIECES pieces of the NPC's path, six doubles
+// each (start point, unit vector, 2-D length, path distance at its start), and 64 ints for the entities in reach.  The lanes of a wave first split
+// the segments of the path's lanelets (stage), then the entities (keep those in reach), then the 5 points of each kept entity (project), and
+// reduce (path distance, point index) with shuffles.
+//
+// Arithmetic: float64 on the float64 lane table, + - * / sqrt only (-ffp-contract=off); entity coordinates are widened from float32.  The
+// one exception is the reported psi, atan2 of the segment's direction; [sin, cos] is that direction's unit vector, as in spawn.hip.
+#include <math.h>
+
+#include "tds_common.h"
+#include "tds_lanes.h"
+
+using tds::LaneRec;
+using tds::LaneView;
+
+namespace {
+
+constexpr int FBLOCK = 256;                      // at most four waves = four NPCs
+constexpr int FOLLOW_MAX_PIECES = 256;           // path segments staged per NPC; a path that needs more ends there (no obstacle)
+constexpr int ENT_WORDS = 8;                     // LDS floats per entity
+constexpr int PIECE_DOUBLES = 6;
+constexpr int NEAR_SLOTS = 64;                   // entities in reach kept per wave before their points are weighed
+
+struct U4 { uint32_t x, y, z, w; };
+
+// Philox4x32-10, the twenty lines of spawn.hip (known answers: tests/test_spawn_model.py)
+__device__ inline U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
+        U4 n;
+        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
+        n.y = (uint32_t)p1;
+        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
+        n.w = (uint32_t)p0;
+        c = n;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+struct FollowArgs {
+    LaneView single;                // the single-map form (views == null)
+    const LaneView *views;
+    int n_views;
+    const int32_t *scene_map;
+    const int64_t *scene_ids;
+    int N, E;
+    const float *boxes, *ent_sc, *ent_speed;
+    const uint8_t *ent_present;
+    const int32_t *self_index;
+    const float *npc_size, *desired_speed;
+    const uint8_t *npc_present;
+    int32_t *lane, *hops, *leader;
+    double *arc;
+    float *state, *sc;
+    uint32_t key0, key1;
+    double dt, horizon, margin, T, s0, a, b, b_max;
+};
+
+// the segment of a centre line that holds arc length s: clip(searchsorted(cum, s, 'right') - 1, 0, n - 2), as spawn.hip's point_at
+__device__ inline int segment_of(const double *cum, int n, double s) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        int mid = (lo + hi) >> 1;
+        if (cum[mid] <= s) lo = mid + 1; else hi = mid;
+    }
+    return min(max(lo - 1, 0), n - 2);
+}
+
+// the successor lanelet `l` takes at hop `hop`, -1 at a dead end (no successor, or one without a centre line to drive on)
+__device__ inline int successor_of(const LaneView &v, int l, uint64_t sid, int npc, int hop, uint32_t key0, uint32_t key1) {
+    if (!v.succ_start) return -1;
+    const int s0 = v.succ_start[l], ns = v.succ_start[l + 1] - s0;
+    if (ns <= 0) return -1;
+    int pick = 0;
+    if (ns > 1) {
+        U4 ctr = {(uint32_t)sid, (uint32_t)(sid >> 32), (uint32_t)npc, (uint32_t)hop};
+        pick = (int)(((uint64_t)philox4x32_10(ctr, key0, key1).x * (uint64_t)(uint32_t)ns) >> 32);
+    }
+    const int j = v.succ_items[s0 + pick];
+    if (j < 0 || j >= v.n) return -1;
+    const LaneRec r = v.rec[j];
+    if (r.cl_n < 2 || !(v.cum[r.cl_start + r.cl_n - 1] > 0.0 && v.cum[r.cl_start + r.cl_n - 1] < INFINITY)) return -1;
+    return j;
+}
+
+__device__ inline void order_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// grid = (B, ceil(N / W)), W = blockDim.x / 64 waves; dynamic LDS = E * ENT_WORDS floats + W * FOLLOW_MAX_PIECES * PIECE_DOUBLES doubles + W * NEAR_SLOTS ints
+__global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
+    extern __shared__ __attribute__((aligned(16))) float ent[];
+    const int tid = threadIdx.x, lane_id = tid & 63, wave = tid >> 6;
+    const int64_t scene = blockIdx.x;
+    const int E = g.E;
+    for (int j = tid; j < E; j += (int)blockDim.x) {
+        const float *bx = g.boxes + (scene * E + j) * 5;
+        float *d = ent + j * ENT_WORDS;
+        d[0] = bx[0], d[1] = bx[1], d[2] = bx[2], d[3] = bx[3];
+        d[4] = g.ent_sc[(scene * E + j) * 2], d[5] = g.ent_sc[(scene * E + j) * 2 + 1];
+        d[6] = g.ent_speed[scene * E + j];
+        d[7] = g.ent_present[scene * E + j] ? 1.f : 0.f;
+    }
+    __syncthreads();                                                         // the only workgroup barrier: waves are on their own from here
+    const int npc = blockIdx.y * (int)(blockDim.x >> 6) + wave;
+    if (npc >= g.N) return;
+    const int64_t row = scene * g.N + npc;
+    double *pieces = (double *)(ent + (size_t)((E * ENT_WORDS + 3) & ~3)) + (size_t)wave * FOLLOW_MAX_PIECES * PIECE_DOUBLES;
+    const int m = g.scene_map ? g.scene_map[scene] : 0;
+    int cur = g.lane[row];
+    const bool has_table = !g.views || (m >= 0 && m < g.n_views);
+    if (!has_table || cur < 0 || !g.npc_present[row] || !(g.desired_speed[row] > 0.f)) {      // rows that do not move (v0 must be > 0; NaN is not)
+        if (lane_id == 0) g.leader[row] = -1;
+        return;
+    }
+    const LaneView v = g.views ? g.views[m] : g.single;
+    if (cur >= v.n || v.rec[cur].cl_n < 2) {
+        if (lane_id == 0) g.leader[row] = -1;
+        return;
+    }
+    const uint64_t sid = g.scene_ids ? (uint64_t)g.scene_ids[scene] : (uint64_t)scene;
+    const double arc0 = g.arc[row];
+    const int hops0 = g.hops[row];
+    const double vel = (double)g.state[row * 4 + 3];
+    const double own_len = (double)g.npc_size[row * 2], own_wid = (double)g.npc_size[row * 2 + 1];
+    const int self = g.self_index ? g.self_index[row] : -1;
+
+    // ---- stage the path: the lanelet's segments from the one that holds arc0, then the successors' --------------------------------
+    int n_piece = 0;
+    double off = 0.0, smin = 0.0;
+    bool dead_end = false;
+    {
+        int l = cur, hop = hops0;
+        for (int visited = 0; visited <= TDS_FOLLOW_MAX_HOPS; ++visited) {
+            const LaneRec r = v.rec[l];
+            const double *cl = v.cl + 3 * (int64_t)r.cl_start, *cum = v.cum + r.cl_start;
+            const int n_seg = r.cl_n - 1;
+            const int k0 = visited == 0 ? segment_of(cum, r.cl_n, arc0) : 0;
+            const int take = min(n_seg - k0, FOLLOW_MAX_PIECES - n_piece);
+            for (int i = lane_id; i < take; i += 64) {
+                const double *p = cl + 3 * (k0 + i);
+                const double dx = p[3] - p[0], dy = p[4] - p[1];
+                const double l2 = sqrt(dx * dx + dy * dy);
+                double *q = pieces + (size_t)(n_piece + i) * PIECE_DOUBLES;
+                q[0] = p[0], q[1] = p[1];
+                q[2] = l2 > 0.0 ? dx / l2 : 0.0, q[3] = l2 > 0.0 ? dy / l2 : 0.0;
+                q[4] = l2;
+            }
+            order_lds();
+            if (visited == 0) {                                              // where on its first segment the NPC stands, as spawn.hip's point_at
+                const double *p = cl + 3 * k0;
+                const double dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
+                const double seg = sqrt((dx * dx + dy * dy) + dz * dz);
+                const double u0 = seg > 0.0 ? (arc0 - cum[k0]) / seg : 0.0;
+                smin = u0 * sqrt(dx * dx + dy * dy);
+            }
+            bool full = false;
+            for (int i = 0; i < take; ++i) {                                 // the running path distance, front to back (every lane the same)
+                double *q = pieces + (size_t)n_piece * PIECE_DOUBLES;
+                if (lane_id == 0) q[5] = off;
+                off = off + (n_piece == 0 ? q[4] - smin : q[4]);
+                n_piece++;
+                if (off >= g.horizon) {
+                    full = true;
+                    break;
+                }
+            }
+            order_lds();
+            if (full || take < n_seg - k0 || visited == TDS_FOLLOW_MAX_HOPS) break;
+            const int nxt = successor_of(v, l, sid, npc, hop, g.key0, g.key1);
+            if (nxt < 0) {
+                dead_end = true;
+                break;
+            }
+            l = nxt, hop++;
+        }
+    }
+
+    // ---- project the entities' points onto the path -----------------------------------------------------------------------------------
+    const double reach = own_wid / 2.0 + g.margin;
+    const double reach2 = reach * reach;
+    double sx0 = 0.0, sy0 = 0.0;                                             // where the path starts
+    if (n_piece > 0) sx0 = pieces[0] + smin * pieces[2], sy0 = pieces[1] + smin * pieces[3];
+    double best_d = INFINITY, best_cos = 0.0;
+    int best_p = 0x7fffffff;
+    // Two passes, so that the loop over the path runs for full waves of points: the lanes first take an entity each and keep the few that are in
+    // reach (compacted through LDS, ascending), then split the 5 points of each of those.
+    int *near = (int *)(pieces + (size_t)((int)(blockDim.x >> 6) - wave) * FOLLOW_MAX_PIECES * PIECE_DOUBLES) + wave * NEAR_SLOTS;
+    int n_near = 0;
+    auto weigh = [&](int n) {                                                // the 5 n points of the kept entities against the path
+        for (int q0 = lane_id; q0 < 5 * n; q0 += 64) {
+            const int j = near[q0 / 5], c = q0 % 5, p = 5 * j + c;
+            const float *e = ent + j * ENT_WORDS;
+            const double ex = (double)e[0], ey = (double)e[1], hl = (double)e[2] / 2.0, hw = (double)e[3] / 2.0, es = (double)e[4], ec = (double)e[5];
+            double px = ex, py = ey;
+            if (c > 0) {                                                     // corners 1..4: (+,+), (+,-), (-,-), (-,+) in the box frame
+                const double fl = (c == 1 || c == 2) ? hl : -hl, fw = (c == 1 || c == 4) ? hw : -hw;
+                px = ex + (fl * ec - fw * es), py = ey + (fl * es + fw * ec);
+            }
+            double bd2 = INFINITY, bs = 0.0;
+            int bi = -1;
+            for (int i = 0; i < n_piece; ++i) {
+                const double *q = pieces + (size_t)i * PIECE_DOUBLES;
+                double s = (px - q[0]) * q[2] + (py - q[1]) * q[3];
+                s = fmin(fmax(s, i == 0 ? smin : 0.0), q[4]);
+                const double fx = px - (q[0] + s * q[2]), fy = py - (q[1] + s * q[3]);
+                const double d2 = fx * fx + fy * fy;
+                if (d2 < bd2) bd2 = d2, bs = s, bi = i;
+            }
+            if (bi < 0 || !(bd2 <= reach2)) continue;
+            const double *q = pieces + (size_t)bi * PIECE_DOUBLES;
+            const double d = q[5] + (bi == 0 ? bs - smin : bs);
+            if (!(d > 0.0)) continue;
+            if (d < best_d || (d == best_d && p < best_p)) best_d = d, best_p = p, best_cos = ec * q[2] + es * q[3];
+        }
+    };
+    for (int j0 = 0; j0 < E; j0 += 64) {
+        const int j = j0 + lane_id;
+        bool in_reach = false;
+        if (j < E && j != self) {
+            const float *e = ent + j * ENT_WORDS;
+            if (e[7] != 0.f) {
+                // nothing of an entity this far from the path's start can lie within `reach` of the path (1e-6: far above the rounding of these sums)
+                const double far = (off + reach + ((double)e[2] / 2.0 + (double)e[3] / 2.0)) * (1.0 + 1e-6) + 1e-6;
+                const double cx = (double)e[0] - sx0, cy = (double)e[1] - sy0;
+                in_reach = !(cx * cx + cy * cy > far * far);
+            }
+        }
+        const unsigned long long m = __ballot(in_reach);
+        const int c = __popcll(m);
+        if (c == 0) continue;
+        if (n_near + c > NEAR_SLOTS) {                                       // wave-uniform: the list is full, weigh what it holds
+            weigh(n_near);
+            n_near = 0;
+            order_lds();
+        }
+        if (in_reach) near[n_near + __popcll(m & ((1ull << lane_id) - 1ull))] = j;
+        n_near += c;
+        order_lds();
+    }
+    weigh(n_near);
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) {
+        const double od = __shfl_xor(best_d, k);
+        const int op = __shfl_xor(best_p, k);
+        const double oc = __shfl_xor(best_cos, k);
+        if (od < best_d || (od == best_d && op < best_p)) best_d = od, best_p = op, best_cos = oc;
+    }
+
+    // ---- IDM (every lane the same numbers; lane 0 writes) -----------------------------------------------------------------------------
+    int leader = -1;
+    double gap = 0.0, v_lead = 0.0;
+    if (best_p != 0x7fffffff) {
+        leader = best_p / 5;
+        gap = best_d - own_len / 2.0;
+        v_lead = (double)ent[leader * ENT_WORDS + 6] * fmax(0.0, best_cos);
+    }
+    if (dead_end) {
+        const double end_gap = off - own_len / 2.0;
+        if (leader == -1 || end_gap < gap) leader = -2, gap = end_gap, v_lead = 0.0;
+    }
+    const double v0 = (double)g.desired_speed[row];
+    const double r1 = vel / v0, r2 = r1 * r1;
+    double acc = 1.0 - r2 * r2;
+    if (leader != -1) {
+        gap = fmax(gap, 0.1);
+        const double s_star = g.s0 + fmax(0.0, vel * g.T + vel * (vel - v_lead) / (2.0 * sqrt(g.a * g.b)));
+        const double q = s_star / gap;
+        acc = acc - q * q;
+    }
+    acc = fmax(-g.b_max, g.a * acc);
+    float v_new = (float)fmax(0.0, vel + acc * g.dt);
+    const double ds = (vel + (double)v_new) / 2.0 * g.dt;
+
+    // ---- move along the lane graph --------------------------------------------------------------------------------------------------
+    double arc = arc0 + ds;
+    int hops = hops0;
+    for (int i = 0; i < TDS_FOLLOW_MAX_HOPS; ++i) {
+        const LaneRec r = v.rec[cur];
+        const double length = v.cum[r.cl_start + r.cl_n - 1];
+        if (!(arc >= length)) break;
+        const int nxt = successor_of(v, cur, sid, npc, hops, g.key0, g.key1);
+        if (nxt < 0) {                                                       // a dead end: stand at the lanelet's end
+            arc = length, v_new = 0.f;
+            break;
+        }
+        arc = arc - length, cur = nxt, hops++;
+    }
+    const LaneRec r = v.rec[cur];
+    const double *cl = v.cl + 3 * (int64_t)r.cl_start, *cum = v.cum + r.cl_start;
+    const double length = cum[r.cl_n - 1];
+    if (!(arc <= length)) arc = length;                                     // more hops in one step than the kernel makes: stop at the end of the last
+    const int k = segment_of(cum, r.cl_n, arc);
+    const double *p = cl + 3 * k;
+    const double dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
+    const double seg = sqrt((dx * dx + dy * dy) + dz * dz);
+    const double u = seg > 0.0 ? (arc - cum[k]) / seg : 0.0;
+    const double l2 = sqrt(dx * dx + dy * dy);
+    if (lane_id != 0) return;
+    float *st = g.state + row * 4;
+    st[0] = (float)(p[0] + u * dx), st[1] = (float)(p[1] + u * dy);
+    st[2] = l2 > 0.0 ? (float)atan2(dy, dx) : 0.f;
+    st[3] = v_new;
+    g.sc[row * 2] = l2 > 0.0 ? (float)(dy / l2) : 0.f, g.sc[row * 2 + 1] = l2 > 0.0 ? (float)(dx / l2) : 1.f;
+    g.lane[row] = cur, g.arc[row] = arc, g.hops[row] = hops, g.leader[row] = leader;
+}
+
+inline bool ok_param(double x) { return x >= 0.0 && x < INFINITY; }
+
+int follow_launch(const char *what, FollowArgs &g, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t N, int64_t E,
+                  const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present, const int32_t *self_index,
+                  const float *npc_size, const float *desired_speed, const uint8_t *npc_present, int32_t *lane, double *arc, int32_t *hops,
+                  float *state, float *sc, int32_t *leader, uint64_t seed, float dt, float horizon, float lateral_margin, const float *idm,
+                  void *stream) {
+    TDS_CHECK_ARG(B >= 0 && N >= 0 && E >= 0 && B < ((int64_t)1 << 31) && N <= 2 * 65535, "%s: bad sizes B=%lld N=%lld E=%lld", what, (long long)B,
+                  (long long)N, (long long)E);
+    if (E > TDS_FOLLOW_MAX_ENTITIES) {
+        tds::set_error("%s: %lld entities exceed the %d a scene's LDS holds", what, (long long)E, TDS_FOLLOW_MAX_ENTITIES);
+        return TDS_ELIMIT;
+    }
+    TDS_CHECK_ARG(idm, "%s: the IDM parameters are null", what);
+    TDS_CHECK_ARG(ok_param(dt) && ok_param(horizon) && ok_param(lateral_margin), "%s: dt, horizon and lateral_margin must be finite and not negative",
+                  what);
+    for (int i = 0; i < 5; i++) TDS_CHECK_ARG(ok_param(idm[i]), "%s: IDM parameter %d must be finite and not negative (got %g)", what, i, (double)idm[i]);
+    TDS_CHECK_ARG(idm[2] > 0.f && idm[3] > 0.f, "%s: the IDM accelerations a and b must be positive", what);
+    if (B == 0 || N == 0) return TDS_OK;
+    TDS_CHECK_ARG(npc_size && desired_speed && npc_present && lane && arc && hops && state && sc && leader, "%s: null argument", what);
+    TDS_CHECK_ARG(E == 0 || (boxes && ent_sc && ent_speed && ent_present), "%s: %lld entities without their arrays", what, (long long)E);
+    g.scene_map = scene_map, g.scene_ids = scene_ids, g.N = (int)N, g.E = (int)E;
+    g.boxes = boxes, g.ent_sc = ent_sc, g.ent_speed = ent_speed, g.ent_present = ent_present, g.self_index = self_index;
+    g.npc_size = npc_size, g.desired_speed = desired_speed, g.npc_present = npc_present;
+    g.lane = lane, g.arc = arc, g.hops = hops, g.state = state, g.sc = sc, g.leader = leader;
+    // the route stream: spawn's key for the same seed with two words folded in ("LANE", "FOLW"), so the two streams never coincide
+    g.key0 = (uint32_t)seed ^ 0x4C414E45u, g.key1 = (uint32_t)(seed >> 32) ^ 0x464F4C57u;
+    g.dt = dt, g.horizon = horizon, g.margin = lateral_margin;
+    g.T = idm[0], g.s0 = idm[1], g.a = idm[2], g.b = idm[3], g.b_max = idm[4];
+    const int waves = E <= 480 ? 4 : 2;                                      // 15 + 48 + 1 KiB, or at most 32 + 24 + 0.5 KiB
+    const size_t lds = (size_t)((E * ENT_WORDS + 3) & ~3) * sizeof(float) +
+                       (size_t)waves * (FOLLOW_MAX_PIECES * PIECE_DOUBLES * sizeof(double) + NEAR_SLOTS * sizeof(int));
+    hipLaunchKernelGGL(lane_follow_kernel, dim3((unsigned)B, (unsigned)((N + waves - 1) / waves)), dim3(64 * waves), lds, (hipStream_t)stream, g);
+    TDS_LAUNCH_CHECK("lane_follow_kernel");
+    return TDS_OK;
+}
+
+}  // namespace
+
+TDS_EXPORT int tds_lane_follow_step(const tds_lanes_t *lanes, const int64_t *scene_ids, int64_t B, int64_t N, int64_t E, const float *boxes,
+                                    const float *ent_sc, const float *ent_speed, const uint8_t *ent_present, const int32_t *self_index,
+                                    const float *npc_size, const float *desired_speed, const uint8_t *npc_present, int32_t *lane, double *arc,
+                                    int32_t *hops, float *state, float *sc, int32_t *leader, uint64_t seed, float dt, float horizon,
+                                    float lateral_margin, const float *idm, void *stream) {
+    TDS_CHECK_ARG(lanes, "tds_lane_follow_step: the lane table is null");
+    FollowArgs g = {};
+    g.single = lanes->view, g.views = nullptr, g.n_views = 0;
+    return follow_launch("tds_lane_follow_step", g, nullptr, scene_ids, B, N, E, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size,
+                         desired_speed, npc_present, lane, arc, hops, state, sc, leader, seed, dt, horizon, lateral_margin, idm, stream);
+}
+
+TDS_EXPORT int tds_lane_follow_step_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t N,
+                                          int64_t E, const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present,
+                                          const int32_t *self_index, const float *npc_size, const float *desired_speed,
+                                          const uint8_t *npc_present, int32_t *lane, double *arc, int32_t *hops, float *state, float *sc,
+                                          int32_t *leader, uint64_t seed, float dt, float horizon, float lateral_margin, const float *idm,
+                                          void *stream) {
+    TDS_CHECK_ARG(set, "tds_lane_follow_step_multi: the lane-table set is null");
+    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_lane_follow_step_multi: a set of %d lane tables needs scene_map", set->n);
+    FollowArgs g = {};
+    g.views = set->d_views, g.n_views = set->n;
+    return follow_launch("tds_lane_follow_step_multi", g, scene_map, scene_ids, B, N, E, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size,
+                         desired_speed, npc_present, lane, arc, hops, state, sc, leader, seed, dt, horizon, lateral_margin, idm, stream);
+}

@@ -254,8 +254,29 @@ TDS_EXPORT int tds_lanes_create(const double *poly_xy, const int32_t *poly_start
 
 TDS_EXPORT int tds_lanes_destroy(tds_lanes_t *h) {
     if (!h) return TDS_OK;
-    for (void *p : {h->d_poly, h->d_cl, h->d_rec, h->d_cell_start, h->d_cell_items, h->d_cum, h->d_eligible}) (void)hipFree(p);
+    for (void *p : {h->d_poly, h->d_cl, h->d_rec, h->d_cell_start, h->d_cell_items, h->d_cum, h->d_eligible, h->d_succ_start, h->d_succ_items}) (void)hipFree(p);
     delete h;
+    return TDS_OK;
+}
+
+// the lane graph: called once, right after tds_lanes_create and before the table joins a set (a set copies the views it is made from)
+TDS_EXPORT int tds_lanes_set_successors(tds_lanes_t *h, const int32_t *succ_start, const int32_t *succ_items) {
+    TDS_CHECK_ARG(h && succ_start, "tds_lanes_set_successors: null argument");
+    TDS_CHECK_ARG(!h->d_succ_start, "tds_lanes_set_successors: the lane table has its successors already");
+    const int n = h->view.n;
+    TDS_CHECK_ARG(succ_start[0] == 0, "tds_lanes_set_successors: succ_start must begin at 0");
+    for (int l = 0; l < n; l++) TDS_CHECK_ARG(succ_start[l + 1] >= succ_start[l], "tds_lanes_set_successors: succ_start must not decrease");
+    const int total = succ_start[n];
+    TDS_CHECK_ARG(total == 0 || succ_items, "tds_lanes_set_successors: succ_items is null");
+    for (int i = 0; i < total; i++)
+        TDS_CHECK_ARG(succ_items[i] >= 0 && succ_items[i] < n, "tds_lanes_set_successors: successor %d is no lanelet of this table", succ_items[i]);
+    int device = 0;
+    TDS_HIP(hipGetDevice(&device));
+    TDS_CHECK_ARG(device == h->device, "tds_lanes_set_successors: the lane table lives on device %d, the current one is %d", h->device, device);
+    std::vector<int32_t> start(succ_start, succ_start + n + 1), items(succ_items, succ_items + total);
+    int rc;
+    if ((rc = upload(&h->d_succ_start, start, &h->bytes)) || (rc = upload(&h->d_succ_items, items, &h->bytes))) return rc;
+    h->view.succ_start = (const int32_t *)h->d_succ_start, h->view.succ_items = (const int32_t *)h->d_succ_items;
     return TDS_OK;
 }
 
@@ -505,4 +526,110 @@ TDS_EXPORT int tds_lanelet_directions_f64(const tds_laneset_t *set, const int32_
                        dirs, dists, count, status, max_dirs, n_points, lanelet_dist_tolerance, 4.f);
     TDS_LAUNCH_CHECK("wrong_way_kernel");
     return TDS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// device: a pose onto a lane (tds_lane_snap; float64 model: tests/lane_follow_model.py).  The same group of 16 lanes per
+// pose, the same grid walk and the same ring distance as the wrong-way query; what differs is what is kept of a lanelet within
+// tolerance: the foot on its 2-D centre line and how well the pose's heading agrees with the line there.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+__global__ __launch_bounds__(256) void lane_snap_kernel(LaneView single, const LaneView *views, int n_views, const int32_t *scene_map,
+                                                        int64_t poses_per_scene, const float *xy, const float *sc, int32_t *lane, double *arc,
+                                                        float *lateral, int64_t n, float tol) {
+    int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
+    int g = threadIdx.x & (GROUP - 1);
+    if (a >= n) return;                               // whole groups leave together
+    int m = scene_map ? scene_map[a / poses_per_scene] : 0;
+    int best_lane = -1;
+    double best_score = 0.0, best_arc = 0.0, best_lat = 0.0;
+    if (!views || (m >= 0 && m < n_views)) {
+        const LaneView v = views ? views[m] : single;
+        const double x = (double)xy[2 * a], y = (double)xy[2 * a + 1];
+        const double sn = (double)sc[2 * a], cs = (double)sc[2 * a + 1];
+        int cx = (int)floor((x - v.ox) * v.inv_cell), cy = (int)floor((y - v.oy) * v.inv_cell);
+        if (cx >= 0 && cy >= 0 && cx < v.nx && cy < v.ny) {              // also false for NaN coordinates
+            int c = cy * v.nx + cx;
+            double t = (double)tol;
+            for (int it = v.cell_start[c]; it < v.cell_start[c + 1]; it++) {      // ascending lanelet index
+                const int l = v.cell_items[it];
+                const LaneRec r = v.rec[l];
+                if (x < (double)r.bx0 - t || x > (double)r.bx1 + t || y < (double)r.by0 - t || y > (double)r.by1 + t) continue;
+                if ((r.flags & 1) || r.cl_n < 2) continue;
+                const double *cum = v.cum + r.cl_start;
+                if (!(cum[r.cl_n - 1] > 0.0 && cum[r.cl_n - 1] < INFINITY)) continue;       // not eligible in spawn's sense
+                double d = sqrt(ring_distance2(v.poly + 2 * (int64_t)r.poly_start, r.poly_n, x, y, g));
+                if (!(d <= t)) continue;
+                const double *cl = v.cl + 3 * (int64_t)r.cl_start;
+                // the foot: closest point of the 2-D centre line, the earliest segment on ties
+                double bd = INFINITY;
+                int sb = 0x7fffffff;
+                for (int i = g; i + 1 < r.cl_n; i += GROUP) {
+                    double ax = cl[3 * i], ay = cl[3 * i + 1], dx = cl[3 * i + 3] - ax, dy = cl[3 * i + 4] - ay;
+                    double l2 = dx * dx + dy * dy;
+                    double u = l2 > 0 ? ((x - ax) * dx + (y - ay) * dy) / l2 : 0.0;
+                    u = fmin(fmax(u, 0.0), 1.0);
+                    double fx = ax + u * dx - x, fy = ay + u * dy - y;
+                    double d2 = fx * fx + fy * fy;
+                    if (d2 < bd) bd = d2, sb = i;
+                }
+#pragma unroll
+                for (int k = GROUP / 2; k > 0; k >>= 1) {
+                    double od = __shfl_xor(bd, k, GROUP);
+                    int oi = __shfl_xor(sb, k, GROUP);
+                    if (lex_less(od, oi, bd, sb)) bd = od, sb = oi;
+                }
+                if (sb == 0x7fffffff) continue;                          // every distance was NaN
+                double ax = cl[3 * sb], ay = cl[3 * sb + 1], dx = cl[3 * sb + 3] - ax, dy = cl[3 * sb + 4] - ay;
+                double l2 = dx * dx + dy * dy;
+                double u = l2 > 0 ? ((x - ax) * dx + (y - ay) * dy) / l2 : 0.0;
+                u = fmin(fmax(u, 0.0), 1.0);
+                double len = sqrt(l2);
+                double tx = len > 0 ? dx / len : 0.0, ty = len > 0 ? dy / len : 0.0;
+                double score = cs * tx + sn * ty;
+                if (score > best_score) {                                 // strictly: the lowest index wins ties, and a winner has a score > 0
+                    best_score = score, best_lane = l;
+                    best_arc = cum[sb] + u * (cum[sb + 1] - cum[sb]);
+                    best_lat = tx * (y - ay) - ty * (x - ax);
+                }
+            }
+        }
+    }
+    if (g != 0) return;
+    lane[a] = best_lane;
+    arc[a] = best_arc;
+    lateral[a] = (float)best_lat;
+}
+
+int lane_snap_launch(const char *what, const LaneView *single, const tds_laneset_t *set, const int32_t *scene_map, int64_t poses_per_scene,
+                     const float *xy, const float *sc, int32_t *lane, double *arc, float *lateral, int64_t n_poses, float tolerance,
+                     float max_tol, void *stream) {
+    TDS_CHECK_ARG(n_poses >= 0 && n_poses < ((int64_t)1 << 40) && poses_per_scene > 0, "%s: bad sizes", what);
+    TDS_CHECK_ARG(tolerance >= 0.f && tolerance <= max_tol, "%s: tolerance %g exceeds the %g the lane tables were built for", what,
+                  (double)tolerance, (double)max_tol);
+    if (n_poses == 0) return TDS_OK;
+    TDS_CHECK_ARG(xy && sc && lane && arc && lateral, "%s: null argument", what);
+    unsigned blocks = (unsigned)((n_poses * GROUP + 255) / 256);
+    hipLaunchKernelGGL(lane_snap_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, single ? *single : LaneView{}, set ? set->d_views : nullptr,
+                       set ? set->n : 0, scene_map, poses_per_scene, xy, sc, lane, arc, lateral, n_poses, tolerance);
+    TDS_LAUNCH_CHECK("lane_snap_kernel");
+    return TDS_OK;
+}
+
+}  // namespace
+
+TDS_EXPORT int tds_lane_snap(const tds_lanes_t *lanes, const float *xy, const float *sc, int32_t *lane, double *arc, float *lateral,
+                             int64_t n_poses, float tolerance, void *stream) {
+    TDS_CHECK_ARG(lanes, "tds_lane_snap: the lane table is null");
+    return lane_snap_launch("tds_lane_snap", &lanes->view, nullptr, nullptr, 1, xy, sc, lane, arc, lateral, n_poses, tolerance, lanes->view.max_tol,
+                            stream);
+}
+
+TDS_EXPORT int tds_lane_snap_multi(const tds_laneset_t *set, const int32_t *scene_map, int64_t poses_per_scene, const float *xy, const float *sc,
+                                   int32_t *lane, double *arc, float *lateral, int64_t n_poses, float tolerance, void *stream) {
+    TDS_CHECK_ARG(set, "tds_lane_snap_multi: the lane-table set is null");
+    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_lane_snap_multi: a set of %d lane tables needs scene_map", set->n);
+    return lane_snap_launch("tds_lane_snap_multi", nullptr, set, scene_map, poses_per_scene, xy, sc, lane, arc, lateral, n_poses, tolerance,
+                            set->max_tol, stream);
 }

@@ -23,13 +23,15 @@ struct LaneView {
     const double *cum;              // per centre-line point: the 3-D length of its centre line up to it (0 at a lanelet's first point)
     const int32_t *eligible;        // the lanelets a point can be drawn on (>= 2 centre-line points, finite positive length), ascending
     int n_eligible;
+    const int32_t *succ_start;      // the lane graph (tds_lanes_set_successors): lanelet l is followed by succ_items[succ_start[l] .. succ_start[l + 1]),
+    const int32_t *succ_items;      // ascending; both null until the graph is set
 };
 
 }  // namespace tds
 
 struct tds_lanes {
     tds::LaneView view;
-    void *d_poly, *d_cl, *d_rec, *d_cell_start, *d_cell_items, *d_cum, *d_eligible;
+    void *d_poly, *d_cl, *d_rec, *d_cell_start, *d_cell_items, *d_cum, *d_eligible, *d_succ_start, *d_succ_items;
     int device;
     int64_t bytes;
 };

@@ -20,12 +20,13 @@ PINNED here against data the reference ships: the projected points and the road 
 `carla_Town01.osm` equal the reference's own `carla_Town01_mesh.json` (generated upstream with the real Lanelet2), see
 `tests/test_lanelet2.py`; the query is pinned by the known answers of the reference's tests/simulator/test_util.py:17-44.
 """
+import collections
 import gzip
 import math
 import random
 import xml.etree.ElementTree as ET
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -450,12 +451,35 @@ class LaneTable:
     poly_start (L+1) i32
     cl_xyz (C,3) f64 : centre lines;  cl_start (L+1) i32
     flags (L) i32 : bit 0 = carries an excluded tag
+    succ_start (L+1) i32, succ_items i32 : the lane graph of `lane_successors` (None: a table without one, e.g. a lone line string)
     """
     poly_xy: np.ndarray
     poly_start: np.ndarray
     cl_xyz: np.ndarray
     cl_start: np.ndarray
     flags: np.ndarray
+    succ_start: Optional[np.ndarray] = None
+    succ_items: Optional[np.ndarray] = None
+
+
+def lane_successors(lanelet_map: LaneletMap) -> Tuple[np.ndarray, np.ndarray]:
+    """
+    The lane graph of a map as `(succ_start (L+1) int32, succ_items int32)`, indices into `laneletLayer`: lanelet j follows lanelet i iff
+    the LAST point id of i's left bound is the FIRST of j's left bound, and the same holds for the right bounds (how Lanelet2's routing graph
+    finds `following` lanelets: shared bound end points).  j != i; the successors of a lanelet are listed in ascending index; a lanelet with
+    an empty bound has no successors and is nobody's successor.
+    """
+    lanelets = lanelet_map.laneletLayer
+    starts: Dict[Tuple[int, int], List[int]] = {}
+    for j, l in enumerate(lanelets):
+        if len(l.left_ids) and len(l.right_ids):
+            starts.setdefault((int(l.left_ids[0]), int(l.right_ids[0])), []).append(j)
+    succ_start, succ_items = [0], []
+    for i, l in enumerate(lanelets):
+        if len(l.left_ids) and len(l.right_ids):
+            succ_items.extend(j for j in starts.get((int(l.left_ids[-1]), int(l.right_ids[-1])), ()) if j != i)
+        succ_start.append(len(succ_items))
+    return np.array(succ_start, np.int32), np.array(succ_items, np.int32)
 
 
 def lane_table(lanelet_map: LaneletMap, tags_to_exclude: Optional[Sequence[str]] = None) -> LaneTable:
@@ -469,7 +493,8 @@ def lane_table(lanelet_map: LaneletMap, tags_to_exclude: Optional[Sequence[str]]
         cs.append(cs[-1] + len(c))
         flags.append(1 if any(t in l.attributes for t in tags) else 0)
     cat = lambda xs, w: np.ascontiguousarray(np.concatenate(xs, 0), np.float64) if xs else np.zeros((0, w))
-    return LaneTable(cat(polys, 2), np.array(ps, np.int32), cat(cls, 3), np.array(cs, np.int32), np.array(flags, np.int32))
+    return LaneTable(cat(polys, 2), np.array(ps, np.int32), cat(cls, 3), np.array(cs, np.int32), np.array(flags, np.int32),
+                     *lane_successors(lanelet_map))
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -529,6 +554,70 @@ def find_direction(linestring, location3d, device=None) -> float:
     if int(status[0]) & 1 or int(count[0]) != 1:
         raise LaneletError('Failed to find direction of the linestring at a given point')
     return float(dirs[0, 0])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the lane tables of a batch (shared by on-lane initialisation, snap_to_lanes and the lane-following controller)
+# ------------------------------------------------------------------------------------------------------------------------
+def group_lanelet_maps(lanelet_maps: 'Union[LaneletMap, Sequence[Optional[LaneletMap]]]', batch_size: int):
+    """One map for all scenes, or a list of `batch_size` of them (the convention of `Simulator(lanelet_map=...)`) -> (the DISTINCT map
+    objects in order of first appearance, scene_map: for every scene the index of its map, -1 for None; None when one map serves all)."""
+    if isinstance(lanelet_maps, LaneletMap):
+        return [lanelet_maps], None
+    maps = list(lanelet_maps)
+    if len(maps) != batch_size:
+        raise ValueError(f'{len(maps)} lanelet maps for {batch_size} scenes')
+    uniq, index, scene_map = [], {}, []
+    for m in maps:
+        if m is None:
+            scene_map.append(-1)
+            continue
+        if id(m) not in index:
+            index[id(m)] = len(uniq)
+            uniq.append(m)
+        scene_map.append(index[id(m)])
+    if not uniq:
+        raise ValueError('no lanelet map given')
+    return uniq, (None if len(uniq) == 1 and -1 not in scene_map else scene_map)
+
+
+_lane_sets = collections.OrderedDict()          # (tables, scene_map) -> LaneTableSet, the last few: a reset loop asks for the same one every time
+
+
+def _lane_set(uniq, scene_map, device):
+    """The device lane tables of the distinct maps and the scenes' indices into them.  Kept between calls: building one allocates and
+    copies, which a call inside a stream capture must not do (the first call with a given map list has to happen outside one)."""
+    from . import _ops
+    from .infractions import LANELET_TAGS_TO_EXCLUDE
+    tables = [m.table(device, LANELET_TAGS_TO_EXCLUDE) for m in uniq]
+    key = (tuple(id(t) for t in tables), None if scene_map is None else tuple(scene_map))
+    s = _lane_sets.get(key)
+    if s is None or s._h is None or any(a is not b for a, b in zip(s.tables, tables)):
+        s = _lane_sets[key] = _ops.LaneTableSet(tables, scene_map)
+        while len(_lane_sets) > 8:
+            _lane_sets.popitem(last=False)
+    else:
+        _lane_sets.move_to_end(key)
+    return s
+
+
+def snap_to_lanes(lanelet_maps, state: Tensor, tolerance: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """
+    Poses onto lanes, one launch (`tds_lane_snap_multi`): `state` (B, N, >= 3) = [x, y, psi, ...] on the device -> `lane` (B, N) int32 index
+    into `laneletLayer` (-1: no lanelet within `tolerance` whose direction the heading agrees with), `arc` (B, N) float64 arc length of
+    the foot on that lanelet's centre line, `lateral` (B, N) float32 signed offset, left positive.  Among the lanelets within tolerance
+    (those of `compute_wrong_way`, minus the ones carrying an excluded tag or too short to drive on) the one whose local direction agrees
+    best with the heading wins -- in a junction, where lanelets overlap, the heading decides.  `lanelet_maps`: one map or B of them.
+    """
+    from . import _ops
+    if not state.is_cuda:
+        raise RuntimeError(f'snap_to_lanes runs on an MI355X; got a {state.device} tensor (no CPU fallback)')
+    if state.dim() != 3 or state.shape[-1] < 3:
+        raise ValueError(f'state must be (B, N, >= 3), got {tuple(state.shape)}')
+    uniq, scene_map = group_lanelet_maps(lanelet_maps, state.shape[0])
+    lane_set = _lane_set(uniq, scene_map, state.device)
+    state = state.detach().to(torch.float32)
+    return _ops.lane_snap(lane_set, state[..., :2], _ops.heading_sc(state[..., 2]), float(tolerance))
 
 
 def pick_random_point_and_orientation(lanelet_map: LaneletMap) -> Tuple[float, float, float]:
