@@ -7,6 +7,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
+    python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
 """
 import argparse
 import os
@@ -34,6 +35,7 @@ def main():
     ap.add_argument('--scan', type=int, default=0, metavar='RAYS', help='observe RAYS-ray range scans (compute_range_scan) instead of images')
     ap.add_argument('--scan-range', type=float, default=50.0)
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
+    ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     gold = os.path.join(ROOT, 'tests', 'golden')
@@ -52,16 +54,23 @@ def main():
         agents = torch.cat([sim.get_state()[..., :2], sim.get_agent_size(), sim.get_state()[..., 2:3]], dim=-1)
         attributes, npc_state, placed = heuristic_initialize_batch(npc_lanes, args.batch, args.npcs, seed=1, occupied=agents, on_failure='mask', device=dev)
         sim.npc_controller = LaneFollowingNPCController(npc_lanes, attributes[..., :2].contiguous(), npc_state, placed, seed=1)
+    if args.route:
+        # route goals: every agent is snapped to the lane under it and dealt a route from there (two launches); then one launch per step.  On
+        # revert_map of the town, like the NPCs: the file stores its lanelets against the direction of travel.
+        from torchdrivesim_amd.goals import RouteGoal
+        sim.route_goals = RouteGoal.sample(lanelet2.revert_map(lanes), sim.get_state(), sim.get_present_mask(), seed=2, length=args.route)
     programme = cfg.traffic_light_controller
     light_ids = [s.actor_id for s in cfg.stoplines if s.agent_type == 'traffic_light']
     res = Resolution(args.res, args.res)
     g = torch.Generator(device=dev).manual_seed(0)
     totals = {k: torch.zeros((), device=dev) for k in ('collision', 'offroad', 'wrong_way', 'red_light')}     # summed on the device: no sync per step
+    advanced = torch.zeros((), device=dev)
     warmup = 3                                   # the first steps build the device maps, lane tables and workspaces (once per simulator): not timed
     for it in range(warmup + args.steps):
         if it == warmup:
             for v in totals.values():
                 v.zero_()
+            advanced.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
         action = torch.rand((args.batch, args.agents, 2), device=dev, generator=g) * 2 - 1
@@ -73,6 +82,10 @@ def main():
             obs = torch.stack([scan.agents, scan.road], dim=-1) / args.scan_range        # (B, A, R, 2) in [0, 1]: distance to the nearest other agent, to the road edge
         else:
             obs = sim.render_egocentric(res=res, fov=35.0)                   # (B, A, 3, H, W): what a policy would consume
+        if args.route:
+            route = sim.compute_route_progress()                           # what sim.step has just computed: the dense term of a reward ...
+            advanced += route.advance.sum()
+            goal_obs = route.lookahead / args.route                         # ... and (B, A, 16, 2): where the route goes, in the agent's frame
         totals['collision'] += (sim.compute_collision() > 0).float().mean()
         totals['offroad'] += (sim.compute_offroad() > 0).float().mean()
         totals['wrong_way'] += (sim.compute_wrong_way() > 0).float().mean()
@@ -85,6 +98,11 @@ def main():
         c = sim.npc_controller
         print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '
               f'{float((c.leader != -1).float().mean()):.3f} behind a leader or a red light, {int(c.hops.sum())} lanelet changes')
+    if args.route:
+        r = sim.route_goals
+        print(f'routes of {args.route:g} m: {float(r.valid.float().mean()):.3f} of the agents have one (mean {float(r.length.sum() / r.valid.sum().clamp(min=1)):.1f} m over '
+              f'{float(r.n.sum() / r.valid.sum().clamp(min=1)):.1f} lanelets), lookahead {tuple(goal_obs.shape)}; advanced {float(advanced) / max(1, int(r.valid.sum())):.2f} m '
+              f'per agent in {args.steps} steps, {float(r.completed.float().mean()):.3f} arrived, {float(route.off_route.float().mean()):.3f} off their route now')
     print('fraction of agents per step: ' + ', '.join(f'{k} {float(v) / args.steps:.3f}' for k, v in totals.items()))
 
 

@@ -504,6 +504,63 @@ int tds_lane_follow_step_multi(const tds_laneset_t *set, const int32_t *scene_ma
                                float horizon, float lateral_margin, const float *idm, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Route goals (no reference counterpart: the definition is this library's own; float64 model: tests/route_model.py).
+ * Everything is float64 with + - * / sqrt only.  Centre lines are 2-D for geometry; arc lengths are on the table's cumulative 3-D lengths
+ * `cum` (the convention of tds_lane_snap, so its arc, or one drawn by tds_spawn_on_lanes_f32, is directly usable).  w_i = cum[i + 1] - cum[i].
+ *
+ * A route (one row = one agent, B x A rows) is n <= TDS_ROUTE_MAX_LANES lanelets route_lanes[0 .. n) (unused entries -1).  Piece j carries
+ * the arc interval [a_j, b_j]: a_0 = start_arc, a_j = 0 otherwise; b_(n-1) = end_arc, b_j = the lanelet's length otherwise.  offsets[j] =
+ * sum_(i<j) (b_i - a_i), summed front to back (unused entries 0); length = offsets[n].
+ *
+ * Sampling, from (lane, arc) with requested length D: a = arc clamped to [0, the lanelet's length], rem = D, off = 0; for j = 0 .. 15:
+ * lanes[j] = l, offsets[j] = off; if rem <= len(l) - a: end_arc = a + rem, off += end_arc - a, stop; else off += len(l) - a, rem -= len(l) - a,
+ * end_arc = len(l); stop at j = 15 (the cap) or at a dead end; else l = the successor for hop j, a = 0.  The successor is
+ * succ[(r0 * n_succ) >> 32], r0 the first word of Philox4x32-10 with key (seed low ^ 0x524F5554, seed high ^ 0x474F414C) and counter (scene id
+ * low, scene id high, agent index, hop) (not drawn where n_succ = 1).  As in tds_lane_follow_step the draw is over ALL successors: a lanelet
+ * without a successor is a dead end, and so is one whose drawn successor is not eligible in the sense of tds_spawn_on_lanes_f32 or carries an
+ * excluded tag -- such successors are skipped by ending the route, never by drawing again.  length then records the shortfall.  A row with
+ * lane < 0 (or not eligible), an absent row (present == 0), a D that is not > 0 or not finite, a scene without a lane table, or a route whose
+ * length is not > 0 gets n = 0 (start_arc = end_arc = length = 0).  Every sampled row also gets cursor = 0, stored = 0, completed = 0; rows
+ * with mask == 0 are left untouched (mask NULL: every row).
+ *
+ * Progress of a pose (x, y, [s, c] = [sin psi, cos psi]) with cursor k (the piece the agent was last found on; never decreases): candidates
+ * are the segments of pieces k .. min(k + 2, n - 1).  Segment i of piece j (points P_i, P_(i+1), d = P_(i+1) - P_i in 2-D) is clipped to its
+ * piece: ulo = a_j > cum[i] ? (a_j - cum[i]) / w_i : 0, uhi = b_j < cum[i + 1] ? (b_j - cum[i]) / w_i : 1; it is skipped unless d.d > 0, w_i > 0
+ * and uhi > ulo.  u = min(max(((x - P_i.x) d.x + (y - P_i.y) d.y) / d.d, ulo), uhi), foot F = P_i + u d, e2 = |F - (x, y)|^2.  The foot is the
+ * candidate with the smallest e2, the earliest (piece, segment) on ties.  With t = d / sqrt(d.d) and arc_foot = cum[i] + u w_i:
+ *   progress  = offsets[j] + (arc_foot - a_j);   advance = progress - stored, then stored = progress (so advance is measured from the route's
+ *               start on the first call after sampling: 0 up to rounding for the pose the route was sampled from)
+ *   lateral   = t.x (y - P_i.y) - t.y (x - P_i.x), left positive;   heading = [s t.x - c t.y, c t.x + s t.y] (sin, cos of the heading error)
+ *   remaining = length - progress;  reached = remaining <= goal_tolerance;  completed |= reached (sticky);
+ *   off_route = sqrt(e2) > off_route_distance;  cursor = j
+ * The point at route arc q: q clamped to [0, length] (a q that is not > 0 is 0); piece j = the last one with offsets[j] <= q; lanelet arc =
+ * a_j + (q - offsets[j]); segment i = clip(searchsorted(cum, arc, right) - 1, 0, points - 2); u = (arc - cum[i]) / w_i (0 where w_i is not > 0);
+ * the point is P_i + u d.  Lookahead point m = 0 .. n_lookahead-1 is the point at progress + (m + 1) * spacing in the agent's frame:
+ * [dx c + dy s, dy c - dx s], (dx, dy) = point - (x, y).  Float outputs are rounded to binary32 once, at the end.
+ * Rows without a route, absent rows and scenes without a table get zeros everywhere, heading = [0, 1], reached = completed = off_route = 0 and
+ * keep cursor and stored; a row whose pose can be weighed against no candidate (NaN) gets the same outputs and keeps completed as well.
+ *   xy            row i reads [x, y] at xy[i * xy_stride], xy_stride >= 2 (4 for a B x A x 4 state); sc B x A x 2 [sin, cos]; present B x A uint8 or NULL
+ *   lookahead     B x A x n_lookahead x 2, n_lookahead <= TDS_ROUTE_MAX_LOOKAHEAD
+ * tds_route_points_multi: q B x A x Q float64 route arcs -> points B x A x Q x 2, world frame ([0, 0] for rows without a route).
+ * One launch each; nothing is allocated, nothing synchronises, every loop is bounded whatever the tensors hold.  A negative or non-finite
+ * goal_tolerance, off_route_distance or spacing, n_lookahead outside [0, 32] or xy_stride < 2 is TDS_EINVAL before any launch. */
+#define TDS_ROUTE_MAX_LANES 16
+#define TDS_ROUTE_MAX_LOOKAHEAD 32
+int tds_route_sample_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t A,
+                           const int32_t *lane, const double *arc, const double *distance, const uint8_t *present, const uint8_t *mask,
+                           uint64_t seed, int32_t *route_lanes, int32_t *route_n, double *start_arc, double *end_arc, double *offsets,
+                           double *length, int32_t *cursor, double *stored, uint8_t *completed, void *stream);
+int tds_route_progress_multi(const tds_laneset_t *set, const int32_t *scene_map, int64_t B, int64_t A, const float *xy, int64_t xy_stride,
+                             const float *sc, const uint8_t *present, const int32_t *route_lanes, const int32_t *route_n,
+                             const double *start_arc, const double *end_arc, const double *offsets, const double *length, int32_t *cursor,
+                             double *stored, uint8_t *completed, float goal_tolerance, float off_route_distance, int n_lookahead,
+                             float spacing, float *progress, float *advance, float *lateral, float *heading, float *remaining,
+                             uint8_t *reached, uint8_t *off_route, float *lookahead, void *stream);
+int tds_route_points_multi(const tds_laneset_t *set, const int32_t *scene_map, int64_t B, int64_t A, int64_t Q, const int32_t *route_lanes,
+                           const int32_t *route_n, const double *start_arc, const double *end_arc, const double *offsets,
+                           const double *length, const double *q, float *points, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K5  range scans (no reference counterpart: the definition is this library's own, DESIGN.md "K5"; float64 model: tests/range_scan_model.py)
  * R rays per exposed agent, from its centre, ray k of agent a along the unit vector [cos, sin] = ray_sc[b, a, k, (1, 0)] -- the caller computes
  * [sin, cos] of psi_a + off_k with torch, like every other angle of this header.

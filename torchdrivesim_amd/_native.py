@@ -125,6 +125,9 @@ _SIGNATURES = {
     'tds_lane_snap_multi': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
     'tds_lane_follow_step': [_vp, _vp, _i64, _i64, _i64] + [_vp] * 14 + [ctypes.c_uint64, _f32, _f32, _f32, _vp, _vp],
     'tds_lane_follow_step_multi': [_vp, _vp, _vp, _i64, _i64, _i64] + [_vp] * 14 + [ctypes.c_uint64, _f32, _f32, _f32, _vp, _vp],
+    'tds_route_sample_multi': [_vp, _vp, _vp, _i64, _i64] + [_vp] * 5 + [ctypes.c_uint64] + [_vp] * 10,
+    'tds_route_progress_multi': [_vp, _vp, _i64, _i64, _vp, _i64] + [_vp] * 11 + [_f32, _f32, _i32, _f32] + [_vp] * 9,
+    'tds_route_points_multi': [_vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
     'tds_range_scan_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
     'tds_range_scan_multi_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
 }
@@ -211,6 +214,7 @@ E_INVAL, E_HIP, E_NOMEM, E_LIMIT = -1, -2, -3, -4          # TDS_EINVAL, TDS_EHI
 BUFFER_DENSE = 1
 SPAWN_MAX_BOXES = 2048           # TDS_SPAWN_MAX_BOXES
 FOLLOW_MAX_HOPS, FOLLOW_MAX_ENTITIES = 8, 1024       # TDS_FOLLOW_MAX_HOPS, TDS_FOLLOW_MAX_ENTITIES
+ROUTE_MAX_LANES, ROUTE_MAX_LOOKAHEAD = 16, 32        # TDS_ROUTE_MAX_LANES, TDS_ROUTE_MAX_LOOKAHEAD
 
 
 class TdsError(RuntimeError):

@@ -1340,17 +1340,23 @@ def _scene_map_ptr(lane_set, B, what):
     return nat.dev_ptr(lane_set.scene_map, i32, 'scene_map')
 
 
-def lane_snap(lane_set, xy, sc, tolerance=1.0):
-    """tds_lane_snap_multi: xy (B,N,2) [x, y], sc (B,N,2) [sin, cos] -> (lane (B,N) int32, arc (B,N) float64, lateral (B,N) float32)."""
+def lane_snap(lane_set, xy, sc, tolerance=1.0, out=None):
+    """tds_lane_snap_multi: xy (B,N,2) [x, y], sc (B,N,2) [sin, cos] -> (lane (B,N) int32, arc (B,N) float64, lateral (B,N) float32).
+    out: the three tensors to write instead of new ones (dense, of exactly those types)."""
     xy, sc = _c(xy), _c(sc)
     if xy.dim() != 3 or xy.shape[-1] != 2 or sc.shape != xy.shape:
         raise RuntimeError(f'lane_snap: xy and sc must be (B,N,2), got {tuple(xy.shape)}, {tuple(sc.shape)}')
     B, N = xy.shape[:2]
     xy_p, sc_p = nat.dev_ptr(xy, f32, 'xy'), nat.dev_ptr(sc, f32, 'sc')
     dev = xy.device
-    lane = torch.empty((B, N), dtype=i32, device=dev)
-    arc = torch.empty((B, N), dtype=torch.float64, device=dev)
-    lateral = torch.empty((B, N), dtype=f32, device=dev)
+    if out is not None:
+        lane, arc, lateral = out
+        if any(tuple(t.shape) != (B, N) for t in out):
+            raise RuntimeError(f'lane_snap: out must be three ({B},{N}) tensors, got {[tuple(t.shape) for t in out]}')
+    else:
+        lane = torch.empty((B, N), dtype=i32, device=dev)
+        arc = torch.empty((B, N), dtype=torch.float64, device=dev)
+        lateral = torch.empty((B, N), dtype=f32, device=dev)
     if B * N == 0:
         return lane, arc, lateral
     nat.call('tds_lane_snap_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'lane_snap'), N, xy_p, sc_p, nat.dev_ptr(lane, i32, 'lane'),
@@ -1412,3 +1418,104 @@ def lane_follow_step(lane_set, scene_ids, boxes, ent_sc, ent_speed, ent_present,
              nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(hops, i32, 'hops'), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
              nat.dev_ptr(leader, i32, 'leader'), int(seed) & 0xFFFFFFFFFFFFFFFF, float(dt), float(horizon), float(lateral_margin),
              ctypes.cast(params, ctypes.c_void_p), nat.stream_ptr(dev))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# route goals (csrc/route.hip)
+# ---------------------------------------------------------------------------------------------------------------
+#: the route tensors of a batch, in the order the entry points take them: name -> (trailing shape, dtype)
+ROUTE_TENSORS = (('lanes', (nat.ROUTE_MAX_LANES,), i32), ('n', (), i32), ('start_arc', (), torch.float64), ('end_arc', (), torch.float64),
+                 ('offsets', (nat.ROUTE_MAX_LANES,), torch.float64), ('length', (), torch.float64))
+ROUTE_STATE = (('cursor', (), i32), ('stored', (), torch.float64), ('completed', (), u8))
+
+
+def check_route_args(goal_tolerance, off_route_distance, lookahead, spacing):
+    """what tds_route_progress_multi refuses, refused before any tensor is touched: TdsError with the code the entry point would return"""
+    for k, x in (('goal_tolerance', goal_tolerance), ('off_route_distance', off_route_distance), ('spacing', spacing)):
+        if not (0.0 <= float(x) < float('inf')):
+            raise nat.TdsError('route_progress', nat.E_INVAL, f'{k} must be finite and not negative (got {x})')
+    if not (0 <= int(lookahead) <= nat.ROUTE_MAX_LOOKAHEAD):
+        raise nat.TdsError('route_progress', nat.E_INVAL, f'{lookahead} lookahead points, at most {nat.ROUTE_MAX_LOOKAHEAD}')
+
+
+def _route_ptrs(what, route, B, A, names):
+    """device pointers of the named route tensors (dict name -> tensor), each a dense (B, A, ...) tensor of exactly the kernel's type"""
+    out = []
+    for name, tail, dtype in names:
+        t = route[name]
+        if tuple(t.shape) != (B, A) + tail:
+            raise RuntimeError(f'{what}: route tensor {name} must be {(B, A) + tail}, got {tuple(t.shape)}')
+        out.append(nat.dev_ptr(t, dtype, name))
+    return out
+
+
+def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, route):
+    """tds_route_sample_multi (include/tdship.h): lane (B,A) int32, arc (B,A) float64, distance (B,A) float64, present / mask (B,A) bool or None;
+    `route` (dict of the ROUTE_TENSORS and ROUTE_STATE) is written IN PLACE for the rows of `mask`.  One launch, no allocation besides the
+    uint8 views of bool masks, no synchronisation."""
+    B, A = lane.shape
+    dev = lane.device
+    for name, t in (('arc', arc), ('distance', distance)):
+        if tuple(t.shape) != (B, A):
+            raise RuntimeError(f'route_sample: {name} must be ({B},{A}), got {tuple(t.shape)}')
+    ids_p = None
+    if scene_ids is not None:
+        if tuple(scene_ids.shape) != (B,):
+            raise RuntimeError(f'route_sample: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
+        ids_p = nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    masks = []
+    for name, t in (('present', present), ('mask', mask)):
+        if t is not None and tuple(t.shape) != (B, A):
+            raise RuntimeError(f'route_sample: {name} must be ({B},{A}), got {tuple(t.shape)}')
+        masks.append(None if t is None else nat.dev_ptr(_u8(t), u8, name))
+    nat.call('tds_route_sample_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_sample'), ids_p, B, A, nat.dev_ptr(lane, i32, 'lane'),
+             nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(distance, torch.float64, 'distance'), masks[0], masks[1],
+             int(seed) & 0xFFFFFFFFFFFFFFFF, *_route_ptrs('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE), nat.stream_ptr(dev))
+
+
+def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing):
+    """tds_route_progress_multi: state (B,A,>=2) float32 with dense rows ([x, y] first), sc (B,A,2) [sin, cos], present (B,A) bool or None; the
+    route's cursor / stored / completed are updated IN PLACE and `out` (dict: progress, advance, lateral, remaining (B,A) float32, heading
+    (B,A,2), reached, off_route (B,A) uint8, lookahead (B,A,K,2)) is written in full.  One launch, no synchronisation."""
+    if not state.is_cuda:
+        raise RuntimeError(f'route_progress: torchdrivesim_amd kernels run on an MI355X; got a {state.device} tensor (no CPU fallback)')
+    if state.dim() != 3 or state.shape[-1] < 2:
+        raise RuntimeError(f'route_progress: state must be (B,A,>=2), got {tuple(state.shape)}')
+    B, A, S = state.shape
+    dev = state.device
+    K = out['lookahead'].shape[2]
+    check_route_args(goal_tolerance, off_route_distance, K, spacing)
+    state = state.detach()
+    if state.dtype != f32 or not state.is_contiguous():
+        state = _c(state[..., :2])
+        S = 2
+    sc = _c(sc.detach())
+    if tuple(sc.shape) != (B, A, 2):
+        raise RuntimeError(f'route_progress: sc must be ({B},{A},2), got {tuple(sc.shape)}')
+    if present is not None and tuple(present.shape) != (B, A):
+        raise RuntimeError(f'route_progress: present must be ({B},{A}), got {tuple(present.shape)}')
+    outs = (('progress', (), f32), ('advance', (), f32), ('lateral', (), f32), ('heading', (2,), f32), ('remaining', (), f32), ('reached', (), u8),
+            ('off_route', (), u8), ('lookahead', (K, 2), f32))
+    nat.call('tds_route_progress_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_progress'), B, A, nat.dev_ptr(state, f32, 'state'), S,
+             nat.dev_ptr(sc, f32, 'sc'), None if present is None else nat.dev_ptr(_u8(present), u8, 'present'),
+             *_route_ptrs('route_progress', route, B, A, ROUTE_TENSORS + ROUTE_STATE), float(goal_tolerance), float(off_route_distance), int(K),
+             float(spacing), *_route_ptrs('route_progress', out, B, A, outs), nat.stream_ptr(dev))
+
+
+def route_points(lane_set, route, arcs):
+    """tds_route_points_multi: arcs (B,A,Q) -> (B,A,Q,2) float32, the world-frame points at those route arcs"""
+    if not arcs.is_cuda:
+        raise RuntimeError(f'route_points: torchdrivesim_amd kernels run on an MI355X; got a {arcs.device} tensor (no CPU fallback)')
+    B, A = route['n'].shape
+    if arcs.dim() != 3 or tuple(arcs.shape[:2]) != (B, A):
+        raise RuntimeError(f'route_points: arcs must be ({B},{A},Q), got {tuple(arcs.shape)}')
+    Q = arcs.shape[2]
+    arcs = _c(arcs.detach(), torch.float64)
+    dev = arcs.device
+    pts = torch.empty((B, A, Q, 2), dtype=f32, device=dev)
+    if B * A * Q == 0:
+        return pts
+    nat.call('tds_route_points_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_points'), B, A, Q,
+             *_route_ptrs('route_points', route, B, A, ROUTE_TENSORS), nat.dev_ptr(arcs, torch.float64, 'arcs'), nat.dev_ptr(pts, f32, 'points'),
+             nat.stream_ptr(dev))
+    return pts

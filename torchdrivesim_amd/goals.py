@@ -3,8 +3,12 @@ Waypoint goals with the reference's surface (torchdrivesim/goals.py:11-217): eve
 waypoints; the collection `state[b, a]` is current, and it is ticked off as soon as the agent comes within `threshold` of any of its
 (valid) waypoints.  Host-side torch bookkeeping on small tensors -- no kernel of its own; the waypoints of the current
 collections are drawn by the K3 rasteriser as per-camera discs (`Simulator.render`, mesh.py:1120-1145 in the reference).
+
+Route goals (`RouteGoal`, no reference counterpart; DESIGN.md 5.5d, csrc/route.hip): every agent is dealt a route of a requested length on the
+lane graph; each step ONE launch reports its progress along it, its offsets from it, whether it has arrived or left it, and the next K route
+points in its own frame.  Yardstick: the float64 model tests/route_model.py.
 """
-from typing import Optional
+from typing import NamedTuple, Optional, Union
 
 import torch
 from torch import Tensor
@@ -71,3 +75,222 @@ class WaypointGoal:
         idx = self.state[..., None].expand(-1, -1, -1, self.mask.shape[-1])              # B x A x 1 x M
         self.mask = self.mask.scatter(2, idx, (valid & ~reached).unsqueeze(2))           # padding entries stay False
         self.state = (self.state + reached).clamp(0, self.max_goal_idx - 1)
+
+
+class RouteProgress(NamedTuple):
+    """What one `RouteGoal.step` reports, (B, A) each unless said otherwise; float32 and bool.  The tensors are buffers of the goal object:
+    the next step overwrites them in place (clone what has to outlive it)."""
+    progress: Tensor       # metres along the route
+    advance: Tensor        # progress minus the progress of the previous step
+    lateral: Tensor        # signed offset from the route, left positive
+    heading: Tensor        # (B, A, 2) [sin, cos] of the heading error against the route's direction
+    remaining: Tensor      # length - progress
+    reached: Tensor        # remaining <= goal_tolerance
+    off_route: Tensor      # farther than off_route_distance from the route
+    lookahead: Tensor      # (B, A, K, 2) the route points at progress + (m + 1) * spacing in the agent's frame
+
+
+_ROUTE_OUT = (('progress', ()), ('advance', ()), ('lateral', ()), ('heading', (2,)), ('remaining', ()), ('reached', ()), ('off_route', ()))
+
+
+class RouteGoal:
+    """
+    Routes on the lane graph, one per agent, and the per-step bookkeeping of them on the device (include/tdship.h "Route goals").
+    Make one with `RouteGoal.sample`.  Per agent it exposes `lanes` (B, A, 16) int32 (indices into `laneletLayer`, -1 unused), `n` (B, A) int32,
+    `start_arc`, `end_arc`, `offsets` (B, A, 16), `length` (float64), `cursor` (int32), `completed` and `valid` (bool).  A row depends on
+    `(seed, scene id, agent index)` and its own pose only, so shards and sub-batches reproduce the whole batch.
+    """
+
+    def __init__(self, lanelet_maps, tensors: dict, *, seed: int, tolerance: float, goal_tolerance: float, off_route_distance: float, lookahead: int,
+                 spacing: float):
+        from torchdrivesim_amd import _ops
+        from torchdrivesim_amd.lanelet2 import LaneletMap
+        _ops.check_route_args(goal_tolerance, off_route_distance, lookahead, spacing)
+        self.lanelet_maps = lanelet_maps if isinstance(lanelet_maps, LaneletMap) else list(lanelet_maps)
+        self.seed, self.tolerance, self.goal_tolerance = int(seed), float(tolerance), float(goal_tolerance)
+        self.off_route_distance, self.lookahead, self.spacing = float(off_route_distance), int(lookahead), float(spacing)
+        self._t = dict(tensors)       # the route tensors, its state, the requested lengths, the scene ids, scratch of the snap and the outputs
+        self._lanes = None
+        self._lane_table_set()
+
+    # ---- construction -------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def sample(cls, lanelet_maps, agent_state: Tensor, present_mask: Optional[Tensor] = None, *, seed: int, scene_ids: Optional[Tensor] = None,
+               length: Union[float, Tensor] = 200.0, tolerance: float = 1.0, goal_tolerance: float = 2.0, off_route_distance: float = 4.0,
+               lookahead: int = 16, spacing: float = 4.0) -> 'RouteGoal':
+        """
+        lanelet_maps: one `LaneletMap` for all scenes or a list of B of them; agent_state (B, A, >= 3) = [x, y, psi, ...] on the device.
+        Every present agent is snapped to a lane (`snap_to_lanes` with `tolerance`) and dealt a route of `length` metres (a number or (B, A))
+        from there; agents that find no lane, absent ones and lengths that are not positive and finite get no route (`valid` False).
+        seed: key of the route stream; scene_ids (B,) int64, default arange(B): the identity of each scene in it.
+        """
+        from torchdrivesim_amd import _ops
+        for name, t in (('agent_state', agent_state), ('present_mask', present_mask), ('scene_ids', scene_ids),
+                        ('length', length if isinstance(length, Tensor) else None)):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError(f'{name}: route goals run on an MI355X; got a {t.device} tensor (no CPU fallback)')
+        if agent_state.dim() != 3 or agent_state.shape[-1] < 3:
+            raise ValueError(f'agent_state must be (B, A, >= 3), got {tuple(agent_state.shape)}')
+        B, A = agent_state.shape[:2]
+        dev = agent_state.device
+        K = int(lookahead)
+        _ops.check_route_args(goal_tolerance, off_route_distance, K, spacing)
+        f32, f64, i32, u8 = torch.float32, torch.float64, torch.int32, torch.uint8
+        t = {name: torch.zeros((B, A) + tail, dtype=dtype, device=dev) for name, tail, dtype in _ops.ROUTE_TENSORS + _ops.ROUTE_STATE}
+        t.update({name: torch.zeros((B, A) + tail, dtype=u8 if name in ('reached', 'off_route') else f32, device=dev) for name, tail in _ROUTE_OUT})
+        t['lookahead'] = torch.zeros((B, A, K, 2), dtype=f32, device=dev)
+        t['scene_ids'] = torch.arange(B, dtype=torch.int64, device=dev) if scene_ids is None else scene_ids.to(torch.int64).clone()
+        if isinstance(length, Tensor):
+            t['distance'] = length.to(f64).expand(B, A).clone()
+        else:
+            t['distance'] = torch.full((B, A), float(length), dtype=f64, device=dev)
+        # what a snap reads and writes: kept, so that `resample` allocates nothing
+        t.update(snap_xy=torch.zeros((B, A, 2), dtype=f32, device=dev), sc=torch.zeros((B, A, 2), dtype=f32, device=dev),
+                 snap_lane=torch.zeros((B, A), dtype=i32, device=dev), snap_arc=torch.zeros((B, A), dtype=f64, device=dev),
+                 snap_lateral=torch.zeros((B, A), dtype=f32, device=dev))
+        me = cls(lanelet_maps, t, seed=seed, tolerance=tolerance, goal_tolerance=goal_tolerance, off_route_distance=off_route_distance, lookahead=K,
+                 spacing=spacing)
+        me._sample(agent_state, present_mask, None)
+        return me
+
+    def _lane_table_set(self):
+        """the device lane tables of this batch: found (or built) outside the step, so that the step allocates and copies nothing"""
+        from torchdrivesim_amd.lanelet2 import _lane_set, group_lanelet_maps
+        B = self._t['n'].shape[0]
+        if self._lanes is None and B > 0:
+            uniq, scene_map = group_lanelet_maps(self.lanelet_maps, B)
+            self._lanes = _lane_set(uniq, scene_map, self._t['n'].device)
+        return self._lanes
+
+    def _heading(self, agent_state: Tensor) -> Tensor:
+        """[sin, cos] of the headings with torch, into the buffer this object keeps for them"""
+        psi = agent_state[..., 2].detach()
+        torch.sin(psi, out=self._t['sc'][..., 0])
+        torch.cos(psi, out=self._t['sc'][..., 1])
+        return self._t['sc']
+
+    def _sample(self, agent_state, present_mask, mask) -> None:
+        from torchdrivesim_amd import _ops
+        t = self._t
+        B, A = t['n'].shape
+        if tuple(agent_state.shape[:2]) != (B, A):
+            raise ValueError(f'agent_state must be ({B}, {A}, >= 3), got {tuple(agent_state.shape)}')
+        if B * A == 0:
+            return
+        with torch.no_grad():
+            t['snap_xy'].copy_(agent_state[..., :2])
+            _ops.lane_snap(self._lane_table_set(), t['snap_xy'], self._heading(agent_state), self.tolerance,
+                           out=(t['snap_lane'], t['snap_arc'], t['snap_lateral']))
+            _ops.route_sample(self._lane_table_set(), t['scene_ids'], t['snap_lane'], t['snap_arc'], t['distance'], present_mask, mask, self.seed, t)
+
+    def resample(self, agent_state: Tensor, scene_ids: Optional[Tensor] = None, mask: Optional[Tensor] = None, present_mask: Optional[Tensor] = None) -> None:
+        """New routes IN PLACE from where the agents are now -- all rows, or the rows of `mask` (B, A) bool; the others keep route, cursor and
+        `completed`.  scene_ids (B,): the scenes' new identities in the route stream (a reset usually moves on to fresh ones).  Two launches and
+        the copies into this object's buffers; nothing is allocated, nothing synchronises."""
+        if not agent_state.is_cuda:
+            raise RuntimeError(f'agent_state: route goals run on an MI355X; got a {agent_state.device} tensor (no CPU fallback)')
+        if scene_ids is not None:
+            self._t['scene_ids'].copy_(scene_ids)
+        self._sample(agent_state, present_mask, mask)
+
+    # ---- the step -----------------------------------------------------------------------------------------------------------------
+    def step(self, agent_state: Tensor, present_mask: Optional[Tensor] = None, sc: Optional[Tensor] = None) -> RouteProgress:
+        """One launch for all agents: agent_state (B, A, >= 3) = [x, y, psi, ...]; sc: (B, A, 2) [sin psi, cos psi] where the caller has them
+        already (else computed here with torch).  Returns the `RouteProgress` of the buffers this object owns."""
+        from torchdrivesim_amd import _ops
+        if not agent_state.is_cuda:
+            raise RuntimeError(f'agent_state: route goals run on an MI355X; got a {agent_state.device} tensor (no CPU fallback)')
+        t = self._t
+        B, A = t['n'].shape
+        if agent_state.dim() != 3 or tuple(agent_state.shape[:2]) != (B, A) or agent_state.shape[-1] < 3:
+            raise ValueError(f'agent_state must be ({B}, {A}, >= 3), got {tuple(agent_state.shape)}')
+        if B * A > 0:
+            with torch.no_grad():
+                if sc is None:
+                    self._heading(agent_state)
+                else:
+                    t['sc'].copy_(sc)                                        # the buffer always holds the [sin, cos] the last launch read
+                _ops.route_progress(self._lane_table_set(), agent_state, t['sc'], present_mask, t, t, self.goal_tolerance, self.off_route_distance,
+                                    self.spacing)
+        return self.last_progress
+
+    @property
+    def last_progress(self) -> RouteProgress:
+        t = self._t
+        return RouteProgress(t['progress'], t['advance'], t['lateral'], t['heading'], t['remaining'], t['reached'].view(torch.bool),
+                             t['off_route'].view(torch.bool), t['lookahead'])
+
+    # ---- what a route is ----------------------------------------------------------------------------------------------------------
+    lanes = property(lambda self: self._t['lanes'])
+    n = property(lambda self: self._t['n'])
+    start_arc = property(lambda self: self._t['start_arc'])
+    end_arc = property(lambda self: self._t['end_arc'])
+    offsets = property(lambda self: self._t['offsets'])
+    length = property(lambda self: self._t['length'])
+    cursor = property(lambda self: self._t['cursor'])
+    scene_ids = property(lambda self: self._t['scene_ids'])
+    requested_length = property(lambda self: self._t['distance'])
+
+    @property
+    def completed(self) -> Tensor:
+        """(B, A) bool, sticky: the agent has been within `goal_tolerance` of its route's end since the route was dealt"""
+        return self._t['completed'].view(torch.bool)
+
+    @property
+    def valid(self) -> Tensor:
+        """(B, A) bool: the agent has a route"""
+        return self._t['n'] > 0
+
+    def points(self, arcs: Tensor) -> Tensor:
+        """World-frame points at route arcs: arcs (B, A, Q), or (Q,) for the same arcs on every route -> (B, A, Q, 2) float32.  Arcs are clamped to
+        [0, length]; rows without a route give [0, 0]."""
+        from torchdrivesim_amd import _ops
+        if not arcs.is_cuda:
+            raise RuntimeError(f'arcs: route goals run on an MI355X; got a {arcs.device} tensor (no CPU fallback)')
+        B, A = self._t['n'].shape
+        if arcs.dim() == 1:
+            arcs = arcs.view(1, 1, -1).expand(B, A, -1)
+        if B * A == 0:
+            return torch.zeros((B, A, arcs.shape[-1], 2), dtype=torch.float32, device=arcs.device)
+        return _ops.route_points(self._lane_table_set(), self._t, arcs)
+
+    def waypoint_goal(self, spacing: float = 4.0) -> WaypointGoal:
+        """The routes as a `WaypointGoal` the renderer draws as goal discs: N = floor(longest route / spacing) + 1 collections of ONE point each,
+        point i at route arc i * spacing (B x A x N x 1 x 2); its mask is True where i * spacing <= the route's length and the row has a route."""
+        if not spacing > 0:
+            raise ValueError(f'spacing must be > 0, got {spacing}')
+        length = self._t['length']
+        longest = float(length.max()) if length.numel() > 0 else 0.0
+        arcs = torch.arange(int(longest / spacing) + 1, dtype=torch.float64, device=length.device) * float(spacing)
+        mask = (arcs.view(1, 1, -1) <= length.unsqueeze(-1)) & self.valid.unsqueeze(-1)
+        return WaypointGoal(self.points(arcs).unsqueeze(3), mask.unsqueeze(3))
+
+    # ---- batch plumbing ---------------------------------------------------------------------------------------------------------
+    def _map(self, f):
+        # the kernels update these in place: dense tensors of their own types, owned by this object
+        self._t = {k: f(v).contiguous() for k, v in self._t.items()}
+        self._lanes = None
+        self._lane_table_set()
+        return self
+
+    def copy(self):
+        return self.__class__(self.lanelet_maps, {k: v.clone() for k, v in self._t.items()}, seed=self.seed, tolerance=self.tolerance,
+                              goal_tolerance=self.goal_tolerance, off_route_distance=self.off_route_distance, lookahead=self.lookahead,
+                              spacing=self.spacing)
+
+    def to(self, device):
+        return self._map(lambda x: x.to(device))
+
+    def extend(self, n: int, in_place: bool = True):
+        from torchdrivesim_amd.lanelet2 import LaneletMap
+        me = self if in_place else self.copy()
+        if not isinstance(me.lanelet_maps, LaneletMap):
+            me.lanelet_maps = [m for m in me.lanelet_maps for _ in range(n)]
+        return me._map(lambda x: x.unsqueeze(1).expand((x.shape[0], n) + x.shape[1:]).reshape((n * x.shape[0],) + x.shape[1:]))
+
+    def select_batch_elements(self, idx, in_place: bool = True):
+        from torchdrivesim_amd.lanelet2 import LaneletMap
+        me = self if in_place else self.copy()
+        if not isinstance(me.lanelet_maps, LaneletMap):
+            me.lanelet_maps = [me.lanelet_maps[int(i)] for i in idx]
+        return me._map(lambda x: x[idx])

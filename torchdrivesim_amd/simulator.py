@@ -224,7 +224,7 @@ class Simulator:
                  birdview_mesh_generator: Optional[BirdviewRGBMeshGenerator] = None, internal_time: int = 0, traffic_controls=None,
                  waypoint_goals=None, agent_types: Optional[Tensor] = None, agent_type_names: Optional[List[str]] = None,
                  npc_controller: Optional[NPCController] = None, agent_lr: Optional[Tensor] = None, lane_features=None,
-                 observation_noise_model=None, action_model_extras: Optional[Dict[str, Any]] = None):
+                 observation_noise_model=None, action_model_extras: Optional[Dict[str, Any]] = None, route_goals=None):
         self._lane_set = None                            # device lane tables of `lanelet_map`, made on the first compute_wrong_way
         self.road_mesh = road_mesh
         self.lanelet_map = lanelet_map
@@ -235,6 +235,8 @@ class Simulator:
         self.action_model_extras = action_model_extras
         self.traffic_controls = traffic_controls        # Dict[str, BaseTrafficControl]: state and violations; not rendered by the fused path
         self.waypoint_goals = waypoint_goals             # WaypointGoal: ticked off in step(), drawn as discs by render_egocentric
+        self.route_goals = route_goals                   # goals.RouteGoal: one launch per step(); compute_route_progress() reports it
+        self._route_progress = None                      # (state tensor, its version, RouteProgress) of the last route step
         self.lane_features = lane_features               # lanelet2.LaneFeatures: carried for policies, not used by any kernel
         if observation_noise_model is None:
             from torchdrivesim_amd.observation_noise import ObservationNoise
@@ -322,6 +324,8 @@ class Simulator:
         if self.traffic_controls is not None:
             self.traffic_controls = {k: v.to(device) for k, v in self.traffic_controls.items()}
         self.waypoint_goals = self.waypoint_goals.to(device) if self.waypoint_goals is not None else None
+        self.route_goals = self.route_goals.to(device) if self.route_goals is not None else None
+        self._route_progress = None
         self.lane_features = self.lane_features.to(device) if self.lane_features is not None else None
         self._scene_cache = None
         return self
@@ -335,7 +339,8 @@ class Simulator:
             agent_types=self.agent_type, agent_type_names=self.agent_types, agent_lr=self.agent_lr, npc_controller=self.npc_controller.copy(),
             traffic_controls={k: v.copy() for k, v in self.traffic_controls.items()} if self.traffic_controls is not None else None,
             waypoint_goals=self.waypoint_goals.copy() if self.waypoint_goals is not None else None,
-            observation_noise_model=self.observation_noise_model, lane_features=self.lane_features.copy() if self.lane_features is not None else None)
+            observation_noise_model=self.observation_noise_model, lane_features=self.lane_features.copy() if self.lane_features is not None else None,
+            route_goals=self.route_goals.copy() if self.route_goals is not None else None)
         other._scene_cache = self._scene_cache          # static maps are immutable and can be shared
         return other
 
@@ -359,6 +364,9 @@ class Simulator:
             self.traffic_controls = {k: v.extend(n) for k, v in self.traffic_controls.items()}
         if self.waypoint_goals is not None:
             self.waypoint_goals = self.waypoint_goals.extend(n)
+        if self.route_goals is not None:
+            self.route_goals = self.route_goals.extend(n)
+            self._route_progress = None
         self._scene_cache = None
         return self
 
@@ -382,6 +390,9 @@ class Simulator:
             self.traffic_controls = {k: v.select_batch_elements(idx) for k, v in self.traffic_controls.items()}
         if self.waypoint_goals is not None:
             self.waypoint_goals = self.waypoint_goals.select_batch_elements(idx)
+        if self.route_goals is not None:
+            self.route_goals = self.route_goals.select_batch_elements(idx)
+            self._route_progress = None
         self._scene_cache = None
         return self
 
@@ -578,6 +589,27 @@ class Simulator:
                 control.step(self.internal_time)
         if self.waypoint_goals is not None:                         # simulator.py:860-861
             self.waypoint_goals.step(self.get_state(), self.internal_time, threshold=self.cfg.waypoint_removal_threshold)
+        if self.route_goals is not None:
+            self._step_route_goals()
+
+    def _step_route_goals(self):
+        state = self.get_state()
+        # the [sin, cos] render / collision / off-road share for this state, where it covers exactly the exposed agents
+        sc = self._heading_sc().detach() if self.npc_count == 0 and state.dtype == torch.float32 else None
+        out = self.route_goals.step(state, self.present_mask, sc=sc)
+        self._route_progress = (state, state._version, out)
+        return out
+
+    def compute_route_progress(self):
+        """The `goals.RouteProgress` of the current state (None without `route_goals`): the one `step` has made, or, after the state was set by
+        other means since, one made now -- which, like every route step, moves the routes' cursors on and measures `advance` from the progress
+        reported before it."""
+        if self.route_goals is None:
+            return None
+        state, cached = self.get_state(), self._route_progress
+        if cached is not None and cached[0] is state and cached[1] == state._version:
+            return cached[2]
+        return self._step_route_goals()
 
     def set_state(self, agent_state: Tensor, mask: Optional[Tensor] = None) -> None:
         if mask is None:
