@@ -1242,6 +1242,26 @@ class LaneTableSet(_Handle):
         self._h = handle
 
 
+def _scene_map_ptr(lane_set, B, what):
+    if lane_set.scene_map is None:
+        return None
+    if lane_set.scene_map.shape[0] != B:
+        raise RuntimeError(f'{what}: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, the batch has {B}')
+    return nat.dev_ptr(lane_set.scene_map, i32, 'scene_map')
+
+
+def _scene_ids_ptr(scene_ids, B, what):
+    if scene_ids is None:
+        return None
+    if tuple(scene_ids.shape) != (B,):
+        raise RuntimeError(f'{what}: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
+    return nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 def wrong_way(lane_set, state, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance):
     """lanelet_orientation_loss (infractions.py:232-304) [* present]: state (B,A,4) -> (B,A) float32.  No gradient, as in the
     reference (the lane directions come from host floats there)."""
@@ -1252,13 +1272,12 @@ def wrong_way(lane_set, state, recenter_offset, present, direction_angle_thresho
     out = torch.empty((B, A), dtype=f32, device=state.device)
     if B * A == 0:
         return out
-    if lane_set.scene_map is not None and lane_set.scene_map.shape[0] != B:
-        raise RuntimeError(f'wrong_way: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, the state has {B}')
+    map_p = _scene_map_ptr(lane_set, B, 'wrong_way')
     off = None if recenter_offset is None else _c(recenter_offset.detach())
     pres = None if present is None else _u8(present)
-    nat.call('tds_wrong_way_f32', state.device, lane_set.handle, None if lane_set.scene_map is None else nat.dev_ptr(lane_set.scene_map, i32, 'scene_map'),
-             A, nat.dev_ptr(state, f32, 'state'), None if off is None else nat.dev_ptr(off, f32, 'recenter_offset'),
-             None if pres is None else nat.dev_ptr(pres, u8, 'present'), nat.dev_ptr(out, f32, 'out'), B * A,
+    nat.call('tds_wrong_way_f32', state.device, lane_set.handle, map_p, A, nat.dev_ptr(state, f32, 'state'),
+             None if off is None else nat.dev_ptr(off, f32, 'recenter_offset'), None if pres is None else nat.dev_ptr(pres, u8, 'present'),
+             nat.dev_ptr(out, f32, 'out'), B * A,
              float(direction_angle_threshold), float(lanelet_dist_tolerance), nat.stream_ptr(state.device))
     return out
 
@@ -1275,9 +1294,11 @@ def lanelet_directions(tables, scene_map, points, lanelet_dist_tolerance, max_di
     dists = torch.zeros((n, max_dirs), dtype=f64, device=dev)
     count = torch.zeros((n,), dtype=i32, device=dev)
     status = torch.zeros((n,), dtype=u8, device=dev)
-    pps = 1 if lane_set.scene_map is None else max(1, n // max(1, lane_set.scene_map.shape[0]))
-    nat.call('tds_lanelet_directions_f64', dev, lane_set.handle, None if lane_set.scene_map is None else nat.dev_ptr(lane_set.scene_map, i32, 'scene_map'),
-             pps, nat.dev_ptr(points, f64, 'points'), nat.dev_ptr(dirs, f64, 'dirs'), nat.dev_ptr(dists, f64, 'dists'),
+    # the points are split evenly among the scenes the set was made for: the helper's size check is met by construction here
+    scenes = None if lane_set.scene_map is None else lane_set.scene_map.shape[0]
+    pps = 1 if scenes is None else max(1, n // max(1, scenes))
+    nat.call('tds_lanelet_directions_f64', dev, lane_set.handle, _scene_map_ptr(lane_set, scenes, 'lanelet_directions'), pps,
+             nat.dev_ptr(points, f64, 'points'), nat.dev_ptr(dirs, f64, 'dirs'), nat.dev_ptr(dists, f64, 'dists'),
              nat.dev_ptr(count, i32, 'count'), nat.dev_ptr(status, u8, 'status'), max_dirs, n, float(lanelet_dist_tolerance),
              nat.stream_ptr(dev))
     return dirs, dists, count, status
@@ -1298,14 +1319,10 @@ def spawn_on_lanes(lane_set, scene_ids, attributes, seed, min_speed=0.0, max_spe
     dev = attributes.device
     B, A = attributes.shape[:2]
     attr_p = nat.dev_ptr(attributes, f32, 'attributes')
-    if lane_set.scene_map is not None and lane_set.scene_map.shape[0] != B:
-        raise RuntimeError(f'spawn_on_lanes: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, attributes have {B}')
-    ids_p = None
+    map_p = _scene_map_ptr(lane_set, B, 'spawn_on_lanes')
     if scene_ids is not None:
         scene_ids = scene_ids.contiguous()
-        if tuple(scene_ids.shape) != (B,):
-            raise RuntimeError(f'spawn_on_lanes: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
-        ids_p = nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    ids_p = _scene_ids_ptr(scene_ids, B, 'spawn_on_lanes')
     M, occ_p, occ_sc_p, occ_mask_p = 0, None, None, None
     if occupied is not None:
         occupied, occupied_sc = _c(occupied), _c(occupied_sc)
@@ -1322,9 +1339,8 @@ def spawn_on_lanes(lane_set, scene_ids, attributes, seed, min_speed=0.0, max_spe
     sc = torch.empty((B, A, 2), dtype=f32, device=dev)
     placed = torch.empty((B, A), dtype=torch.bool, device=dev)
     attempts = torch.empty((B, A), dtype=i32, device=dev)
-    nat.call('tds_spawn_on_lanes_f32', dev, lane_set.handle, None if lane_set.scene_map is None else nat.dev_ptr(lane_set.scene_map, i32, 'scene_map'),
-             ids_p, B, A, attr_p, occ_p, occ_sc_p, occ_mask_p, M, int(seed) & 0xFFFFFFFFFFFFFFFF, float(min_speed), float(max_speed),
-             float(gap[0]), float(gap[1]), int(max_attempts), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
+    nat.call('tds_spawn_on_lanes_f32', dev, lane_set.handle, map_p, ids_p, B, A, attr_p, occ_p, occ_sc_p, occ_mask_p, M, _seed64(seed),
+             float(min_speed), float(max_speed), float(gap[0]), float(gap[1]), int(max_attempts), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
              ctypes.c_void_p(placed.data_ptr()), nat.dev_ptr(attempts, i32, 'attempts'), nat.stream_ptr(dev))
     return state, sc, placed, attempts
 
@@ -1332,14 +1348,6 @@ def spawn_on_lanes(lane_set, scene_ids, attributes, seed, min_speed=0.0, max_spe
 # ---------------------------------------------------------------------------------------------------------------
 # lane-following NPC traffic (csrc/lanes.hip: tds_lane_snap; csrc/follow.hip: tds_lane_follow_step)
 # ---------------------------------------------------------------------------------------------------------------
-def _scene_map_ptr(lane_set, B, what):
-    if lane_set.scene_map is None:
-        return None
-    if lane_set.scene_map.shape[0] != B:
-        raise RuntimeError(f'{what}: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, the batch has {B}')
-    return nat.dev_ptr(lane_set.scene_map, i32, 'scene_map')
-
-
 def lane_snap(lane_set, xy, sc, tolerance=1.0, out=None):
     """tds_lane_snap_multi: xy (B,N,2) [x, y], sc (B,N,2) [sin, cos] -> (lane (B,N) int32, arc (B,N) float64, lateral (B,N) float32).
     out: the three tensors to write instead of new ones (dense, of exactly those types)."""
@@ -1405,18 +1413,14 @@ def lane_follow_step(lane_set, scene_ids, boxes, ent_sc, ent_speed, ent_present,
         if tuple(self_index.shape) != (B, N):
             raise RuntimeError(f'lane_follow_step: self_index must be ({B},{N}), got {tuple(self_index.shape)}')
         self_p = nat.dev_ptr(self_index, i32, 'self_index')
-    ids_p = None
-    if scene_ids is not None:
-        if tuple(scene_ids.shape) != (B,):
-            raise RuntimeError(f'lane_follow_step: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
-        ids_p = nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    ids_p = _scene_ids_ptr(scene_ids, B, 'lane_follow_step')
     params = (ctypes.c_float * 5)(*[float(x) for x in idm])
     nat.call('tds_lane_follow_step_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'lane_follow_step'), ids_p, B, N, E,
              nat.dev_ptr(_c(boxes), f32, 'boxes'), nat.dev_ptr(_c(ent_sc), f32, 'ent_sc'), nat.dev_ptr(_c(ent_speed), f32, 'ent_speed'),
              nat.dev_ptr(_u8(ent_present), u8, 'ent_present'), self_p, nat.dev_ptr(_c(npc_size), f32, 'npc_size'),
              nat.dev_ptr(_c(desired_speed), f32, 'desired_speed'), nat.dev_ptr(_u8(npc_present), u8, 'npc_present'), nat.dev_ptr(lane, i32, 'lane'),
              nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(hops, i32, 'hops'), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
-             nat.dev_ptr(leader, i32, 'leader'), int(seed) & 0xFFFFFFFFFFFFFFFF, float(dt), float(horizon), float(lateral_margin),
+             nat.dev_ptr(leader, i32, 'leader'), _seed64(seed), float(dt), float(horizon), float(lateral_margin),
              ctypes.cast(params, ctypes.c_void_p), nat.stream_ptr(dev))
 
 
@@ -1458,11 +1462,7 @@ def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, 
     for name, t in (('arc', arc), ('distance', distance)):
         if tuple(t.shape) != (B, A):
             raise RuntimeError(f'route_sample: {name} must be ({B},{A}), got {tuple(t.shape)}')
-    ids_p = None
-    if scene_ids is not None:
-        if tuple(scene_ids.shape) != (B,):
-            raise RuntimeError(f'route_sample: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
-        ids_p = nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    ids_p = _scene_ids_ptr(scene_ids, B, 'route_sample')
     masks = []
     for name, t in (('present', present), ('mask', mask)):
         if t is not None and tuple(t.shape) != (B, A):
@@ -1470,7 +1470,7 @@ def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, 
         masks.append(None if t is None else nat.dev_ptr(_u8(t), u8, name))
     nat.call('tds_route_sample_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_sample'), ids_p, B, A, nat.dev_ptr(lane, i32, 'lane'),
              nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(distance, torch.float64, 'distance'), masks[0], masks[1],
-             int(seed) & 0xFFFFFFFFFFFFFFFF, *_route_ptrs('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE), nat.stream_ptr(dev))
+             _seed64(seed), *_route_ptrs('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE), nat.stream_ptr(dev))
 
 
 def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing):

@@ -16,7 +16,7 @@ from torch import Tensor
 from torchdrivesim_amd import _native as nat
 from torchdrivesim_amd import _ops
 from torchdrivesim_amd.behavior.common import InitializationFailedError
-from torchdrivesim_amd.lanelet2 import LaneletMap, _lane_set, group_lanelet_maps  # noqa: F401  (group_lanelet_maps is part of this module's surface)
+from torchdrivesim_amd.lanelet2 import LaneletMap, group_lanelet_maps, lane_set_for  # noqa: F401  (group_lanelet_maps is part of this module's surface)
 
 # heuristic.py:11-16
 LENGTH, WIDTH, LR = 4.97, 2.04, 1.96
@@ -63,7 +63,6 @@ def heuristic_initialize_batch(lanelet_maps, batch_size: int, agent_num: int, mi
         if t is not None and not t.is_cuda:
             raise RuntimeError(f'{name}: heuristic initialisation runs on an MI355X; got a {t.device} tensor (no CPU fallback)')
     device = _device(device)
-    uniq, scene_map = group_lanelet_maps(lanelet_maps, B)
     if agent_attributes is None:
         agent_attributes = torch.empty((B, A, 3), dtype=torch.float32, device=device)       # three fills: nothing crosses from the host, so
         for k, v in enumerate((LENGTH, WIDTH, LR)):                                          # the call can be captured into a graph
@@ -82,7 +81,7 @@ def heuristic_initialize_batch(lanelet_maps, batch_size: int, agent_num: int, mi
         occupied_sc = _ops.metric_sc(inflated, 'discs')
     elif occupied_mask is not None:
         raise ValueError('occupied_mask without occupied')
-    lane_set = _lane_set(uniq, scene_map, device)
+    lane_set = lane_set_for(lanelet_maps, B, device)
     states, _, placed, _ = _ops.spawn_on_lanes(lane_set, scene_ids, agent_attributes, seed, min_speed, max_speed, (LONGITUDINAL_GAP, LATERAL_GAP),
                                                num_attempts_per_agent, occupied, occupied_sc, occupied_mask)
     if on_failure == 'raise':

@@ -16,7 +16,7 @@ import torch
 from torch import Tensor
 
 from torchdrivesim_amd import _ops
-from torchdrivesim_amd.lanelet2 import LaneletMap, _lane_set, group_lanelet_maps
+from torchdrivesim_amd.lanelet2 import LaneletMap, lane_set_for
 from torchdrivesim_amd.simulator import CompoundNPCController, NPCController, SpawnController, _enlarge
 
 # IDM defaults: time headway T [s], standstill gap s0 [m], acceleration a, comfortable braking b, hardest braking b_max [m/s^2]
@@ -90,8 +90,7 @@ class LaneFollowingNPCController(NPCController):
     def _lane_table_set(self):
         """the device lane tables of this batch: found (or built) outside the step, so that the step allocates and copies nothing"""
         if self._lanes is None and self.npc_state.shape[0] > 0:
-            uniq, scene_map = group_lanelet_maps(self.lanelet_maps, self.npc_state.shape[0])
-            self._lanes = _lane_set(uniq, scene_map, self.npc_state.device)
+            self._lanes = lane_set_for(self.lanelet_maps, self.npc_state.shape[0], self.npc_state.device)
         return self._lanes
 
     def _map(self, f):

@@ -11,7 +11,7 @@
 // reduce (path distance, point index) with shuffles.
 //
 // Arithmetic: float64 on the float64 lane table, + - * / sqrt only (-ffp-contract=off); entity coordinates are widened from float32.  The
-// one exception is the reported psi, atan2 of the segment's direction; [sin, cos] is that direction's unit vector, as in spawn.hip.
+// one exception is the reported psi, atan2 of the segment's direction; [sin, cos] is that direction's unit vector, as on-lane initialisation has it.
 #include <math.h>
 
 #include "tds_common.h"
@@ -19,6 +19,8 @@
 
 using tds::LaneRec;
 using tds::LaneView;
+using tds::order_lds;
+using tds::segment_of;
 
 namespace {
 
@@ -27,25 +29,6 @@ constexpr int FOLLOW_MAX_PIECES = 256;           // path segments staged per NPC
 constexpr int ENT_WORDS = 8;                     // LDS floats per entity
 constexpr int PIECE_DOUBLES = 6;
 constexpr int NEAR_SLOTS = 64;                   // entities in reach kept per wave before their points are weighed
-
-struct U4 { uint32_t x, y, z, w; };
-
-// Philox4x32-10, the twenty lines of spawn.hip (known answers: tests/test_spawn_model.py)
-__device__ inline U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        U4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 struct FollowArgs {
     LaneView single;                // the single-map form (views == null)
@@ -66,38 +49,6 @@ struct FollowArgs {
     double dt, horizon, margin, T, s0, a, b, b_max;
 };
 
-// the segment of a centre line that holds arc length s: clip(searchsorted(cum, s, 'right') - 1, 0, n - 2), as spawn.hip's point_at
-__device__ inline int segment_of(const double *cum, int n, double s) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (cum[mid] <= s) lo = mid + 1; else hi = mid;
-    }
-    return min(max(lo - 1, 0), n - 2);
-}
-
-// the successor lanelet `l` takes at hop `hop`, -1 at a dead end (no successor, or one without a centre line to drive on)
-__device__ inline int successor_of(const LaneView &v, int l, uint64_t sid, int npc, int hop, uint32_t key0, uint32_t key1) {
-    if (!v.succ_start) return -1;
-    const int s0 = v.succ_start[l], ns = v.succ_start[l + 1] - s0;
-    if (ns <= 0) return -1;
-    int pick = 0;
-    if (ns > 1) {
-        U4 ctr = {(uint32_t)sid, (uint32_t)(sid >> 32), (uint32_t)npc, (uint32_t)hop};
-        pick = (int)(((uint64_t)philox4x32_10(ctr, key0, key1).x * (uint64_t)(uint32_t)ns) >> 32);
-    }
-    const int j = v.succ_items[s0 + pick];
-    if (j < 0 || j >= v.n) return -1;
-    const LaneRec r = v.rec[j];
-    if (r.cl_n < 2 || !(v.cum[r.cl_start + r.cl_n - 1] > 0.0 && v.cum[r.cl_start + r.cl_n - 1] < INFINITY)) return -1;
-    return j;
-}
-
-__device__ inline void order_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // grid = (B, ceil(N / W)), W = blockDim.x / 64 waves; dynamic LDS = E * ENT_WORDS floats + W * FOLLOW_MAX_PIECES * PIECE_DOUBLES doubles + W * NEAR_SLOTS ints
 __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
     extern __shared__ __attribute__((aligned(16))) float ent[];
@@ -117,14 +68,12 @@ __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
     if (npc >= g.N) return;
     const int64_t row = scene * g.N + npc;
     double *pieces = (double *)(ent + (size_t)((E * ENT_WORDS + 3) & ~3)) + (size_t)wave * FOLLOW_MAX_PIECES * PIECE_DOUBLES;
-    const int m = g.scene_map ? g.scene_map[scene] : 0;
     int cur = g.lane[row];
-    const bool has_table = !g.views || (m >= 0 && m < g.n_views);
-    if (!has_table || cur < 0 || !g.npc_present[row] || !(g.desired_speed[row] > 0.f)) {      // rows that do not move (v0 must be > 0; NaN is not)
+    LaneView v;
+    if (!tds::view_of(g.views, g.n_views, g.scene_map, scene, v, &g.single) || cur < 0 || !g.npc_present[row] || !(g.desired_speed[row] > 0.f)) {      // rows that do not move (v0 must be > 0; NaN is not)
         if (lane_id == 0) g.leader[row] = -1;
         return;
     }
-    const LaneView v = g.views ? g.views[m] : g.single;
     if (cur >= v.n || v.rec[cur].cl_n < 2) {
         if (lane_id == 0) g.leader[row] = -1;
         return;
@@ -158,12 +107,9 @@ __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
                 q[4] = l2;
             }
             order_lds();
-            if (visited == 0) {                                              // where on its first segment the NPC stands, as spawn.hip's point_at
-                const double *p = cl + 3 * k0;
-                const double dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
-                const double seg = sqrt((dx * dx + dy * dy) + dz * dz);
-                const double u0 = seg > 0.0 ? (arc0 - cum[k0]) / seg : 0.0;
-                smin = u0 * sqrt(dx * dx + dy * dy);
+            if (visited == 0) {                                              // where on its first segment the NPC stands
+                const tds::ArcPoint p = tds::point_at_arc(cl, cum, k0, arc0);
+                smin = p.t * sqrt(p.dx * p.dx + p.dy * p.dy);
             }
             bool full = false;
             for (int i = 0; i < take; ++i) {                                 // the running path distance, front to back (every lane the same)
@@ -178,8 +124,8 @@ __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
             }
             order_lds();
             if (full || take < n_seg - k0 || visited == TDS_FOLLOW_MAX_HOPS) break;
-            const int nxt = successor_of(v, l, sid, npc, hop, g.key0, g.key1);
-            if (nxt < 0) {
+            const int nxt = tds::successor_draw(v, l, sid, npc, hop, g.key0, g.key1);
+            if (!tds::drivable(v, nxt)) {                                    // no successor, or one without a centre line to drive on
                 dead_end = true;
                 break;
             }
@@ -290,8 +236,8 @@ __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
         const LaneRec r = v.rec[cur];
         const double length = v.cum[r.cl_start + r.cl_n - 1];
         if (!(arc >= length)) break;
-        const int nxt = successor_of(v, cur, sid, npc, hops, g.key0, g.key1);
-        if (nxt < 0) {                                                       // a dead end: stand at the lanelet's end
+        const int nxt = tds::successor_draw(v, cur, sid, npc, hops, g.key0, g.key1);
+        if (!tds::drivable(v, nxt)) {                                        // a dead end: stand at the lanelet's end
             arc = length, v_new = 0.f;
             break;
         }
@@ -301,22 +247,17 @@ __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
     const double *cl = v.cl + 3 * (int64_t)r.cl_start, *cum = v.cum + r.cl_start;
     const double length = cum[r.cl_n - 1];
     if (!(arc <= length)) arc = length;                                     // more hops in one step than the kernel makes: stop at the end of the last
-    const int k = segment_of(cum, r.cl_n, arc);
-    const double *p = cl + 3 * k;
-    const double dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
-    const double seg = sqrt((dx * dx + dy * dy) + dz * dz);
-    const double u = seg > 0.0 ? (arc - cum[k]) / seg : 0.0;
+    const tds::ArcPoint p = tds::point_at_arc(cl, cum, segment_of(cum, r.cl_n, arc), arc);
+    const double dx = p.dx, dy = p.dy;
     const double l2 = sqrt(dx * dx + dy * dy);
     if (lane_id != 0) return;
     float *st = g.state + row * 4;
-    st[0] = (float)(p[0] + u * dx), st[1] = (float)(p[1] + u * dy);
+    st[0] = (float)p.x, st[1] = (float)p.y;
     st[2] = l2 > 0.0 ? (float)atan2(dy, dx) : 0.f;
     st[3] = v_new;
     g.sc[row * 2] = l2 > 0.0 ? (float)(dy / l2) : 0.f, g.sc[row * 2 + 1] = l2 > 0.0 ? (float)(dx / l2) : 1.f;
     g.lane[row] = cur, g.arc[row] = arc, g.hops[row] = hops, g.leader[row] = leader;
 }
-
-inline bool ok_param(double x) { return x >= 0.0 && x < INFINITY; }
 
 int follow_launch(const char *what, FollowArgs &g, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t N, int64_t E,
                   const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present, const int32_t *self_index,
@@ -330,9 +271,9 @@ int follow_launch(const char *what, FollowArgs &g, const int32_t *scene_map, con
         return TDS_ELIMIT;
     }
     TDS_CHECK_ARG(idm, "%s: the IDM parameters are null", what);
-    TDS_CHECK_ARG(ok_param(dt) && ok_param(horizon) && ok_param(lateral_margin), "%s: dt, horizon and lateral_margin must be finite and not negative",
+    TDS_CHECK_ARG(tds::ok_param(dt) && tds::ok_param(horizon) && tds::ok_param(lateral_margin), "%s: dt, horizon and lateral_margin must be finite and not negative",
                   what);
-    for (int i = 0; i < 5; i++) TDS_CHECK_ARG(ok_param(idm[i]), "%s: IDM parameter %d must be finite and not negative (got %g)", what, i, (double)idm[i]);
+    for (int i = 0; i < 5; i++) TDS_CHECK_ARG(tds::ok_param(idm[i]), "%s: IDM parameter %d must be finite and not negative (got %g)", what, i, (double)idm[i]);
     TDS_CHECK_ARG(idm[2] > 0.f && idm[3] > 0.f, "%s: the IDM accelerations a and b must be positive", what);
     if (B == 0 || N == 0) return TDS_OK;
     TDS_CHECK_ARG(npc_size && desired_speed && npc_present && lane && arc && hops && state && sc && leader, "%s: null argument", what);
@@ -374,7 +315,7 @@ TDS_EXPORT int tds_lane_follow_step_multi(const tds_laneset_t *set, const int32_
                                           int32_t *leader, uint64_t seed, float dt, float horizon, float lateral_margin, const float *idm,
                                           void *stream) {
     TDS_CHECK_ARG(set, "tds_lane_follow_step_multi: the lane-table set is null");
-    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_lane_follow_step_multi: a set of %d lane tables needs scene_map", set->n);
+    TDS_CHECK_SCENE_MAP("tds_lane_follow_step_multi", set, scene_map);
     FollowArgs g = {};
     g.views = set->d_views, g.n_views = set->n;
     return follow_launch("tds_lane_follow_step_multi", g, scene_map, scene_ids, B, N, E, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size,

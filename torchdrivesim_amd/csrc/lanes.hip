@@ -498,7 +498,7 @@ TDS_EXPORT int tds_wrong_way_f32(const tds_laneset_t *set, const int32_t *scene_
     TDS_CHECK_ARG(lanelet_dist_tolerance >= 0.f && lanelet_dist_tolerance <= set->max_tol,
                   "tds_wrong_way_f32: lanelet_dist_tolerance %g exceeds the %g the lane tables were built for", lanelet_dist_tolerance,
                   set->max_tol);
-    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_wrong_way_f32: a set of %d lane tables needs scene_map", set->n);
+    TDS_CHECK_SCENE_MAP("tds_wrong_way_f32", set, scene_map);
     if (n_agents == 0) return TDS_OK;
     TDS_CHECK_ARG(state, "tds_wrong_way_f32: state is null");
     unsigned blocks = (unsigned)((n_agents * GROUP + 255) / 256);
@@ -517,7 +517,7 @@ TDS_EXPORT int tds_lanelet_directions_f64(const tds_laneset_t *set, const int32_
     TDS_CHECK_ARG(lanelet_dist_tolerance >= 0.f && lanelet_dist_tolerance <= set->max_tol,
                   "tds_lanelet_directions_f64: lanelet_dist_tolerance %g exceeds the %g the lane tables were built for",
                   lanelet_dist_tolerance, set->max_tol);
-    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_lanelet_directions_f64: a set of %d lane tables needs scene_map", set->n);
+    TDS_CHECK_SCENE_MAP("tds_lanelet_directions_f64", set, scene_map);
     if (n_points == 0) return TDS_OK;
     TDS_CHECK_ARG(xy, "tds_lanelet_directions_f64: xy is null");
     unsigned blocks = (unsigned)((n_points * GROUP + 255) / 256);
@@ -541,11 +541,10 @@ __global__ __launch_bounds__(256) void lane_snap_kernel(LaneView single, const L
     int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
     int g = threadIdx.x & (GROUP - 1);
     if (a >= n) return;                               // whole groups leave together
-    int m = scene_map ? scene_map[a / poses_per_scene] : 0;
     int best_lane = -1;
     double best_score = 0.0, best_arc = 0.0, best_lat = 0.0;
-    if (!views || (m >= 0 && m < n_views)) {
-        const LaneView v = views ? views[m] : single;
+    LaneView v;
+    if (tds::view_of(views, n_views, scene_map, a / poses_per_scene, v, &single)) {
         const double x = (double)xy[2 * a], y = (double)xy[2 * a + 1];
         const double sn = (double)sc[2 * a], cs = (double)sc[2 * a + 1];
         int cx = (int)floor((x - v.ox) * v.inv_cell), cy = (int)floor((y - v.oy) * v.inv_cell);
@@ -556,9 +555,8 @@ __global__ __launch_bounds__(256) void lane_snap_kernel(LaneView single, const L
                 const int l = v.cell_items[it];
                 const LaneRec r = v.rec[l];
                 if (x < (double)r.bx0 - t || x > (double)r.bx1 + t || y < (double)r.by0 - t || y > (double)r.by1 + t) continue;
-                if ((r.flags & 1) || r.cl_n < 2) continue;
+                if ((r.flags & 1) || !tds::drivable(v, l)) continue;
                 const double *cum = v.cum + r.cl_start;
-                if (!(cum[r.cl_n - 1] > 0.0 && cum[r.cl_n - 1] < INFINITY)) continue;       // not eligible in spawn's sense
                 double d = sqrt(ring_distance2(v.poly + 2 * (int64_t)r.poly_start, r.poly_n, x, y, g));
                 if (!(d <= t)) continue;
                 const double *cl = v.cl + 3 * (int64_t)r.cl_start;
@@ -629,7 +627,7 @@ TDS_EXPORT int tds_lane_snap(const tds_lanes_t *lanes, const float *xy, const fl
 TDS_EXPORT int tds_lane_snap_multi(const tds_laneset_t *set, const int32_t *scene_map, int64_t poses_per_scene, const float *xy, const float *sc,
                                    int32_t *lane, double *arc, float *lateral, int64_t n_poses, float tolerance, void *stream) {
     TDS_CHECK_ARG(set, "tds_lane_snap_multi: the lane-table set is null");
-    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_lane_snap_multi: a set of %d lane tables needs scene_map", set->n);
+    TDS_CHECK_SCENE_MAP("tds_lane_snap_multi", set, scene_map);
     return lane_snap_launch("tds_lane_snap_multi", nullptr, set, scene_map, poses_per_scene, xy, sc, lane, arc, lateral, n_poses, tolerance,
                             set->max_tol, stream);
 }

@@ -17,31 +17,15 @@
 
 using tds::LaneRec;
 using tds::LaneView;
+using tds::drivable;
+using tds::segment_of;
+using tds::view_of;
 
 namespace {
 
 constexpr int RBLOCK = 256;                      // four waves = four rows of the progress kernel
 constexpr int ROUTE_LANES = TDS_ROUTE_MAX_LANES;
 constexpr int SEG_BITS = 28;                     // (piece of the window, segment) packed into one int for the arg-min's tie rule
-
-struct U4 { uint32_t x, y, z, w; };
-
-// Philox4x32-10, the twenty lines of spawn.hip (known answers: tests/test_spawn_model.py)
-__device__ inline U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        U4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 // what every kernel here reads of a batch: the lane tables and the route tensors (B x A rows)
 struct RouteArgs {
@@ -84,33 +68,6 @@ struct ProgressArgs {
     uint8_t *reached, *off_route;
 };
 
-// the table of a scene, or false: a scene without a lane map
-__device__ inline bool table_of(const LaneView *views, int n_views, const int32_t *scene_map, int64_t scene, LaneView &v) {
-    const int m = scene_map ? scene_map[scene] : 0;
-    if (m < 0 || m >= n_views) return false;
-    v = views[m];
-    return true;
-}
-
-// a lanelet one can drive on: eligible in the sense of tds_spawn_on_lanes_f32
-__device__ inline bool drivable(const LaneView &v, int l) {
-    if (l < 0 || l >= v.n) return false;
-    const LaneRec r = v.rec[l];
-    if (r.cl_n < 2) return false;
-    const double len = v.cum[r.cl_start + r.cl_n - 1];
-    return len > 0.0 && len < INFINITY;
-}
-
-// the segment of a centre line that holds arc length s: clip(searchsorted(cum, s, 'right') - 1, 0, n - 2), as follow.hip
-__device__ inline int segment_of(const double *cum, int n, double s) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (cum[mid] <= s) lo = mid + 1; else hi = mid;
-    }
-    return min(max(lo - 1, 0), n - 2);
-}
-
 // segment i of a centre line, clipped to the arc interval [a, b] of its piece, against the pose (x, y): false for a segment that is skipped
 // (no length in 2-D or on `cum`, or nothing of it inside [a, b]); else u = the foot's parameter on the whole segment, d2 = its squared distance
 __device__ inline bool weigh_segment(const double *cl, const double *cum, int i, double a, double b, double x, double y, double &u, double &d2) {
@@ -127,7 +84,8 @@ __device__ inline bool weigh_segment(const double *cl, const double *cum, int i,
     return true;
 }
 
-// the point at route arc q, world frame
+// the point at route arc q, world frame.  Not tds::point_at_arc: a route measures a segment by w = cum[k + 1] - cum[k] (include/tdship.h), the
+// same w its progress is computed with, and that is not the segment's own 3-D length bit for bit.
 __device__ inline void route_point(const LaneView &v, const int32_t *lanes, const double *offs, int n, double a0, double length, double q,
                                    double &x, double &y) {
     x = 0.0, y = 0.0;
@@ -163,7 +121,7 @@ __global__ void __launch_bounds__(RBLOCK) route_sample_kernel(SampleArgs g) {
     LaneView v;
     int l = g.lane[row];
     double rem = g.distance[row];
-    if (table_of(g.views, g.n_views, g.scene_map, scene, v) && (!g.present || g.present[row]) && rem > 0.0 && rem < INFINITY && drivable(v, l)) {
+    if (view_of(g.views, g.n_views, g.scene_map, scene, v) && (!g.present || g.present[row]) && rem > 0.0 && rem < INFINITY && drivable(v, l)) {
         const uint64_t sid = g.scene_ids ? (uint64_t)g.scene_ids[scene] : (uint64_t)scene;
         double a = g.arc[row];
         const double len0 = v.cum[v.rec[l].cl_start + v.rec[l].cl_n - 1];
@@ -182,22 +140,9 @@ __global__ void __launch_bounds__(RBLOCK) route_sample_kernel(SampleArgs g) {
             bend = len;
             off = off + (len - a), rem = rem - (len - a);
             if (j == ROUTE_LANES - 1) break;                                 // the cap: the route is short by what is left
-            // the successor for hop j, as follow.hip chooses it: one draw over ALL successors; a choice that cannot be driven on (or, here,
-            // carries an excluded tag) is a dead end, not a reason to draw again
-            int nxt = -1;
-            if (v.succ_start) {
-                const int s0 = v.succ_start[l], ns = v.succ_start[l + 1] - s0;
-                if (ns > 0) {
-                    int pick = 0;
-                    if (ns > 1) {
-                        U4 ctr = {(uint32_t)sid, (uint32_t)(sid >> 32), (uint32_t)agent, (uint32_t)j};
-                        pick = (int)(((uint64_t)philox4x32_10(ctr, g.key0, g.key1).x * (uint64_t)(uint32_t)ns) >> 32);
-                    }
-                    nxt = v.succ_items[s0 + pick];
-                    if (!drivable(v, nxt) || (v.rec[nxt].flags & 1)) nxt = -1;
-                }
-            }
-            if (nxt < 0) break;                                              // a dead end: the route ends at this lanelet's end
+            // the successor for hop j: one that cannot be driven on or carries an excluded tag is a dead end, the route ends at this lanelet's end
+            const int nxt = tds::successor_draw(v, l, sid, agent, j, g.key0, g.key1);
+            if (!drivable(v, nxt) || (v.rec[nxt].flags & 1)) break;
             l = nxt, a = 0.0;
         }
         if (!(off > 0.0)) n = 0;                                             // nothing to drive: a start at the very end of a dead end
@@ -217,7 +162,7 @@ __global__ void __launch_bounds__(RBLOCK) route_progress_kernel(ProgressArgs g) 
     const int K = g.K;
     int n = min(g.r.route_n[row], ROUTE_LANES);
     LaneView v;
-    if (!table_of(g.r.views, g.r.n_views, g.r.scene_map, scene, v) || (g.present && !g.present[row])) n = 0;
+    if (!view_of(g.r.views, g.r.n_views, g.r.scene_map, scene, v) || (g.present && !g.present[row])) n = 0;
     const int32_t *lanes = g.r.route_lanes + row * ROUTE_LANES;
     const double *offs = g.r.offsets + row * ROUTE_LANES;
     const double x = (double)g.xy[row * g.xy_stride], y = (double)g.xy[row * g.xy_stride + 1];
@@ -311,17 +256,15 @@ __global__ void __launch_bounds__(RBLOCK) route_points_kernel(RouteArgs g, int Q
     const int n = min(g.route_n[row], ROUTE_LANES);
     LaneView v;
     double px = 0.0, py = 0.0;
-    if (n > 0 && table_of(g.views, g.n_views, g.scene_map, row / g.A, v))
+    if (n > 0 && view_of(g.views, g.n_views, g.scene_map, row / g.A, v))
         route_point(v, g.route_lanes + row * ROUTE_LANES, g.offsets + row * ROUTE_LANES, n, g.start_arc[row], g.length[row], q[idx], px, py);
     out[idx * 2] = (float)px, out[idx * 2 + 1] = (float)py;
 }
 
-inline bool ok_param(double x) { return x >= 0.0 && x < INFINITY; }
-
 int route_args(const char *what, RouteArgs &r, const tds_laneset_t *set, const int32_t *scene_map, int64_t B, int64_t A, const int32_t *route_lanes,
                const int32_t *route_n, const double *start_arc, const double *end_arc, const double *offsets, const double *length) {
     TDS_CHECK_ARG(set, "%s: the lane-table set is null", what);
-    TDS_CHECK_ARG(scene_map || set->n == 1, "%s: a set of %d lane tables needs scene_map", what, set->n);
+    TDS_CHECK_SCENE_MAP(what, set, scene_map);
     TDS_CHECK_ARG(B >= 0 && A >= 0 && A < ((int64_t)1 << 31) && (A == 0 || B <= (((int64_t)1 << 31) - 1) / A), "%s: bad sizes B=%lld A=%lld", what,
                   (long long)B, (long long)A);
     TDS_CHECK_ARG(B * A == 0 || (route_lanes && route_n && start_arc && end_arc && offsets && length), "%s: a route tensor is null", what);
@@ -364,7 +307,7 @@ TDS_EXPORT int tds_route_progress_multi(const tds_laneset_t *set, const int32_t 
     if (rc != TDS_OK) return rc;
     TDS_CHECK_ARG(n_lookahead >= 0 && n_lookahead <= TDS_ROUTE_MAX_LOOKAHEAD, "tds_route_progress_multi: %d lookahead points, at most %d", n_lookahead,
                   TDS_ROUTE_MAX_LOOKAHEAD);
-    TDS_CHECK_ARG(ok_param(goal_tolerance) && ok_param(off_route_distance) && ok_param(spacing),
+    TDS_CHECK_ARG(tds::ok_param(goal_tolerance) && tds::ok_param(off_route_distance) && tds::ok_param(spacing),
                   "tds_route_progress_multi: goal_tolerance, off_route_distance and spacing must be finite and not negative");
     TDS_CHECK_ARG(xy_stride >= 2, "tds_route_progress_multi: xy_stride %lld is less than 2", (long long)xy_stride);
     if (g.r.rows == 0) return TDS_OK;

@@ -24,54 +24,12 @@
 using tds::Box;
 using tds::LaneRec;
 using tds::LaneView;
+using tds::U4;
+using tds::order_lds;
 
 namespace {
 
-struct U4 { uint32_t x, y, z, w; };
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's known answers: tests/test_spawn_model.py)
-__device__ inline U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        U4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-// the point of a centre line at arc length s (lanelet2.py:183-208 as torchdrivesim_amd/lanelet2.py restates it [UNVERIFIED-UPSTREAM]):
-// i = clip(searchsorted(cum, s, 'right') - 1, 0, n_seg - 1); t = (s - cum[i]) / seg[i] (0 on a segment of length 0); p = c[i] + t (c[i+1] - c[i])
-__device__ inline void point_at(const double *cl, const double *cum, int n, double s, double *px, double *py) {
-    int lo = 0, hi = n;                                  // first index with cum > s
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (cum[mid] <= s) lo = mid + 1; else hi = mid;
-    }
-    int i = min(max(lo - 1, 0), n - 2);
-    const double *a = cl + 3 * i;
-    // the segment's own length, as the host summed it: sqrt((dx*dx + dy*dy) + dz*dz) (cum[i + 1] - cum[i] is NOT that number bit for bit)
-    double dx = a[3] - a[0], dy = a[4] - a[1], dz = a[5] - a[2];
-    double seg = sqrt((dx * dx + dy * dy) + dz * dz);
-    double t = seg > 0.0 ? (s - cum[i]) / seg : 0.0;
-    *px = a[0] + t * dx;
-    *py = a[1] + t * dy;
-}
-
 constexpr int BOX_FLOATS = 6;
-
-// One wave per workgroup: LDS operations of a wave complete in issue order, so all that is needed between lane 0's append and the other
-// lanes' reads is that the compiler keeps that order.
-__device__ inline void order_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ inline Box lds_box(const float *p) {
     Box b;
@@ -97,7 +55,6 @@ __global__ __launch_bounds__(64) void spawn_on_lanes_kernel(const LaneView *view
     const int lane = threadIdx.x;
     const int64_t scene = blockIdx.x;
     const uint64_t sid = scene_ids ? (uint64_t)scene_ids[scene] : (uint64_t)scene;
-    const int m = scene_map ? scene_map[scene] : 0;
     // the occupied boxes, compacted: the absent ones are never tested
     int n_box = 0;
     for (int j0 = 0; j0 < M; j0 += 64) {
@@ -112,11 +69,11 @@ __global__ __launch_bounds__(64) void spawn_on_lanes_kernel(const LaneView *view
         }
         n_box += __popcll(b);
     }
-    order_lds();
+    order_lds();                                                           // one wave per workgroup: no barrier needed
     int n_placed = 0;
-    const bool has_lanes = m >= 0 && m < n_tables && views[m].n_eligible > 0;
+    LaneView v;
+    const bool has_lanes = tds::view_of(views, n_tables, scene_map, scene, v) && v.n_eligible > 0;
     if (has_lanes) {
-        const LaneView v = views[m];
         const float dv = max_speed - min_speed;
         for (; n_placed < A; ++n_placed) {
             const int i = n_placed;
@@ -130,19 +87,19 @@ __global__ __launch_bounds__(64) void spawn_on_lanes_kernel(const LaneView *view
                 float x = 0.f, y = 0.f, psi = 0.f, speed = 0.f, s = 0.f, c = 1.f;
                 if (a < max_attempts) {
                     U4 ctr = {(uint32_t)sid, (uint32_t)(sid >> 32), (uint32_t)i, (uint32_t)a};
-                    U4 r = philox4x32_10(ctr, key0, key1);
-                    const int k = (int)(((uint64_t)r.x * (uint64_t)(uint32_t)v.n_eligible) >> 32);
+                    U4 r = tds::philox4x32_10(ctr, key0, key1);
+                    const int k = tds::pick_of(r.x, v.n_eligible);
                     const LaneRec rec = v.rec[v.eligible[k]];
                     const double *cl = v.cl + 3 * (int64_t)rec.cl_start, *cum = v.cum + rec.cl_start;
                     const double length = cum[rec.cl_n - 1];
                     const double dist = (length * ((double)r.y + 0.5)) * 0x1p-32;
                     speed = min_speed + dv * ((float)(r.z >> 8) * 0x1p-24f);
-                    double px, py, qx, qy;
-                    point_at(cl, cum, rec.cl_n, dist, &px, &py);
-                    point_at(cl, cum, rec.cl_n, fmin(dist + 1.0, length), &qx, &qy);
-                    const double ddx = qx - px, ddy = qy - py;
+                    const double ahead = fmin(dist + 1.0, length);
+                    const tds::ArcPoint p = tds::point_at_arc(cl, cum, tds::segment_of(cum, rec.cl_n, dist), dist);
+                    const tds::ArcPoint q = tds::point_at_arc(cl, cum, tds::segment_of(cum, rec.cl_n, ahead), ahead);
+                    const double ddx = q.x - p.x, ddy = q.y - p.y;
                     const double norm = sqrt(ddx * ddx + ddy * ddy);
-                    x = (float)px, y = (float)py;
+                    x = (float)p.x, y = (float)p.y;
                     if (norm > 0.0) {
                         psi = (float)atan2(ddy, ddx);
                         s = (float)(ddy / norm), c = (float)(ddx / norm);
@@ -208,7 +165,7 @@ TDS_EXPORT int tds_spawn_on_lanes_f32(const tds_laneset_t *set, const int32_t *s
     TDS_CHECK_ARG(isfinite(min_speed) && isfinite(max_speed) && isfinite(gap_long) && isfinite(gap_lat),
                   "tds_spawn_on_lanes_f32: speeds and gaps must be finite");
     TDS_CHECK_ARG(set, "tds_spawn_on_lanes_f32: the lane-table set is null");
-    TDS_CHECK_ARG(scene_map || set->n == 1, "tds_spawn_on_lanes_f32: a set of %d lane tables needs scene_map", set->n);
+    TDS_CHECK_SCENE_MAP("tds_spawn_on_lanes_f32", set, scene_map);
     if (n_scenes == 0 || agents_per_scene == 0) return TDS_OK;
     TDS_CHECK_ARG(attributes && state && sc && placed && attempts, "tds_spawn_on_lanes_f32: null argument");
     TDS_CHECK_ARG(n_occupied == 0 || (occupied && occupied_sc), "tds_spawn_on_lanes_f32: n_occupied = %d without occupied / occupied_sc", n_occupied);

@@ -155,11 +155,10 @@ class RouteGoal:
 
     def _lane_table_set(self):
         """the device lane tables of this batch: found (or built) outside the step, so that the step allocates and copies nothing"""
-        from torchdrivesim_amd.lanelet2 import _lane_set, group_lanelet_maps
-        B = self._t['n'].shape[0]
-        if self._lanes is None and B > 0:
-            uniq, scene_map = group_lanelet_maps(self.lanelet_maps, B)
-            self._lanes = _lane_set(uniq, scene_map, self._t['n'].device)
+        from torchdrivesim_amd.lanelet2 import lane_set_for
+        n = self._t['n']
+        if self._lanes is None and n.shape[0] > 0:
+            self._lanes = lane_set_for(self.lanelet_maps, n.shape[0], n.device)
         return self._lanes
 
     def _heading(self, agent_state: Tensor) -> Tensor:

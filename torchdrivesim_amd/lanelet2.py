@@ -601,6 +601,11 @@ def _lane_set(uniq, scene_map, device):
     return s
 
 
+def lane_set_for(lanelet_maps, batch_size: int, device):
+    """The device lane tables of a batch: `lanelet_maps` is one map for all scenes or a list of `batch_size` of them."""
+    return _lane_set(*group_lanelet_maps(lanelet_maps, batch_size), device)
+
+
 def snap_to_lanes(lanelet_maps, state: Tensor, tolerance: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
     """
     Poses onto lanes, one launch (`tds_lane_snap_multi`): `state` (B, N, >= 3) = [x, y, psi, ...] on the device -> `lane` (B, N) int32 index
@@ -614,8 +619,7 @@ def snap_to_lanes(lanelet_maps, state: Tensor, tolerance: float = 1.0) -> Tuple[
         raise RuntimeError(f'snap_to_lanes runs on an MI355X; got a {state.device} tensor (no CPU fallback)')
     if state.dim() != 3 or state.shape[-1] < 3:
         raise ValueError(f'state must be (B, N, >= 3), got {tuple(state.shape)}')
-    uniq, scene_map = group_lanelet_maps(lanelet_maps, state.shape[0])
-    lane_set = _lane_set(uniq, scene_map, state.device)
+    lane_set = lane_set_for(lanelet_maps, state.shape[0], state.device)
     state = state.detach().to(torch.float32)
     return _ops.lane_snap(lane_set, state[..., :2], _ops.heading_sc(state[..., 2]), float(tolerance))
 
