@@ -27,6 +27,74 @@ def exported_symbols(path):
     return sorted(ln.split()[-1] for ln in out.splitlines() if ' T tds_' in ln)
 
 
+def declared_prototypes(testing=False):
+    """name -> [(C type without const, e.g. 'float *' or 'int64_t', parameter name), ...] of every prototype of include/tdship.h"""
+    protos = {}
+    for name, params in re.findall(r'\b(?:int|void)\s*\*?\s*(tds_\w+)\s*\(([^)]*)\)\s*;', _header(testing)):
+        protos[name] = []
+        for p in ([] if params.strip() == 'void' else params.split(',')):
+            ctype, pname = re.fullmatch(r'(.*?)(\w+)', ' '.join(p.split())).groups()
+            ctype = ' '.join(ctype.replace('const', ' ').replace('*', ' * ').split())
+            protos[name].append((ctype, pname))
+    return protos
+
+
+#: what a pointer of the header must point to for a typed device pointer of the binding (the tensors _ops.py passes)
+ELEMENT_OF = {'float *': 'f32*', 'double *': 'f64*', 'uint8_t *': 'u8*', 'int32_t *': 'i32*', 'uint32_t *': 'i32*', 'int64_t *': 'i64*', 'uint64_t *': 'i64*'}
+SCALAR_OF = {'int': 'int', 'int64_t': 'int64', 'uint64_t': 'uint64', 'float': 'float', 'size_t': 'size_t'}
+
+
+def declaration_mismatches(decl, proto):
+    """how a declaration of _native.py ([(kind, name), ...]) differs from the header's prototype ([(C type, name), ...]): a list of words"""
+    bad = []
+    if [n for _, n in decl] != [n for _, n in proto]:
+        return [f'parameters {[n for _, n in decl]}, the header has {[n for _, n in proto]}']
+    for (kind, name), (ctype, _) in zip(decl, proto):
+        if '*' not in ctype:
+            want = SCALAR_OF[ctype]                                      # a scalar: the same C type
+        elif kind in ('host*', 'void*', 'handle', 'stream'):
+            want = kind                                                  # any pointer will do ...
+            if kind == 'stream' and ctype != 'void *' or kind == 'handle' and not (ctype.startswith('tds_') or ctype == 'void *'):
+                want = f'not {kind}'                                     # ... but a stream is a void *, a handle an object of the library (or a stream)
+        else:
+            want = ELEMENT_OF.get(ctype, 'host* / void* / handle')       # a typed device pointer: the element type the header states
+        if kind != want:
+            bad.append(f'{name}: declared {kind}, the header says {ctype} ({want})')
+    return bad
+
+
+@pytest.mark.parametrize('testing', [False, True])
+def test_every_declaration_matches_its_prototype(testing):
+    """the binding's table against the header, parameter by parameter: number, order, names, pointer or scalar, the scalar's C type, the
+    element type of typed device pointers"""
+    from torchdrivesim_amd import _native
+    protos = declared_prototypes(testing)
+    decls = _native.TESTING_DECLARATIONS if testing else _native.DECLARATIONS
+    assert sorted(protos) == declared_symbols(testing) == sorted(decls)
+    bad = {name: m for name in protos for m in [declaration_mismatches(decls[name], protos[name])] if m}
+    assert not bad, bad
+    table = _native._TESTING_SIGNATURES if testing else _native._SIGNATURES
+    for name, proto in protos.items():                                   # and the argtypes derived from it
+        want = [ctypes.c_void_p if '*' in c else getattr(ctypes, 'c_' + SCALAR_OF[c]) for c, _ in proto]
+        assert table[name] == want, name
+
+
+def test_a_cpu_tensor_is_refused_by_the_declared_parameter_name():
+    """nat.call marshals from the declaration: a CPU tensor for a device pointer is refused under the header's name of the parameter,
+    before the library is entered"""
+    import torch
+    from torchdrivesim_amd import _native as nat
+    box, sc, corners = torch.zeros(2, 5), torch.zeros(2, 2), torch.zeros(2, 4, 2)
+    with pytest.raises(RuntimeError, match=r'^corners: .*no CPU fallback'):
+        nat.call('tds_box2corners_f32', torch.device('cuda', 0), ctypes.c_void_p(0), None, corners, 2, None)
+    with pytest.raises(RuntimeError, match=r'^box: .*no CPU fallback'):
+        nat.call('tds_box2corners_f32', box.device, box, sc, corners, 2)
+    with pytest.raises(RuntimeError, match=r'^rows: .*no CPU fallback'):                # an untyped pointer too
+        nat.call('tds_rows_hash_u64', box.device, box, 2, 20, 20, 1, None)
+    with pytest.raises(TypeError, match='takes 5 arguments'):
+        nat.call('tds_box2corners_f32', box.device, None, None, None)
+
+
 def test_header_symbols_are_exported_and_bound():
     from torchdrivesim_amd import _native
     _native.build()

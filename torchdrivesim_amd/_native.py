@@ -7,7 +7,9 @@ There is deliberately NO fallback: if the shared library is missing or a call fa
 import contextlib
 import ctypes
 import enum
+import functools
 import os
+import re
 import subprocess
 
 import torch
@@ -58,95 +60,139 @@ class RasterAux(ctypes.Structure):
                 ('n_keys', ctypes.c_int32), ('index_bits', ctypes.c_int32), ('flags', ctypes.c_int32)]
 
 
-_vp, _i64, _i32, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-
-# name -> argtypes  (mirrors include/tdship.h; tests/test_abi.py checks that every declared symbol is exported)
-_SIGNATURES = {
-    'tds_version': [],
-    'tds_last_error': [ctypes.c_char_p, ctypes.c_size_t],
-    'tds_bicycle_step_f32': [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _i32, _i32, _vp],
-    'tds_bicycle_step_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _i32, _i32, _vp],
-    'tds_simple_step_f32': [_vp, _vp, _vp, _i64, _f32, ctypes.POINTER(_f32), _i32, _vp],
-    'tds_simple_step_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _i64, _f32, ctypes.POINTER(_f32), _i32, _vp],
-    'tds_unicycle_step_f32': [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp],
-    'tds_unicycle_step_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp],
-    'tds_collision_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
-    'tds_collision_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
-    'tds_overlap_count_f32': [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
-    'tds_pairwise_overlap_f32': [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    'tds_pairwise_discs_f32': [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    'tds_box2corners_f32': [_vp, _vp, _vp, _i64, _vp],
-    'tds_occlusion_mask_f32': [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp],
-    'tds_map_create': [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _f32, ctypes.POINTER(_vp)],
-    'tds_map_destroy': [_vp],
-    'tds_map_info': [_vp, ctypes.POINTER(_i64)],
-    'tds_map_info_ex': [_vp, ctypes.POINTER(_i64), _i32],
-    'tds_rows_hash_u64': [_vp, _i64, _i64, _i64, ctypes.c_uint64, _vp, _vp],
-    'tds_rows_equal_u8': [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
-    'tds_mapset_create': [ctypes.POINTER(_vp), _i32, ctypes.POINTER(_vp)],
-    'tds_mapset_destroy': [_vp],
-    'tds_offroad_multi_f32': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
-    'tds_offroad_multi_bwd_f32': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
-    'tds_raster_scene_multi': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp],
-    'tds_offroad_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
-    'tds_offroad_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
-    'tds_raster_scene': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp],
-    'tds_raster_index_slices_bytes': [_i64, _i32, ctypes.POINTER(_i64)],
-    'tds_raster_scene_bwd_idx_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
-    'tds_raster_scene_bwd_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp],
-    'tds_raster_scene_masks': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp],
-    'tds_raster_scene_masks_multi': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp],
-    'tds_raster_scene_workspace_bytes': [_i64, _i32, ctypes.POINTER(_i64)],
-    'tds_raster_scene_workspace_bytes_for': [_i64, _i32, _i32, _i32, ctypes.POINTER(_i64)],
-    'tds_map_keys': [_vp, _vp, _i32, ctypes.POINTER(_i32)],
-    'tds_mapset_keys': [_vp, _vp, _i32, ctypes.POINTER(_i32)],
-    'tds_raster_mesh': [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _vp, _i32, _vp],
-    'tds_buffer_create': [_i64, _i32, _i32, ctypes.POINTER(_vp)],
-    'tds_buffer_ptr': [_vp],
-    'tds_buffer_info': [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)],
-    'tds_buffer_destroy': [_vp],
-    'tds_torch_alloc': [ctypes.c_size_t, _i32, _vp],
-    'tds_torch_free': [_vp, ctypes.c_size_t, _i32, _vp],
-    'tds_stream_create': [_i32, _vp, _i32, ctypes.POINTER(_vp)],
-    'tds_stream_destroy': [_i32, _vp],
-    'tds_device_cu_count': [_i32, ctypes.POINTER(_i32)],
-    'tds_stream_places': [_vp, _vp, _i32],
-    'tds_lanelet_centerline_f64': [_vp, _i32, _vp, _i32, _vp, ctypes.POINTER(_i32)],
-    'tds_lanes_create': [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, ctypes.POINTER(_vp)],
-    'tds_lanes_destroy': [_vp],
-    'tds_lanes_info': [_vp, ctypes.POINTER(_i64)],
-    'tds_laneset_create': [ctypes.POINTER(_vp), _i32, ctypes.POINTER(_vp)],
-    'tds_laneset_destroy': [_vp],
-    'tds_wrong_way_f32': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp],
-    'tds_lanelet_directions_f64': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp],
-    'tds_spawn_on_lanes_f32': [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_uint64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
-    'tds_lanes_set_successors': [_vp, _vp, _vp],
-    'tds_lane_snap': [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
-    'tds_lane_snap_multi': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
-    'tds_lane_follow_step': [_vp, _vp, _i64, _i64, _i64] + [_vp] * 14 + [ctypes.c_uint64, _f32, _f32, _f32, _vp, _vp],
-    'tds_lane_follow_step_multi': [_vp, _vp, _vp, _i64, _i64, _i64] + [_vp] * 14 + [ctypes.c_uint64, _f32, _f32, _f32, _vp, _vp],
-    'tds_route_sample_multi': [_vp, _vp, _vp, _i64, _i64] + [_vp] * 5 + [ctypes.c_uint64] + [_vp] * 10,
-    'tds_route_progress_multi': [_vp, _vp, _i64, _i64, _vp, _i64] + [_vp] * 11 + [_f32, _f32, _i32, _f32] + [_vp] * 9,
-    'tds_route_points_multi': [_vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
-    'tds_range_scan_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
-    'tds_range_scan_multi_f32': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp],
-}
-
-
-#: entry points that do not return an error code
-_RESTYPES = {'tds_buffer_ptr': _vp, 'tds_torch_alloc': _vp, 'tds_torch_free': None}
+# One declaration per entry point of include/tdship.h, its parameters under the header's names (tests/test_abi.py holds the table to the header).
+# Kinds: f32* f64* u8* i32* i64* = device pointer to such elements (a dense CUDA tensor of that dtype), void* = device pointer to what the call says,
+# host* = pointer into host memory (arrays, structs, out-parameters), handle = an object of the library, stream = the hipStream_t; else C scalars.
+_ABI = '''
+tds_version()
+tds_last_error(host* buf, size_t n)
+tds_bicycle_step_f32(f32* state, f32* action, f32* lr, f32* out, int64 n, float dt, float max_acc, float max_steer, int left_handed, int no_reversing, stream stream)
+tds_bicycle_step_bwd_f32(f32* state, f32* action, f32* lr, f32* grad_out, f32* grad_state, f32* grad_action, f32* grad_lr, int64 n, float dt, float max_acc, float max_steer,
+    int left_handed, int no_reversing, stream stream)
+tds_simple_step_f32(f32* state, f32* action, f32* out, int64 n, float dt, host* norm, int oriented, stream stream)
+tds_simple_step_bwd_f32(f32* state, f32* action, f32* grad_out, f32* grad_state, f32* grad_action, int64 n, float dt, host* norm, int oriented, stream stream)
+tds_unicycle_step_f32(f32* state, f32* action, f32* out, int64 n, float dt, float max_acc, float max_yaw_rate, stream stream)
+tds_unicycle_step_bwd_f32(f32* state, f32* action, f32* grad_out, f32* grad_state, f32* grad_action, int64 n, float dt, float max_acc, float max_yaw_rate, stream stream)
+tds_collision_f32(f32* boxes, f32* sc, u8* present, f32* out, i64* overlap, i32* partner, int64 B, int64 A, int64 N, int metric, stream stream)
+tds_collision_bwd_f32(f32* boxes, f32* sc, u8* present, f32* grad_out, f32* grad_boxes, f32* grad_sc, int64 B, int64 A, int64 N, int metric, stream stream)
+tds_overlap_count_f32(f32* boxes, f32* sc, u8* present, f64* out, int64 B, int64 A, stream stream)
+tds_pairwise_overlap_f32(f32* box1, f32* sc1, f32* box2, f32* sc2, f32* out, int64 n, int metric, stream stream)
+tds_pairwise_discs_f32(f32* box1, f32* sc1, f32* box2, f32* sc2, f32* out, int64 n, int num_discs, stream stream)
+tds_box2corners_f32(f32* box, f32* sc, f32* corners, int64 n, stream stream)
+tds_occlusion_mask_f32(f32* state, f32* size, u8* present, u8* out, int64 B, int64 A, int64 E, stream stream)
+tds_map_create(host* verts, host* faces, host* face_z, host* face_rgb, int64 V, int64 F, host* levels, int n_levels, float cell_size, host* out)
+tds_map_destroy(handle map)
+tds_map_info(handle map, host* info)
+tds_map_info_ex(handle map, host* info, int n_words)
+tds_map_keys(handle map, host* keys, int cap, host* n)
+tds_mapset_create(host* maps, int n, host* out)
+tds_mapset_destroy(handle set)
+tds_mapset_keys(handle set, host* keys, int cap, host* n)
+tds_rows_hash_u64(void* rows, int64 n_rows, int64 row_bytes, int64 row_stride_bytes, uint64 seed, i64* out, stream stream)
+tds_rows_equal_u8(void* rows, int64 n_rows, int64 row_bytes, int64 row_stride_bytes, i32* rep, u8* equal, stream stream)
+tds_offroad_f32(handle map, f32* state, f32* lenwid, f32* sc, u8* present, f32* out, int64 n_agents, float threshold, stream stream)
+tds_offroad_bwd_f32(handle map, f32* state, f32* lenwid, f32* sc, u8* present, f32* grad_out, f32* grad_state, f32* grad_lenwid, f32* grad_sc, int64 n_agents, float threshold,
+    stream stream)
+tds_offroad_multi_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* state, f32* lenwid, f32* sc, u8* present, f32* out, int64 n_agents, float threshold,
+    stream stream)
+tds_offroad_multi_bwd_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* state, f32* lenwid, f32* sc, u8* present, f32* grad_out, f32* grad_state, f32* grad_lenwid,
+    f32* grad_sc, int64 n_agents, float threshold, stream stream)
+tds_raster_index_slices_bytes(int64 n_img, int res, host* bytes)
+tds_raster_scene(handle map, f32* state, f32* agent_sc, f32* tmpl, i32* actor_key, u8* mask, f32* cam_xy, f32* cam_sc, int64 B, int64 Nc, int64 N, float scale, int res,
+    int out_mode, void* out, void* workspace, int64 workspace_bytes, host* actor_keys, int n_actor_keys, int actor_key_per_camera, f32* extra_tri, i32* extra_key,
+    int64 n_extra, host* aux, stream stream)
+tds_raster_scene_multi(handle set, i32* scene_map, f32* state, f32* agent_sc, f32* tmpl, i32* actor_key, u8* mask, f32* cam_xy, f32* cam_sc, int64 B, int64 Nc, int64 N,
+    float scale, int res, int out_mode, void* out, void* workspace, int64 workspace_bytes, host* actor_keys, int n_actor_keys, int actor_key_per_camera, f32* extra_tri,
+    i32* extra_key, int64 n_extra, host* aux, stream stream)
+tds_raster_scene_masks(handle map, f32* state, f32* agent_sc, f32* tmpl, i32* actor_key, u8* mask, f32* cam_xy, f32* cam_sc, int64 B, int64 Nc, int64 N, float scale, int res,
+    int out_mode, void* out, void* workspace, int64 workspace_bytes, host* actor_keys, int n_actor_keys, f32* extra_tri, i32* extra_key, int64 n_extra, host* key_channels,
+    int n_channels, host* aux, stream stream)
+tds_raster_scene_masks_multi(handle set, i32* scene_map, f32* state, f32* agent_sc, f32* tmpl, i32* actor_key, u8* mask, f32* cam_xy, f32* cam_sc, int64 B, int64 Nc, int64 N,
+    float scale, int res, int out_mode, void* out, void* workspace, int64 workspace_bytes, host* actor_keys, int n_actor_keys, f32* extra_tri, i32* extra_key, int64 n_extra,
+    host* key_channels, int n_channels, host* aux, stream stream)
+tds_raster_scene_workspace_bytes(int64 n_img, int res, host* bytes)
+tds_raster_scene_workspace_bytes_for(int64 n_img, int res, int out_mode, int n_keys, host* bytes)
+tds_buffer_create(int64 bytes, int device, int flags, host* out)
+tds_buffer_ptr(handle buf)
+tds_buffer_info(handle buf, host* bytes, host* chunks, host* spread)
+tds_buffer_destroy(handle buf)
+tds_torch_alloc(size_t size, int device, stream stream)
+tds_torch_free(void* ptr, size_t size, int device, stream stream)
+tds_stream_create(int device, host* cu_mask, int n_words, host* stream)
+tds_stream_destroy(int device, handle stream)
+tds_device_cu_count(int device, host* cus)
+tds_stream_places(stream stream, i32* places, int n)
+tds_raster_scene_bwd_f32(f32* state, f32* agent_sc, f32* tmpl, u8* mask, f32* cam_xy, f32* cam_sc, f32* image, f32* grad_out, int64 B, int64 Nc, int64 N, float scale, int res,
+    f32* grad_agent, f32* grad_cam, f32* grad_tmpl, stream stream)
+tds_raster_scene_bwd_idx_f32(f32* state, f32* agent_sc, f32* tmpl, u8* mask, f32* cam_xy, f32* cam_sc, i32* index_slices, host* keys, int n_keys, f32* grad_out,
+    int64 grad_out_stride, int64 B, int64 Nc, int64 N, float scale, int res, f32* grad_agent, f32* grad_cam, f32* grad_color, f32* grad_tmpl, stream stream)
+tds_raster_mesh(f32* verts, f32* attrs, i32* faces, int64 n_img, int64 V, int64 F, f32* cam_xy, f32* cam_sc, host* levels, int n_levels, float scale, int res, int out_mode,
+    void* out, int flags, stream stream)
+tds_lanelet_centerline_f64(host* left, int n_left, host* right, int n_right, host* out, host* n_out)
+tds_lanes_create(host* poly_xy, host* poly_start, host* cl_xyz, host* cl_start, host* flags, int n_lanelets, float cell_size, float max_tolerance, host* out)
+tds_lanes_destroy(handle lanes)
+tds_lanes_info(handle lanes, host* info)
+tds_laneset_create(host* lanes, int n, host* out)
+tds_laneset_destroy(handle set)
+tds_wrong_way_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* state, f32* recenter_offset, u8* present, f32* out, int64 n_agents, float direction_angle_threshold,
+    float lanelet_dist_tolerance, stream stream)
+tds_lanelet_directions_f64(handle set, i32* scene_map, int64 points_per_scene, f64* xy, f64* dirs, f64* dists, i32* count, u8* status, int max_dirs, int64 n_points,
+    float lanelet_dist_tolerance, stream stream)
+tds_spawn_on_lanes_f32(handle set, i32* scene_map, i64* scene_ids, int64 n_scenes, int agents_per_scene, f32* attributes, f32* occupied, f32* occupied_sc, u8* occupied_mask,
+    int n_occupied, uint64 seed, float min_speed, float max_speed, float gap_long, float gap_lat, int max_attempts, f32* state, f32* sc, u8* placed, i32* attempts,
+    stream stream)
+tds_lanes_set_successors(handle lanes, host* succ_start, host* succ_items)
+tds_lane_snap(handle lanes, f32* xy, f32* sc, i32* lane, f64* arc, f32* lateral, int64 n_poses, float tolerance, stream stream)
+tds_lane_snap_multi(handle set, i32* scene_map, int64 poses_per_scene, f32* xy, f32* sc, i32* lane, f64* arc, f32* lateral, int64 n_poses, float tolerance, stream stream)
+tds_lane_follow_step(handle lanes, i64* scene_ids, int64 B, int64 N, int64 E, f32* boxes, f32* ent_sc, f32* ent_speed, u8* ent_present, i32* self_index, f32* npc_size,
+    f32* desired_speed, u8* npc_present, i32* lane, f64* arc, i32* hops, f32* state, f32* sc, i32* leader, uint64 seed, float dt, float horizon, float lateral_margin,
+    host* idm, stream stream)
+tds_lane_follow_step_multi(handle set, i32* scene_map, i64* scene_ids, int64 B, int64 N, int64 E, f32* boxes, f32* ent_sc, f32* ent_speed, u8* ent_present, i32* self_index,
+    f32* npc_size, f32* desired_speed, u8* npc_present, i32* lane, f64* arc, i32* hops, f32* state, f32* sc, i32* leader, uint64 seed, float dt, float horizon,
+    float lateral_margin, host* idm, stream stream)
+tds_route_sample_multi(handle set, i32* scene_map, i64* scene_ids, int64 B, int64 A, i32* lane, f64* arc, f64* distance, u8* present, u8* mask, uint64 seed, i32* route_lanes,
+    i32* route_n, f64* start_arc, f64* end_arc, f64* offsets, f64* length, i32* cursor, f64* stored, u8* completed, stream stream)
+tds_route_progress_multi(handle set, i32* scene_map, int64 B, int64 A, f32* xy, int64 xy_stride, f32* sc, u8* present, i32* route_lanes, i32* route_n, f64* start_arc,
+    f64* end_arc, f64* offsets, f64* length, i32* cursor, f64* stored, u8* completed, float goal_tolerance, float off_route_distance, int n_lookahead, float spacing,
+    f32* progress, f32* advance, f32* lateral, f32* heading, f32* remaining, u8* reached, u8* off_route, f32* lookahead, stream stream)
+tds_route_points_multi(handle set, i32* scene_map, int64 B, int64 A, int64 Q, i32* route_lanes, i32* route_n, f64* start_arc, f64* end_arc, f64* offsets, f64* length, f64* q,
+    f32* points, stream stream)
+tds_range_scan_f32(handle map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E, int R, float max_range,
+    float gap_tolerance, stream stream)
+tds_range_scan_multi_f32(handle set, i32* scene_map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E,
+    int R, float max_range, float gap_tolerance, stream stream)
+'''
 
 #: entry points that only libtdship_testing.so exports (include/tdship.h, "testing hooks")
-_TESTING_SIGNATURES = {
-    'tds_raster_set_strip_width': [_i32],
-    'tds_raster_set_bits_waves': [_i32],
-    'tds_raster_set_list_lds': [_i32],
-    'tds_raster_set_list_waves': [_i32],
-    'tds_raster_set_debug': [_i32],
-    'tds_raster_get_stats': [ctypes.POINTER(ctypes.c_ulonglong)],
-    'tds_testing_set_near_lists': [_i32],
-    'tds_raster_plan': [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-}
+_TESTING_ABI = '''
+tds_raster_set_strip_width(int tw)
+tds_raster_set_bits_waves(int n)
+tds_raster_set_list_lds(int lds_kb)
+tds_raster_set_list_waves(int waves)
+tds_raster_set_debug(int flags)
+tds_raster_get_stats(host* out16)
+tds_raster_plan(int64 n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64 workspace_bytes, int cus, int force_tw,
+    int bits_waves, int list_waves, int list_lds_kb, int debug, host* out)
+tds_testing_set_near_lists(int enabled)
+'''
+
+ELEMENTS = {'f32*': torch.float32, 'f64*': torch.float64, 'u8*': torch.uint8, 'i32*': torch.int32, 'i64*': torch.int64, 'void*': None}
+SCALARS = {'int': ctypes.c_int, 'int64': ctypes.c_int64, 'uint64': ctypes.c_uint64, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t}
+
+
+def _parse(abi):
+    """name -> [(kind, parameter name), ...]"""
+    decls = {name: [tuple(p.split()) for p in params.split(',') if p.strip()] for name, params in re.findall(r'(\w+)\((.*?)\)', abi, flags=re.S)}
+    assert all(k in ELEMENTS or k in SCALARS or k in ('host*', 'handle', 'stream') for d in decls.values() for k, _ in d)
+    return decls
+
+
+DECLARATIONS, TESTING_DECLARATIONS = _parse(_ABI), _parse(_TESTING_ABI)
+# name -> argtypes: every pointer kind is a void *
+_SIGNATURES = {name: [SCALARS.get(k, ctypes.c_void_p) for k, _ in d] for name, d in DECLARATIONS.items()}
+_TESTING_SIGNATURES = {name: [SCALARS.get(k, ctypes.c_void_p) for k, _ in d] for name, d in TESTING_DECLARATIONS.items()}
+#: entry points that do not return an error code
+_RESTYPES = {'tds_buffer_ptr': ctypes.c_void_p, 'tds_torch_alloc': ctypes.c_void_p, 'tds_torch_free': None}
 
 
 def build(force=False):
@@ -235,21 +281,47 @@ def stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+@functools.lru_cache(maxsize=None)
+def _device_pointer(dtype, name):
+    """what `call` does to the argument of a device-pointer parameter: a tensor is refused unless the kernels can read it as it is (dtype None:
+    any element type) and becomes its address; None, numbers and ctypes values pass through"""
+    def convert(t):
+        if not isinstance(t, torch.Tensor):
+            return t
+        if not t.is_cuda:
+            raise RuntimeError(f'{name}: torchdrivesim_amd kernels run on an MI355X; got a {t.device} tensor (no CPU fallback)')
+        if dtype is not None and t.dtype != dtype:
+            raise RuntimeError(f'{name}: expected {dtype}, got {t.dtype}')
+        if not t.is_contiguous():
+            raise RuntimeError(f'{name}: tensor must be contiguous')
+        return ctypes.c_void_p(t.data_ptr())
+    return convert
+
+
 def dev_ptr(t, dtype, name):
     """Device pointer of a dense tensor; refuses anything the kernels cannot read as-is."""
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise RuntimeError(f'{name}: torchdrivesim_amd kernels run on an MI355X; got a {t.device} tensor (no CPU fallback)')
-    if t.dtype != dtype:
-        raise RuntimeError(f'{name}: expected {dtype}, got {t.dtype}')
-    if not t.is_contiguous():
-        raise RuntimeError(f'{name}: tensor must be contiguous')
-    return ctypes.c_void_p(t.data_ptr())
+    return _device_pointer(dtype, name)(t)
+
+
+def _stream_arg(s):
+    return s.cuda_stream if isinstance(s, torch.cuda.Stream) else s
+
+
+# name -> (one converter per parameter -- None: the argument is passed on as it is --, whether the last parameter is the launch stream)
+_MARSHAL = {name: (tuple(_stream_arg if k == 'stream' else _device_pointer(ELEMENTS[k], p) if k in ELEMENTS else None for k, p in d),
+                   bool(d) and d[-1][0] == 'stream') for name, d in {**DECLARATIONS, **TESTING_DECLARATIONS}.items()}
 
 
 def call(name, device, *args):
-    """Run a C-ABI entry point with `device` current (the stream argument must belong to it)."""
+    """Run a C-ABI entry point with `device` current, its arguments converted as the declaration says.  A launch stream that is the last
+    parameter may be left out: torch's current stream of `device` (a stream that is given must belong to `device`)."""
+    convert, stream_last = _MARSHAL[name]
+    missing = len(convert) - len(args)
+    if missing and not (missing == 1 and stream_last):
+        raise TypeError(f'{name} takes {len(convert)} arguments, got {len(args)}')
+    args = [a if c is None else c(a) for c, a in zip(convert, args)]
+    if missing:
+        args.append(torch.cuda.current_stream(device).cuda_stream)
     with torch.cuda.device(device):
         rc = getattr(lib(), name)(*args)
     check(rc, name)

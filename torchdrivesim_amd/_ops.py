@@ -126,9 +126,7 @@ class _BicycleStep(torch.autograd.Function):
         state, action, lr = _c(state), _c(action), _c(lr)
         out = torch.empty_like(state)
         n = lr.numel()
-        nat.call('tds_bicycle_step_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(action, f32, 'action'),
-                 nat.dev_ptr(lr, f32, 'lr'), nat.dev_ptr(out, f32, 'out'), n, dt, max_acc, max_steer, int(left_handed),
-                 int(no_reversing), nat.stream_ptr(state.device))
+        nat.call('tds_bicycle_step_f32', state.device, state, action, lr, out, n, dt, max_acc, max_steer, int(left_handed), int(no_reversing))
         ctx.save_for_backward(state, action, lr)
         ctx.cfg = (dt, max_acc, max_steer, int(left_handed), int(no_reversing))
         return out
@@ -139,9 +137,7 @@ class _BicycleStep(torch.autograd.Function):
         dt, max_acc, max_steer, lh, norev = ctx.cfg
         gout = _c(gout)
         gs, ga, gl = torch.empty_like(state), torch.empty_like(action), torch.empty_like(lr)
-        nat.call('tds_bicycle_step_bwd_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(action, f32, 'action'),
-                 nat.dev_ptr(lr, f32, 'lr'), nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gs, f32, 'gs'), nat.dev_ptr(ga, f32, 'ga'),
-                 nat.dev_ptr(gl, f32, 'gl'), lr.numel(), dt, max_acc, max_steer, lh, norev, nat.stream_ptr(state.device))
+        nat.call('tds_bicycle_step_bwd_f32', state.device, state, action, lr, gout, gs, ga, gl, lr.numel(), dt, max_acc, max_steer, lh, norev)
         return gs, ga, gl, None, None, None, None, None
 
 
@@ -158,8 +154,7 @@ class _SimpleStep(torch.autograd.Function):
         state, action = _c(state), _c(action)
         out = torch.empty_like(state)
         cn = (ctypes.c_float * 4)(*norm)
-        nat.call('tds_simple_step_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(action, f32, 'action'),
-                 nat.dev_ptr(out, f32, 'out'), state.numel() // 4, dt, cn, int(oriented), nat.stream_ptr(state.device))
+        nat.call('tds_simple_step_f32', state.device, state, action, out, state.numel() // 4, dt, cn, int(oriented))
         ctx.save_for_backward(state, action)
         ctx.cfg = (dt, tuple(norm), int(oriented))
         return out
@@ -171,9 +166,7 @@ class _SimpleStep(torch.autograd.Function):
         gout = _c(gout)
         gs, ga = torch.empty_like(state), torch.empty_like(action)
         cn = (ctypes.c_float * 4)(*norm)
-        nat.call('tds_simple_step_bwd_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(action, f32, 'action'),
-                 nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gs, f32, 'gs'), nat.dev_ptr(ga, f32, 'ga'), state.numel() // 4, dt, cn,
-                 oriented, nat.stream_ptr(state.device))
+        nat.call('tds_simple_step_bwd_f32', state.device, state, action, gout, gs, ga, state.numel() // 4, dt, cn, oriented)
         return gs, ga, None, None, None
 
 
@@ -187,8 +180,7 @@ class _UnicycleStep(torch.autograd.Function):
     def forward(ctx, state, action, dt, max_acc, max_w):
         state, action = _c(state), _c(action)
         out = torch.empty_like(state)
-        nat.call('tds_unicycle_step_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(action, f32, 'action'),
-                 nat.dev_ptr(out, f32, 'out'), state.numel() // 4, dt, max_acc, max_w, nat.stream_ptr(state.device))
+        nat.call('tds_unicycle_step_f32', state.device, state, action, out, state.numel() // 4, dt, max_acc, max_w)
         ctx.save_for_backward(state, action)
         ctx.cfg = (dt, max_acc, max_w)
         return out
@@ -199,9 +191,7 @@ class _UnicycleStep(torch.autograd.Function):
         dt, max_acc, max_w = ctx.cfg
         gout = _c(gout)
         gs, ga = torch.empty_like(state), torch.empty_like(action)
-        nat.call('tds_unicycle_step_bwd_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(action, f32, 'action'),
-                 nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gs, f32, 'gs'), nat.dev_ptr(ga, f32, 'ga'), state.numel() // 4, dt,
-                 max_acc, max_w, nat.stream_ptr(state.device))
+        nat.call('tds_unicycle_step_bwd_f32', state.device, state, action, gout, gs, ga, state.numel() // 4, dt, max_acc, max_w)
         return gs, ga, None, None, None
 
 
@@ -233,9 +223,7 @@ def collision_forward(boxes, sc, present, n_exposed, metric, want_overlap=False,
     out = torch.empty((B, A), dtype=f32, device=boxes.device)
     overlap = torch.empty((B, A), dtype=torch.int64, device=boxes.device) if want_overlap else None
     partner = torch.empty((B, A), dtype=i32, device=boxes.device) if want_partner else None
-    nat.call('tds_collision_f32', boxes.device, nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(present, u8, 'present'),
-             nat.dev_ptr(out, f32, 'out'), nat.dev_ptr(overlap, torch.int64, 'overlap'), nat.dev_ptr(partner, i32, 'partner'), B, A, N,
-             _METRICS[metric], nat.stream_ptr(boxes.device))
+    nat.call('tds_collision_f32', boxes.device, boxes, sc, present, out, overlap, partner, B, A, N, _METRICS[metric])
     return out, overlap, partner
 
 
@@ -247,8 +235,7 @@ def overlap_count(boxes, present, sc=None):
     present = _u8(present)
     B, A = boxes.shape[:2]
     out = torch.empty((B, A), dtype=torch.float64, device=boxes.device)
-    nat.call('tds_overlap_count_f32', boxes.device, nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(present, u8, 'present'),
-             nat.dev_ptr(out, torch.float64, 'out'), B, A, nat.stream_ptr(boxes.device))
+    nat.call('tds_overlap_count_f32', boxes.device, boxes, sc, present, out, B, A)
     return out
 
 
@@ -270,9 +257,7 @@ class _Collision(torch.autograd.Function):
         gout = _c(gout)
         pres = _u8(present)
         gb, gsc = torch.empty_like(boxes), torch.empty_like(sc)
-        nat.call('tds_collision_bwd_f32', boxes.device, nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'),
-                 nat.dev_ptr(pres, u8, 'present'), nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gb, f32, 'gb'), nat.dev_ptr(gsc, f32, 'gsc'),
-                 B, A, N, _METRICS[metric], nat.stream_ptr(boxes.device))
+        nat.call('tds_collision_bwd_f32', boxes.device, boxes, sc, pres, gout, gb, gsc, B, A, N, _METRICS[metric])
         return gb, gsc, None, None, None
 
 
@@ -294,11 +279,9 @@ def pairwise_overlap(box1, box2, metric='iou', sc1=None, sc2=None, num_discs=5):
     b1, b2, s1, s2 = _c(box1).reshape(-1, 5), _c(box2).reshape(-1, 5), _c(sc1).reshape(-1, 2), _c(sc2).reshape(-1, 2)
     out = torch.empty(b1.shape[0], dtype=f32, device=b1.device)
     if metric == 'discs' and num_discs != 5:
-        nat.call('tds_pairwise_discs_f32', b1.device, nat.dev_ptr(b1, f32, 'box1'), nat.dev_ptr(s1, f32, 'sc1'), nat.dev_ptr(b2, f32, 'box2'),
-                 nat.dev_ptr(s2, f32, 'sc2'), nat.dev_ptr(out, f32, 'out'), b1.shape[0], int(num_discs), nat.stream_ptr(b1.device))
-        return out.reshape(shape)
-    nat.call('tds_pairwise_overlap_f32', b1.device, nat.dev_ptr(b1, f32, 'box1'), nat.dev_ptr(s1, f32, 'sc1'), nat.dev_ptr(b2, f32, 'box2'),
-             nat.dev_ptr(s2, f32, 'sc2'), nat.dev_ptr(out, f32, 'out'), b1.shape[0], _METRICS[metric], nat.stream_ptr(b1.device))
+        nat.call('tds_pairwise_discs_f32', b1.device, b1, s1, b2, s2, out, b1.shape[0], int(num_discs))
+    else:
+        nat.call('tds_pairwise_overlap_f32', b1.device, b1, s1, b2, s2, out, b1.shape[0], _METRICS[metric])
     return out.reshape(shape)
 
 
@@ -308,8 +291,7 @@ def box2corners(box, sc=None):
         sc = heading_sc(box[..., 4])
     b, s = _c(box).reshape(-1, 5), _c(sc).reshape(-1, 2)
     out = torch.empty((b.shape[0], 4, 2), dtype=f32, device=b.device)
-    nat.call('tds_box2corners_f32', b.device, nat.dev_ptr(b, f32, 'box'), nat.dev_ptr(s, f32, 'sc'), nat.dev_ptr(out, f32, 'out'), b.shape[0],
-             nat.stream_ptr(b.device))
+    nat.call('tds_box2corners_f32', b.device, b, s, out, b.shape[0])
     return out.reshape(box.shape[:-1] + (4, 2))
 
 
@@ -323,8 +305,7 @@ def occlusion_mask(state, size, present, n_exposed):
     state, size = _c(state.detach()), _c(size.detach())
     p8 = _u8(present)
     out = torch.empty((B, int(n_exposed), E), dtype=u8, device=state.device)
-    nat.call('tds_occlusion_mask_f32', state.device, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(size, f32, 'size'), nat.dev_ptr(p8, u8, 'present'),
-             nat.dev_ptr(out, u8, 'out'), B, int(n_exposed), E, nat.stream_ptr(state.device))
+    nat.call('tds_occlusion_mask_f32', state.device, state, size, p8, out, B, int(n_exposed), E)
     return out.view(torch.bool)
 
 
@@ -427,7 +408,7 @@ def _rows_view(t):
     n = t.shape[0]
     if n > 1 and t.stride(0) == 0:
         t, n = t[:1], 1
-    if t.numel() and not t[0].is_contiguous():
+    if not t.is_contiguous():                      # (rows a stride apart too: the entry points take them, the binding's check of `rows` does not)
         t = t.contiguous()
     row_bytes = (t[0].numel() if n else 0) * t.element_size()
     stride = t.stride(0) * t.element_size() if n > 1 else row_bytes
@@ -447,8 +428,7 @@ def row_hashes(tensors):
         for seed in _ROW_SEEDS:
             h = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
             if n:
-                nat.call('tds_rows_hash_u64', dev, ctypes.c_void_p(v.data_ptr()), n, row_bytes, stride, ctypes.c_uint64(seed), ctypes.c_void_p(h.data_ptr()),
-                         nat.stream_ptr(dev))
+                nat.call('tds_rows_hash_u64', dev, v, n, row_bytes, stride, seed, h)
             cols.append(h[:n].expand(B) if n != B else h)
     return torch.stack(cols, dim=1) if cols else torch.zeros(B, 0, dtype=torch.int64, device=dev)
 
@@ -480,8 +460,7 @@ def group_rows(tensors):
         for t in tensors:
             v, n, row_bytes, stride = _rows_view(t.detach())
             if n == B:
-                nat.call('tds_rows_equal_u8', dev, ctypes.c_void_p(v.data_ptr()), n, row_bytes, stride, nat.dev_ptr(rep, i32, 'rep'), nat.dev_ptr(equal, u8, 'equal'),
-                         nat.stream_ptr(dev))
+                nat.call('tds_rows_equal_u8', dev, v, n, row_bytes, stride, rep, equal)
         bad = np.nonzero(equal.cpu().numpy() == 0)[0]
         for b in bad:                                                            # a hash collision: the row gets a map of its own
             scene_map[b] = len(reps)
@@ -579,19 +558,20 @@ def _agents_per_scene(smap, state):
     return n // n_scenes
 
 
+def _map_head(fn, suffix, smap, dev, agents=None):
+    """the start of a call that takes one map or a map set: entry point, device, handle -- for a StaticMapSet the _multi form, whose handle is
+    followed by the scene map and, where the entry point takes it (`agents`: the agent tensor), the agents per scene"""
+    if isinstance(smap, StaticMapSet):
+        return (fn + '_multi' + suffix, dev, smap.handle, smap.scene_map) + (() if agents is None else (_agents_per_scene(smap, agents),))
+    return fn + suffix, dev, None if smap is None else smap.handle
+
+
 def offroad_forward(smap, state, lenwid, sc, present, threshold):
     state, lenwid, sc = _c(state), _c(lenwid), _c(sc)
     n = state.numel() // 4
     out = torch.empty(state.shape[:-1], dtype=f32, device=state.device)
     pres = None if present is None else _u8(present)
-    if isinstance(smap, StaticMapSet):
-        nat.call('tds_offroad_multi_f32', state.device, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map'), _agents_per_scene(smap, state),
-                 nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(lenwid, f32, 'lenwid'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(pres, u8, 'present'),
-                 nat.dev_ptr(out, f32, 'out'), n, float(threshold), nat.stream_ptr(state.device))
-        return out
-    nat.call('tds_offroad_f32', state.device, smap.handle, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(lenwid, f32, 'lenwid'),
-             nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(pres, u8, 'present'), nat.dev_ptr(out, f32, 'out'), n, float(threshold),
-             nat.stream_ptr(state.device))
+    nat.call(*_map_head('tds_offroad', '_f32', smap, state.device, state), state, lenwid, sc, pres, out, n, float(threshold))
     return out
 
 
@@ -611,15 +591,7 @@ class _Offroad(torch.autograd.Function):
         gout = _c(gout)
         pres = None if present is None else _u8(present)
         gs, gl, gsc = torch.empty_like(state), torch.empty_like(lenwid), torch.empty_like(sc)
-        if isinstance(smap, StaticMapSet):
-            nat.call('tds_offroad_multi_bwd_f32', state.device, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map'), _agents_per_scene(smap, state),
-                     nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(lenwid, f32, 'lenwid'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(pres, u8, 'present'),
-                     nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gs, f32, 'gs'), nat.dev_ptr(gl, f32, 'gl'), nat.dev_ptr(gsc, f32, 'gsc'),
-                     state.numel() // 4, float(threshold), nat.stream_ptr(state.device))
-            return None, gs, gl, gsc, None, None
-        nat.call('tds_offroad_bwd_f32', state.device, smap.handle, nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(lenwid, f32, 'lenwid'),
-                 nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(pres, u8, 'present'), nat.dev_ptr(gout, f32, 'grad_out'), nat.dev_ptr(gs, f32, 'gs'),
-                 nat.dev_ptr(gl, f32, 'gl'), nat.dev_ptr(gsc, f32, 'gsc'), state.numel() // 4, float(threshold), nat.stream_ptr(state.device))
+        nat.call(*_map_head('tds_offroad', '_bwd_f32', smap, state.device, state), state, lenwid, sc, pres, gout, gs, gl, gsc, state.numel() // 4, float(threshold))
         return None, gs, gl, gsc, None, None
 
 
@@ -662,7 +634,6 @@ def range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_toler
     boxes, sc, ray_sc = _c(boxes.detach()), _c(sc.detach()), _c(ray_sc.detach())
     present = _u8(present)
     dev = boxes.device
-    ptrs = [nat.dev_ptr(boxes, f32, 'boxes'), nat.dev_ptr(sc, f32, 'sc'), nat.dev_ptr(present, u8, 'present'), nat.dev_ptr(ray_sc, f32, 'ray_sc')]
     if smap is not None and smap.device != dev:
         raise RuntimeError(f'range scan: the map lives on {smap.device}, the agents on {dev}')
     if isinstance(smap, StaticMapSet) and smap.scene_map.shape[0] != B:
@@ -670,12 +641,7 @@ def range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_toler
     agents = torch.empty((B, A, R), dtype=f32, device=dev) if want_agents else None
     road = torch.empty((B, A, R), dtype=f32, device=dev)
     hit = torch.empty((B, A, R), dtype=i32, device=dev)
-    tail = [nat.dev_ptr(agents, f32, 'agents'), nat.dev_ptr(road, f32, 'road'), nat.dev_ptr(hit, i32, 'hit'), B, A, E, R, float(max_range),
-            float(gap_tolerance), nat.stream_ptr(dev)]
-    if isinstance(smap, StaticMapSet):
-        nat.call('tds_range_scan_multi_f32', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map'), *ptrs, *tail)
-    else:
-        nat.call('tds_range_scan_f32', dev, None if smap is None else smap.handle, *ptrs, *tail)
+    nat.call(*_map_head('tds_range_scan', '_f32', smap, dev), boxes, sc, present, ray_sc, agents, road, hit, B, A, E, R, float(max_range), float(gap_tolerance))
     if agents is None:
         agents = torch.full((B, A, R), float(max_range), dtype=f32, device=dev)
     return agents, road, hit
@@ -834,7 +800,7 @@ def stream_places(stream, n: int = 8192):
     dev = stream.device
     out = torch.full((n,), -1, dtype=i32, device=dev)
     stream.wait_stream(torch.cuda.current_stream(dev))
-    nat.call('tds_stream_places', dev, ctypes.c_void_p(stream.cuda_stream), ctypes.c_void_p(out.data_ptr()), n)      # (with `dev` current)
+    nat.call('tds_stream_places', dev, stream, out, n)      # (with `dev` current)
     stream.synchronize()
     return sorted(set(out.cpu().tolist()))
 
@@ -953,17 +919,14 @@ def _scene_call(fn, smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc
         K = extra_tri.shape[2]
         assert tuple(extra_tri.shape) == (B, Nc, K, 3, 2) and tuple(extra_key.shape) == (B, Nc, K), 'extra_tri must be (B,Nc,K,3,2), extra_key (B,Nc,K)'
         extra_tri, extra_key = _c(extra_tri), _c(extra_key, i32)
-    multi = isinstance(smap, StaticMapSet)
-    if multi and smap.scene_map.shape[0] != B:
+    if isinstance(smap, StaticMapSet) and smap.scene_map.shape[0] != B:
         raise RuntimeError(f'the StaticMapSet is for {smap.scene_map.shape[0]} scenes, the cameras for {B}')
-    p = lambda t, d, nme: nat.dev_ptr(t, d, nme) if N > 0 else None      # noqa: E731
+    actors = (state, agent_sc, tmpl, actor_key, mask) if N > 0 else (None,) * 5
+    extra = (extra_tri, extra_key) if K > 0 else (None, None)
 
     def call(middle, tail):
-        head = (fn + '_multi', dev, smap.handle, nat.dev_ptr(smap.scene_map, i32, 'scene_map')) if multi else (fn, dev, smap.handle)
-        nat.call(*head, p(state, f32, 'state'), p(agent_sc, f32, 'agent_sc'), p(tmpl, f32, 'tmpl'), p(actor_key, i32, 'actor_key'),
-                 p(mask, u8, 'mask'), nat.dev_ptr(cam_xy, f32, 'cam_xy'), nat.dev_ptr(cam_sc, f32, 'cam_sc'), B, Nc, N, float(2.0 / fov), int(res),
-                 mode, nat.dev_ptr(out, out_dtype, 'out'), *middle, nat.dev_ptr(extra_tri, f32, 'extra_tri') if K > 0 else None,
-                 nat.dev_ptr(extra_key, i32, 'extra_key') if K > 0 else None, K, *tail)
+        nat.call(*_map_head(fn, '', smap, dev), *actors, cam_xy, cam_sc, B, Nc, N, float(2.0 / fov), int(res), mode, nat.dev_ptr(out, out_dtype, 'out'),
+                 *middle, *extra, K, *tail)
     return B, Nc, N, K, actor_key, extra_key, out, call
 
 
@@ -1008,9 +971,8 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
         aux = aux if aux is not None else nat.RasterAux()
         aux.flags = nat.RASTER_NO_TRIM
     def launch(aux):
-        call((None if ws is None else ctypes.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(),
-              None if kt is None else ctypes.cast(kt, ctypes.c_void_p), 0 if kt is None else len(key_table), 1 if (N > 0 and actor_key.dim() == 4) else 0),
-             (None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev)))
+        call((ws, 0 if ws is None else ws.numel(), kt, 0 if kt is None else len(key_table), 1 if (N > 0 and actor_key.dim() == 4) else 0),
+             (None if aux is None else ctypes.byref(aux),))
 
     global raster_calls
     raster_calls += 1
@@ -1070,8 +1032,7 @@ def raster_scene_masks(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam
     # (more than 15 keys: the call reports TDS_ELIMIT; the workspace is sized as for 15 rather than for the packed-key kernels' lists)
     ws = _raster_workspace(dev, B * Nc, int(res), mode, min(len(table), 15))
     aux = None if trim else nat.RasterAux(flags=nat.RASTER_NO_TRIM)
-    call((ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.cast(kt, ctypes.c_void_p), len(actors)),
-         (ctypes.cast(kc, ctypes.c_void_p), C, None if aux is None else ctypes.cast(ctypes.pointer(aux), ctypes.c_void_p), nat.stream_ptr(dev)))
+    call((ws, ws.numel(), kt, len(actors)), (kc, C, None if aux is None else ctypes.byref(aux)))
     return out
 
 
@@ -1123,25 +1084,21 @@ class _RasterScene(torch.autograd.Function):
         g_agent = torch.empty((B, Nc, max(N, 1), 4), dtype=f32, device=dev)
         g_cam = torch.empty((B, Nc, 4), dtype=f32, device=dev)
         m8 = _u8(mask)
-        p = lambda t, d, nme: nat.dev_ptr(_c(t, d), d, nme) if N > 0 else None
         ev = None
         if raster_bwd_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record(torch.cuda.current_stream(dev))
-        poses = (p(state, f32, 'state'), p(agent_sc, f32, 'agent_sc'), p(tmpl, f32, 'tmpl'), None if N == 0 else nat.dev_ptr(m8, u8, 'mask'),
-                 nat.dev_ptr(_c(cam_xy), f32, 'cam_xy'), nat.dev_ptr(_c(cam_sc), f32, 'cam_sc'))
+        poses = ((_c(state), _c(agent_sc), _c(tmpl), m8) if N > 0 else (None,) * 4) + (_c(cam_xy), _c(cam_sc))
         g_tmpl = torch.empty((B, Nc, N, 7, 2), dtype=f32, device=dev) if (N > 0 and ctx.needs_input_grad[6]) else None      # template vertices: actor sizes
-        tail = (B, Nc, N, float(2.0 / ctx.fov), int(ctx.res), nat.dev_ptr(g_agent, f32, 'grad_agent'), nat.dev_ptr(g_cam, f32, 'grad_cam'),
-                nat.dev_ptr(g_tmpl, f32, 'grad_tmpl'), nat.stream_ptr(dev))
+        tail = (B, Nc, N, float(2.0 / ctx.fov), int(ctx.res), g_agent, g_cam)
         g_color = None
         if ctx.keys is not None:
             kt = (ctypes.c_uint32 * 16)(*ctx.keys)
             if ctx.color_keys is not None and ctx.needs_input_grad[4]:
                 g_color = torch.empty((B, Nc, 16, 4), dtype=f32, device=dev)
-            nat.call('tds_raster_scene_bwd_idx_f32', dev, *poses, nat.dev_ptr(kept, i32, 'index_slices'), ctypes.cast(kt, ctypes.c_void_p), len(ctx.keys),
-                     nat.dev_ptr(gout, f32, 'grad_out'), gstride, *tail[:-2], nat.dev_ptr(g_color, f32, 'grad_color'), tail[-2], tail[-1])
+            nat.call('tds_raster_scene_bwd_idx_f32', dev, *poses, kept, kt, len(ctx.keys), gout, gstride, *tail, g_color, g_tmpl)
         else:
-            nat.call('tds_raster_scene_bwd_f32', dev, *poses, nat.dev_ptr(kept, f32, 'image'), nat.dev_ptr(gout, f32, 'grad_out'), *tail)
+            nat.call('tds_raster_scene_bwd_f32', dev, *poses, kept, gout, *tail, g_tmpl)
         if ev is not None:
             ev[1].record(torch.cuda.current_stream(dev))
             raster_bwd_events.append(ev)
@@ -1184,11 +1141,8 @@ def raster_mesh(verts, attrs, faces, cam_xy, cam_sc, levels, scale, res, out_dty
     faces = _c(faces, i32)
     out = torch.empty((n, 3, res, res), dtype=out_dtype, device=dev)
     lv = (ctypes.c_float * max(len(levels), 1))(*[float(x) for x in levels])
-    nat.call('tds_raster_mesh', dev, nat.dev_ptr(verts, f32, 'verts'), nat.dev_ptr(attrs, f32, 'attrs'), nat.dev_ptr(faces, i32, 'faces'),
-             n, verts.shape[1], faces.shape[1], nat.dev_ptr(cam_xy, f32, 'cam_xy'), nat.dev_ptr(cam_sc, f32, 'cam_sc'),
-             ctypes.cast(lv, ctypes.c_void_p), len(levels), float(scale), int(res),
-             nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8, nat.dev_ptr(out, out_dtype, 'out'), 0 if trim else nat.RASTER_NO_TRIM,
-             nat.stream_ptr(dev))
+    nat.call('tds_raster_mesh', dev, verts, attrs, faces, n, verts.shape[1], faces.shape[1], cam_xy, cam_sc, lv, len(levels), float(scale), int(res),
+             nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8, nat.dev_ptr(out, out_dtype, 'out'), 0 if trim else nat.RASTER_NO_TRIM)
     return out
 
 
@@ -1242,20 +1196,17 @@ class LaneTableSet(_Handle):
         self._h = handle
 
 
-def _scene_map_ptr(lane_set, B, what):
-    if lane_set.scene_map is None:
-        return None
-    if lane_set.scene_map.shape[0] != B:
+def _scene_map(lane_set, B, what):
+    """the set's scene map (None: table 0 everywhere), which must be for B scenes"""
+    if lane_set.scene_map is not None and lane_set.scene_map.shape[0] != B:
         raise RuntimeError(f'{what}: the lane-table set was made for {lane_set.scene_map.shape[0]} scenes, the batch has {B}')
-    return nat.dev_ptr(lane_set.scene_map, i32, 'scene_map')
+    return lane_set.scene_map
 
 
-def _scene_ids_ptr(scene_ids, B, what):
-    if scene_ids is None:
-        return None
-    if tuple(scene_ids.shape) != (B,):
+def _scene_ids(scene_ids, B, what):
+    if scene_ids is not None and tuple(scene_ids.shape) != (B,):
         raise RuntimeError(f'{what}: scene_ids must be ({B},), got {tuple(scene_ids.shape)}')
-    return nat.dev_ptr(scene_ids, torch.int64, 'scene_ids')
+    return scene_ids
 
 
 def _seed64(seed):
@@ -1272,13 +1223,10 @@ def wrong_way(lane_set, state, recenter_offset, present, direction_angle_thresho
     out = torch.empty((B, A), dtype=f32, device=state.device)
     if B * A == 0:
         return out
-    map_p = _scene_map_ptr(lane_set, B, 'wrong_way')
     off = None if recenter_offset is None else _c(recenter_offset.detach())
     pres = None if present is None else _u8(present)
-    nat.call('tds_wrong_way_f32', state.device, lane_set.handle, map_p, A, nat.dev_ptr(state, f32, 'state'),
-             None if off is None else nat.dev_ptr(off, f32, 'recenter_offset'), None if pres is None else nat.dev_ptr(pres, u8, 'present'),
-             nat.dev_ptr(out, f32, 'out'), B * A,
-             float(direction_angle_threshold), float(lanelet_dist_tolerance), nat.stream_ptr(state.device))
+    nat.call('tds_wrong_way_f32', state.device, lane_set.handle, _scene_map(lane_set, B, 'wrong_way'), A, state, off, pres, out, B * A,
+             float(direction_angle_threshold), float(lanelet_dist_tolerance))
     return out
 
 
@@ -1297,10 +1245,8 @@ def lanelet_directions(tables, scene_map, points, lanelet_dist_tolerance, max_di
     # the points are split evenly among the scenes the set was made for: the helper's size check is met by construction here
     scenes = None if lane_set.scene_map is None else lane_set.scene_map.shape[0]
     pps = 1 if scenes is None else max(1, n // max(1, scenes))
-    nat.call('tds_lanelet_directions_f64', dev, lane_set.handle, _scene_map_ptr(lane_set, scenes, 'lanelet_directions'), pps,
-             nat.dev_ptr(points, f64, 'points'), nat.dev_ptr(dirs, f64, 'dirs'), nat.dev_ptr(dists, f64, 'dists'),
-             nat.dev_ptr(count, i32, 'count'), nat.dev_ptr(status, u8, 'status'), max_dirs, n, float(lanelet_dist_tolerance),
-             nat.stream_ptr(dev))
+    nat.call('tds_lanelet_directions_f64', dev, lane_set.handle, _scene_map(lane_set, scenes, 'lanelet_directions'), pps, points, dirs, dists, count, status,
+             max_dirs, n, float(lanelet_dist_tolerance))
     return dirs, dists, count, status
 
 
@@ -1318,30 +1264,27 @@ def spawn_on_lanes(lane_set, scene_ids, attributes, seed, min_speed=0.0, max_spe
         raise RuntimeError(f'spawn_on_lanes: attributes must be (B,A,3), got {tuple(attributes.shape)}')
     dev = attributes.device
     B, A = attributes.shape[:2]
-    attr_p = nat.dev_ptr(attributes, f32, 'attributes')
-    map_p = _scene_map_ptr(lane_set, B, 'spawn_on_lanes')
-    if scene_ids is not None:
-        scene_ids = scene_ids.contiguous()
-    ids_p = _scene_ids_ptr(scene_ids, B, 'spawn_on_lanes')
-    M, occ_p, occ_sc_p, occ_mask_p = 0, None, None, None
+    nat.dev_ptr(attributes, f32, 'attributes')                 # (a CPU tensor is refused before the lane set is looked at)
+    scene_map = _scene_map(lane_set, B, 'spawn_on_lanes')
+    scene_ids = _scene_ids(None if scene_ids is None else scene_ids.contiguous(), B, 'spawn_on_lanes')
+    M = 0
     if occupied is not None:
         occupied, occupied_sc = _c(occupied), _c(occupied_sc)
         M = occupied.shape[1]
         if tuple(occupied.shape) != (B, M, 5) or tuple(occupied_sc.shape) != (B, M, 2):
             raise RuntimeError(f'spawn_on_lanes: occupied must be ({B},M,5) with occupied_sc ({B},M,2), got {tuple(occupied.shape)}, {tuple(occupied_sc.shape)}')
-        occ_p, occ_sc_p = nat.dev_ptr(occupied, f32, 'occupied'), nat.dev_ptr(occupied_sc, f32, 'occupied_sc')
         if occupied_mask is not None:
             occupied_mask = _u8(occupied_mask)
             if tuple(occupied_mask.shape) != (B, M):
                 raise RuntimeError(f'spawn_on_lanes: occupied_mask must be ({B},{M}), got {tuple(occupied_mask.shape)}')
-            occ_mask_p = nat.dev_ptr(occupied_mask, u8, 'occupied_mask')
+    else:
+        occupied_sc = occupied_mask = None                     # (read only beside `occupied`)
     state = torch.empty((B, A, 4), dtype=f32, device=dev)
     sc = torch.empty((B, A, 2), dtype=f32, device=dev)
     placed = torch.empty((B, A), dtype=torch.bool, device=dev)
     attempts = torch.empty((B, A), dtype=i32, device=dev)
-    nat.call('tds_spawn_on_lanes_f32', dev, lane_set.handle, map_p, ids_p, B, A, attr_p, occ_p, occ_sc_p, occ_mask_p, M, _seed64(seed),
-             float(min_speed), float(max_speed), float(gap[0]), float(gap[1]), int(max_attempts), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
-             ctypes.c_void_p(placed.data_ptr()), nat.dev_ptr(attempts, i32, 'attempts'), nat.stream_ptr(dev))
+    nat.call('tds_spawn_on_lanes_f32', dev, lane_set.handle, scene_map, scene_ids, B, A, attributes, occupied, occupied_sc, occupied_mask, M, _seed64(seed),
+             float(min_speed), float(max_speed), float(gap[0]), float(gap[1]), int(max_attempts), state, sc, _u8(placed), attempts)
     return state, sc, placed, attempts
 
 
@@ -1355,7 +1298,7 @@ def lane_snap(lane_set, xy, sc, tolerance=1.0, out=None):
     if xy.dim() != 3 or xy.shape[-1] != 2 or sc.shape != xy.shape:
         raise RuntimeError(f'lane_snap: xy and sc must be (B,N,2), got {tuple(xy.shape)}, {tuple(sc.shape)}')
     B, N = xy.shape[:2]
-    xy_p, sc_p = nat.dev_ptr(xy, f32, 'xy'), nat.dev_ptr(sc, f32, 'sc')
+    nat.dev_ptr(xy, f32, 'xy'), nat.dev_ptr(sc, f32, 'sc')       # (CPU tensors are refused before `out` is looked at)
     dev = xy.device
     if out is not None:
         lane, arc, lateral = out
@@ -1367,8 +1310,7 @@ def lane_snap(lane_set, xy, sc, tolerance=1.0, out=None):
         lateral = torch.empty((B, N), dtype=f32, device=dev)
     if B * N == 0:
         return lane, arc, lateral
-    nat.call('tds_lane_snap_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'lane_snap'), N, xy_p, sc_p, nat.dev_ptr(lane, i32, 'lane'),
-             nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(lateral, f32, 'lateral'), B * N, float(tolerance), nat.stream_ptr(dev))
+    nat.call('tds_lane_snap_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'lane_snap'), N, xy, sc, lane, arc, lateral, B * N, float(tolerance))
     return lane, arc, lateral
 
 
@@ -1408,20 +1350,12 @@ def lane_follow_step(lane_set, scene_ids, boxes, ent_sc, ent_speed, ent_present,
         if tuple(given[k].shape) != shp:
             raise RuntimeError(f'lane_follow_step: {k} must be {shp}, got {tuple(given[k].shape)}')
     dev = state.device
-    self_p = None
-    if self_index is not None:
-        if tuple(self_index.shape) != (B, N):
-            raise RuntimeError(f'lane_follow_step: self_index must be ({B},{N}), got {tuple(self_index.shape)}')
-        self_p = nat.dev_ptr(self_index, i32, 'self_index')
-    ids_p = _scene_ids_ptr(scene_ids, B, 'lane_follow_step')
+    if self_index is not None and tuple(self_index.shape) != (B, N):
+        raise RuntimeError(f'lane_follow_step: self_index must be ({B},{N}), got {tuple(self_index.shape)}')
     params = (ctypes.c_float * 5)(*[float(x) for x in idm])
-    nat.call('tds_lane_follow_step_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'lane_follow_step'), ids_p, B, N, E,
-             nat.dev_ptr(_c(boxes), f32, 'boxes'), nat.dev_ptr(_c(ent_sc), f32, 'ent_sc'), nat.dev_ptr(_c(ent_speed), f32, 'ent_speed'),
-             nat.dev_ptr(_u8(ent_present), u8, 'ent_present'), self_p, nat.dev_ptr(_c(npc_size), f32, 'npc_size'),
-             nat.dev_ptr(_c(desired_speed), f32, 'desired_speed'), nat.dev_ptr(_u8(npc_present), u8, 'npc_present'), nat.dev_ptr(lane, i32, 'lane'),
-             nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(hops, i32, 'hops'), nat.dev_ptr(state, f32, 'state'), nat.dev_ptr(sc, f32, 'sc'),
-             nat.dev_ptr(leader, i32, 'leader'), _seed64(seed), float(dt), float(horizon), float(lateral_margin),
-             ctypes.cast(params, ctypes.c_void_p), nat.stream_ptr(dev))
+    nat.call('tds_lane_follow_step_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'lane_follow_step'), _scene_ids(scene_ids, B, 'lane_follow_step'),
+             B, N, E, _c(boxes), _c(ent_sc), _c(ent_speed), _u8(ent_present), self_index, _c(npc_size), _c(desired_speed), _u8(npc_present), lane, arc, hops,
+             state, sc, leader, _seed64(seed), float(dt), float(horizon), float(lateral_margin), params)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1442,15 +1376,12 @@ def check_route_args(goal_tolerance, off_route_distance, lookahead, spacing):
         raise nat.TdsError('route_progress', nat.E_INVAL, f'{lookahead} lookahead points, at most {nat.ROUTE_MAX_LOOKAHEAD}')
 
 
-def _route_ptrs(what, route, B, A, names):
-    """device pointers of the named route tensors (dict name -> tensor), each a dense (B, A, ...) tensor of exactly the kernel's type"""
-    out = []
-    for name, tail, dtype in names:
-        t = route[name]
-        if tuple(t.shape) != (B, A) + tail:
-            raise RuntimeError(f'{what}: route tensor {name} must be {(B, A) + tail}, got {tuple(t.shape)}')
-        out.append(nat.dev_ptr(t, dtype, name))
-    return out
+def _route_tensors(what, route, B, A, names):
+    """the named route tensors (dict name -> tensor), each (B, A, ...); that they are dense and of exactly the kernel's type is checked by the call"""
+    for name, tail, _ in names:
+        if tuple(route[name].shape) != (B, A) + tail:
+            raise RuntimeError(f'{what}: route tensor {name} must be {(B, A) + tail}, got {tuple(route[name].shape)}')
+    return [route[name] for name, _, _ in names]
 
 
 def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, route):
@@ -1462,15 +1393,13 @@ def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, 
     for name, t in (('arc', arc), ('distance', distance)):
         if tuple(t.shape) != (B, A):
             raise RuntimeError(f'route_sample: {name} must be ({B},{A}), got {tuple(t.shape)}')
-    ids_p = _scene_ids_ptr(scene_ids, B, 'route_sample')
     masks = []
     for name, t in (('present', present), ('mask', mask)):
         if t is not None and tuple(t.shape) != (B, A):
             raise RuntimeError(f'route_sample: {name} must be ({B},{A}), got {tuple(t.shape)}')
-        masks.append(None if t is None else nat.dev_ptr(_u8(t), u8, name))
-    nat.call('tds_route_sample_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_sample'), ids_p, B, A, nat.dev_ptr(lane, i32, 'lane'),
-             nat.dev_ptr(arc, torch.float64, 'arc'), nat.dev_ptr(distance, torch.float64, 'distance'), masks[0], masks[1],
-             _seed64(seed), *_route_ptrs('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE), nat.stream_ptr(dev))
+        masks.append(None if t is None else _u8(t))
+    nat.call('tds_route_sample_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'route_sample'), _scene_ids(scene_ids, B, 'route_sample'), B, A, lane, arc,
+             distance, *masks, _seed64(seed), *_route_tensors('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE))
 
 
 def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing):
@@ -1496,10 +1425,9 @@ def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off
         raise RuntimeError(f'route_progress: present must be ({B},{A}), got {tuple(present.shape)}')
     outs = (('progress', (), f32), ('advance', (), f32), ('lateral', (), f32), ('heading', (2,), f32), ('remaining', (), f32), ('reached', (), u8),
             ('off_route', (), u8), ('lookahead', (K, 2), f32))
-    nat.call('tds_route_progress_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_progress'), B, A, nat.dev_ptr(state, f32, 'state'), S,
-             nat.dev_ptr(sc, f32, 'sc'), None if present is None else nat.dev_ptr(_u8(present), u8, 'present'),
-             *_route_ptrs('route_progress', route, B, A, ROUTE_TENSORS + ROUTE_STATE), float(goal_tolerance), float(off_route_distance), int(K),
-             float(spacing), *_route_ptrs('route_progress', out, B, A, outs), nat.stream_ptr(dev))
+    nat.call('tds_route_progress_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'route_progress'), B, A, state, S, sc,
+             None if present is None else _u8(present), *_route_tensors('route_progress', route, B, A, ROUTE_TENSORS + ROUTE_STATE), float(goal_tolerance),
+             float(off_route_distance), int(K), float(spacing), *_route_tensors('route_progress', out, B, A, outs))
 
 
 def route_points(lane_set, route, arcs):
@@ -1515,7 +1443,6 @@ def route_points(lane_set, route, arcs):
     pts = torch.empty((B, A, Q, 2), dtype=f32, device=dev)
     if B * A * Q == 0:
         return pts
-    nat.call('tds_route_points_multi', dev, lane_set.handle, _scene_map_ptr(lane_set, B, 'route_points'), B, A, Q,
-             *_route_ptrs('route_points', route, B, A, ROUTE_TENSORS), nat.dev_ptr(arcs, torch.float64, 'arcs'), nat.dev_ptr(pts, f32, 'points'),
-             nat.stream_ptr(dev))
+    nat.call('tds_route_points_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'route_points'), B, A, Q,
+             *_route_tensors('route_points', route, B, A, ROUTE_TENSORS), arcs, pts)
     return pts
