@@ -8,6 +8,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
     python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
+    python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
 """
 import argparse
 import os
@@ -36,7 +37,10 @@ def main():
     ap.add_argument('--scan-range', type=float, default=50.0)
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
+    ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
     args = ap.parse_args()
+    if args.route and args.route_to:
+        ap.error('--route and --route-to are two ways to deal the one route an agent has')
     dev = torch.device('cuda', 0)
     gold = os.path.join(ROOT, 'tests', 'golden')
     lanes = lanelet2.load_lanelet_map(os.path.join(gold, 'carla_Town01.osm.gz'), origin=(0.0, 0.0))
@@ -59,6 +63,16 @@ def main():
         # revert_map of the town, like the NPCs: the file stores its lanelets against the direction of travel.
         from torchdrivesim_amd.goals import RouteGoal
         sim.route_goals = RouteGoal.sample(lanelet2.revert_map(lanes), sim.get_state(), sim.get_present_mask(), seed=2, length=args.route)
+    if args.route_to:
+        # routes to a destination: the destinations are the poses of a second on-lane initialisation; agents and destinations are snapped to their
+        # lanes and every agent is dealt the shortest route between the two (the first call builds the map's distance table, once)
+        from torchdrivesim_amd.behavior import heuristic_initialize_batch
+        from torchdrivesim_amd.goals import RouteGoal
+        route_lanes = lanelet2.revert_map(lanes)
+        _, destination, found = heuristic_initialize_batch(route_lanes, args.batch, args.agents, seed=3, on_failure='mask', device=dev)
+        sim.route_goals = RouteGoal.to(route_lanes, sim.get_state(), destination[..., :3].contiguous(), present_mask=sim.get_present_mask() & found)
+    routed = bool(args.route) or args.route_to
+    replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller
     light_ids = [s.actor_id for s in cfg.stoplines if s.agent_type == 'traffic_light']
     res = Resolution(args.res, args.res)
@@ -82,10 +96,16 @@ def main():
             obs = torch.stack([scan.agents, scan.road], dim=-1) / args.scan_range        # (B, A, R, 2) in [0, 1]: distance to the nearest other agent, to the road edge
         else:
             obs = sim.render_egocentric(res=res, fov=35.0)                   # (B, A, 3, H, W): what a policy would consume
-        if args.route:
+        if routed:
             route = sim.compute_route_progress()                           # what sim.step has just computed: the dense term of a reward ...
             advanced += route.advance.sum()
-            goal_obs = route.lookahead / args.route                         # ... and (B, A, 16, 2): where the route goes, in the agent's frame
+            goal_obs = route.lookahead / (args.route or 64.0)               # ... and (B, A, 16, 2): where the route goes, in the agent's frame
+        if args.route_to:
+            # plan again, on the device and without a synchronisation, for the agents that have left their route and for those at the end of a
+            # route that was cut at 16 lanelets; everybody else keeps route and progress
+            again = route.off_route | (sim.route_goals.completed & sim.route_goals.truncated)
+            replanned += again.sum()
+            sim.route_goals.resample_to(sim.get_state(), mask=again, present_mask=sim.get_present_mask())
         totals['collision'] += (sim.compute_collision() > 0).float().mean()
         totals['offroad'] += (sim.compute_offroad() > 0).float().mean()
         totals['wrong_way'] += (sim.compute_wrong_way() > 0).float().mean()
@@ -103,6 +123,12 @@ def main():
         print(f'routes of {args.route:g} m: {float(r.valid.float().mean()):.3f} of the agents have one (mean {float(r.length.sum() / r.valid.sum().clamp(min=1)):.1f} m over '
               f'{float(r.n.sum() / r.valid.sum().clamp(min=1)):.1f} lanelets), lookahead {tuple(goal_obs.shape)}; advanced {float(advanced) / max(1, int(r.valid.sum())):.2f} m '
               f'per agent in {args.steps} steps, {float(r.completed.float().mean()):.3f} arrived, {float(route.off_route.float().mean()):.3f} off their route now')
+    if args.route_to:
+        r = sim.route_goals
+        print(f'routes to a destination: {float(r.valid.float().mean()):.3f} of the agents have one (mean {float(r.length.sum() / r.valid.sum().clamp(min=1)):.1f} m over '
+              f'{float(r.n.sum() / r.valid.sum().clamp(min=1)):.1f} lanelets, {float(r.truncated.float().mean()):.3f} cut at 16 lanelets), lookahead '
+              f'{tuple(goal_obs.shape)}; advanced {float(advanced) / max(1, int(r.valid.sum())):.2f} m per agent in {args.steps} steps, {int(replanned)} routes '
+              f'planned again, {float(r.completed.float().mean()):.3f} arrived')
     print('fraction of agents per step: ' + ', '.join(f'{k} {float(v) / args.steps:.3f}' for k, v in totals.items()))
 
 

@@ -560,6 +560,38 @@ int tds_route_points_multi(const tds_laneset_t *set, const int32_t *scene_map, i
                            const int32_t *route_n, const double *start_arc, const double *end_arc, const double *offsets,
                            const double *length, const double *q, float *points, void *stream);
 
+/* Routes to a destination: shortest paths on the lane graph (float64 model: tests/route_to_model.py).  Float64, + and
+ * compares only.  A lanelet is USABLE if it is eligible in the sense of tds_spawn_on_lanes_f32 and carries no excluded tag; len(l) is its
+ * cumulative 3-D length, the last `cum` of its centre line.
+ *
+ * tds_lane_distances_f64 fills to_go, L x L float64 owned by the caller (L = the table's lanelets): to_go[t][l] is the distance from the
+ * START of lanelet l to the START of lanelet t along usable lanelets: to_go[t][t] = 0, otherwise to_go[t][l] = len(l) + min over the usable
+ * successors s of l of to_go[t][s], +inf where t cannot be reached; the row and the column of a lanelet that is not usable are +inf
+ * throughout, its diagonal entry included.  This is the least fixed point of a monotone operator, so it does not depend on the order of
+ * relaxation.  One launch, a workgroup per destination, at most L sweeps each.  L > TDS_ROUTE_MAX_GRAPH is TDS_ELIMIT, a table without a
+ * successor graph TDS_EINVAL.
+ *
+ * tds_route_to_multi deals every row (B x A) the shortest route from (lane, arc) to (dest_lane, dest_arc), into the route tensors and the
+ * state of tds_route_sample_multi plus rest (B x A float64).  tables: per lane table of the set the address of its to_go (int64, 0 = none).
+ * With l0 = lane, t = dest_lane, a0 = arc clamped to [0, len(l0)], b = dest_arc clamped to [0, len(t)] (a value that is not > 0 is 0):
+ *   no route (n = 0, rest = +inf): an absent row (present == 0), l0 or t not usable, a scene without a lane table or whose table has no to_go;
+ *   t == l0 and b >= a0: one piece, start_arc = a0, end_arc = b, rest = 0;
+ *   otherwise piece 0 runs from a0 to the end of l0, and for j = 0 .. 15, at the end of piece j on lanelet l: next = the usable successor s
+ *   of l with the smallest to_go[t][s], the first in succ_items order on ties (a destination behind the agent on its own lanelet is reached
+ *   round the graph this way); no successor with a finite value: no route, rest = +inf; next == t and b == 0: the route ends here, rest = 0;
+ *   j == 15: the route ends here, TRUNCATED, rest = to_go[t][next] + b; next == t: piece j + 1 = t with end_arc = b, rest = 0; else l = next.
+ * offsets and length are summed front to back as in sampling (length is not a table entry bit for bit); a route whose length is not > 0
+ * is no route (n = 0; rest keeps its 0: the agent stands at its destination).  Every dealt row also gets cursor = 0, stored = 0,
+ * completed = 0; rows with mask == 0 are left untouched (mask NULL: every row).  One launch, a thread per row; nothing is allocated, nothing
+ * synchronises, every loop is bounded.  Not covered: lane changes (edges to adjacent lanes), more than TDS_ROUTE_MAX_LANES lanelets in one
+ * stored route (continue from its end), costs other than length. */
+#define TDS_ROUTE_MAX_GRAPH 2048
+int tds_lane_distances_f64(const tds_lanes_t *lanes, double *to_go, void *stream);
+int tds_route_to_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *tables, int64_t B, int64_t A, const int32_t *lane,
+                       const double *arc, const int32_t *dest_lane, const double *dest_arc, const uint8_t *present, const uint8_t *mask,
+                       int32_t *route_lanes, int32_t *route_n, double *start_arc, double *end_arc, double *offsets, double *length,
+                       int32_t *cursor, double *stored, uint8_t *completed, double *rest, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * K5  range scans (no reference counterpart: the definition is this library's own, DESIGN.md "K5"; float64 model: tests/range_scan_model.py)
  * R rays per exposed agent, from its centre, ray k of agent a along the unit vector [cos, sin] = ray_sc[b, a, k, (1, 0)] -- the caller computes

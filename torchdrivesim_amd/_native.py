@@ -157,6 +157,9 @@ tds_route_progress_multi(handle set, i32* scene_map, int64 B, int64 A, f32* xy, 
     f32* progress, f32* advance, f32* lateral, f32* heading, f32* remaining, u8* reached, u8* off_route, f32* lookahead, stream stream)
 tds_route_points_multi(handle set, i32* scene_map, int64 B, int64 A, int64 Q, i32* route_lanes, i32* route_n, f64* start_arc, f64* end_arc, f64* offsets, f64* length, f64* q,
     f32* points, stream stream)
+tds_lane_distances_f64(handle lanes, f64* to_go, stream stream)
+tds_route_to_multi(handle set, i32* scene_map, i64* tables, int64 B, int64 A, i32* lane, f64* arc, i32* dest_lane, f64* dest_arc, u8* present, u8* mask, i32* route_lanes,
+    i32* route_n, f64* start_arc, f64* end_arc, f64* offsets, f64* length, i32* cursor, f64* stored, u8* completed, f64* rest, stream stream)
 tds_range_scan_f32(handle map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E, int R, float max_range,
     float gap_tolerance, stream stream)
 tds_range_scan_multi_f32(handle set, i32* scene_map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E,
@@ -261,6 +264,7 @@ BUFFER_DENSE = 1
 SPAWN_MAX_BOXES = 2048           # TDS_SPAWN_MAX_BOXES
 FOLLOW_MAX_HOPS, FOLLOW_MAX_ENTITIES = 8, 1024       # TDS_FOLLOW_MAX_HOPS, TDS_FOLLOW_MAX_ENTITIES
 ROUTE_MAX_LANES, ROUTE_MAX_LOOKAHEAD = 16, 32        # TDS_ROUTE_MAX_LANES, TDS_ROUTE_MAX_LOOKAHEAD
+ROUTE_MAX_GRAPH = 2048                               # TDS_ROUTE_MAX_GRAPH
 
 
 class TdsError(RuntimeError):

@@ -1159,6 +1159,7 @@ class LaneTableHandle(_Handle):
             raise RuntimeError('lane tables live on an MI355X; there is no CPU implementation')
         self.max_tolerance = float(max_tolerance)
         self.n_lanelets = int(len(table.flags))
+        self._to_go = None                           # the distance table of routes to a destination: built by `lane_distances` when first asked for
         poly = np.ascontiguousarray(table.poly_xy, np.float64)
         cl = np.ascontiguousarray(table.cl_xyz, np.float64)
         ps, cs = np.ascontiguousarray(table.poly_start, np.int32), np.ascontiguousarray(table.cl_start, np.int32)
@@ -1194,6 +1195,30 @@ class LaneTableSet(_Handle):
         handle = ctypes.c_void_p()
         nat.call('tds_laneset_create', self.device, arr, len(self.tables), ctypes.byref(handle))
         self._h = handle
+        self._distance_tables = None
+
+    def distance_tables(self):
+        """(n tables,) int64 on the device: the address of every table's `lane_distances`, what tds_route_to_multi reads them through.  Built
+        the first time a route to a destination is asked for (allocations and one launch per table not seen before: outside any capture);
+        the tensors themselves live on the table objects, which this set keeps alive."""
+        if self._distance_tables is None:
+            self._distance_tables = torch.tensor([lane_distances(t).data_ptr() for t in self.tables], dtype=torch.int64, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()            # once: whatever stream deals routes later finds the tables complete
+        return self._distance_tables
+
+
+def lane_distances(table):
+    """tds_lane_distances_f64: the (L, L) float64 table of a `LaneTableHandle`, to_go[t][l] = distance from the start of lanelet l to the start
+    of lanelet t on the lane graph (+inf: cannot be reached).  Built once per table and kept on it."""
+    to_go = table._to_go
+    if to_go is None:
+        L = table.n_lanelets
+        if L > nat.ROUTE_MAX_GRAPH:
+            raise nat.TdsError('lane_distances', nat.E_LIMIT, f'{L} lanelets exceed the {nat.ROUTE_MAX_GRAPH} a destination\'s distance field holds in LDS')
+        to_go = torch.empty((L, L), dtype=torch.float64, device=table.device)
+        nat.call('tds_lane_distances_f64', table.device, table.handle, to_go)
+        table._to_go = to_go
+    return to_go
 
 
 def _scene_map(lane_set, B, what):
@@ -1400,6 +1425,23 @@ def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, 
         masks.append(None if t is None else _u8(t))
     nat.call('tds_route_sample_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'route_sample'), _scene_ids(scene_ids, B, 'route_sample'), B, A, lane, arc,
              distance, *masks, _seed64(seed), *_route_tensors('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE))
+
+
+def route_to(lane_set, lane, arc, dest_lane, dest_arc, present, mask, route):
+    """tds_route_to_multi (include/tdship.h): lane, dest_lane (B,A) int32, arc, dest_arc (B,A) float64, present / mask (B,A) bool or None; `route`
+    (dict of the ROUTE_TENSORS, ROUTE_STATE and `rest` (B,A) float64) is written IN PLACE for the rows of `mask`.  One launch, no allocation
+    besides the uint8 views of bool masks, no synchronisation -- once the set's distance tables exist (`LaneTableSet.distance_tables`)."""
+    B, A = lane.shape
+    for name, t in (('arc', arc), ('dest_lane', dest_lane), ('dest_arc', dest_arc)):
+        if tuple(t.shape) != (B, A):
+            raise RuntimeError(f'route_to: {name} must be ({B},{A}), got {tuple(t.shape)}')
+    masks = []
+    for name, t in (('present', present), ('mask', mask)):
+        if t is not None and tuple(t.shape) != (B, A):
+            raise RuntimeError(f'route_to: {name} must be ({B},{A}), got {tuple(t.shape)}')
+        masks.append(None if t is None else _u8(t))
+    nat.call('tds_route_to_multi', lane.device, lane_set.handle, _scene_map(lane_set, B, 'route_to'), lane_set.distance_tables(), B, A, lane, arc, dest_lane,
+             dest_arc, *masks, *_route_tensors('route_to', route, B, A, ROUTE_TENSORS + ROUTE_STATE + (('rest', (), torch.float64),)))
 
 
 def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing):

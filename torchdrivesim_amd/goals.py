@@ -6,7 +6,8 @@ collections are drawn by the K3 rasteriser as per-camera discs (`Simulator.rende
 
 Route goals (`RouteGoal`, no reference counterpart; DESIGN.md 5.5d, csrc/route.hip): every agent is dealt a route of a requested length on the
 lane graph; each step ONE launch reports its progress along it, its offsets from it, whether it has arrived or left it, and the next K route
-points in its own frame.  Yardstick: the float64 model tests/route_model.py.
+points in its own frame.  Yardstick: the float64 model tests/route_model.py.  `RouteGoal.to` deals the shortest route to a destination instead
+of a random one (csrc/route_to.hip; model: tests/route_to_model.py).
 """
 from typing import NamedTuple, Optional, Union
 
@@ -93,11 +94,22 @@ class RouteProgress(NamedTuple):
 _ROUTE_OUT = (('progress', ()), ('advance', ()), ('lateral', ()), ('heading', (2,)), ('remaining', ()), ('reached', ()), ('off_route', ()))
 
 
+class _ClassOrInstance:
+    """`RouteGoal.to(...)` on the class deals routes to destinations; `goal.to(device)` on an object moves it, as on every goal object"""
+
+    def __init__(self, on_class, on_instance):
+        self.on_class, self.on_instance = on_class, on_instance
+        self.__doc__ = on_class.__doc__
+
+    def __get__(self, obj, cls):
+        return self.on_class.__get__(None, cls) if obj is None else self.on_instance.__get__(obj, cls)
+
+
 class RouteGoal:
     """
     Routes on the lane graph, one per agent, and the per-step bookkeeping of them on the device (include/tdship.h "Route goals").
-    Make one with `RouteGoal.sample`.  Per agent it exposes `lanes` (B, A, 16) int32 (indices into `laneletLayer`, -1 unused), `n` (B, A) int32,
-    `start_arc`, `end_arc`, `offsets` (B, A, 16), `length` (float64), `cursor` (int32), `completed` and `valid` (bool).  A row depends on
+    Make one with `RouteGoal.sample` (a random route of a requested length) or `RouteGoal.to` (the shortest route to a destination).  Per agent it
+    exposes `lanes` (B, A, 16) int32 (indices into `laneletLayer`, -1 unused), `n` (B, A) int32, `start_arc`, `end_arc`, `offsets` (B, A, 16), `length` (float64), `cursor` (int32), `completed` and `valid` (bool).  A row depends on
     `(seed, scene id, agent index)` and its own pose only, so shards and sub-batches reproduce the whole batch.
     """
 
@@ -135,22 +147,59 @@ class RouteGoal:
         dev = agent_state.device
         K = int(lookahead)
         _ops.check_route_args(goal_tolerance, off_route_distance, K, spacing)
-        f32, f64, i32, u8 = torch.float32, torch.float64, torch.int32, torch.uint8
-        t = {name: torch.zeros((B, A) + tail, dtype=dtype, device=dev) for name, tail, dtype in _ops.ROUTE_TENSORS + _ops.ROUTE_STATE}
-        t.update({name: torch.zeros((B, A) + tail, dtype=u8 if name in ('reached', 'off_route') else f32, device=dev) for name, tail in _ROUTE_OUT})
-        t['lookahead'] = torch.zeros((B, A, K, 2), dtype=f32, device=dev)
+        f64 = torch.float64
+        t = cls._buffers(B, A, K, dev)
         t['scene_ids'] = torch.arange(B, dtype=torch.int64, device=dev) if scene_ids is None else scene_ids.to(torch.int64).clone()
         if isinstance(length, Tensor):
             t['distance'] = length.to(f64).expand(B, A).clone()
         else:
             t['distance'] = torch.full((B, A), float(length), dtype=f64, device=dev)
-        # what a snap reads and writes: kept, so that `resample` allocates nothing
-        t.update(snap_xy=torch.zeros((B, A, 2), dtype=f32, device=dev), sc=torch.zeros((B, A, 2), dtype=f32, device=dev),
-                 snap_lane=torch.zeros((B, A), dtype=i32, device=dev), snap_arc=torch.zeros((B, A), dtype=f64, device=dev),
-                 snap_lateral=torch.zeros((B, A), dtype=f32, device=dev))
         me = cls(lanelet_maps, t, seed=seed, tolerance=tolerance, goal_tolerance=goal_tolerance, off_route_distance=off_route_distance, lookahead=K,
                  spacing=spacing)
         me._sample(agent_state, present_mask, None)
+        return me
+
+    @staticmethod
+    def _buffers(B, A, K, dev) -> dict:
+        """what every route goal holds: the route tensors, their state, the outputs of a step and what a snap reads and writes (kept, so that
+        dealing new routes allocates nothing)"""
+        from torchdrivesim_amd import _ops
+        f32, f64, i32, u8 = torch.float32, torch.float64, torch.int32, torch.uint8
+        t = {name: torch.zeros((B, A) + tail, dtype=dtype, device=dev) for name, tail, dtype in _ops.ROUTE_TENSORS + _ops.ROUTE_STATE}
+        t.update({name: torch.zeros((B, A) + tail, dtype=u8 if name in ('reached', 'off_route') else f32, device=dev) for name, tail in _ROUTE_OUT})
+        t['lookahead'] = torch.zeros((B, A, K, 2), dtype=f32, device=dev)
+        t.update(snap_xy=torch.zeros((B, A, 2), dtype=f32, device=dev), sc=torch.zeros((B, A, 2), dtype=f32, device=dev),
+                 snap_lane=torch.zeros((B, A), dtype=i32, device=dev), snap_arc=torch.zeros((B, A), dtype=f64, device=dev),
+                 snap_lateral=torch.zeros((B, A), dtype=f32, device=dev))
+        return t
+
+    @classmethod
+    def _to_destination(cls, lanelet_maps, agent_state: Tensor, destination: Optional[Tensor] = None, *, destination_lanes: Optional[Tensor] = None,
+                        destination_arcs: Optional[Tensor] = None, present_mask: Optional[Tensor] = None, tolerance: float = 1.0,
+                        goal_tolerance: float = 2.0, off_route_distance: float = 4.0, lookahead: int = 16, spacing: float = 4.0) -> 'RouteGoal':
+        """
+        RouteGoal.to(lanelet_maps, agent_state, destination): the SHORTEST route on the lane graph from every agent to its destination.
+        lanelet_maps, agent_state, tolerance and the step's parameters: as for `sample`.  The destination is given in exactly one of two forms:
+        `destination` (B, A, 3) poses [x, y, psi], snapped to a lane like the agents (`snap_to_lanes` with `tolerance`), or `destination_lanes`
+        (B, A) int lanelet indices with `destination_arcs` (B, A) arc lengths on them.  Agents and destinations that find no lane, absent agents and
+        destinations that cannot be reached get no route (`valid` False, `rest` inf).  A route holds at most 16 lanelets: one that would need
+        more ends at the end of its 16th (`truncated`; `rest` = what is left from there) and is continued with
+        `resample_to(state, mask=goal.completed & goal.truncated)`.  The first call with a map builds its distance tables (L x L float64, one
+        launch): outside any stream capture.  No lane changes, no cost but length, no gradients.
+        """
+        from torchdrivesim_amd import _ops
+        if not agent_state.is_cuda:
+            raise RuntimeError(f'agent_state: route goals run on an MI355X; got a {agent_state.device} tensor (no CPU fallback)')
+        if agent_state.dim() != 3 or agent_state.shape[-1] < 3:
+            raise ValueError(f'agent_state must be (B, A, >= 3), got {tuple(agent_state.shape)}')
+        B, A = agent_state.shape[:2]
+        K = int(lookahead)
+        _ops.check_route_args(goal_tolerance, off_route_distance, K, spacing)
+        if destination is None and destination_lanes is None:
+            raise ValueError('RouteGoal.to needs `destination` poses or `destination_lanes` and `destination_arcs`')
+        me = cls(lanelet_maps, cls._buffers(B, A, K, agent_state.device), seed=0, tolerance=tolerance, goal_tolerance=goal_tolerance,
+                 off_route_distance=off_route_distance, lookahead=K, spacing=spacing)
+        me.resample_to(agent_state, destination, present_mask=present_mask, destination_lanes=destination_lanes, destination_arcs=destination_arcs)
         return me
 
     def _lane_table_set(self):
@@ -161,16 +210,18 @@ class RouteGoal:
             self._lanes = lane_set_for(self.lanelet_maps, n.shape[0], n.device)
         return self._lanes
 
-    def _heading(self, agent_state: Tensor) -> Tensor:
+    def _heading(self, agent_state: Tensor, into: str = 'sc') -> Tensor:
         """[sin, cos] of the headings with torch, into the buffer this object keeps for them"""
         psi = agent_state[..., 2].detach()
-        torch.sin(psi, out=self._t['sc'][..., 0])
-        torch.cos(psi, out=self._t['sc'][..., 1])
-        return self._t['sc']
+        torch.sin(psi, out=self._t[into][..., 0])
+        torch.cos(psi, out=self._t[into][..., 1])
+        return self._t[into]
 
     def _sample(self, agent_state, present_mask, mask) -> None:
         from torchdrivesim_amd import _ops
         t = self._t
+        if 'distance' not in t:
+            raise RuntimeError('this RouteGoal was made by RouteGoal.to: it has no requested lengths to sample routes of (use resample_to)')
         B, A = t['n'].shape
         if tuple(agent_state.shape[:2]) != (B, A):
             raise ValueError(f'agent_state must be ({B}, {A}, >= 3), got {tuple(agent_state.shape)}')
@@ -191,6 +242,68 @@ class RouteGoal:
         if scene_ids is not None:
             self._t['scene_ids'].copy_(scene_ids)
         self._sample(agent_state, present_mask, mask)
+
+    def _set_destinations(self, destination, lanes, arcs, mask) -> None:
+        """the stored destinations of all rows, or of the rows of `mask`, from poses or from (lane, arc); without either they must exist"""
+        t = self._t
+        B, A = t['n'].shape
+        if (destination is not None) == (lanes is not None) or (lanes is None) != (arcs is None):
+            if destination is None and lanes is None and arcs is None:
+                if 'dest_lane' not in t:
+                    raise RuntimeError('this RouteGoal has no stored destinations (it was made by RouteGoal.sample): give `destination` or '
+                                       '`destination_lanes` and `destination_arcs`')
+                return
+            raise ValueError('give either `destination` poses or both `destination_lanes` and `destination_arcs`')
+        for name, x in (('destination', destination), ('destination_lanes', lanes), ('destination_arcs', arcs), ('mask', mask)):
+            if x is not None and not x.is_cuda:
+                raise RuntimeError(f'{name}: route goals run on an MI355X; got a {x.device} tensor (no CPU fallback)')
+        if 'dest_lane' not in t:                                             # the first destinations of this object: its buffers for them
+            dev, f32 = t['n'].device, torch.float32
+            t.update(dest_lane=torch.full((B, A), -1, dtype=torch.int32, device=dev), dest_arc=torch.zeros((B, A), dtype=torch.float64, device=dev),
+                     rest=torch.full((B, A), float('inf'), dtype=torch.float64, device=dev), dest_xy=torch.zeros((B, A, 2), dtype=f32, device=dev),
+                     dest_sc=torch.zeros((B, A, 2), dtype=f32, device=dev))
+        if destination is not None:
+            from torchdrivesim_amd import _ops
+            if destination.dim() != 3 or tuple(destination.shape[:2]) != (B, A) or destination.shape[-1] < 3:
+                raise ValueError(f'destination must be ({B}, {A}, >= 3), got {tuple(destination.shape)}')
+            if B * A == 0:
+                return
+            t['dest_xy'].copy_(destination[..., :2])
+            _ops.lane_snap(self._lane_table_set(), t['dest_xy'], self._heading(destination, 'dest_sc'), self.tolerance,
+                           out=(t['snap_lane'], t['snap_arc'], t['snap_lateral']))      # (the agents' snap, which follows, overwrites these)
+            lanes, arcs = t['snap_lane'], t['snap_arc']
+        elif tuple(lanes.shape) != (B, A) or tuple(arcs.shape) != (B, A):
+            raise ValueError(f'destination_lanes and destination_arcs must be ({B}, {A}), got {tuple(lanes.shape)}, {tuple(arcs.shape)}')
+        if mask is None:
+            t['dest_lane'].copy_(lanes), t['dest_arc'].copy_(arcs)
+        else:                                                               # rows outside the mask keep the destination their route leads to
+            torch.where(mask, lanes.to(torch.int32), t['dest_lane'], out=t['dest_lane'])
+            torch.where(mask, arcs.to(torch.float64), t['dest_arc'], out=t['dest_arc'])
+
+    def resample_to(self, agent_state: Tensor, destination: Optional[Tensor] = None, mask: Optional[Tensor] = None, present_mask: Optional[Tensor] = None, *,
+                    destination_lanes: Optional[Tensor] = None, destination_arcs: Optional[Tensor] = None) -> None:
+        """Shortest routes IN PLACE from where the agents are now to the stored destinations, or to new ones (`destination` poses, or
+        `destination_lanes` with `destination_arcs`, as for `RouteGoal.to`) -- all rows, or the rows of `mask` (B, A) bool; the others keep route,
+        destination, `rest`, cursor and `completed`.  `mask=goal.completed & goal.truncated` continues routes that were cut at 16 lanelets,
+        `mask=progress.off_route` plans again for agents that have left theirs.  With the stored destinations, or with new ones in tensors of this
+        object's types (int32 / float64), nothing is allocated and nothing synchronises."""
+        from torchdrivesim_amd import _ops
+        if not agent_state.is_cuda:
+            raise RuntimeError(f'agent_state: route goals run on an MI355X; got a {agent_state.device} tensor (no CPU fallback)')
+        t = self._t
+        B, A = t['n'].shape
+        if agent_state.dim() != 3 or tuple(agent_state.shape[:2]) != (B, A) or agent_state.shape[-1] < 3:
+            raise ValueError(f'agent_state must be ({B}, {A}, >= 3), got {tuple(agent_state.shape)}')
+        if mask is not None and tuple(mask.shape) != (B, A):
+            raise ValueError(f'mask must be ({B}, {A}), got {tuple(mask.shape)}')
+        with torch.no_grad():
+            self._set_destinations(destination, destination_lanes, destination_arcs, mask)
+            if B * A == 0:
+                return
+            t['snap_xy'].copy_(agent_state[..., :2])
+            _ops.lane_snap(self._lane_table_set(), t['snap_xy'], self._heading(agent_state), self.tolerance,
+                           out=(t['snap_lane'], t['snap_arc'], t['snap_lateral']))
+            _ops.route_to(self._lane_table_set(), t['snap_lane'], t['snap_arc'], t['dest_lane'], t['dest_arc'], present_mask, mask, t)
 
     # ---- the step -----------------------------------------------------------------------------------------------------------------
     def step(self, agent_state: Tensor, present_mask: Optional[Tensor] = None, sc: Optional[Tensor] = None) -> RouteProgress:
@@ -229,6 +342,21 @@ class RouteGoal:
     cursor = property(lambda self: self._t['cursor'])
     scene_ids = property(lambda self: self._t['scene_ids'])
     requested_length = property(lambda self: self._t['distance'])
+    # of routes to a destination (`RouteGoal.to`, `resample_to`); objects that never had destinations do not have them
+    destination_lanes = property(lambda self: self._t['dest_lane'])
+    destination_arcs = property(lambda self: self._t['dest_arc'])
+
+    @property
+    def rest(self) -> Tensor:
+        """(B, A) float64: what is left to the destination from the END of the route: 0 for a route that reaches it, positive for one cut at 16
+        lanelets, inf where the destination cannot be reached or the row has no route to one"""
+        return self._t['rest']
+
+    @property
+    def truncated(self) -> Tensor:
+        """(B, A) bool: the route was cut at 16 lanelets short of its destination (`rest` > 0 and finite)"""
+        rest = self._t['rest']
+        return (rest > 0) & torch.isfinite(rest)
 
     @property
     def completed(self) -> Tensor:
@@ -277,8 +405,10 @@ class RouteGoal:
                               goal_tolerance=self.goal_tolerance, off_route_distance=self.off_route_distance, lookahead=self.lookahead,
                               spacing=self.spacing)
 
-    def to(self, device):
+    def _to_device(self, device):
         return self._map(lambda x: x.to(device))
+
+    to = _ClassOrInstance(_to_destination, _to_device)
 
     def extend(self, n: int, in_place: bool = True):
         from torchdrivesim_amd.lanelet2 import LaneletMap
