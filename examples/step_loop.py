@@ -9,6 +9,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
     python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
     python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
+    python examples/step_loop.py --route-grad       # a few steps of gradient descent on the actions through the simulator, with a route loss
 """
 import argparse
 import os
@@ -27,6 +28,31 @@ from torchdrivesim_amd.traffic_lights import current_light_state_tensor_from_con
 from torchdrivesim_amd.utils import Resolution  # noqa: E402
 
 
+def route_grad_loop(args, sim, lanes, dev):
+    """--route-grad: "get somewhere" by backpropagation.  Every agent is dealt a route with differentiable=True; each step the actions are applied,
+    the route loss of the state they lead to is differentiated to them through the kinematic step (one backward launch for the route step, one for
+    the kinematics), and they take a gradient step.  No policy, no images: the loop only shows the task term of a loss reaching the actions."""
+    from torchdrivesim_amd.goals import RouteGoal
+    sim.route_goals = RouteGoal.sample(lanelet2.revert_map(lanes), sim.get_state(), sim.get_present_mask(), seed=2, length=args.route or 200.0,
+                                       differentiable=True)
+    valid = sim.route_goals.valid
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    steps = min(args.steps, 20)
+    for it in range(steps):
+        sim.kinematic_model.set_state(sim.get_state().detach())             # each step differentiates through itself alone
+        sim.step(action)
+        route = sim.compute_route_progress()                               # float fields with the graph; the flags are plain buffers
+        # advance differentiates as progress (the stored progress is a constant); stay on the route's line and along it
+        loss = -route.advance.sum() + 0.1 * (route.lateral ** 2).sum() + (route.heading[..., 0] ** 2).sum()
+        grad, = torch.autograd.grad(loss, action)
+        with torch.no_grad():
+            action.sub_(0.5 * grad).clamp_(-1.0, 1.0)
+        if it in (0, steps - 1):
+            n = valid.sum().clamp(min=1)
+            print(f'step {it}: advance {float(route.advance.detach().sum() / n):.3f} m, |lateral| {float(route.lateral.detach().abs().sum() / n):.3f} m per routed agent, '
+                  f'|d loss / d action| {float(grad.abs().mean()):.4f}, mean acceleration command {float(action[..., 0].mean()):+.3f}')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -38,6 +64,7 @@ def main():
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
+    ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
     args = ap.parse_args()
     if args.route and args.route_to:
         ap.error('--route and --route-to are two ways to deal the one route an agent has')
@@ -71,6 +98,8 @@ def main():
         route_lanes = lanelet2.revert_map(lanes)
         _, destination, found = heuristic_initialize_batch(route_lanes, args.batch, args.agents, seed=3, on_failure='mask', device=dev)
         sim.route_goals = RouteGoal.to(route_lanes, sim.get_state(), destination[..., :3].contiguous(), present_mask=sim.get_present_mask() & found)
+    if args.route_grad:
+        return route_grad_loop(args, sim, lanes, dev)
     routed = bool(args.route) or args.route_to
     replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller

@@ -560,6 +560,42 @@ int tds_route_points_multi(const tds_laneset_t *set, const int32_t *scene_map, i
                            const int32_t *route_n, const double *start_arc, const double *end_arc, const double *offsets,
                            const double *length, const double *q, float *points, void *stream);
 
+/* Differentiable route progress (float64 torch-autograd model: tests/route_grad_model.py): the gradients of progress, advance,
+ * remaining, lateral, heading and lookahead of tds_route_progress_multi to the pose, [x, y] and [s, c] = [sin psi, cos psi] (psi gets its
+ * gradient through the caller's sin / cos, as everywhere in this header).  The discrete choices of the forward are constants of
+ * differentiation: the piece, the segment, which clamp is active, and the lookahead's pieces and segments.
+ *
+ * The foot.  In the winning segment i of piece j, with d = P_(i+1) - P_i, l2 = d.d, w = w_i, ulo, uhi as above: u_raw = ((x - P_i.x) d.x +
+ * (y - P_i.y) d.y) / l2; u moves with the pose iff ulo <= u_raw <= uhi (equality counts as interior, the rule of torch.clamp); then
+ * D = d progress / d[x, y] = (w d) / l2, otherwise D = 0.  With t = d / sqrt(l2) and the incoming gradients g_*:
+ *   gp    = (g_progress + g_advance) - g_remaining      advance differentiates as progress (the stored progress of the previous step is a
+ *                                                       constant), remaining as its negative
+ *   g_xy  = gp D + g_lateral [-t.y, t.x]                lateral is measured against the segment's LINE: this holds clamped or not
+ *   g_sc  = [g_heading.s t.x + g_heading.c t.y, g_heading.c t.x - g_heading.s t.y]
+ * Lookahead point m, with q = progress + (m + 1) * spacing, (px, py) the point at q, inside segment k of its piece with e = P_(k+1) - P_k, and
+ * (gox, goy) its incoming gradient: q moves with progress iff 0 < q <= length (the complement of the two clamps of the point at a route arc);
+ * then Q = d[px, py] / dq = e / w_k (0 where w_k is not > 0), otherwise Q = 0.  With (ex, ey) = (px - x, py - y):
+ *   gq    = gox (Q.x c + Q.y s) + goy (Q.y c - Q.x s)
+ *   g_xy += [(goy s - gox c) + gq D.x, gq D.y - (gox s + goy c)];   g_sc += [gox ey - goy ex, gox ex + goy ey]
+ * Float64, + - * / and the forward's sqrt of l2 only; the foot's terms and the n_lookahead points' are summed in a fixed order (a result is the
+ * same bits from run to run) and each of the four outputs of a row is rounded to binary32 once.  Exact zeros: rows without a foot (a pose no
+ * segment can be weighed against: NaN), absent rows, rows with n = 0, scenes without a table.  No gradients to the route tensors, no double
+ * backward.
+ *   piece         B x A int32: the cursor as tds_route_progress_multi LEFT it for these poses.  No segment is saved: piece `piece` (clamped to
+ *                 [0, n - 1]) alone is searched, with the forward's candidates and tie rule, which finds the forward's foot again -- it lay in
+ *                 that piece, and a row that found nothing in the window finds nothing in a part of it
+ *   g_progress, g_advance, g_lateral, g_remaining B x A, g_heading B x A x 2, g_lookahead B x A x n_lookahead x 2: each may be NULL = zero
+ *   g_xy, g_sc    B x A x 2 float32, written in full
+ * Everything else as tds_route_progress_multi reads it.  One launch; nothing is allocated, nothing synchronises, every loop is bounded whatever
+ * the tensors hold.  n_lookahead outside [0, 32], a negative or non-finite spacing, xy_stride < 2 or a null output is TDS_EINVAL before any
+ * launch. */
+int tds_route_progress_bwd_multi(const tds_laneset_t *set, const int32_t *scene_map, int64_t B, int64_t A, const float *xy, int64_t xy_stride,
+                                 const float *sc, const uint8_t *present, const int32_t *route_lanes, const int32_t *route_n,
+                                 const double *start_arc, const double *end_arc, const double *offsets, const double *length,
+                                 const int32_t *piece, const float *g_progress, const float *g_advance, const float *g_lateral,
+                                 const float *g_heading, const float *g_remaining, const float *g_lookahead, int n_lookahead, float spacing,
+                                 float *g_xy, float *g_sc, void *stream);
+
 /* Routes to a destination: shortest paths on the lane graph (float64 model: tests/route_to_model.py).  Float64, + and
  * compares only.  A lanelet is USABLE if it is eligible in the sense of tds_spawn_on_lanes_f32 and carries no excluded tag; len(l) is its
  * cumulative 3-D length, the last `cum` of its centre line.

@@ -155,6 +155,9 @@ tds_route_sample_multi(handle set, i32* scene_map, i64* scene_ids, int64 B, int6
 tds_route_progress_multi(handle set, i32* scene_map, int64 B, int64 A, f32* xy, int64 xy_stride, f32* sc, u8* present, i32* route_lanes, i32* route_n, f64* start_arc,
     f64* end_arc, f64* offsets, f64* length, i32* cursor, f64* stored, u8* completed, float goal_tolerance, float off_route_distance, int n_lookahead, float spacing,
     f32* progress, f32* advance, f32* lateral, f32* heading, f32* remaining, u8* reached, u8* off_route, f32* lookahead, stream stream)
+tds_route_progress_bwd_multi(handle set, i32* scene_map, int64 B, int64 A, f32* xy, int64 xy_stride, f32* sc, u8* present, i32* route_lanes, i32* route_n, f64* start_arc,
+    f64* end_arc, f64* offsets, f64* length, i32* piece, f32* g_progress, f32* g_advance, f32* g_lateral, f32* g_heading, f32* g_remaining, f32* g_lookahead, int n_lookahead,
+    float spacing, f32* g_xy, f32* g_sc, stream stream)
 tds_route_points_multi(handle set, i32* scene_map, int64 B, int64 A, int64 Q, i32* route_lanes, i32* route_n, f64* start_arc, f64* end_arc, f64* offsets, f64* length, f64* q,
     f32* points, stream stream)
 tds_lane_distances_f64(handle lanes, f64* to_go, stream stream)

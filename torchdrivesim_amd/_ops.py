@@ -1409,6 +1409,13 @@ def _route_tensors(what, route, B, A, names):
     return [route[name] for name, _, _ in names]
 
 
+def _routes_dealt(route):
+    """the kernels write the route tensors behind torch's back: move their version counters on, so that a backward of a step made on the old
+    routes (route_progress_grad) can tell.  Host only: no launch."""
+    for name, _, _ in ROUTE_TENSORS:
+        torch.autograd.graph.increment_version(route[name])
+
+
 def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, route):
     """tds_route_sample_multi (include/tdship.h): lane (B,A) int32, arc (B,A) float64, distance (B,A) float64, present / mask (B,A) bool or None;
     `route` (dict of the ROUTE_TENSORS and ROUTE_STATE) is written IN PLACE for the rows of `mask`.  One launch, no allocation besides the
@@ -1425,6 +1432,7 @@ def route_sample(lane_set, scene_ids, lane, arc, distance, present, mask, seed, 
         masks.append(None if t is None else _u8(t))
     nat.call('tds_route_sample_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'route_sample'), _scene_ids(scene_ids, B, 'route_sample'), B, A, lane, arc,
              distance, *masks, _seed64(seed), *_route_tensors('route_sample', route, B, A, ROUTE_TENSORS + ROUTE_STATE))
+    _routes_dealt(route)
 
 
 def route_to(lane_set, lane, arc, dest_lane, dest_arc, present, mask, route):
@@ -1442,6 +1450,7 @@ def route_to(lane_set, lane, arc, dest_lane, dest_arc, present, mask, route):
         masks.append(None if t is None else _u8(t))
     nat.call('tds_route_to_multi', lane.device, lane_set.handle, _scene_map(lane_set, B, 'route_to'), lane_set.distance_tables(), B, A, lane, arc, dest_lane,
              dest_arc, *masks, *_route_tensors('route_to', route, B, A, ROUTE_TENSORS + ROUTE_STATE + (('rest', (), torch.float64),)))
+    _routes_dealt(route)
 
 
 def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing):
@@ -1470,6 +1479,61 @@ def route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off
     nat.call('tds_route_progress_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'route_progress'), B, A, state, S, sc,
              None if present is None else _u8(present), *_route_tensors('route_progress', route, B, A, ROUTE_TENSORS + ROUTE_STATE), float(goal_tolerance),
              float(off_route_distance), int(K), float(spacing), *_route_tensors('route_progress', out, B, A, outs))
+
+
+#: the float outputs of a route step, in the order route_progress_grad returns them
+ROUTE_FLOATS = ('progress', 'advance', 'lateral', 'heading', 'remaining', 'lookahead')
+
+
+class _RouteProgressGrad(torch.autograd.Function):
+    """the in-place route step as an autograd node: forward = route_progress, backward = tds_route_progress_bwd_multi (csrc/route_bwd.hip)"""
+
+    @staticmethod
+    def forward(ctx, state, sc, lane_set, present, route, out, goal_tolerance, off_route_distance, spacing):
+        route_progress(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(state, sc, route['cursor'].clone())           # the cursor as this launch left it: the next step moves it on
+        ctx.lane_set, ctx.present, ctx.spacing = lane_set, present, float(spacing)
+        ctx.route = [route[name] for name, _, _ in ROUTE_TENSORS]           # by reference: a route is not copied per step ...
+        ctx.versions = [t._version for t in ctx.route]                      # ... so dealing new ones before the backward has to be noticed
+        return tuple(out[k].clone() for k in ROUTE_FLOATS)                  # clones: the next step overwrites the buffers
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        state, sc, piece = ctx.saved_tensors
+        if [t._version for t in ctx.route] != ctx.versions:
+            raise RuntimeError('route_progress_grad: the routes were dealt again (resample / resample_to) between this step and its backward; '
+                               'the gradient of a step belongs to the routes it was made on')
+        B, A, S = state.shape
+        dev = state.device
+        xy = state.detach()
+        if xy.dtype != f32 or not xy.is_contiguous():                       # as route_progress read it
+            xy, S = _c(xy[..., :2]), 2
+        K = grads[5].shape[2] if grads[5] is not None else 0
+        g_xy, g_sc = torch.empty((B, A, 2), dtype=f32, device=dev), torch.empty((B, A, 2), dtype=f32, device=dev)
+        gin = [None if g is None else _c(g) for g in grads]
+        nat.call('tds_route_progress_bwd_multi', dev, ctx.lane_set.handle, _scene_map(ctx.lane_set, B, 'route_progress_grad'), B, A, xy, S, _c(sc.detach()),
+                 None if ctx.present is None else _u8(ctx.present), *ctx.route, piece, *gin, int(K), ctx.spacing, g_xy, g_sc)
+        g_state = None
+        if ctx.needs_input_grad[0]:
+            extra = state.shape[2] - 2
+            g_state = torch.cat([g_xy, _zeros_const((B, A, extra), dev)], dim=-1) if extra else g_xy
+            g_state = g_state.to(state.dtype)
+        return (g_state, g_sc.to(sc.dtype) if ctx.needs_input_grad[1] else None) + (None,) * 7
+
+
+def route_progress_grad(lane_set, state, sc, present, route, out, goal_tolerance, off_route_distance, spacing):
+    """The route step, differentiable: arguments as `route_progress`, which it launches -- cursor, stored progress and
+    `completed` move exactly as there, `out` is written in full -- and CLONES of the six float outputs are returned, in the order of
+    ROUTE_FLOATS = (progress, advance, lateral, heading, remaining, lookahead), carrying the graph to `state` ([x, y]; the other columns get
+    zeros) and to `sc` = [sin psi, cos psi].  The backward is ONE launch (tds_route_progress_bwd_multi).  The forward's discrete choices are
+    constants.  `advance` differentiates as `progress`: the stored progress of the previous step is a constant, so a caller who wants the
+    telescoped sum through time differences `progress` itself.  No gradients to the route tensors, no double backward; dealing new routes
+    (`route_sample`, `route_to`) between a step and its backward makes that backward raise."""
+    if state.dim() != 3 or state.shape[0] * state.shape[1] == 0:
+        raise RuntimeError(f'route_progress_grad: state must be a non-empty (B,A,>=2), got {tuple(state.shape)}')
+    return _RouteProgressGrad.apply(state, sc, lane_set, present, route, out, goal_tolerance, off_route_distance, spacing)
 
 
 def route_points(lane_set, route, arcs):

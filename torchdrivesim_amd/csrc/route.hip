@@ -14,29 +14,23 @@
 
 #include "tds_common.h"
 #include "tds_lanes.h"
+#include "tds_route.h"
 
 using tds::LaneRec;
 using tds::LaneView;
+using tds::RouteArgs;
+using tds::route_args;
 using tds::drivable;
+using tds::route_point;
 using tds::segment_of;
 using tds::view_of;
+using tds::weigh_segment;
 
 namespace {
 
 constexpr int RBLOCK = 256;                      // four waves = four rows of the progress kernel
 constexpr int ROUTE_LANES = TDS_ROUTE_MAX_LANES;
 constexpr int SEG_BITS = 28;                     // (piece of the window, segment) packed into one int for the arg-min's tie rule
-
-// what every kernel here reads of a batch: the lane tables and the route tensors (B x A rows)
-struct RouteArgs {
-    const LaneView *views;
-    int n_views;
-    const int32_t *scene_map;
-    int64_t rows;
-    int A;
-    const int32_t *route_lanes, *route_n;       // rows x TDS_ROUTE_MAX_LANES, rows
-    const double *start_arc, *end_arc, *offsets, *length;
-};
 
 struct SampleArgs {
     const LaneView *views;
@@ -67,45 +61,6 @@ struct ProgressArgs {
     float *progress, *advance, *lateral, *heading, *remaining, *lookahead;
     uint8_t *reached, *off_route;
 };
-
-// segment i of a centre line, clipped to the arc interval [a, b] of its piece, against the pose (x, y): false for a segment that is skipped
-// (no length in 2-D or on `cum`, or nothing of it inside [a, b]); else u = the foot's parameter on the whole segment, d2 = its squared distance
-__device__ inline bool weigh_segment(const double *cl, const double *cum, int i, double a, double b, double x, double y, double &u, double &d2) {
-    const double *p = cl + 3 * (int64_t)i;
-    const double dx = p[3] - p[0], dy = p[4] - p[1];
-    const double l2 = dx * dx + dy * dy, w = cum[i + 1] - cum[i];
-    if (!(l2 > 0.0) || !(w > 0.0)) return false;
-    const double ulo = a > cum[i] ? (a - cum[i]) / w : 0.0, uhi = b < cum[i + 1] ? (b - cum[i]) / w : 1.0;
-    if (!(uhi > ulo)) return false;
-    u = ((x - p[0]) * dx + (y - p[1]) * dy) / l2;
-    u = fmin(fmax(u, ulo), uhi);
-    const double fx = (p[0] + u * dx) - x, fy = (p[1] + u * dy) - y;
-    d2 = fx * fx + fy * fy;
-    return true;
-}
-
-// the point at route arc q, world frame.  Not tds::point_at_arc: a route measures a segment by w = cum[k + 1] - cum[k] (include/tdship.h), the
-// same w its progress is computed with, and that is not the segment's own 3-D length bit for bit.
-__device__ inline void route_point(const LaneView &v, const int32_t *lanes, const double *offs, int n, double a0, double length, double q,
-                                   double &x, double &y) {
-    x = 0.0, y = 0.0;
-    if (!(q > 0.0)) q = 0.0;
-    if (q > length) q = length;
-    int j = 0;
-    for (int i = 1; i < n; ++i)
-        if (offs[i] <= q) j = i;                                             // the last piece that starts at or before q
-    const int l = lanes[j];
-    if (l < 0 || l >= v.n) return;
-    const LaneRec r = v.rec[l];
-    if (r.cl_n < 2) return;
-    const double *cl = v.cl + 3 * (int64_t)r.cl_start, *cum = v.cum + r.cl_start;
-    const double arc = (j == 0 ? a0 : 0.0) + (q - offs[j]);
-    const int k = segment_of(cum, r.cl_n, arc);
-    const double *p = cl + 3 * (int64_t)k;
-    const double w = cum[k + 1] - cum[k];
-    const double u = w > 0.0 ? (arc - cum[k]) / w : 0.0;
-    x = p[0] + u * (p[3] - p[0]), y = p[1] + u * (p[4] - p[1]);
-}
 
 // ---- sampling: a thread per row ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(RBLOCK) route_sample_kernel(SampleArgs g) {
@@ -259,18 +214,6 @@ __global__ void __launch_bounds__(RBLOCK) route_points_kernel(RouteArgs g, int Q
     if (n > 0 && view_of(g.views, g.n_views, g.scene_map, row / g.A, v))
         route_point(v, g.route_lanes + row * ROUTE_LANES, g.offsets + row * ROUTE_LANES, n, g.start_arc[row], g.length[row], q[idx], px, py);
     out[idx * 2] = (float)px, out[idx * 2 + 1] = (float)py;
-}
-
-int route_args(const char *what, RouteArgs &r, const tds_laneset_t *set, const int32_t *scene_map, int64_t B, int64_t A, const int32_t *route_lanes,
-               const int32_t *route_n, const double *start_arc, const double *end_arc, const double *offsets, const double *length) {
-    TDS_CHECK_ARG(set, "%s: the lane-table set is null", what);
-    TDS_CHECK_SCENE_MAP(what, set, scene_map);
-    TDS_CHECK_ARG(B >= 0 && A >= 0 && A < ((int64_t)1 << 31) && (A == 0 || B <= (((int64_t)1 << 31) - 1) / A), "%s: bad sizes B=%lld A=%lld", what,
-                  (long long)B, (long long)A);
-    TDS_CHECK_ARG(B * A == 0 || (route_lanes && route_n && start_arc && end_arc && offsets && length), "%s: a route tensor is null", what);
-    r.views = set->d_views, r.n_views = set->n, r.scene_map = scene_map, r.rows = B * A, r.A = (int)A;
-    r.route_lanes = route_lanes, r.route_n = route_n, r.start_arc = start_arc, r.end_arc = end_arc, r.offsets = offsets, r.length = length;
-    return TDS_OK;
 }
 
 }  // namespace

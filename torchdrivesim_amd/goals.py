@@ -7,7 +7,8 @@ collections are drawn by the K3 rasteriser as per-camera discs (`Simulator.rende
 Route goals (`RouteGoal`, no reference counterpart; DESIGN.md 5.5d, csrc/route.hip): every agent is dealt a route of a requested length on the
 lane graph; each step ONE launch reports its progress along it, its offsets from it, whether it has arrived or left it, and the next K route
 points in its own frame.  Yardstick: the float64 model tests/route_model.py.  `RouteGoal.to` deals the shortest route to a destination instead
-of a random one (csrc/route_to.hip; model: tests/route_to_model.py).
+of a random one (csrc/route_to.hip; model: tests/route_to_model.py).  With `differentiable=True` the step's float outputs carry
+gradients to the pose, one backward launch (csrc/route_bwd.hip; model: tests/route_grad_model.py).
 """
 from typing import NamedTuple, Optional, Union
 
@@ -114,13 +115,14 @@ class RouteGoal:
     """
 
     def __init__(self, lanelet_maps, tensors: dict, *, seed: int, tolerance: float, goal_tolerance: float, off_route_distance: float, lookahead: int,
-                 spacing: float):
+                 spacing: float, differentiable: bool = False):
         from torchdrivesim_amd import _ops
         from torchdrivesim_amd.lanelet2 import LaneletMap
         _ops.check_route_args(goal_tolerance, off_route_distance, lookahead, spacing)
         self.lanelet_maps = lanelet_maps if isinstance(lanelet_maps, LaneletMap) else list(lanelet_maps)
         self.seed, self.tolerance, self.goal_tolerance = int(seed), float(tolerance), float(goal_tolerance)
         self.off_route_distance, self.lookahead, self.spacing = float(off_route_distance), int(lookahead), float(spacing)
+        self.differentiable = bool(differentiable)       # `step` returns float outputs that carry the graph to the pose; settable
         self._t = dict(tensors)       # the route tensors, its state, the requested lengths, the scene ids, scratch of the snap and the outputs
         self._lanes = None
         self._lane_table_set()
@@ -129,12 +131,13 @@ class RouteGoal:
     @classmethod
     def sample(cls, lanelet_maps, agent_state: Tensor, present_mask: Optional[Tensor] = None, *, seed: int, scene_ids: Optional[Tensor] = None,
                length: Union[float, Tensor] = 200.0, tolerance: float = 1.0, goal_tolerance: float = 2.0, off_route_distance: float = 4.0,
-               lookahead: int = 16, spacing: float = 4.0) -> 'RouteGoal':
+               lookahead: int = 16, spacing: float = 4.0, differentiable: bool = False) -> 'RouteGoal':
         """
         lanelet_maps: one `LaneletMap` for all scenes or a list of B of them; agent_state (B, A, >= 3) = [x, y, psi, ...] on the device.
         Every present agent is snapped to a lane (`snap_to_lanes` with `tolerance`) and dealt a route of `length` metres (a number or (B, A))
         from there; agents that find no lane, absent ones and lengths that are not positive and finite get no route (`valid` False).
         seed: key of the route stream; scene_ids (B,) int64, default arange(B): the identity of each scene in it.
+        differentiable: `step` hands out float outputs with gradients to the pose (see `step`).
         """
         from torchdrivesim_amd import _ops
         for name, t in (('agent_state', agent_state), ('present_mask', present_mask), ('scene_ids', scene_ids),
@@ -155,7 +158,7 @@ class RouteGoal:
         else:
             t['distance'] = torch.full((B, A), float(length), dtype=f64, device=dev)
         me = cls(lanelet_maps, t, seed=seed, tolerance=tolerance, goal_tolerance=goal_tolerance, off_route_distance=off_route_distance, lookahead=K,
-                 spacing=spacing)
+                 spacing=spacing, differentiable=differentiable)
         me._sample(agent_state, present_mask, None)
         return me
 
@@ -176,7 +179,8 @@ class RouteGoal:
     @classmethod
     def _to_destination(cls, lanelet_maps, agent_state: Tensor, destination: Optional[Tensor] = None, *, destination_lanes: Optional[Tensor] = None,
                         destination_arcs: Optional[Tensor] = None, present_mask: Optional[Tensor] = None, tolerance: float = 1.0,
-                        goal_tolerance: float = 2.0, off_route_distance: float = 4.0, lookahead: int = 16, spacing: float = 4.0) -> 'RouteGoal':
+                        goal_tolerance: float = 2.0, off_route_distance: float = 4.0, lookahead: int = 16, spacing: float = 4.0,
+                        differentiable: bool = False) -> 'RouteGoal':
         """
         RouteGoal.to(lanelet_maps, agent_state, destination): the SHORTEST route on the lane graph from every agent to its destination.
         lanelet_maps, agent_state, tolerance and the step's parameters: as for `sample`.  The destination is given in exactly one of two forms:
@@ -185,7 +189,7 @@ class RouteGoal:
         destinations that cannot be reached get no route (`valid` False, `rest` inf).  A route holds at most 16 lanelets: one that would need
         more ends at the end of its 16th (`truncated`; `rest` = what is left from there) and is continued with
         `resample_to(state, mask=goal.completed & goal.truncated)`.  The first call with a map builds its distance tables (L x L float64, one
-        launch): outside any stream capture.  No lane changes, no cost but length, no gradients.
+        launch): outside any stream capture.  No lane changes, no cost but length.  differentiable: as for `sample`.
         """
         from torchdrivesim_amd import _ops
         if not agent_state.is_cuda:
@@ -198,7 +202,7 @@ class RouteGoal:
         if destination is None and destination_lanes is None:
             raise ValueError('RouteGoal.to needs `destination` poses or `destination_lanes` and `destination_arcs`')
         me = cls(lanelet_maps, cls._buffers(B, A, K, agent_state.device), seed=0, tolerance=tolerance, goal_tolerance=goal_tolerance,
-                 off_route_distance=off_route_distance, lookahead=K, spacing=spacing)
+                 off_route_distance=off_route_distance, lookahead=K, spacing=spacing, differentiable=differentiable)
         me.resample_to(agent_state, destination, present_mask=present_mask, destination_lanes=destination_lanes, destination_arcs=destination_arcs)
         return me
 
@@ -308,7 +312,14 @@ class RouteGoal:
     # ---- the step -----------------------------------------------------------------------------------------------------------------
     def step(self, agent_state: Tensor, present_mask: Optional[Tensor] = None, sc: Optional[Tensor] = None) -> RouteProgress:
         """One launch for all agents: agent_state (B, A, >= 3) = [x, y, psi, ...]; sc: (B, A, 2) [sin psi, cos psi] where the caller has them
-        already (else computed here with torch).  Returns the `RouteProgress` of the buffers this object owns."""
+        already (else computed here with torch).  Returns the `RouteProgress` of the buffers this object owns.
+
+        With `differentiable` set, grad mode on and an `agent_state` or `sc` that requires grad, the same launch runs as an autograd node
+        (`_ops.route_progress_grad`): the float fields of what is returned are CLONES that carry the graph to [x, y] and to [sin psi, cos psi]
+        (computed here with `_ops.heading_sc` when not handed in, so psi gets its gradient through torch's sin / cos); the flags stay this
+        object's buffers, and `last_progress` still gives the buffers.  The forward's discrete choices (piece, segment, clamps) are constants;
+        `advance` differentiates as `progress` (the stored progress of the previous step is a constant: for the telescoped sum through time,
+        differentiate `progress` itself).  The backward is one launch; new routes (`resample`, `resample_to`) before it make it raise."""
         from torchdrivesim_amd import _ops
         if not agent_state.is_cuda:
             raise RuntimeError(f'agent_state: route goals run on an MI355X; got a {agent_state.device} tensor (no CPU fallback)')
@@ -316,6 +327,14 @@ class RouteGoal:
         B, A = t['n'].shape
         if agent_state.dim() != 3 or tuple(agent_state.shape[:2]) != (B, A) or agent_state.shape[-1] < 3:
             raise ValueError(f'agent_state must be ({B}, {A}, >= 3), got {tuple(agent_state.shape)}')
+        if self.differentiable and B * A > 0 and torch.is_grad_enabled() and (agent_state.requires_grad or (sc is not None and sc.requires_grad)):
+            if sc is None:
+                sc = _ops.heading_sc(agent_state[..., 2])
+            with torch.no_grad():
+                t['sc'].copy_(sc)                                            # the buffer always holds the [sin, cos] the last launch read
+            f = _ops.route_progress_grad(self._lane_table_set(), agent_state, sc, present_mask, t, t, self.goal_tolerance, self.off_route_distance,
+                                         self.spacing)
+            return RouteProgress(f[0], f[1], f[2], f[3], f[4], t['reached'].view(torch.bool), t['off_route'].view(torch.bool), f[5])
         if B * A > 0:
             with torch.no_grad():
                 if sc is None:
@@ -403,7 +422,7 @@ class RouteGoal:
     def copy(self):
         return self.__class__(self.lanelet_maps, {k: v.clone() for k, v in self._t.items()}, seed=self.seed, tolerance=self.tolerance,
                               goal_tolerance=self.goal_tolerance, off_route_distance=self.off_route_distance, lookahead=self.lookahead,
-                              spacing=self.spacing)
+                              spacing=self.spacing, differentiable=self.differentiable)
 
     def _to_device(self, device):
         return self._map(lambda x: x.to(device))

@@ -595,7 +595,10 @@ class Simulator:
     def _step_route_goals(self):
         state = self.get_state()
         # the [sin, cos] render / collision / off-road share for this state, where it covers exactly the exposed agents
-        sc = self._heading_sc().detach() if self.npc_count == 0 and state.dtype == torch.float32 else None
+        # (a differentiable goal gets the shared node itself: its gradient to psi joins those of render / collision / off-road there)
+        sc = self._heading_sc() if self.npc_count == 0 and state.dtype == torch.float32 else None
+        if sc is not None and not getattr(self.route_goals, 'differentiable', False):
+            sc = sc.detach()
         out = self.route_goals.step(state, self.present_mask, sc=sc)
         self._route_progress = (state, state._version, out)
         return out
@@ -603,7 +606,8 @@ class Simulator:
     def compute_route_progress(self):
         """The `goals.RouteProgress` of the current state (None without `route_goals`): the one `step` has made, or, after the state was set by
         other means since, one made now -- which, like every route step, moves the routes' cursors on and measures `advance` from the progress
-        reported before it."""
+        reported before it.  With `route_goals.differentiable` and a state that requires grad its float fields carry the graph to the state
+        (`RouteGoal.step`); the price of the option is the six clones every such step makes of its output buffers."""
         if self.route_goals is None:
             return None
         state, cached = self.get_state(), self._route_progress
