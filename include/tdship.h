@@ -238,6 +238,26 @@ int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t *scene_map,
  *   keys, n_keys, index_bits   filled by the call (HOST): the ascending key table of the launch (n_keys = 0 when another kernel ran)
  *   flags         input: TDS_RASTER_NO_TRIM draws every face as the reference does with trim_mesh_before_rendering = False */
 #define TDS_RASTER_NO_TRIM 1   /* trim_mesh_before_rendering = False (rendering/cv2.py:15,32-41): keep faces without a vertex in view */
+/* Coverage record (optional): lets a render into a buffer that still holds an EARLIER render of this library skip the 128-byte lines that
+ * held only background then and hold only background now (a loop that renders into a ring of buffers: about half the lines at 256 x 256).
+ *   coverage        DEVICE buffer of at least tds_raster_coverage_bytes(B * Nc, res) bytes, 16-byte aligned, or NULL.  It belongs to ONE
+ *                   output buffer: a 64-byte header (magic, res, cameras, the address of `out`, the background's bits per channel, the mode of the
+ *                   launch in flight) and uint32 [camera][x / 32][y / 32], bit x % 32 = "the line of column x, rows 32 (y / 32) .. + 31 holds a
+ *                   covered pixel" (x, y as for index_slices; one line per channel, all three share the bit).  The call checks the header on the
+ *                   device, in stream order: a record that was never written, or written for another resolution, camera count or `out`, makes
+ *                   the launch store every line; either way the launch leaves a valid record of what `out` holds now.  Needs no clearing.
+ *   coverage_bytes  size of that buffer (too small for the call: TDS_EINVAL)
+ *   flags           TDS_RASTER_REWRITE_ALL: store every line whatever the record says, and still record the coverage
+ *   coverage_maintained   filled by the call (HOST): 1 when the launch maintained the record.  The rule: a float32 image whose side is a multiple of
+ *                   32, no index_slices, and the launch is the fused bit-plane kernel in 4-wave workgroups at three per CU (its LDS per workgroup lies
+ *                   between 40 and 52 KiB: e.g. five keys at 256 x 256, nine keys there in two strips, seven keys at 192 x 192).  0: any other launch
+ *                   (uint8 output, the masks, other sides, the split form up to 160 x 160, 8-wave workgroups -- six or seven keys at 256 x 256 --,
+ *                   four workgroups per CU -- five keys at 192 x 192, eight keys at 256 x 256 in half strips --, more than 15 keys): every pixel was
+ *                   stored and the record was NOT touched: it no longer describes `out` and must not be passed again without TDS_RASTER_REWRITE_ALL.
+ * THE CONTRACT IS THE CALLER'S: between two calls that pass the same record without TDS_RASTER_REWRITE_ALL nothing but this library's
+ * renders with that record may have written to `out` -- the skipped lines are assumed to hold the background (0.0f) the earlier call left
+ * there.  aux == NULL or coverage == NULL: every pixel is stored, as before. */
+#define TDS_RASTER_REWRITE_ALL 2
 typedef struct tds_raster_aux {
     uint32_t *index_slices;
     int64_t index_slices_bytes;
@@ -245,8 +265,13 @@ typedef struct tds_raster_aux {
     int32_t n_keys;
     int32_t index_bits;
     int32_t flags;              /* in: TDS_RASTER_* */
+    int32_t coverage_maintained;    /* out */
+    uint32_t *coverage;         /* in */
+    int64_t coverage_bytes;     /* in */
 } tds_raster_aux_t;
 int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes);
+/* bytes of the coverage record of n_img images of res x res (0: no lines are tracked at this resolution -- res is no multiple of 32) */
+int tds_raster_coverage_bytes(int64_t n_img, int res, int64_t *bytes);
 
 int tds_raster_scene(const tds_map_t *map, const float *state, const float *agent_sc, const float *tmpl,
                      const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc,

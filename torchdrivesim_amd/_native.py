@@ -24,6 +24,7 @@ METRIC_IOU, METRIC_DISCS = 0, 1
 OUT_F32, OUT_U8 = 0, 1
 OUT_MASK_U8, OUT_MASK_BITS = 2, 3     # semantic masks (tds_raster_scene_masks): 0 / 1 bytes, packed bits
 RASTER_NO_TRIM = 1
+RASTER_REWRITE_ALL = 2
 
 
 class RasterDebug(enum.IntFlag):
@@ -57,7 +58,8 @@ _lib = None
 class RasterAux(ctypes.Structure):
     """tds_raster_aux_t (include/tdship.h): optional outputs of tds_raster_scene for a later backward pass"""
     _fields_ = [('index_slices', ctypes.c_void_p), ('index_slices_bytes', ctypes.c_int64), ('keys', ctypes.c_uint32 * 16),
-                ('n_keys', ctypes.c_int32), ('index_bits', ctypes.c_int32), ('flags', ctypes.c_int32)]
+                ('n_keys', ctypes.c_int32), ('index_bits', ctypes.c_int32), ('flags', ctypes.c_int32), ('coverage_maintained', ctypes.c_int32),
+                ('coverage', ctypes.c_void_p), ('coverage_bytes', ctypes.c_int64)]
 
 
 # One declaration per entry point of include/tdship.h, its parameters under the header's names (tests/test_abi.py holds the table to the header).
@@ -98,6 +100,7 @@ tds_offroad_multi_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* s
 tds_offroad_multi_bwd_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* state, f32* lenwid, f32* sc, u8* present, f32* grad_out, f32* grad_state, f32* grad_lenwid,
     f32* grad_sc, int64 n_agents, float threshold, stream stream)
 tds_raster_index_slices_bytes(int64 n_img, int res, host* bytes)
+tds_raster_coverage_bytes(int64 n_img, int res, host* bytes)
 tds_raster_scene(handle map, f32* state, f32* agent_sc, f32* tmpl, i32* actor_key, u8* mask, f32* cam_xy, f32* cam_sc, int64 B, int64 Nc, int64 N, float scale, int res,
     int out_mode, void* out, void* workspace, int64 workspace_bytes, host* actor_keys, int n_actor_keys, int actor_key_per_camera, f32* extra_tri, i32* extra_key,
     int64 n_extra, host* aux, stream stream)

@@ -753,7 +753,7 @@ class _OwnedBuffer:
     def __del__(self, _finalizing=sys.is_finalizing):      # (bound at definition: module globals are gone when the interpreter shuts down)
         h, self.handle = getattr(self, 'handle', None), None
         if h and not _finalizing():                        # at interpreter shutdown the driver takes the memory back itself
-
+            _owned_buffers.pop(self.__cuda_array_interface__['data'][0], None)      # with it the coverage record: the address may be handed out again
             try:
                 torch.cuda.synchronize(self.device)            # nothing in flight may still write to pages that are about to be unmapped
             except Exception:                                  # noqa: BLE001 -- interpreter shutdown
@@ -767,7 +767,81 @@ def owned_image(shape, dtype=torch.float32, device="cuda", dense=False) -> torch
     device = torch.device(device)
     if device.index is None:
         device = torch.device('cuda', torch.cuda.current_device())
-    return torch.as_tensor(_OwnedBuffer(shape, dtype, device, dense=dense), device=device)
+    buf = _OwnedBuffer(shape, dtype, device, dense=dense)
+    t = torch.as_tensor(buf, device=device)
+    _owned_buffers[t.data_ptr()] = dict(nbytes=t.numel() * t.element_size(), shape=tuple(t.shape), dtype=dtype, record=None)
+    return t
+
+
+# ---- which lines of an owned image hold something ---------------------------------------------------------------------------------------
+#: A loop renders into a ring of owned buffers: what a buffer holds when it is rendered into is the same cameras' image of `count` steps ago,
+#: and about half of its 128-byte lines held only background then and hold only background now.  The fused bit-plane kernel keeps a COVERAGE
+#: RECORD per buffer (include/tdship.h, tds_raster_aux_t::coverage: one bit per line) and leaves those lines alone (53 % of the lines
+#: in tests/test_gpu_write_skipping.py; the headline launch 6.90 -> 6.13 ms, profiles/write_skip_timing.json).  Only the buffers of `owned_image` are tracked (the library sees them die); the image pool and arbitrary caller tensors
+#: are written in full as ever.  What the host knows about a buffer's contents is torch's version counter of the tensor it was handed:
+#:     WRITES THAT DO NOT BUMP IT ARE NOT SEEN -- raw-pointer writes of other libraries, writes through `.data`, a replayed graph that
+#:     writes into the buffer.  A caller that does any of these switches skipping off (`use_write_skipping = False`,
+#:     HipRendererConfig.write_skipping) or calls `forget_coverage(buf)` after the write.
+#: False: every line is stored (the record is still kept up to date, so that switching back on needs no full write).
+use_write_skipping = True
+_owned_buffers = {}          # address of an _OwnedBuffer -> dict(nbytes, shape, dtype, record); gone with the buffer
+_NO_VERSION = object()
+
+
+def write_skip_decision(record, whole_buffer, res, n_img, version, capturing, enabled):
+    """What a float32 render into an owned buffer does with the buffer's coverage record.  Plain values in, so that a CPU test can drive it:
+    `record` None or dict(res, n_img, version (the tensor's version counter after the last render), valid); `whole_buffer`: `out` is the buffer as it
+    was allocated (same address, shape and dtype, contiguous); `version`: out._version now, _NO_VERSION when it cannot be read (inference
+    tensors); `capturing`: the stream is being captured; `enabled`: the two switches.  ->
+      'untracked'  no record is passed and the one there is is dropped: every line is stored.  Part of the buffer, a resolution that is no multiple
+                   of 32, no version counter -- and stream capture: a graph must not hold the address of a record that dies with its buffer.
+      'rewrite'    TDS_RASTER_REWRITE_ALL: every line is stored and the coverage recorded.  No (valid) record, another resolution or camera
+                   count, the tensor was written to since the last render, or skipping is switched off.
+      'skip'       the lines that were background and stay background are left alone."""
+    if not whole_buffer or res % 32 != 0 or version is _NO_VERSION or capturing:
+        return 'untracked'
+    if record is None or not record.get('valid') or (record['res'], record['n_img']) != (res, n_img) or record['version'] != version or not enabled:
+        return 'rewrite'
+    return 'skip'
+
+
+def _owned_overlapping(t):
+    lo = t.data_ptr()
+    hi = lo + max(t.numel() * t.element_size(), 1)
+    return [ent for ptr, ent in _owned_buffers.items() if ptr < hi and lo < ptr + ent['nbytes']]
+
+
+def forget_coverage(buf) -> None:
+    """Drop what the library believes an owned buffer holds: the next render into it (or into the buffer any part of which `buf` views) stores
+    every line.  For writers the version counter does not show (see use_write_skipping)."""
+    if isinstance(buf, torch.Tensor) and buf.is_cuda and _owned_buffers:
+        for ent in _owned_overlapping(buf):
+            if ent['record'] is not None:
+                ent['record']['valid'] = False             # (the allocation stays: nothing is freed, nothing waits, between two renders)
+
+
+def _coverage_aux(out, res, n_img, enabled):
+    """-> (entry of the owned buffer `out` is, decision, record) for a float32 colour render into the caller's `out`; (None, 'untracked', None) when
+    `out` is no owned buffer or only touches one (whose record is dropped: its lines are about to change under it)"""
+    ent = _owned_buffers.get(out.data_ptr())
+    whole = ent is not None and ent['shape'] == tuple(out.shape) and ent['dtype'] == out.dtype and out.is_contiguous()
+    try:
+        version = out._version
+    except Exception:                                          # noqa: BLE001 -- inference tensors have no version counter
+        version = _NO_VERSION
+    decision = write_skip_decision(ent['record'] if whole else None, whole, res, n_img, version, torch.cuda.is_current_stream_capturing(), enabled)
+    if decision == 'untracked':
+        forget_coverage(out)
+        return None, decision, None
+    rec = ent['record']
+    if rec is None or (rec['res'], rec['n_img']) != (res, n_img):
+        nbytes = ctypes.c_int64(0)
+        nat.call('tds_raster_coverage_bytes', out.device, n_img, int(res), ctypes.byref(nbytes))
+        # the library's memory like the buffer itself, not torch's: it lives as long as the buffer, whatever stream renders into it
+        cov = torch.as_tensor(_OwnedBuffer((nbytes.value // 4,), i32, out.device), device=out.device)
+        rec = dict(cov=cov, res=res, n_img=n_img, version=None, valid=False)
+    ent['record'] = None                                       # until the call has come back and said that it maintained the record
+    return ent, decision, rec
 
 
 # ---- streams confined to a part of the CUs ---------------------------------------------------------------------------------------------
@@ -931,17 +1005,20 @@ def _scene_call(fn, smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc
 
 
 def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, out_dtype=torch.float32, out=None, key_table=None,
-                 extra_tri=None, extra_key=None, index_slices=False, trim=True):
+                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True):
     """Fused Simulator.render: state (B,N,4), agent_sc (B,N,2), tmpl (B,N,7,2), actor_key (B,N,2) int32 bit patterns -- or (B,Nc,N,2)
     when every camera sees its own colours (custom_agent_colors) --, mask (B,Nc,N) bool/uint8, cam_xy / cam_sc (B,Nc,2)
     -> (B,Nc,3,res,res) float32 [0,255] or uint8.  extra_tri (B,Nc,K,3,2) world-space triangles with keys extra_key (B,Nc,K) int32
     (0 = none) are drawn per camera (waypoint discs); their keys belong into `key_table` too.
     index_slices=True: returns (image, slices, keys) -- the per-pixel key index as bit-slices (int32 tensor, layout in include/tdship.h)
     and the ascending key table of the launch, what the backward pass reads instead of the image; (image, None, None) when the call
-    cannot be served by the bit-plane kernel."""
+    cannot be served by the bit-plane kernel.
+    `out` an `owned_image` buffer (float32): the lines that held background after the last render into it and hold background again are not
+    stored a second time (see `use_write_skipping` for what the caller must not do to the buffer in between); write_skipping=False stores them."""
     assert out_dtype in (torch.float32, torch.uint8)
     dev = cam_xy.device
     mode = nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8
+    caller_out = out
     B, Nc, N, K, actor_key, extra_key, out, call = _scene_call('tds_raster_scene', smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc,
                                                                extra_tri, extra_key, fov, res, mode, out, (3, res, res), out_dtype)
     # distinct actor keys (host side): enables the bit-plane kernel.  Callers that know them (Simulator) pass `key_table`;
@@ -970,6 +1047,17 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     if not trim:
         aux = aux if aux is not None else nat.RasterAux()
         aux.flags = nat.RASTER_NO_TRIM
+    cov_ent = cov_rec = None
+    if caller_out is not None and _owned_buffers:
+        if out_dtype == torch.float32 and slices is None and B * Nc > 0:
+            cov_ent, decision, cov_rec = _coverage_aux(caller_out, int(res), B * Nc, use_write_skipping and write_skipping)
+            if cov_rec is not None:
+                aux = aux if aux is not None else nat.RasterAux()
+                aux.coverage, aux.coverage_bytes = cov_rec['cov'].data_ptr(), cov_rec['cov'].numel() * 4
+                if decision != 'skip':
+                    aux.flags |= nat.RASTER_REWRITE_ALL
+        else:
+            forget_coverage(caller_out)
     def launch(aux):
         call((ws, 0 if ws is None else ws.numel(), kt, 0 if kt is None else len(key_table), 1 if (N > 0 and actor_key.dim() == 4) else 0),
              (None if aux is None else ctypes.byref(aux),))
@@ -986,6 +1074,14 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
         slices = None
         aux = None if trim else nat.RasterAux(flags=nat.RASTER_NO_TRIM)
         launch(aux)
+    if cov_rec is not None:
+        # a call that raised has left the buffer without a record; one that another kernel served (aux.coverage_maintained == 0: every line was stored,
+        # the record not touched) keeps the allocation for the next call, marked as describing nothing
+        try:
+            cov_rec.update(version=caller_out._version, valid=bool(aux is not None and aux.coverage_maintained))
+            cov_ent['record'] = cov_rec
+        except Exception:                                      # noqa: BLE001 -- no version counter after all
+            pass
     if ev is not None:
         ev[1].record(torch.cuda.current_stream(dev))
         raster_events.append(ev)
@@ -1023,6 +1119,7 @@ def raster_scene_masks(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam
     dev = cam_xy.device
     mode = nat.OUT_MASK_BITS if packed else nat.OUT_MASK_U8
     tail, dtype = ((C, (res + 31) // 32, res), i32) if packed else ((C, res, res), torch.bool)
+    forget_coverage(out)                        # (masks rendered over an owned image buffer: its lines are no longer what the record says)
     B, Nc, _, _, _, _, out, call = _scene_call('tds_raster_scene_masks', smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, extra_tri,
                                                extra_key, fov, res, mode, out, tail, dtype)
     actors = [int(v) & 0xffffffff for v in key_table]

@@ -85,7 +85,9 @@ struct CommonArgs {
     void *out;
     int no_trim;                // trim_mesh_before_rendering = False (cv2.py:15,32): faces are kept whether or not a vertex is in view
     uint32_t *slices;           // optional: bit-slices of the winning key index per pixel, kept for the backward pass (bit-plane kernel
-                                // only; layout in include/tdship.h, tds_raster_aux_t)
+                                // only; layout in include/tdship.h, tds_raster_aux_t) -- or, in a plain float32 colour launch of the fused
+                                // bit-plane kernel (no slices wanted), the COVERAGE RECORD of the output buffer (tds_raster_aux_t::coverage):
+                                // one kernel argument serves both, the kernel has no register to spare for another
     int debug;                  // ablation switches for profiling (tds_raster_set_debug): TDS_RASTER_DBG_* of include/tdship.h
 };
 
@@ -2064,7 +2066,16 @@ template <int NB> struct PairTab<NB, uint8_t> { using E = uint32_t; };        //
 
 __device__ __forceinline__ uint32_t rotl32(uint32_t v, int n) { return __builtin_rotateleft32(v, (unsigned)n & 31u); }
 
-template <int BBLOCK, int NB, typename OutT, bool EMIT>
+// The coverage record of an output buffer (tds_raster_aux_t::coverage; float32 images whose side is a multiple of 32): behind a header of
+// COV_HEADER_DW words, one word per (camera, word column x / 32, row block y / 32) whose bit p says "the 128-byte line of column x = 32 xw + p,
+// rows 32 o .. 32 o + 31 (one line in each of the three channels) holds a covered pixel".  A line that held only background before the launch
+// and holds only background after it is not stored again.  Header: [0] magic, [1] res, [2..3] cameras, [4..5] the image buffer's address,
+// [6..8] the bits of the background colour per channel, [COV_MODE] what the launch in flight does (written by coverage_prepare_kernel
+// right before it, in stream order): COV_SKIP = the record describes the buffer, else every line is stored.
+constexpr int COV_HEADER_DW = 16, COV_MODE = 9;
+constexpr uint32_t COV_MAGIC = 0x31564f43u, COV_SKIP = 1u;      // 'COV1'
+
+template <int BBLOCK, int NB, typename OutT, bool EMIT, bool TRACK = false>
 __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typename PairTab<NB, OutT>::E *tab, int K, OutT *out, int64_t img, int res,
                                       int X0, int TWp, int wpr, int tid, uint32_t *slices) {
     using E = typename PairTab<NB, OutT>::E;
@@ -2171,11 +2182,28 @@ __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typ
     if ((H & 3) == 0) {
         const int quads = H >> 2;
         const bool full = (cols & 31) == 0;                          // wave-uniform: no partial 32-column word
+        // TRACK (plain float32 colour launches): `slices` is the buffer's coverage record, or null.  H a multiple of 32: the eight lanes of an
+        // aligned octet hold the row quads 8 o .. 8 o + 7 of ONE word column (quads, BBLOCK and quads * wpr are multiples of 8, so an octet
+        // is never split by the loop bound or by a strip's end) -- together the 32 rows of one 128-byte line per column and channel.
+        bool track = false, skip = false;
+        if constexpr (TRACK) {
+            track = slices != nullptr && (H & 31) == 0;
+            if (track) skip = (uint32_t)__builtin_amdgcn_readfirstlane((int)slices[COV_MODE]) == COV_SKIP;
+        }
         for (int item = tid; item < quads * wpr; item += BBLOCK) {
             // A wave takes 64 consecutive row quads of one word column: its plane reads are consecutive 16-byte pieces of LDS (conflict-free
             // ds_read_b128) and a store instruction writes one run of 1 KiB.
             const int rq = item % quads, xw = item / quads, y0 = rq * 4;
             if (xw * 32 >= cols) continue;
+            uint32_t *crec = nullptr;
+            uint32_t lines = 0xffffffffu;                            // bit p: column p of this word column is stored
+            if constexpr (TRACK) {
+                if (track) {
+                    // this octet's word: read early (what it held is needed only when the stores begin), every (camera, strip) item touches only its own words
+                    crec = slices + COV_HEADER_DW + ((size_t)img * (size_t)(W >> 5) + (size_t)((X0 >> 5) + xw)) * (size_t)(H >> 5) + (size_t)(rq >> 3);
+                    lines = skip ? *crec : 0xffffffffu;
+                }
+            }
             uint32_t s[NB][4], cov[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int b = 0; b < NB; ++b)
@@ -2193,6 +2221,19 @@ __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typ
                     cov[j] |= wd;
 #pragma unroll
                     for (int b = 0; b < NB; ++b) s[b][j] |= ((idx >> b) & 1) ? sn : 0u;
+                }
+            }
+            if constexpr (TRACK) {
+                if (track) {
+                    // columns with a covered pixel in these four rows, OR-ed over the octet in three DPP steps (lane ^ 1, lane ^ 2, then the
+                    // mirror image within the half row: both quads are uniform by then)
+                    uint32_t L = (cov[0] | cov[1]) | (cov[2] | cov[3]);
+                    L |= (uint32_t)dpp_from<0xB1, 0xf>((int)L);      // quad_perm [1, 0, 3, 2]
+                    L |= (uint32_t)dpp_from<0x4E, 0xf>((int)L);      // quad_perm [2, 3, 0, 1]
+                    L |= (uint32_t)dpp_from<0x141, 0xf>((int)L);     // row_half_mirror
+                    if ((rq & 7) == 0) *crec = L;                    // (behind the read above: same wave, same address, program order)
+                    lines |= L;                                      // stored: what is covered now or was covered before
+                    if (lines == 0) continue;                        // background then and now in all 32 columns
                 }
             }
             if constexpr (EMIT) {
@@ -2232,6 +2273,7 @@ __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typ
                     for (int m = 0; m < 4; ++m) {
                         const int p = ph + 8 * m;
                         if (CHECK && p >= ncol) continue;
+                        if constexpr (TRACK) { if (!(lines & (1u << p))) continue; }     // one predicate for the three channels' stores
                         const uint32_t i01 = (A0 >> (8 * m)) & (uint32_t)(P - 1), i23 = (A1 >> (8 * m)) & (uint32_t)(P - 1);
                         const uint32_t off = off0 + (uint32_t)p * colb;
 #pragma unroll
@@ -2527,7 +2569,12 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         if constexpr (sizeof(OutT) != 4) __builtin_amdgcn_s_setprio(0);
         if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) {
             if constexpr (is_mask<OutT>::value) write_out_masks<BBLOCK, OutT>(planes, c.slices, c.out, img, res, X0, TWp, wpr, tid);
-            else write_out_bits<BBLOCK, NB, OutT, EMIT>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, c.slices);
+            else {
+                // (only the 4-wave instantiations for three workgroups per CU track the coverage; the 8-wave kernel and the 128-VGPR
+                // instantiations keep the write-out they had and store every line)
+                constexpr bool TRACK = PERSIST && sizeof(OutT) == 4 && !EMIT;
+                write_out_bits<BBLOCK, NB, OutT, EMIT, TRACK>(planes, tab, K, (OutT *)c.out, img, res, X0, TWp, wpr, tid, c.slices);
+            }
         }
         if constexpr (!PERSIST) break;
     }
@@ -3126,6 +3173,11 @@ TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys,
 
 #endif  // TDS_TESTING
 
+// bytes of the coverage record of n_img float32 images of res x res (0: no record at this resolution -- lines are tracked where res is a multiple of 32)
+static int64_t coverage_bytes(int64_t n_img, int res) {
+    return (res & 31) ? 0 : (int64_t)COV_HEADER_DW * 4 + n_img * (int64_t)(res >> 5) * (int64_t)(res >> 5) * 4;
+}
+
 static int common_checks(const char *fn, int64_t n_img, int res, int out_mode, const void *out, int &tw) {
     TDS_CHECK_ARG(n_img >= 0, "%s: negative image count", fn);
     TDS_CHECK_ARG(res > 0 && res <= 4096, "%s: resolution %d out of range (1..4096)", fn, res);
@@ -3142,6 +3194,13 @@ TDS_EXPORT int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *by
     TDS_CHECK_ARG(bytes, "tds_raster_index_slices_bytes: null output");
     TDS_CHECK_ARG(n_img >= 0 && res > 0 && res <= 4096, "tds_raster_index_slices_bytes: bad sizes");
     *bytes = (res & 3) ? 0 : n_img * (int64_t)((res + 31) / 32) * (int64_t)(res / 4) * 64;
+    return TDS_OK;
+}
+
+TDS_EXPORT int tds_raster_coverage_bytes(int64_t n_img, int res, int64_t *bytes) {
+    TDS_CHECK_ARG(bytes, "tds_raster_coverage_bytes: null output");
+    TDS_CHECK_ARG(n_img >= 0 && res > 0 && res <= 4096, "tds_raster_coverage_bytes: bad sizes");
+    *bytes = coverage_bytes(n_img, res);
     return TDS_OK;
 }
 
@@ -3257,13 +3316,25 @@ __global__ void put_mask_table_kernel(uint32_t *dst, MaskTable t) {
 #endif  // TDS_RASTER_MASKS_TU
 
 namespace {
+// One thread, in stream order right before a launch that maintains a coverage record: does the record's header describe this launch's output
+// (then, unless the caller asked for every line, the launch may leave alone the lines that were and stay background), and the header of
+// what the launch leaves behind.  The background is index 0 of the pair table: 0.0f in every channel.
+__global__ void coverage_prepare_kernel(uint32_t *hdr, uint32_t res, uint64_t n_img, uint64_t out, int rewrite_all) {
+    if (threadIdx.x != 0) return;
+    const uint32_t bg = __float_as_uint(0.0f);
+    const uint32_t want[COV_MODE] = {COV_MAGIC, res, (uint32_t)n_img, (uint32_t)(n_img >> 32), (uint32_t)out, (uint32_t)(out >> 32), bg, bg, bg};
+    bool same = true;
+    for (int i = 0; i < COV_MODE; ++i) { same = same && hdr[i] == want[i]; hdr[i] = want[i]; }
+    hdr[COV_MODE] = (same && !rewrite_all) ? COV_SKIP : 0u;
+}
+
 // The launches of a Bits or Split plan, the output tag F where `first`, else S: float / uint8_t for the image, MaskBits / MaskU8 for the masks.
 // Split: K3s lists each camera's faces, K3r rasterises the lists, and the bit-plane launch runs over the cameras whose list overflowed (normally
 // none).  cm.slices: where a float32 image's differentiable call stores its index slices (the 4-wave instantiation that does), or the masks'
 // channel table.  fn: the entry point, for the errors.
 template <typename F, typename S>
 auto launch_bit_planes(const char *fn, const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff,
-                       bool first, hipStream_t s) {
+                       bool first, bool emit_slices, hipStream_t s) {
     auto with_tag = [&](auto f) { if (first) f(F()); else f(S()); };
     const int64_t n_img = cm.n_img;
     const uint32_t *only = nullptr;
@@ -3290,7 +3361,8 @@ auto launch_bit_planes(const char *fn, const RasterPlan &p, const SceneArgsEx &a
     with_tag([&](auto t) {
         using T = decltype(t);
         if constexpr (std::is_same<T, float>::value) {
-            if (cm.slices) {            // differentiable calls (float32, four waves): the instantiation that also stores the index slices
+            if (emit_slices) {          // differentiable calls (float32, four waves): the instantiation that also stores the index slices
+                                        // (cm.slices alone does not say so: a plain launch carries the coverage record there)
                 with_args(a, [&](const auto &args) { with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<4, nb, float, std::decay_t<decltype(args)>, true>, args); }); });
                 return;
             }
@@ -3311,7 +3383,7 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
                       void *workspace, int64_t workspace_bytes, const uint32_t *actor_keys, int n_actor_keys, int actor_key_per_camera, const float *extra_tri, const uint32_t *extra_key, int64_t n_extra, tds_raster_aux_t *aux, void *stream,
                       const uint32_t *key_channels, int n_channels) {
     TDS_CHECK_ARG(B >= 0 && Nc >= 0 && N >= 0 && N < (1 << 20), "tds_raster_scene: bad sizes");
-    if (aux) { aux->n_keys = 0; aux->index_bits = 0; }
+    if (aux) { aux->n_keys = 0; aux->index_bits = 0; aux->coverage_maintained = 0; }
     TDS_CHECK_ARG(ms.renders, "tds_raster_scene: the map was created without rendering data");
     const bool masks = is_mask_mode(out_mode);
     if (masks) {
@@ -3337,6 +3409,11 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
         TDS_CHECK_ARG(need > 0 && out_mode == TDS_OUT_F32, "tds_raster_scene: index slices need a float32 image whose resolution is a multiple of 4");
         TDS_CHECK_ARG(aux->index_slices_bytes >= need, "tds_raster_scene: index slices buffer too small (%lld < %lld bytes)",
                       (long long)aux->index_slices_bytes, (long long)need);
+    }
+    const int64_t cov_need = (aux && aux->coverage && !masks && out_mode == TDS_OUT_F32 && !want_slices) ? coverage_bytes(n_img, res) : 0;
+    if (cov_need > 0) {
+        TDS_CHECK_ARG(aux->coverage_bytes >= cov_need, "tds_raster_scene: coverage record too small (%lld < %lld bytes)", (long long)aux->coverage_bytes, (long long)cov_need);
+        TDS_CHECK_ARG(((uintptr_t)aux->coverage & 15) == 0, "tds_raster_scene: the coverage record must be 16-byte aligned");
     }
     // the key table: the distinct keys of the map(s) and, where there are agents or per-camera triangles, the actor keys the caller listed; ascending
     const bool listed = actor_keys && n_actor_keys > 0;
@@ -3379,10 +3456,21 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     cm.slices = (uint32_t *)(ws + qoff - MASK_TABLE_BYTES);
     hipLaunchKernelGGL(put_mask_table_kernel, dim3(1), dim3(MASK_TABLE_DW), 0, s, cm.slices, mt);
     TDS_LAUNCH_CHECK("put_mask_table_kernel");
-    return launch_bit_planes<MaskBits, MaskU8>("tds_raster_scene_masks", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_MASK_BITS, s);
+    return launch_bit_planes<MaskBits, MaskU8>("tds_raster_scene_masks", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_MASK_BITS, false, s);
 #else
+    // The rule (stated in include/tdship.h, coverage_maintained): the fused bit-plane launch of a plain float32 image in 4-wave workgroups at three per
+    // CU (p.nwv == 4 && !p.four_per_cu: the `..., false, 3>` instantiations, whole images or strips) maintains the buffer's coverage record (in cm.slices:
+    // no slices are wanted) and, unless told to rewrite everything, leaves alone the background lines the record vouches for; every other form and
+    // workgroup shape (eight waves; four workgroups per CU) stores every pixel and leaves the record alone
+    if (p.form == RasterForm::Bits && p.nwv == 4 && !p.four_per_cu && cov_need > 0 && !(g_knobs.debug & TDS_RASTER_DBG_NO_STORE)) {
+        hipLaunchKernelGGL(coverage_prepare_kernel, dim3(1), dim3(64), 0, s, aux->coverage, (uint32_t)res, (uint64_t)n_img, (uint64_t)(uintptr_t)out,
+                           (aux->flags & TDS_RASTER_REWRITE_ALL) ? 1 : 0);
+        TDS_LAUNCH_CHECK("coverage_prepare_kernel");
+        cm.slices = aux->coverage;
+        aux->coverage_maintained = 1;
+    }
     if (p.form == RasterForm::Split || p.form == RasterForm::Bits)
-        return launch_bit_planes<float, uint8_t>("tds_raster_scene", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_F32, s);
+        return launch_bit_planes<float, uint8_t>("tds_raster_scene", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_F32, want_slices, s);
     if (p.form == RasterForm::Binned) {
         uint32_t *counts = (uint32_t *)ws; uint4 *lists = (uint4 *)(ws + p.ws.lists);
         launch(bin_faces_kernel, (n_img + BIN_WAVES - 1) / BIN_WAVES, BIN_WAVES * 64, 0, s, a, cm, p.tw, counts, lists, (int)p.caps);

@@ -24,6 +24,9 @@ from torchdrivesim_amd.utils import Resolution
 class HipRendererConfig(RendererConfig):
     backend: str = 'hip'
     out_dtype: str = 'float32'      #: 'float32' (reference-faithful values 0..255) or 'uint8' (same values, 4x fewer bytes)
+    #: renders into an `_ops.owned_image` buffer (allocate_image_ring) do not store again the lines that were and stay background.  Switch off
+    #: where something writes into those buffers that torch's version counter does not show (`_ops.use_write_skipping`)
+    write_skipping: bool = True
 
 
 @dataclass
@@ -128,7 +131,8 @@ class HipRenderer(BirdviewRenderer):
                                           extra_tri=extra_tri, extra_key=extra_key, key_colors=key_colors, color_keys=color_keys, trim=self.trim,
                                           ego_cameras=ego_cameras)
         return _ops.raster_scene(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, side, out_dtype=self.out_dtype,
-                                 key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out)
+                                 key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out,
+                                 write_skipping=bool(getattr(self.cfg, 'write_skipping', True)))
 
     def render_scene_masks(self, static_map, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor, camera_xy: Tensor,
                            camera_sc: Tensor, key_channels: Dict[int, int], n_channels: int, res: Optional[Resolution] = None,
@@ -169,11 +173,17 @@ class _DeviceTimer:
         torch.cuda.synchronize(self.device)
         return [ev[r].elapsed_time(ev[r + 1]) for r in range(reps)]
 
+    def _full_render(self, buf):
+        # the probe judges the WRITE PATH into the buffer's pages: every timed render stores every line (a render that skips the background lines of
+        # the image before it would be timed on half the stream); the render still leaves the buffer with an image and a valid coverage record
+        _ops.forget_coverage(buf)
+        self.render(buf)
+
     def first_touch(self, buf) -> float:
-        return self._ms(lambda: self.render(buf), 1)[0]
+        return self._ms(lambda: self._full_render(buf), 1)[0]
 
     def launch(self, buf) -> float:
-        return min(self._ms(lambda: self.render(buf), self.reps))
+        return min(self._ms(lambda: self._full_render(buf), self.reps))
 
     def fill(self, buf) -> float:
         return min(self._ms(lambda: buf.fill_(0), 2))
