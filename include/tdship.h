@@ -82,7 +82,8 @@ int tds_unicycle_step_bwd_f32(const float *state, const float *action, const flo
  *   present B x N      uint8 (already restricted to the requested agent types, simulator.py:1086-1089)
  *   out     B x A      collision_i = sum_j o_ij present_j - max_j o_ij present_j   
  *   overlap B x A      uint64 bit j set iff o_ij present_j > 0, j != i   (NULL to skip; requires N <= 64)
- *   partner B x A      int32 arg-max_j!=i of o_ij present_j, -1 if none   (NULL to skip)   [new outputs, SURVEY R8] */
+ *   partner B x A      int32 arg-max_j!=i of o_ij present_j, -1 if none   (NULL to skip)   [new outputs, SURVEY R8]
+ *                      ties: the LOWEST j != i that attains the largest o_ij present_j > 0 */
 int tds_collision_f32(const float *boxes, const float *sc, const uint8_t *present, float *out, uint64_t *overlap,
                       int32_t *partner, int64_t B, int64_t A, int64_t N, int metric, void *stream);
 /* backward: grad_out B x A -> grad_boxes B x N x 5 (psi column = 0), grad_sc B x N x 2; both are OVERWRITTEN */

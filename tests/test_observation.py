@@ -31,6 +31,21 @@ def test_oracle_occlusion_matches_reference(oracle):
         assert (~m & g[f'{tag}_present'][:, None, :]).any()          # somebody is hidden behind somebody
 
 
+def test_oracle_occlusion_matches_reference_on_edge_cases(oracle):
+    """the reference's own masks where line_circle_intersection branches: a target at the ego's place (a_safe), a sight line tangent to a disc
+    (discriminant 0), zero-width, absent and NaN entities -- the sets of tests/occlusion_cases.py, which tests/test_gpu_occlusion.py runs larger"""
+    import occlusion_cases as oc
+    g = load_golden('g10b_observation_edges.npz')
+    A = int(g['n_exposed'])
+    for name in oc.SETS[1:]:
+        state, size, present, marks = oc.make(2, A, 16, name)
+        for key, a in (('state', state), ('size', size), ('present', present)):          # the fixture holds these very inputs
+            np.testing.assert_array_equal(g[f'{name}_{key}'], a)
+        m = oracle.occlusion_mask(state, size, present, A)
+        np.testing.assert_array_equal(m, g[f'{name}_mask'])
+        oc.check_conditions(2, A, 16, name, state, size, present, marks, g[f'{name}_mask'])
+
+
 def test_noise_levels_and_noise_free_accessors():
     from torchdrivesim_amd.observation_noise import StandardSensingObservationNoise
     g = load_golden('g10_observation.npz')

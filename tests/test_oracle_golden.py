@@ -116,6 +116,24 @@ def test_sort_indices_example(oracle):
     assert nv[0] == 4 and idx[0].tolist() == [0, 5, 6, 3, 0, 8, 8, 8, 8]
 
 
+def test_iou_sliver_with_a_vertex_on_its_centroid(oracle):
+    """g2c: the intersection is a sliver with three valid vertices, one of them ON their centroid.  Its angle is NaN, argsort lists it behind the
+    masked-out candidates (angle +inf), and the reference closes the polygon through the masked-out candidate its (unstable) argsort lists
+    first: a masked intersection, (0, 0), IoU 2.4e-3.  The oracle keeps the two sortable vertices in the reference's order and takes the
+    masked-out candidate of the LOWEST index (corner 0 of box 1), IoU 2.1e-4; the true overlap is below 1e-9 m^2, either figure is rounding
+    noise of the shoelace sum 3 km from the origin.  K2a follows the oracle's rule (tests/test_gpu_collision_paths.py, (8, 512) rim)."""
+    g = load_golden('g2c_iou_sliver.npz')
+    iou, idx, nvalid, area = oracle.iou_pairs(g['box1'], g['box2'], g['sc1'], g['sc2'], debug=True)
+    assert nvalid[0] == 3
+    corners = np.concatenate([oracle.box2corners(g['box1'], g['sc1'])[0], oracle.box2corners(g['box2'], g['sc2'])[0]])
+    poly = g['polygon'][0]
+    assert idx[0, 1] < 8 and idx[0, 2] < 8 and idx[0, 3] == idx[0, 0]              # ..., a corner of box 2, corner 0 of box 1, closed
+    np.testing.assert_array_equal(poly[1], corners[idx[0, 1]])                      # the sortable vertices and their order are the reference's
+    np.testing.assert_array_equal(poly[0], poly[3])
+    np.testing.assert_array_equal(poly[2], [0.0, 0.0])                              # the reference's third vertex is a masked-out candidate
+    assert idx[0, 2] == 0 and 0 < iou[0] < g['iou'][0] < 3e-3
+
+
 @pytest.mark.parametrize('metric', ['iou', 'discs'])
 def test_scene_collision(oracle, metric):
     g = load_golden('g2_scene_collision.npz')

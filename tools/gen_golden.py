@@ -644,6 +644,23 @@ def gen_traffic(out):
     print('g8 violations per step', [int(d[f'violation_{t}'].sum()) for t in range(T + 2)], 'of', B * A)
 
 
+# G2c: a Rotated-IoU pair whose intersection is a sliver a few fp32 spacings wide, 3 km from the origin: one of its three valid vertices
+#      coincides with their centroid, its angle is NaN, argsort puts it behind the masked-out candidates (angle +inf), and the polygon is closed
+#      through whichever masked-out candidate argsort (not stable) lists first.  Recorded: the pair, the reference's IoU and its polygon.
+def gen_iou_sliver(out):
+    from torchdrivesim.infractions import iou_differentiable
+    from torchdrivesim._iou_utils import box2corners_th, oriented_box_intersection_2d
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import collision_cases as cc
+    boxes, _ = cc.make(8, 512, 'iou', 'rim')
+    b1, b2 = torch.from_numpy(boxes[0, 5])[None, None], torch.from_numpy(boxes[0, 314])[None, None]
+    area, polygon = oriented_box_intersection_2d(box2corners_th(b1), box2corners_th(b2))
+    sc = lambda b: torch.stack([torch.sin(b[..., 4]), torch.cos(b[..., 4])], -1)
+    np.savez_compressed(os.path.join(out, 'g2c_iou_sliver.npz'), box1=npy(b1[0]), box2=npy(b2[0]), sc1=npy(sc(b1)[0]), sc2=npy(sc(b2)[0]),
+                        iou=npy(iou_differentiable(b1, b2)[0]), area=npy(area[0]), polygon=npy(polygon[0]))
+    print('g2c iou', float(iou_differentiable(b1, b2)), 'area', float(area))
+
+
 # --------------------------------------------------------------------------------------
 # G10: observation model for non-visual policies: occlusion mask of StandardSensingObservationNoise, the distance-dependent
 #      standard deviation of its state noise, and get_noisy_all_agents_relative with the noise-free base model
@@ -678,6 +695,25 @@ def gen_observation(out):
         d[f'{tag}_noisy_absolute'] = npy(sim.get_noisy_all_agents_absolute())
     np.savez_compressed(os.path.join(out, 'g10_observation.npz'), **d)
     print('g10 occluded fraction', {t: float(1 - d[f'{t}_mask'].mean()) for t in 'abc'})
+
+
+# G10b: the same mask on the hand-placed edge cases of tests/occlusion_cases.py (inputs only are taken from there) at E = 16: collinear,
+#       coincident (a target at the ego's place), tangent, zero-width, absent and NaN entities
+def gen_observation_edges(out):
+    from torchdrivesim.observation_noise import StandardSensingObservationNoise, StandardSensingObservationNoiseConfig
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import occlusion_cases as oc
+    B, A, E = 2, 3, 16
+    d = dict(n_exposed=np.array(A))
+    for name in oc.SETS[1:]:
+        state, size, present = (torch.from_numpy(a) for a in oc.make(B, A, E, name)[:3])
+        sim = make_sim(state[:, :A].clone(), size[:, :A].clone(), present[:, :A].clone(),
+                       npc=dict(state=state[:, A:].clone(), size=size[:, A:].clone(), present=present[:, A:].clone()))
+        std = StandardSensingObservationNoise(StandardSensingObservationNoiseConfig())
+        d[f'{name}_state'], d[f'{name}_size'], d[f'{name}_present'] = npy(state), npy(size), npy(present)
+        d[f'{name}_mask'] = npy(std.get_noisy_present_mask(sim))
+    np.savez_compressed(os.path.join(out, 'g10b_observation_edges.npz'), **d)
+    print('g10b hidden fraction', {n: float(1 - d[f'{n}_mask'].mean()) for n in oc.SETS[1:]})
 
 
 # --------------------------------------------------------------------------------------
@@ -889,6 +925,12 @@ def main():
     if args.only == 'noisy':
         gen_noisy_perception(args.out, cv2, load_town01())
         return
+    if args.only == 'iou_sliver':
+        gen_iou_sliver(args.out)
+        return
+    if args.only == 'observation_edges':
+        gen_observation_edges(args.out)
+        return
     if args.only == 'discs_n':
         gen_discs_n(args.out)
         return
@@ -907,12 +949,14 @@ def main():
     gen_kinematic(args.out)
     gen_collision(args.out)
     gen_scene_collision(args.out)
+    gen_iou_sliver(args.out)
     town = gen_town01(args.out)
     gen_offroad(args.out, town)
     gen_mesh_and_preraster(args.out, cv2, town)
     gen_grads(args.out, town)
     gen_traffic(args.out)
     gen_observation(args.out)
+    gen_observation_edges(args.out)
     gen_waypoints(args.out, cv2, town)
     gen_traffic_lights(args.out)
     gen_discs_n(args.out)

@@ -166,6 +166,7 @@ __device__ float intersection_area(const Corners &c1, const Corners &c2, float *
     // angular sort of the <= 8 valid vertices.  acos is monotone, so ordering by the angle equals ordering by
     // key = (dy > 0) ? -q : 2 + q with q = dx / r  (_iou_utils.py:181-186); invalid slots sort last.
     float sxv[8], syv[8], key[8];
+    unsigned nan_live = 0;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         float x = scr[(2 * s) * 64 + lane], y = scr[(2 * s + 1) * 64 + lane];
@@ -175,7 +176,29 @@ __device__ float intersection_area(const Corners &c1, const Corners &c2, float *
         bool live = s < n;
         sxv[s] = live ? x : 0.0f;
         syv[s] = live ? y : 0.0f;
-        key[s] = live ? ((k == k) ? k : 3.5f) : 4.0f;      // NaN keys after valid ones, dead slots last
+        key[s] = live ? k : 4.0f;                           // dead slots last
+        if (live && k != k) nan_live |= 1u << s;
+    }
+    if (nan_live) {
+        // A valid vertex whose angle is NaN (it coincides with the centroid: slivers a few ulps wide far from the origin) sorts AFTER the
+        // masked-out candidates, whose angle is +inf (_iou_utils.py:186-187, argsort puts NaN last), so the first n sorted indices hold,
+        // in its place, the masked-out candidate of the lowest index: a corner that is not inside the other box, or a masked intersection (0, 0).
+        int cand = 0;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            if ((nan_live >> s) & 1) {
+                while ((mask >> cand) & 1) ++cand;          // n <= 8 of the 24 candidates are valid: always found
+                float x = 0.0f, y = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (cand == k) { x = c1.x[k]; y = c1.y[k]; }
+                    if (cand == 4 + k) { x = c2.x[k]; y = c2.y[k]; }
+                }
+                sxv[s] = x; syv[s] = y;
+                key[s] = 3.125f + 0.03125f * (float)cand;   // after every valid key (<= 3), in index order, before the dead slots (4)
+                ++cand;
+            }
+        }
     }
 #define TDS_CSWAP(a, b)                                                                      \
     {                                                                                        \
@@ -241,13 +264,18 @@ __device__ float discs_pair_n(const Box &b1, const Box &b2, int nps) {
     return (l != l) ? l : fmaxf(l, 0.0f);
 }
 
+template <int METRIC>
 __device__ __forceinline__ Box load_box(const float *boxes, const float *sc, int64_t idx) {
     Box b;
     const float *p = boxes + idx * 5;
     b.x = scrub(p[0]); b.y = scrub(p[1]); b.l = scrub(p[2]); b.w = scrub(p[3]);
     float psi = p[4];
     b.s = sc[idx * 2]; b.c = sc[idx * 2 + 1];
-    if (psi != psi) { b.s = 0.0f; b.c = 1.0f; }      // a NaN heading is scrubbed to 0 before sin/cos (simulator.py:1095)
+    if (psi != psi) {                                // a NaN heading is scrubbed to 0 before sin/cos (simulator.py:1095) ...
+        b.s = 0.0f; b.c = 1.0f;
+        // ... and the discs metric then still turns a box that is wider than long by fl32(pi/2) (infractions.py:404): [sin, cos] of that angle
+        if (METRIC == TDS_METRIC_DISCS && b.w > b.l) { b.s = 1.0f; b.c = -4.37113883e-8f; }
+    }
     return b;
 }
 
@@ -281,28 +309,27 @@ __device__ __forceinline__ void row_acc_chunk(RowAcc &a, float o, bool valid, in
     }
 }
 
-// grid = (B, ceil(A / (4 waves * ROWS_PER_WAVE))), dynamic LDS = 4 * (16*64 + Npad) floats
+// grid = (B, ceil(A / (4 waves * ROWS_PER_WAVE))), dynamic LDS = 4 * 16*64 floats (16 KiB) whatever N is
 template <int METRIC>
 __global__ void __launch_bounds__(CBLOCK) collision_kernel(const float *__restrict__ boxes, const float *__restrict__ sc,
                                                            const uint8_t *__restrict__ present, float *__restrict__ out,
                                                            uint64_t *__restrict__ overlap, int32_t *__restrict__ partner, int A, int N) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int npad = (N + 63) & ~63;
-    float *scr = smem + wave * (16 * 64 + npad);
+    float *scr = smem + wave * (16 * 64);
     const int64_t b = blockIdx.x;
     const int row0 = (blockIdx.y * (CBLOCK / 64) + wave) * ROWS_PER_WAVE;
     for (int r = 0; r < ROWS_PER_WAVE; ++r) {
         const int i = row0 + r;
         if (i >= A) break;                                           // wave-uniform
-        Box bi = load_box(boxes, sc, b * N + i);
+        Box bi = load_box<METRIC>(boxes, sc, b * N + i);
         Corners ci = corners_of(bi);
         RowAcc acc = row_acc_init();
         for (int j0 = 0; j0 < N; j0 += 64) {
             int j = j0 + lane;
             float o = 0.0f;
             if (j < N) {
-                Box bj = load_box(boxes, sc, b * N + j);
+                Box bj = load_box<METRIC>(boxes, sc, b * N + j);
                 if (METRIC == TDS_METRIC_IOU) {
                     Corners cj = corners_of(bj);
                     o = iou_pair(bi, ci, bj, cj, scr, lane);
@@ -338,7 +365,7 @@ __global__ void __launch_bounds__(CBLOCK) collision_scene_iou_kernel(const float
     uint32_t *list = (uint32_t *)(O + A * N);               // A x N at most
     if (tid == 0) n_near = 0;
     for (int j = tid; j < N; j += CBLOCK) {
-        const Box q = load_box(boxes, sc, b * N + j);
+        const Box q = load_box<TDS_METRIC_IOU>(boxes, sc, b * N + j);
         bx[6 * j] = q.x; bx[6 * j + 1] = q.y; bx[6 * j + 2] = q.l; bx[6 * j + 3] = q.w; bx[6 * j + 4] = q.s; bx[6 * j + 5] = q.c;
     }
     __syncthreads();
@@ -444,7 +471,7 @@ TDS_EXPORT int tds_collision_f32(const float *boxes, const float *sc, const uint
     }
     const int rows_per_block = (CBLOCK / 64) * ROWS_PER_WAVE;
     dim3 grid((unsigned)B, (unsigned)((A + rows_per_block - 1) / rows_per_block));
-    size_t lds = (size_t)(CBLOCK / 64) * (16 * 64 + ((N + 63) & ~63)) * sizeof(float);
+    const size_t lds = (size_t)(CBLOCK / 64) * (16 * 64) * sizeof(float);      // the per-wave scratch of intersection_area
     if (metric == TDS_METRIC_IOU)
         hipLaunchKernelGGL(collision_kernel<TDS_METRIC_IOU>, grid, dim3(CBLOCK), lds, (hipStream_t)stream, boxes, sc, present, out,
                            overlap, partner, (int)A, (int)N);
