@@ -259,6 +259,18 @@ int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t *scene_map,
  * renders with that record may have written to `out` -- the skipped lines are assumed to hold the background (0.0f) the earlier call left
  * there.  aux == NULL or coverage == NULL: every pixel is stored, as before. */
 #define TDS_RASTER_REWRITE_ALL 2
+/* Prepared scan set-ups (optional): a scratch table that lets the persistent bit-plane launch compute each camera's scan set-up (trim polygon,
+ * grid window, grid rows) once, in a small kernel in front of it, instead of in every wave of the camera's workgroup.
+ *   camera_prep        DEVICE buffer of at least tds_raster_camera_prep_bytes(B * Nc, res, out_mode, n_keys) bytes, 16-byte aligned, or NULL.  The
+ *                      call writes it and reads it in stream order; it carries nothing from call to call, and two launches that may overlap in
+ *                      time must not share one.  It is NOT part of the workspace.
+ *   camera_prep_bytes  size of that buffer
+ *   flags              TDS_RASTER_HAS_CAMERA_PREP: the struct the caller passes HAS these two fields.  They were appended to a struct that ended
+ *                      with coverage_bytes (112 bytes); the library reads past that only when the flag is set, so a caller built against the
+ *                      shorter struct stays valid and simply gets no table.
+ * The pixels never depend on it: no flag, NULL, a buffer that is too small or misaligned, or a call served by another launch (uint8 or float32 in 8-wave
+ * workgroups or at four workgroups per CU, the split form, the masks, packed keys) renders exactly as before and leaves the buffer alone. */
+#define TDS_RASTER_HAS_CAMERA_PREP 4
 typedef struct tds_raster_aux {
     uint32_t *index_slices;
     int64_t index_slices_bytes;
@@ -269,10 +281,15 @@ typedef struct tds_raster_aux {
     int32_t coverage_maintained;    /* out */
     uint32_t *coverage;         /* in */
     int64_t coverage_bytes;     /* in */
+    void *camera_prep;          /* in; read only with TDS_RASTER_HAS_CAMERA_PREP */
+    int64_t camera_prep_bytes;  /* in; read only with TDS_RASTER_HAS_CAMERA_PREP */
 } tds_raster_aux_t;
 int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes);
 /* bytes of the coverage record of n_img images of res x res (0: no lines are tracked at this resolution -- res is no multiple of 32) */
 int tds_raster_coverage_bytes(int64_t n_img, int res, int64_t *bytes);
+/* bytes of the table of prepared scan set-ups for n_img images of res x res in `out_mode` with `n_keys` distinct keys (-1: not known): one
+ * record per camera and strip of the launch; 0 where no launch of that shape takes the table.  Bad arguments: TDS_EINVAL. */
+int tds_raster_camera_prep_bytes(int64_t n_img, int res, int out_mode, int n_keys, int64_t *bytes);
 
 int tds_raster_scene(const tds_map_t *map, const float *state, const float *agent_sc, const float *tmpl,
                      const uint32_t *actor_key, const uint8_t *mask, const float *cam_xy, const float *cam_sc,
@@ -710,6 +727,8 @@ int tds_range_scan_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, 
 #define TDS_RASTER_DBG_NO_8WAVES 524288        /* ... in half-image strips instead */
 #define TDS_RASTER_DBG_WIDEST_STRIPS 1048576   /* strips as wide as the LDS allows instead of equal ones (nine and more keys) */
 #define TDS_RASTER_DBG_NO_EXTRA_STRIP 2097152  /* never one strip more than necessary (nine and more keys) */
+#define TDS_RASTER_DBG_PROLOGUE_TWICE 4194304  /* the fused bit-plane kernel runs its per-item prologue (trim polygon, scan window, grid rows) a second
+                                                  time and drops the result: the difference to a plain launch is what the prologue costs */
 
 #ifdef TDS_TESTING
 /* force the LDS strip width of K3 (0 = automatic, else 8 .. 128 output rows) */
@@ -724,6 +743,9 @@ int tds_raster_set_list_waves(int waves);
 int tds_raster_set_debug(int flags);
 /* read and reset the 16 work counters of the bit-plane kernel */
 int tds_raster_get_stats(unsigned long long *out16);
+/* read and reset the two counters of the prepared scan set-ups (TDS_RASTER_DBG_STATS): work items of the persistent bit-plane launches that used
+ * their record of tds_raster_aux_t::camera_prep, and work items that computed their set-up in the kernel */
+int tds_raster_get_prep_stats(unsigned long long *out2);
 /* which launches tds_raster_scene makes for a call of this shape (its plan_raster_scene, with explicit knobs: those of the four setters above).
  * n_keys: distinct keys (-1: more than 15); workspace_bytes: as the caller passes it (0: none).
  * form: 0 bit planes, 1 split (K3s + K3r + the bit planes over overflowed cameras), 2 packed keys binned, 3 packed keys fused, 4 TDS_ELIMIT.

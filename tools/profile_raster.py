@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Runs only the K3 raster kernel on the bench workload (for rocprofv3 and for ablations).
-   python tools/profile_raster.py [--batch 256] [--iters 5] [--tw 0] [--debug 0] [--u8]"""
+   python tools/profile_raster.py [--batch 256] [--iters 5] [--tw 0] [--debug 0] [--u8] [--owned]"""
 import argparse
 import ctypes
 import os
@@ -32,6 +32,8 @@ def main():
     ap.add_argument('--list-lds', type=int, nargs='*', default=[], help='testing build: LDS budgets (KiB per workgroup) of the list rasteriser of the split path to sweep')
     ap.add_argument('--no-bits', action='store_true', help='packed-key kernels instead of the bit-plane kernel')
     ap.add_argument('--no-ws', action='store_true', help='fused per-strip kernel instead of the binned persistent kernel')
+    ap.add_argument('--owned', action='store_true', help='render every time into ONE owned buffer (_ops.owned_image): after the first render the launches '
+                    'are the write-skipping ones of a loop over a ring (float32, resolutions that are a multiple of 32)')
     ap.add_argument('--steps-before', type=int, default=5, help='simulation steps before rendering (spreads the agents)')
     args = ap.parse_args()
     from torchdrivesim_amd import _native, _ops
@@ -77,7 +79,13 @@ def main():
     torch.cuda.synchronize()
     nbytes = img.numel() * img.element_size()
     print(f'images {img.shape[0] * img.shape[1]}, output {nbytes / 1e9:.2f} GB, nonzero fraction {(img[:8] > 0).float().mean().item():.3f}')
+    shape, dtype = tuple(img.shape), img.dtype
     del img
+    out = {}
+    if args.owned:
+        out['out'] = _ops.owned_image(shape, dtype, dev)
+        sim.render_egocentric(res=res, fov=bench.FOV, **out)          # stores every line and leaves the coverage record the next launches skip by
+        torch.cuda.synchronize()
     for tw, bw, ll, lwv in [(t, b, l, w) for t in args.tw for b in args.bits_waves for l in (args.list_lds or [0]) for w in (args.list_waves or [0])]:
         hooks = L is not None and hasattr(L, 'tds_raster_set_debug')          # (a product build loaded with --lib has none)
         if hooks:
@@ -91,7 +99,7 @@ def main():
                 L.tds_raster_set_debug(dbg)
             _ops.raster_events = []
             for _ in range(args.iters):
-                sim.render_egocentric(res=res, fov=bench.FOV)
+                sim.render_egocentric(res=res, fov=bench.FOV, **out)
             torch.cuda.synchronize()
             ms = np.array([a.elapsed_time(b) for a, b in _ops.raster_events])
             _ops.raster_events = None

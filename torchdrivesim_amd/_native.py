@@ -25,6 +25,7 @@ OUT_F32, OUT_U8 = 0, 1
 OUT_MASK_U8, OUT_MASK_BITS = 2, 3     # semantic masks (tds_raster_scene_masks): 0 / 1 bytes, packed bits
 RASTER_NO_TRIM = 1
 RASTER_REWRITE_ALL = 2
+RASTER_HAS_CAMERA_PREP = 4
 
 
 class RasterDebug(enum.IntFlag):
@@ -51,6 +52,7 @@ class RasterDebug(enum.IntFlag):
     NO_8WAVES = 524288
     WIDEST_STRIPS = 1048576
     NO_EXTRA_STRIP = 2097152
+    PROLOGUE_TWICE = 4194304
 
 _lib = None
 
@@ -60,6 +62,12 @@ class RasterAux(ctypes.Structure):
     _fields_ = [('index_slices', ctypes.c_void_p), ('index_slices_bytes', ctypes.c_int64), ('keys', ctypes.c_uint32 * 16),
                 ('n_keys', ctypes.c_int32), ('index_bits', ctypes.c_int32), ('flags', ctypes.c_int32), ('coverage_maintained', ctypes.c_int32),
                 ('coverage', ctypes.c_void_p), ('coverage_bytes', ctypes.c_int64)]
+
+
+class RasterAuxPrep(RasterAux):
+    """tds_raster_aux_t with the two fields appended to it for the table of prepared scan set-ups; the library reads them only when `flags` has
+    RASTER_HAS_CAMERA_PREP, so the shorter RasterAux stays a valid argument"""
+    _fields_ = [('camera_prep', ctypes.c_void_p), ('camera_prep_bytes', ctypes.c_int64)]
 
 
 # One declaration per entry point of include/tdship.h, its parameters under the header's names (tests/test_abi.py holds the table to the header).
@@ -101,6 +109,7 @@ tds_offroad_multi_bwd_f32(handle set, i32* scene_map, int64 agents_per_scene, f3
     f32* grad_sc, int64 n_agents, float threshold, stream stream)
 tds_raster_index_slices_bytes(int64 n_img, int res, host* bytes)
 tds_raster_coverage_bytes(int64 n_img, int res, host* bytes)
+tds_raster_camera_prep_bytes(int64 n_img, int res, int out_mode, int n_keys, host* bytes)
 tds_raster_scene(handle map, f32* state, f32* agent_sc, f32* tmpl, i32* actor_key, u8* mask, f32* cam_xy, f32* cam_sc, int64 B, int64 Nc, int64 N, float scale, int res,
     int out_mode, void* out, void* workspace, int64 workspace_bytes, host* actor_keys, int n_actor_keys, int actor_key_per_camera, f32* extra_tri, i32* extra_key,
     int64 n_extra, host* aux, stream stream)
@@ -180,6 +189,7 @@ tds_raster_set_list_lds(int lds_kb)
 tds_raster_set_list_waves(int waves)
 tds_raster_set_debug(int flags)
 tds_raster_get_stats(host* out16)
+tds_raster_get_prep_stats(host* out2)
 tds_raster_plan(int64 n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64 workspace_bytes, int cus, int force_tw,
     int bits_waves, int list_waves, int list_lds_kb, int debug, host* out)
 tds_testing_set_near_lists(int enabled)

@@ -682,6 +682,36 @@ def _raster_workspace(dev, n_img, res, out_mode=None, n_keys=-1):
     return ws if ws is not False else None
 
 
+#: The persistent bit-plane launch computes each camera's scan set-up (trim polygon, grid window, grid rows) once, in a small kernel in front of
+#: it, when it is given a table for the records (include/tdship.h, tds_raster_aux_t::camera_prep).  The table is scratch like the workspace -- one
+#: per (device, stream, thread, shape of the launch), its size asked for on a cache miss only, the least recently used dropped, nothing carried between calls -- but not part of it.  False: every workgroup
+#: computes its camera's set-up itself, as before; the pixels are the same either way (tests/test_gpu_camera_prep.py).
+use_camera_prep = True
+#: ... and for differentiable calls too.  Off by default: the launch that also stores the index slices writes every line and is bound by that
+#: stream, so the instructions saved buy nothing and the records' loads cost (config 5's forward launch at B = 256: 1.85 -> 1.87 - 1.89 ms with the
+#: table, three alternating runs each: profiles/camera_prep_timing.json); the native path takes the table all the same and is tested.
+use_camera_prep_with_slices = False
+_camera_preps = collections.OrderedDict()
+
+
+def _camera_prep_table(dev, n_img, res, out_mode, n_keys):
+    """the table of prepared scan set-ups for a launch of this shape, or None where no launch of that shape takes one"""
+    if not 0 < n_keys <= 15:                  # not known, or more than the bit-plane kernels take: packed keys, no table
+        return None
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (idx, torch.cuda.current_stream(dev).cuda_stream, threading.get_ident(), n_img, res, out_mode, int(n_keys))
+    tab = _camera_preps.get(key)
+    if tab is None:                           # the size is asked for on a miss only, as the workspace's is (False: this shape takes no table)
+        n = ctypes.c_int64(0)
+        nat.call('tds_raster_camera_prep_bytes', dev, n_img, res, out_mode, n_keys, ctypes.byref(n))
+        tab = _camera_preps[key] = torch.empty(int(n.value), dtype=torch.uint8, device=dev) if n.value > 0 else False
+        while len(_camera_preps) > _WORKSPACES_MAX:
+            _camera_preps.popitem(last=False)          # the tensor is freed stream-ordered by the caching allocator
+    else:
+        _camera_preps.move_to_end(key)
+    return tab if tab is not False else None
+
+
 # ---- where the images live --------------------------------------------------------------------------------------------------------
 #: The raster launch is bound by the HBM write stream, and what that stream reaches depends on the PHYSICAL pages under the image: about one
 #: large hipMalloc in three is served at 7/8 of the rate for as long as it lives, a buffer whose pages are spread out hardly ever is (one of 100 probed in round 4, in the 15/16 class; csrc/alloc.hip,
@@ -1005,7 +1035,7 @@ def _scene_call(fn, smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc
 
 
 def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, out_dtype=torch.float32, out=None, key_table=None,
-                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True):
+                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True, camera_prep=True):
     """Fused Simulator.render: state (B,N,4), agent_sc (B,N,2), tmpl (B,N,7,2), actor_key (B,N,2) int32 bit patterns -- or (B,Nc,N,2)
     when every camera sees its own colours (custom_agent_colors) --, mask (B,Nc,N) bool/uint8, cam_xy / cam_sc (B,Nc,2)
     -> (B,Nc,3,res,res) float32 [0,255] or uint8.  extra_tri (B,Nc,K,3,2) world-space triangles with keys extra_key (B,Nc,K) int32
@@ -1014,7 +1044,8 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     and the ascending key table of the launch, what the backward pass reads instead of the image; (image, None, None) when the call
     cannot be served by the bit-plane kernel.
     `out` an `owned_image` buffer (float32): the lines that held background after the last render into it and hold background again are not
-    stored a second time (see `use_write_skipping` for what the caller must not do to the buffer in between); write_skipping=False stores them."""
+    stored a second time (see `use_write_skipping` for what the caller must not do to the buffer in between); write_skipping=False stores them.
+    camera_prep=False (or `use_camera_prep`): no table of prepared scan set-ups is passed -- same pixels, the set-up is computed per workgroup."""
     assert out_dtype in (torch.float32, torch.uint8)
     dev = cam_xy.device
     mode = nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8
@@ -1043,21 +1074,29 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
         nbytes = ctypes.c_int64(0)
         nat.call('tds_raster_index_slices_bytes', dev, B * Nc, int(res), ctypes.byref(nbytes))
         slices = torch.empty(nbytes.value // 4, dtype=i32, device=dev)
-        aux = nat.RasterAux(index_slices=slices.data_ptr(), index_slices_bytes=nbytes.value)
+        aux = nat.RasterAuxPrep(index_slices=slices.data_ptr(), index_slices_bytes=nbytes.value)
     if not trim:
-        aux = aux if aux is not None else nat.RasterAux()
+        aux = aux if aux is not None else nat.RasterAuxPrep()
         aux.flags = nat.RASTER_NO_TRIM
     cov_ent = cov_rec = None
     if caller_out is not None and _owned_buffers:
         if out_dtype == torch.float32 and slices is None and B * Nc > 0:
             cov_ent, decision, cov_rec = _coverage_aux(caller_out, int(res), B * Nc, use_write_skipping and write_skipping)
             if cov_rec is not None:
-                aux = aux if aux is not None else nat.RasterAux()
+                aux = aux if aux is not None else nat.RasterAuxPrep()
                 aux.coverage, aux.coverage_bytes = cov_rec['cov'].data_ptr(), cov_rec['cov'].numel() * 4
                 if decision != 'skip':
                     aux.flags |= nat.RASTER_REWRITE_ALL
         else:
             forget_coverage(caller_out)
+    prep = None
+    if use_camera_prep and camera_prep and ws is not None and B * Nc > 0 and (slices is None or use_camera_prep_with_slices):
+        prep = _camera_prep_table(dev, B * Nc, int(res), mode, n_keys)
+    if prep is not None:
+        aux = aux if aux is not None else nat.RasterAuxPrep()
+        aux.camera_prep, aux.camera_prep_bytes = prep.data_ptr(), prep.numel()
+        aux.flags |= nat.RASTER_HAS_CAMERA_PREP          # (RasterAuxPrep: the struct has the two fields)
+
     def launch(aux):
         call((ws, 0 if ws is None else ws.numel(), kt, 0 if kt is None else len(key_table), 1 if (N > 0 and actor_key.dim() == 4) else 0),
              (None if aux is None else ctypes.byref(aux),))

@@ -89,6 +89,8 @@ struct CommonArgs {
                                 // bit-plane kernel (no slices wanted), the COVERAGE RECORD of the output buffer (tds_raster_aux_t::coverage):
                                 // one kernel argument serves both, the kernel has no register to spare for another
     int debug;                  // ablation switches for profiling (tds_raster_set_debug): TDS_RASTER_DBG_* of include/tdship.h
+    const void *prep;           // optional: one PrepRecord per work item (camera, strip), written by camera_prepare_kernel in front of the launch
+                                // (persistent bit-plane instantiations only; nullptr: every workgroup computes its item's scan set-up itself)
 };
 
 struct Camera {
@@ -101,7 +103,8 @@ struct Camera {
 // ---------------------------------------------------------------------------------------------------------
 
 // Cameras.reverse_transform_points_screen of the image corners + 1.05 margin (cv2.py:32-40, base.py:117-130)
-__device__ inline void make_polygon(Camera &cam, float scale, int res) {
+// (polygon_corners: the values alone -- camera_prepare_kernel computes them one camera per LANE; make_polygon: ... for the workgroup's camera)
+__device__ inline void polygon_corners(Camera &cam, float scale, int res) {
     const float cor[4][2] = {{0.f, 0.f}, {0.f, (float)res}, {(float)res, (float)res}, {(float)res, 0.f}};
     float mn = (float)res / 2.0f;
     float sumx = 0.0f, sumy = 0.0f;
@@ -121,11 +124,17 @@ __device__ inline void make_polygon(Camera &cam, float scale, int res) {
         cam.px[k] = mx + (cam.px[k] - mx) * 1.05f;
         cam.py[k] = my + (cam.py[k] - my) * 1.05f;
     }
-    // the camera is the same for the whole workgroup: keep it in scalar registers (the values were computed on the vector ALU)
+}
+// the camera is the same for the whole workgroup: keep it in scalar registers (the values were computed on, or loaded through, the vector unit)
+__device__ inline void camera_uniform(Camera &cam) {
     auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
 #pragma unroll
     for (int k = 0; k < 4; ++k) { cam.px[k] = uni(cam.px[k]); cam.py[k] = uni(cam.py[k]); }
     cam.cx = uni(cam.cx); cam.cy = uni(cam.cy); cam.s = uni(cam.s); cam.c = uni(cam.c);
+}
+__device__ inline void make_polygon(Camera &cam, float scale, int res) {
+    polygon_corners(cam, scale, res);
+    camera_uniform(cam);
 }
 
 // utils.is_inside_polygon :99-122
@@ -707,50 +716,58 @@ struct ScanState {
 // Lane r prepares grid row `row0 + r` of the scan: the cells of that row under the window polygon (the pixel window plus a 2 px
 // margin, a rotated rectangle in world space) and where their entries start and end.  The entries of consecutive cells of a
 // grid row are contiguous, so a row is ONE range of entries.
-__device__ __forceinline__ void scan_load_rows(ScanState &st, const MapView &m, const CommonArgs &c, const Camera &cam, int lane, int X0, int TWw,
-                                               int row0) {
+struct ScanQuad { float qx[4], qy[4], eps; };           // corners in order around the rectangle
+__device__ __forceinline__ void scan_quad(ScanQuad &q, const CommonArgs &c, const Camera &cam, int X0, int TWw) {
     const int res = c.res;
     const float half = (float)res / 2.0f;
     const float pxs[2] = {(float)X0 - 2.0f, (float)min(X0 + TWw, res) + 2.0f}, pys[2] = {-2.0f, (float)res + 2.0f};
-    float qx[4], qy[4];                                    // corners in order around the rectangle
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float x = -((pxs[(k == 1 || k == 2) ? 1 : 0] - half) / half) / c.scale, y = -((pys[k >= 2 ? 1 : 0] - half) / half) / c.scale;
-        qx[k] = cam.c * x - cam.s * y + cam.cx; qy[k] = cam.s * x + cam.c * y + cam.cy;
+        q.qx[k] = cam.c * x - cam.s * y + cam.cx; q.qy[k] = cam.s * x + cam.c * y + cam.cy;
     }
-    const float eps = 1e-3f + 1e-6f * (fabsf(cam.cx) + fabsf(cam.cy));
+    q.eps = 1e-3f + 1e-6f * (fabsf(cam.cx) + fabsf(cam.cy));
+}
+// grid row r (< nrows) of the cell rectangle (cx0 .. cx1, from cy0): its cell range (lo | hi << 16, SCAN_EMPTY_ROW: none under the window),
+// the end of its first cell and its entry range [re0, re1)
+__device__ __forceinline__ void scan_row(const ScanQuad &q, const MapView &m, int cx0, int cx1, int cy0, int r, int &rw, int &rfe, int &re0, int &re1) {
+    const float eps = q.eps;
+    const int cy = cy0 + r;
+    const float ya = m.oy + (float)cy * m.cell - eps - 1e-4f * m.cell, yb = m.oy + (float)(cy + 1) * m.cell + eps + 1e-4f * m.cell;
+    float xmin = 3.0e38f, xmax = -3.0e38f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float x0 = q.qx[k], y0 = q.qy[k], x1 = q.qx[(k + 1) & 3], y1 = q.qy[(k + 1) & 3];
+        if (y0 >= ya && y0 <= yb) { xmin = fminf(xmin, x0); xmax = fmaxf(xmax, x0); }
+        const float dy = y1 - y0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float yl = j == 0 ? ya : yb;
+            if ((y0 - yl) * (y1 - yl) <= 0.0f && dy != 0.0f) {
+                const float x = x0 + (yl - y0) / dy * (x1 - x0);
+                xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
+            }
+        }
+    }
+    if (xmin <= xmax) {
+        const float pad = eps + 1e-4f * m.cell;
+        const float f0 = fminf(fmaxf((xmin - pad - m.ox) * m.inv_cell, -1.0f), (float)m.nx), f1 = fminf(fmaxf((xmax + pad - m.ox) * m.inv_cell, -1.0f), (float)m.nx);
+        const int lo = max((int)floorf(f0), cx0), hi = min((int)floorf(f1), cx1);
+        if (lo <= hi) {
+            const int32_t *cs = m.cell_start + (size_t)cy * m.nx;
+            rw = lo | (hi << 16);
+            re0 = cs[lo]; re1 = cs[hi + 1]; rfe = cs[lo + 1];
+        }
+    }
+}
+__device__ __forceinline__ void scan_load_rows(ScanState &st, const MapView &m, const CommonArgs &c, const Camera &cam, int lane, int X0, int TWw,
+                                               int row0) {
+    ScanQuad q;
+    scan_quad(q, c, cam, X0, TWw);
     const int r = row0 + lane;
     st.rw = SCAN_EMPTY_ROW; st.rfe = 0;
     int re0 = 0, re1 = 0;
-    if (r < st.nrows) {
-        const int cy = st.cy0 + r;
-        const float ya = m.oy + (float)cy * m.cell - eps - 1e-4f * m.cell, yb = m.oy + (float)(cy + 1) * m.cell + eps + 1e-4f * m.cell;
-        float xmin = 3.0e38f, xmax = -3.0e38f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float x0 = qx[k], y0 = qy[k], x1 = qx[(k + 1) & 3], y1 = qy[(k + 1) & 3];
-            if (y0 >= ya && y0 <= yb) { xmin = fminf(xmin, x0); xmax = fmaxf(xmax, x0); }
-            const float dy = y1 - y0;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float yl = j == 0 ? ya : yb;
-                if ((y0 - yl) * (y1 - yl) <= 0.0f && dy != 0.0f) {
-                    const float x = x0 + (yl - y0) / dy * (x1 - x0);
-                    xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
-                }
-            }
-        }
-        if (xmin <= xmax) {
-            const float pad = eps + 1e-4f * m.cell;
-            const float f0 = fminf(fmaxf((xmin - pad - m.ox) * m.inv_cell, -1.0f), (float)m.nx), f1 = fminf(fmaxf((xmax + pad - m.ox) * m.inv_cell, -1.0f), (float)m.nx);
-            const int lo = max((int)floorf(f0), st.cx0), hi = min((int)floorf(f1), st.cx1);
-            if (lo <= hi) {
-                const int32_t *cs = m.cell_start + (size_t)cy * m.nx;
-                st.rw = lo | (hi << 16);
-                re0 = cs[lo]; re1 = cs[hi + 1]; st.rfe = cs[lo + 1];
-            }
-        }
-    }
+    if (r < st.nrows) scan_row(q, m, st.cx0, st.cx1, st.cy0, r, st.rw, st.rfe, re0, re1);
     // the entry ranges of the block's rows form one list: number the entries once per block (scan_fetch cuts the list into chunks of 64)
     const int cnt = re1 - re0, incl = wave_scan_add(cnt);
     st.rex = incl - cnt;
@@ -758,16 +775,103 @@ __device__ __forceinline__ void scan_load_rows(ScanState &st, const MapView &m, 
     st.rtotal = __builtin_amdgcn_readlane(incl, 63);
 }
 
+// world-space bounding box of the window (2 px margin: int truncation moves a vertex by < 1 px) -> grid cell rectangle cx0 .. cx1, cy0 .. cy1
+// (empty where cx0 > cx1 or cy0 > cy1)
+__device__ __forceinline__ void scan_window(const MapView &m, const CommonArgs &c, const Camera &cam, int X0, int TWw, int &cx0, int &cx1, int &cy0, int &cy1) {
+    const int res = c.res;
+    float wx0 = 3.0e38f, wx1 = -3.0e38f, wy0 = 3.0e38f, wy1 = -3.0e38f;
+    const float half = (float)res / 2.0f;
+    const float pxs[2] = {(float)X0 - 2.0f, (float)min(X0 + TWw, res) + 2.0f}, pys[2] = {-2.0f, (float)res + 2.0f};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float x = -((pxs[i] - half) / half) / c.scale, y = -((pys[j] - half) / half) / c.scale;
+            float rx = cam.c * x - cam.s * y + cam.cx, ry = cam.s * x + cam.c * y + cam.cy;
+            wx0 = fminf(wx0, rx); wx1 = fmaxf(wx1, rx); wy0 = fminf(wy0, ry); wy1 = fmaxf(wy1, ry);
+        }
+    const float eps = 1e-3f + 1e-6f * (fabsf(cam.cx) + fabsf(cam.cy));
+    float fx0 = fminf(fmaxf((wx0 - eps - m.ox) * m.inv_cell, -1.0f), (float)m.nx), fx1 = fminf(fmaxf((wx1 + eps - m.ox) * m.inv_cell, -1.0f), (float)m.nx);
+    float fy0 = fminf(fmaxf((wy0 - eps - m.oy) * m.inv_cell, -1.0f), (float)m.ny), fy1 = fminf(fmaxf((wy1 + eps - m.oy) * m.inv_cell, -1.0f), (float)m.ny);
+    cx0 = max((int)floorf(fx0), 0); cx1 = min((int)floorf(fx1), m.nx - 1);
+    cy0 = max((int)floorf(fy0), 0);
+    cy1 = min((int)floorf(fy1), m.ny - 1);
+}
+
+// ---- the scan set-up of a work item, computed ONCE per item instead of by all the lanes of all the waves of its workgroup ----------------
+// What the prologue of the bit-plane kernel derives from a camera and a strip: the trim polygon, the cell rectangle of the window, and for
+// each grid row under the window what lane r of scan_load_rows holds.  Every input is the same for the whole workgroup (or is per grid row, and
+// a 35 m view spans about four), yet the prologue costs each wave 552 vector instructions per image (measured: DESIGN.md 5.1a).
+// camera_prepare_kernel computes a record per item with the very functions the raster kernel uses (polygon_corners, scan_window, scan_quad,
+// scan_row; -ffp-contract=off and IEEE division: the same bits), one item per thread, and the raster workgroups load it: the window and the
+// flag through scalar loads, the camera and its polygon through three 16-byte vector loads and readfirstlane (camera_uniform), the rows with
+// one 16-byte load by lane r.  An item with more grid rows than the record holds is flagged and computed in the raster kernel as before.
+constexpr int PREP_ROWS = 16;                   // (a 35 m view spans about four grid rows)
+constexpr int PREP_COMPUTE = 1;                 // PrepRecord::flags: not prepared (more than PREP_ROWS grid rows), the kernel computes
+struct alignas(16) PrepRecord {
+    float cam[12];                              // cx, cy, s, c, px[4], py[4]
+    int cx0, cx1, cy0, nrows;
+    int rtotal, flags, pad0, pad1;
+    int4 rows[PREP_ROWS];                       // row r: rw, rex, rbase, rfe
+};
+static_assert(sizeof(PrepRecord) == 80 + 16 * PREP_ROWS, "PrepRecord layout");
+
+__global__ void __launch_bounds__(256) camera_prepare_kernel(SceneArgs a, CommonArgs c, int TWp, PrepRecord *__restrict__ tab) {
+    const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (item >= c.n_img * c.strips) return;
+    const int64_t img = item / c.strips;
+    const int X0 = (int)(item - img * c.strips) * TWp;
+    PrepRecord &rec = tab[item];
+    Camera cam;
+    {
+        float2 xy = c.cam_xy[img], sc = c.cam_sc[img];
+        cam.cx = xy.x; cam.cy = xy.y; cam.s = sc.x; cam.c = sc.y;
+        polygon_corners(cam, c.scale, c.res);
+    }
+    MapView m = a.map;
+    if (a.views != nullptr) m = a.views[a.scene_map[img / a.Nc]];
+    int cx0 = 0, cx1 = -1, cy0 = 0, nrows = 0, rtotal = 0;
+    if (m.nx > 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STATIC)) {
+        int cy1;
+        scan_window(m, c, cam, X0, TWp, cx0, cx1, cy0, cy1);
+        nrows = (cx0 <= cx1 && cy0 <= cy1) ? cy1 - cy0 + 1 : 0;
+    }
+    if (nrows > 0 && nrows <= PREP_ROWS) {
+        ScanQuad q;
+        scan_quad(q, c, cam, X0, TWp);
+        for (int r = 0; r < nrows; ++r) {                  // the serial form of scan_load_rows' prefix sum over the rows' entry counts
+            int rw = SCAN_EMPTY_ROW, rfe = 0, re0 = 0, re1 = 0;
+            scan_row(q, m, cx0, cx1, cy0, r, rw, rfe, re0, re1);
+            rec.rows[r] = make_int4(rw, rtotal, re0 - rtotal, rfe);
+            rtotal += re1 - re0;
+        }
+    }
+    float *f = rec.cam;
+    f[0] = cam.cx; f[1] = cam.cy; f[2] = cam.s; f[3] = cam.c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { f[4 + k] = cam.px[k]; f[8 + k] = cam.py[k]; }
+    rec.cx0 = cx0; rec.cx1 = cx1; rec.cy0 = cy0; rec.nrows = nrows;
+    rec.rtotal = rtotal; rec.flags = nrows > PREP_ROWS ? PREP_COMPUTE : 0; rec.pad0 = 0; rec.pad1 = 0;
+}
+
+// The integer words of a work item's record (window, row count, entry total, flag) as the raster kernel reads them: the address is the same for
+// the whole workgroup and nothing writes the table while the launch runs, so these loads go through the constant address space -- scalar loads
+// into scalar registers.  (The camera floats and the rows are read through ordinary vector loads.)
+typedef const __attribute__((address_space(4))) int PrepWords;
+__device__ __forceinline__ PrepWords *prep_words(const void *tab, int item) {
+    return (PrepWords *)((uintptr_t)tab + (uintptr_t)(unsigned)item * sizeof(PrepRecord));
+}
+
 // window = pixel columns [X0, X0 + TWw) of the image (the whole image when binning)
 // POLY: the walk is over the rendering grid with paired faces (MapView::qentries / qcell_start: the bit-plane kernels); the cells are the same
 template <typename SA, bool POLY = false>
 __device__ __forceinline__ void scan_init(ScanState &st, const SA &a, const CommonArgs &c, const Camera &cam, int64_t img, int lane, int wave, int X0,
-                                          int TWw) {   // wave = index among the cooperating waves
+                                          int TWw, const PrepRecord *rec = nullptr) {   // wave = index among the cooperating waves; rec: the item's
+                                                                                        // prepared record (wave-uniform), nullptr: compute
     st.map = a.map;
     if (a.views != nullptr) st.map = a.views[a.scene_map[img / a.Nc]];
     if constexpr (POLY) st.map.cell_start = st.map.qcell_start;
     const MapView &m = st.map;
-    const int res = c.res;
     st.phase = (a.N > 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_ACTORS)) ? 0 : 2;      // 0 actors, 1 masked-agent dot, 3 per-camera triangles, 2 static map
     if constexpr (POLY) {
         // The scan kernel of the split form reads the first phase through the launch's (always zero, in the product) debug word: a phase the
@@ -783,26 +887,21 @@ __device__ __forceinline__ void scan_init(ScanState &st, const SA &a, const Comm
     st.have = false; st.cur_i = -1; st.dyn = nullptr; st.done = 0;
     st.pu0 = st.pu1 = st.pu2 = make_uint4(0, 0, 0, 0);
     if (m.nx > 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STATIC)) {
-        // world-space bounding box of the window (2 px margin: int truncation moves a vertex by < 1 px) -> grid cell rectangle
-        float wx0 = 3.0e38f, wx1 = -3.0e38f, wy0 = 3.0e38f, wy1 = -3.0e38f;
-        const float half = (float)res / 2.0f;
-        const float pxs[2] = {(float)X0 - 2.0f, (float)min(X0 + TWw, res) + 2.0f}, pys[2] = {-2.0f, (float)res + 2.0f};
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float x = -((pxs[i] - half) / half) / c.scale, y = -((pys[j] - half) / half) / c.scale;
-                float rx = cam.c * x - cam.s * y + cam.cx, ry = cam.s * x + cam.c * y + cam.cy;
-                wx0 = fminf(wx0, rx); wx1 = fmaxf(wx1, rx); wy0 = fminf(wy0, ry); wy1 = fmaxf(wy1, ry);
+        if (rec != nullptr) {
+            // prepared (at most PREP_ROWS grid rows): lanes beyond the last row hold what scan_load_rows leaves there
+            PrepWords *w = prep_words(rec, 0);
+            st.cx0 = w[12]; st.cx1 = w[13]; st.cy0 = w[14]; st.nrows = w[15]; st.rtotal = w[16];
+            st.rex = st.rtotal; st.rbase = -st.rtotal;
+            if (lane < st.nrows) {
+                const int4 v = rec->rows[lane];
+                st.rw = v.x; st.rex = v.y; st.rbase = v.z; st.rfe = v.w;
             }
-        const float eps = 1e-3f + 1e-6f * (fabsf(cam.cx) + fabsf(cam.cy));
-        float fx0 = fminf(fmaxf((wx0 - eps - m.ox) * m.inv_cell, -1.0f), (float)m.nx), fx1 = fminf(fmaxf((wx1 + eps - m.ox) * m.inv_cell, -1.0f), (float)m.nx);
-        float fy0 = fminf(fmaxf((wy0 - eps - m.oy) * m.inv_cell, -1.0f), (float)m.ny), fy1 = fminf(fmaxf((wy1 + eps - m.oy) * m.inv_cell, -1.0f), (float)m.ny);
-        st.cx0 = max((int)floorf(fx0), 0); st.cx1 = min((int)floorf(fx1), m.nx - 1);
-        st.cy0 = max((int)floorf(fy0), 0);
-        const int cy1 = min((int)floorf(fy1), m.ny - 1);
-        st.nrows = (st.cx0 <= st.cx1 && st.cy0 <= cy1) ? __builtin_amdgcn_readfirstlane(cy1 - st.cy0 + 1) : 0;
-        if (st.nrows > 0) scan_load_rows(st, m, c, cam, lane, X0, TWw, 0);
+        } else {
+            int cy1;
+            scan_window(m, c, cam, X0, TWw, st.cx0, st.cx1, st.cy0, cy1);
+            st.nrows = (st.cx0 <= st.cx1 && st.cy0 <= cy1) ? __builtin_amdgcn_readfirstlane(cy1 - st.cy0 + 1) : 0;
+            if (st.nrows > 0) scan_load_rows(st, m, c, cam, lane, X0, TWw, 0);
+        }
     }
 }
 
@@ -1536,7 +1635,7 @@ __device__ inline bool clip_line_small(int W, int H, int &x1, int &y1, int &x2, 
 // (checked exhaustively against the iterative walk in tests/test_oracle_fill.py::test_line_rows_closed_form)
 // optional work counters (profiling hook tds_raster_get_stats of the testing build; active with debug flag TDS_RASTER_DBG_STATS)
 #ifdef TDS_TESTING
-__device__ unsigned long long g_stats[16];
+__device__ unsigned long long g_stats[18];       // [16], [17]: work items that used their prepared record / computed their scan set-up (tds_raster_get_prep_stats)
 #define TDS_STAT_LANES(W, I, V) do { if ((W).debug & TDS_RASTER_DBG_STATS) { const unsigned long long v_ = (unsigned long long)(V); if (v_) atomicAdd(&g_stats[I], v_); } } while (0)
 #define TDS_STAT(W, I, V) do { if (((W).debug & TDS_RASTER_DBG_STATS) && (W).lane == 0) atomicAdd(&g_stats[I], (unsigned long long)(V)); } while (0)
 #else
@@ -2513,12 +2612,20 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
     for (;;) {
         int64_t img;
         int X0;
+        const PrepRecord *rec = nullptr;                                     // the item's prepared scan set-up, where the launch has a table
         if constexpr (PERSIST) {
             __syncthreads();                                                 // the next item is known; every wave has left the planes of the previous one
             const int item = __builtin_amdgcn_readfirstlane((int)lkeys[16]);
             if (item < 0) break;
             img = item / c.strips;
             X0 = (item - (int)img * c.strips) * TWp;
+            if (c.prep != nullptr) {
+                rec = (const PrepRecord *)c.prep + item;
+                if (prep_words(rec, 0)[17] & PREP_COMPUTE) rec = nullptr;    // more grid rows than a record holds
+            }
+#ifdef TDS_TESTING
+            if ((c.debug & TDS_RASTER_DBG_STATS) && tid == 0) atomicAdd(&g_stats[rec != nullptr ? 16 : 17], 1ull);
+#endif
         } else {
             int strip;
             block_to_image(c.n_img * c.strips, c.strips, img, strip);
@@ -2543,17 +2650,45 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
             ci.scale = __int_as_float(sb); ci.res = rb;
         }
         Camera cam;
-        {
+        if (rec != nullptr) {
+            const float4 *f = (const float4 *)rec->cam;
+            const float4 f0 = f[0], f1 = f[1], f2 = f[2];
+            cam.cx = f0.x; cam.cy = f0.y; cam.s = f0.z; cam.c = f0.w;
+            cam.px[0] = f1.x; cam.px[1] = f1.y; cam.px[2] = f1.z; cam.px[3] = f1.w;
+            cam.py[0] = f2.x; cam.py[1] = f2.y; cam.py[2] = f2.z; cam.py[3] = f2.w;
+        } else {
             float2 xy = c.cam_xy[img], sc = c.cam_sc[img];
             cam.cx = xy.x; cam.cy = xy.y; cam.s = sc.x; cam.c = sc.y;
-            make_polygon(cam, ci.scale, ci.res);
+            polygon_corners(cam, ci.scale, ci.res);
         }
+        camera_uniform(cam);
         __syncthreads();
         // (the fused kernel walks the grid of single triangles: the 48-byte entries of the grid with paired faces cost it four more registers for
         // the chunk in flight, which it does not have -- DESIGN_HISTORY.md, appendix R3; the split form's scan kernel takes the pairs)
         ScanState st;
-        scan_init(st, a, ci, cam, img, lane, wave, X0, TWp);
+        scan_init(st, a, ci, cam, img, lane, wave, X0, TWp, rec);
         st.dyn = lkeys + 15;
+#ifdef TDS_TESTING
+        if (c.debug & TDS_RASTER_DBG_PROLOGUE_TWICE) {
+            // the ablation that prices the prologue: the same computation once more on inputs the compiler cannot tell from new ones,
+            // every result folded into a value that an empty asm consumes
+            CommonArgs c2 = c;
+            int sb = __float_as_int(c.scale), rb = c.res;
+            float2 xy = c.cam_xy[img], sc = c.cam_sc[img];
+            asm volatile("" : "+s"(sb), "+s"(rb), "+v"(xy.x), "+v"(xy.y), "+v"(sc.x), "+v"(sc.y));
+            c2.scale = __int_as_float(sb); c2.res = rb;
+            Camera cam2;
+            cam2.cx = xy.x; cam2.cy = xy.y; cam2.s = sc.x; cam2.c = sc.y;
+            make_polygon(cam2, c2.scale, c2.res);
+            ScanState st2;
+            scan_init(st2, a, c2, cam2, img, lane, wave, X0, TWp);
+            float f = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f += cam2.px[k] + cam2.py[k];
+            const int sink = __float_as_int(f) ^ st2.rw ^ st2.rex ^ st2.rbase ^ st2.rfe ^ st2.rtotal ^ st2.cx0 ^ st2.cx1 ^ st2.cy0 ^ st2.nrows;
+            asm volatile("" :: "v"(sink));
+        }
+#endif
         for (;;) {
             bool acc;
             uint32_t key;
@@ -3138,6 +3273,16 @@ TDS_EXPORT int tds_raster_get_stats(unsigned long long *out16) {
     return TDS_OK;
 }
 
+// read and reset the two counters of the prepared scan set-ups (debug flag TDS_RASTER_DBG_STATS): work items of the persistent bit-plane
+// launches that used their record, and that computed their set-up in the kernel
+TDS_EXPORT int tds_raster_get_prep_stats(unsigned long long *out2) {
+    TDS_CHECK_ARG(out2, "tds_raster_get_prep_stats: null output");
+    unsigned long long zero[2] = {0, 0};
+    if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_stats), sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+
 // K3r (the list rasteriser of the split bit-plane path): the LDS a workgroup may take in KiB, which sets the strip width
 TDS_EXPORT int tds_raster_set_list_lds(int lds_kb) {
     TDS_CHECK_ARG(lds_kb >= 16 && lds_kb <= 150, "tds_raster_set_list_lds: 16..150 KiB");
@@ -3236,6 +3381,27 @@ TDS_EXPORT int tds_raster_scene_workspace_bytes_for(int64_t n_img, int res, int 
 #endif
         lists = split_layout(n_img, LIST_CAPS).lists3;
     *bytes = with_queue_tail(lists);
+    return TDS_OK;
+}
+
+// The table of prepared scan set-ups (tds_raster_aux_t::camera_prep): one record per work item (camera, strip) of the launch that takes it -- the
+// fused bit-plane kernel in persistent 4-wave workgroups; 0 where the call is served by another launch.  The strips are the plan's: of a plain
+// and of a differentiable call (which may cut the image in two where the plain call takes eight waves) the larger count.
+TDS_EXPORT int tds_raster_camera_prep_bytes(int64_t n_img, int res, int out_mode, int n_keys, int64_t *bytes) {
+    TDS_CHECK_ARG(bytes, "tds_raster_camera_prep_bytes: null output");
+    *bytes = 0;
+    TDS_CHECK_ARG(n_img >= 0 && n_img < ((int64_t)1 << 31) && res > 0 && res <= 4096, "tds_raster_camera_prep_bytes: bad sizes");
+    TDS_CHECK_ARG(out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode), "tds_raster_camera_prep_bytes: unknown output mode %d", out_mode);
+    TDS_CHECK_ARG(n_keys >= -1 && n_keys <= MAX_KEYS, "tds_raster_camera_prep_bytes: n_keys must be -1 (not known) .. %d", MAX_KEYS);
+    if (is_mask_mode(out_mode) || n_keys <= 0 || n_img == 0) return TDS_OK;
+    int64_t items = 0, ws_bytes = 0;            // (with the workspace the library recommends: where that makes the plan the split form, no table)
+    (void)tds_raster_scene_workspace_bytes_for(n_img, res, out_mode, n_keys, &ws_bytes);
+    for (int slices = 0; slices < (out_mode == TDS_OUT_F32 ? 2 : 1); ++slices) {
+        const PlanInput in = {n_img, res, out_mode, n_keys, true, true, false, slices != 0, lists_room(ws_bytes, false), 256};
+        const RasterPlan p = plan_raster_scene(in, g_knobs);
+        if (p.form == RasterForm::Bits && p.persist) items = std::max<int64_t>(items, n_img * p.strips);
+    }
+    *bytes = items * (int64_t)sizeof(PrepRecord);
     return TDS_OK;
 }
 #endif  // !TDS_RASTER_MASKS_TU
@@ -3443,6 +3609,7 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
     cm.strips = p.strips; cm.n_img = n_img; cm.out = out; cm.slices = want_slices ? aux->index_slices : nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (aux && (aux->flags & TDS_RASTER_NO_TRIM)) ? 1 : 0;
+    cm.prep = nullptr;
     char *const ws = (char *)workspace;
 #ifdef TDS_RASTER_MASKS_TU
     // (this translation unit serves the mask entry points only: raster_masks.hip; their plan is the uint8 image's, Bits or Split)
@@ -3468,6 +3635,16 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
         TDS_LAUNCH_CHECK("coverage_prepare_kernel");
         cm.slices = aux->coverage;
         aux->coverage_maintained = 1;
+    }
+    // The persistent launch of the fused bit-plane kernel over all the cameras (not the one over the cameras K3s marked) takes the caller's table of
+    // prepared scan set-ups, written in stream order right in front of it.  No table, or one too small or misaligned: as before -- never an error.
+    // (The two fields were appended to the struct: they are read only from a caller that says its struct has them.)
+    if (p.form == RasterForm::Bits && p.persist && aux && (aux->flags & TDS_RASTER_HAS_CAMERA_PREP) && aux->camera_prep && ((uintptr_t)aux->camera_prep & 15) == 0 &&
+        aux->camera_prep_bytes >= n_img * p.strips * (int64_t)sizeof(PrepRecord)) {
+        const int64_t items = n_img * p.strips;
+        hipLaunchKernelGGL(camera_prepare_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const SceneArgs &)a, cm, p.twp, (PrepRecord *)aux->camera_prep);
+        TDS_LAUNCH_CHECK("camera_prepare_kernel");
+        cm.prep = aux->camera_prep;
     }
     if (p.form == RasterForm::Split || p.form == RasterForm::Bits)
         return launch_bit_planes<float, uint8_t>("tds_raster_scene", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_F32, want_slices, s);
@@ -3509,6 +3686,7 @@ TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int
     cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
     cm.strips = (res + tw - 1) / tw; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (flags & TDS_RASTER_NO_TRIM) ? 1 : 0;
+    cm.prep = nullptr;
     with_out(out_mode, [&](auto t) { with_tw(tw, [&](auto w) {
         launch(raster_mesh_kernel<w, decltype(t)>, n_img * cm.strips, RBLOCK, lds_bytes(w, res), (hipStream_t)stream, a, cm);
     }); });

@@ -27,6 +27,9 @@ class HipRendererConfig(RendererConfig):
     #: renders into an `_ops.owned_image` buffer (allocate_image_ring) do not store again the lines that were and stay background.  Switch off
     #: where something writes into those buffers that torch's version counter does not show (`_ops.use_write_skipping`)
     write_skipping: bool = True
+    #: the persistent bit-plane launch computes each camera's scan set-up once, in a small kernel in front of it (`_ops.use_camera_prep`); the
+    #: pixels are the same with it switched off
+    camera_prep: bool = True
 
 
 @dataclass
@@ -132,7 +135,8 @@ class HipRenderer(BirdviewRenderer):
                                           ego_cameras=ego_cameras)
         return _ops.raster_scene(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, side, out_dtype=self.out_dtype,
                                  key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out,
-                                 write_skipping=bool(getattr(self.cfg, 'write_skipping', True)))
+                                 write_skipping=bool(getattr(self.cfg, 'write_skipping', True)),
+                                 camera_prep=bool(getattr(self.cfg, 'camera_prep', True)))
 
     def render_scene_masks(self, static_map, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor, camera_xy: Tensor,
                            camera_sc: Tensor, key_channels: Dict[int, int], n_channels: int, res: Optional[Resolution] = None,
