@@ -2165,6 +2165,16 @@ template <int NB> struct PairTab<NB, uint8_t> { using E = uint32_t; };        //
 
 __device__ __forceinline__ uint32_t rotl32(uint32_t v, int n) { return __builtin_rotateleft32(v, (unsigned)n & 31u); }
 
+// One float32 entry of the pair table, `byte_off` bytes into it.  The table is the first thing in the LDS of the bit-plane kernels, which have no
+// static LDS (tests/test_write_out_static.py holds them to it): its entries sit at the LDS addresses 0 .. 3 * P * 8, and the address is formed
+// from the offset alone -- through the table's pointer the compiler adds the LDS base to every index (v_add_u32 v, 0, v: the base is known only
+// after instruction selection).  Volatile: left alone, the optimiser pairs the reads of two CHANNELS at one index (ds_read2st64_b64) and then
+// copies six registers per column to put the entries of two INDICES into the four consecutive registers a float4 store takes.
+typedef float vf2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ vf2 pair_tab_read(uint32_t byte_off) {
+    return *(const volatile __attribute__((address_space(3))) vf2 *)(uintptr_t)byte_off;
+}
+
 // The coverage record of an output buffer (tds_raster_aux_t::coverage; float32 images whose side is a multiple of 32): behind a header of
 // COV_HEADER_DW words, one word per (camera, word column x / 32, row block y / 32) whose bit p says "the 128-byte line of column x = 32 xw + p,
 // rows 32 o .. 32 o + 31 (one line in each of the three channels) holds a covered pixel".  A line that held only background before the launch
@@ -2281,6 +2291,9 @@ __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typ
     if ((H & 3) == 0) {
         const int quads = H >> 2;
         const bool full = (cols & 31) == 0;                          // wave-uniform: no partial 32-column word
+        // float32: table entries straight into the stores' operands (pair_tab_read).  The instantiations that also emit the index slices (bound by
+        // their writes; six more spilled registers) and those for two index bits keep reading through `tab`: 64 -> 80 B of scratch per lane otherwise.
+        constexpr bool DIRECT = sizeof(OutT) == 4 && !EMIT && NB >= 3;
         // TRACK (plain float32 colour launches): `slices` is the buffer's coverage record, or null.  H a multiple of 32: the eight lanes of an
         // aligned octet hold the row quads 8 o .. 8 o + 7 of ONE word column (quads, BBLOCK and quads * wpr are multiples of 8, so an octet
         // is never split by the loop bound or by a strip's end) -- together the 32 rows of one 128-byte line per column and channel.
@@ -2373,15 +2386,33 @@ __device__ __forceinline__ void write_out_bits(const uint32_t *planes, const typ
                         const int p = ph + 8 * m;
                         if (CHECK && p >= ncol) continue;
                         if constexpr (TRACK) { if (!(lines & (1u << p))) continue; }     // one predicate for the three channels' stores
-                        const uint32_t i01 = (A0 >> (8 * m)) & (uint32_t)(P - 1), i23 = (A1 >> (8 * m)) & (uint32_t)(P - 1);
                         const uint32_t off = off0 + (uint32_t)p * colb;
+                        if constexpr (DIRECT) {
+                            // byte m of A0 / A1 is the pair index (its upper bits are 0 below four index bits), times 8 the entry's place in the
+                            // table: one byte-select shift per index, and the two entries land in the halves of the store's operand (pair_tab_read)
+                            const uint32_t b01 = ((A0 >> (8 * m)) & 255u) << 3, b23 = ((A1 >> (8 * m)) & 255u) << 3;
+                            // the six reads of a column first, then its stores: a volatile read is not moved across a store, and read - wait - store
+                            // per channel is three LDS round trips per column where this is one
+                            vf2 lo[3], hi[3];
 #pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) {
-                            const E lo = tab[ch * P + i01], hi = tab[ch * P + i23];
-                            char *dst = (char *)(ch == 0 ? ob0 : (ch == 1 ? ob1 : ob2)) + off;
-                            // streamed out, never read again by this kernel: non-temporal, so that the grid entries keep their place in L2
-                            if constexpr (sizeof(OutT) == 4) { typedef float vf4 __attribute__((ext_vector_type(4))); const vf4 v = {lo.x, lo.y, hi.x, hi.y}; __builtin_nontemporal_store(v, (vf4 *)dst); }
-                            else __builtin_nontemporal_store(lo | (hi << 16), (uint32_t *)dst);
+                            for (int ch = 0; ch < 3; ++ch) { lo[ch] = pair_tab_read((uint32_t)(ch * P * 8) + b01); hi[ch] = pair_tab_read((uint32_t)(ch * P * 8) + b23); }
+#pragma unroll
+                            for (int ch = 0; ch < 3; ++ch) {
+                                char *dst = (char *)(ch == 0 ? ob0 : (ch == 1 ? ob1 : ob2)) + off;
+                                // streamed out, never read again by this kernel: non-temporal, so that the grid entries keep their place in L2
+                                typedef float vf4 __attribute__((ext_vector_type(4)));
+                                const vf4 v = {lo[ch].x, lo[ch].y, hi[ch].x, hi[ch].y};
+                                __builtin_nontemporal_store(v, (vf4 *)dst);
+                            }
+                        } else {
+                            const uint32_t i01 = (A0 >> (8 * m)) & (uint32_t)(P - 1), i23 = (A1 >> (8 * m)) & (uint32_t)(P - 1);
+#pragma unroll
+                            for (int ch = 0; ch < 3; ++ch) {
+                                const E lo = tab[ch * P + i01], hi = tab[ch * P + i23];
+                                char *dst = (char *)(ch == 0 ? ob0 : (ch == 1 ? ob1 : ob2)) + off;
+                                if constexpr (sizeof(OutT) == 4) { typedef float vf4 __attribute__((ext_vector_type(4))); const vf4 v = {lo.x, lo.y, hi.x, hi.y}; __builtin_nontemporal_store(v, (vf4 *)dst); }
+                                else __builtin_nontemporal_store(lo | (hi << 16), (uint32_t *)dst);
+                            }
                         }
                     }
                 }
