@@ -1081,3 +1081,40 @@ def test_k3_camera_counts_that_do_not_divide_by_eight(ops, oracle, town, B, A):
             img, ref = render_both(ops, oracle, smap, static, state, size, mask, state[..., :2].copy(), cam_sc, 35.0, res, dtype)
             assert img.shape == (B, A, 3, res, res)
             np.testing.assert_array_equal(img.astype(np.float32), ref)
+
+
+@pytest.mark.parametrize('n_img,nbytes', [(1, 1408), (3, 4160)])
+def test_k3_binned_strip_lists_stay_inside_the_workspace(ops, oracle, town, n_img, nbytes):
+    """The binned form (K3a + K3b: actor keys not listed, a workspace) with fewer than 16 strip lists: the 256-byte alignment of the counts costs
+    each list more than one record, and K3a fills a list that overflows to its last record.  One strip per camera at 64 x 64, cameras over
+    more Town01 faces than twice the largest capacity allowed here, and a workspace that is an interior slice of a zeroed tensor: the bytes
+    around the slice stay zero, and the image is the fused kernel's (no workspace), byte for byte."""
+    from test_raster_plan import BINNED, plan
+    res, fov, guard = 64, 60.0, 512
+    p = plan(res, -1, n_img=n_img, listed=False, ws=nbytes)
+    assert p['form'] == BINNED and p['strips'] == 1 and p['grid'] == n_img and 64 <= p['caps'] <= 128, p
+    g = load_golden('g45_mesh_preraster.npz')
+    st, sz = g['g5_town01_128_state'][:1, :n_img], g['g5_town01_128_size'][:1, :n_img]
+    mask = np.ones((1, n_img, n_img), bool)
+    cam_sc = sc_np(ops.heading_sc(dev(st)[..., 2]))
+    sv, sa, sf = oracle_static(oracle, town['verts'], town['faces'], town['vert_category'], town['categories'])
+    faces_drawn = oracle.render_scenes(st, sz, mask, st[..., :2].copy(), cam_sc, sv, sa, sf, fov, res, agent_sc=cam_sc, record=True, images=False)[3]
+    assert (faces_drawn >= 2 * 128).all(), f'every list must overflow: the oracle draws {faces_drawn} faces'
+    smap = make_map(ops, town['verts'], town['faces'], town['vert_category'], town['categories'])
+    sd = dev(st)
+    args = (smap, sd, ops.heading_sc(sd[..., 2]), dev(oracle.actor_template(sz)), actor_keys(smap, 1, n_img), dev(mask), dev(st[..., :2].copy()), dev(cam_sc), fov, res)
+    around = torch.zeros(guard + nbytes + guard, dtype=torch.uint8, device=DEV)
+    real_ws = ops._raster_workspace
+    ops.use_bitplanes = False
+    ops._raster_workspace = lambda *a: around[guard:guard + nbytes]
+    try:
+        binned = ops.raster_scene(*args)
+        ops.use_workspace = False
+        fused = ops.raster_scene(*args)
+    finally:
+        ops.use_workspace, ops.use_bitplanes, ops._raster_workspace = True, True, real_ws
+    torch.cuda.synchronize()
+    assert not around[guard + nbytes:].any(), f'{int((around[guard + nbytes:] != 0).sum())} bytes written behind the workspace'
+    assert not around[:guard].any()
+    assert around[guard:guard + nbytes].any(), 'the lists were written'
+    assert torch.equal(binned, fused) and bool((binned > 0).any())

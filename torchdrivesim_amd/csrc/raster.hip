@@ -18,6 +18,7 @@
 //     explicit per-camera RGB mesh.
 // Roofline: HBM write, 3*H*W*4 B per camera (fp32) -- DESIGN.md.
 #include "tds_common.h"
+#include "tds_raster_plan.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -25,6 +26,7 @@
 
 using tds::GridEntry;
 using tds::MapView;
+using namespace tds_raster;     // the launch planning and the constants it shares with the kernels (RWAVES, QCAP, MAX_KEYS, ...): tds_raster_plan.h
 
 // Ablation switches, work counters and tuning knobs exist only in the TESTING build of the library (libtdship_testing.so, -DTDS_TESTING:
 // tools/ and tests/); in the product they are compiled out -- TDS_DBG(x) is the constant 0 there.
@@ -36,12 +38,7 @@ using tds::MapView;
 
 namespace {
 
-constexpr int RWAVES = 4;
 constexpr int RBLOCK = RWAVES * 64;
-constexpr int QCAP = 64;                          // per-wave face queue (entries): key + 3 packed vertices
-constexpr int Q_DW = 4 * QCAP;
-constexpr int BLOCK_CAP = 256;                    // per-wave list of (face, block) pairs
-constexpr int WAVE_LDS_DW = Q_DW + BLOCK_CAP;
 constexpr int NO_SWITCH = 0x7fffffff;
 constexpr int COORD_LIMIT = 16000;                // |pixel coordinate| below this: int16 packing and int32 16.16 slopes are exact
 
@@ -814,7 +811,7 @@ struct alignas(16) PrepRecord {
     int rtotal, flags, pad0, pad1;
     int4 rows[PREP_ROWS];                       // row r: rw, rex, rbase, rfe
 };
-static_assert(sizeof(PrepRecord) == 80 + 16 * PREP_ROWS, "PrepRecord layout");
+static_assert(sizeof(PrepRecord) == 80 + 16 * PREP_ROWS && sizeof(PrepRecord) == PREP_RECORD_BYTES, "PrepRecord layout");
 
 __global__ void __launch_bounds__(256) camera_prepare_kernel(SceneArgs a, CommonArgs c, int TWp, PrepRecord *__restrict__ tab) {
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1307,7 +1304,6 @@ __global__ void __launch_bounds__(RBLOCK, 4) raster_scene_kernel(SceneArgsEx a, 
 // A strip whose list overflowed, or that met a face outside the packed coordinate range, is poisoned (count > caps) and
 // scans the grid for itself in K3b, so the result never depends on the capacity.
 constexpr int BIN_WAVES = 4;          // cameras per workgroup of K3a
-constexpr int MAX_STRIPS = 128;
 
 __global__ void __launch_bounds__(BIN_WAVES * 64) bin_faces_kernel(SceneArgsEx a, CommonArgs c, int tw, uint32_t *__restrict__ counts,
                                                                      uint4 *__restrict__ lists, int caps) {
@@ -1391,10 +1387,6 @@ __global__ void __launch_bounds__(RBLOCK, 4) raster_scene_list_kernel(SceneArgsE
 // the final pass resolves, per pixel, the highest key whose bit is set.  Equal keys paint the same bit, so -- exactly as
 // with ds_max on packed keys -- the result does not depend on the order in which faces are processed.
 // =========================================================================================================
-constexpr int MAX_KEYS = 15;              // key indices 1..15 fit 4 bits (0 = background)
-constexpr int EQCAP = 128;                    // ring of queued outline edges per wave (power of two, >= 2 * 64)
-constexpr int BITS_WAVE_LDS_DW = Q_DW + 64 + 2 * EQCAP;   // per wave: face queue + owner markers + edge ring
-
 struct KeyTable { uint32_t key[16]; int n; };      // ascending = painter order (later wins)
 
 struct BitCtx {
@@ -2181,7 +2173,7 @@ __device__ __forceinline__ vf2 pair_tab_read(uint32_t byte_off) {
 // and holds only background after it is not stored again.  Header: [0] magic, [1] res, [2..3] cameras, [4..5] the image buffer's address,
 // [6..8] the bits of the background colour per channel, [COV_MODE] what the launch in flight does (written by coverage_prepare_kernel
 // right before it, in stream order): COV_SKIP = the record describes the buffer, else every line is stored.
-constexpr int COV_HEADER_DW = 16, COV_MODE = 9;
+constexpr int COV_MODE = 9;                         // (COV_HEADER_DW words in all: tds_raster_plan.h)
 constexpr uint32_t COV_MAGIC = 0x31564f43u, COV_SKIP = 1u;      // 'COV1'
 
 template <int BBLOCK, int NB, typename OutT, bool EMIT, bool TRACK = false>
@@ -2451,8 +2443,6 @@ constexpr int pair_tab_dw() { return is_mask<OutT>::value ? 0 : 3 * (1 << (2 * N
 
 // The channel table of a mask launch, in the caller's workspace (written by the call, in stream order): [0] = C channels, [1 + c] = the planes
 // (bit k: key k of the launch's ascending key table) whose union is channel c.  The mask instantiations find it in CommonArgs::slices.
-constexpr int MASK_TABLE_DW = 64;
-constexpr int64_t MASK_TABLE_BYTES = MASK_TABLE_DW * 4;
 struct MaskTable { uint32_t w[MASK_TABLE_DW]; };
 
 // Mask stream-out of one (camera, strip): channel c of a pixel is set iff one of the planes of chan[1 + c] holds it -- coverage, no occlusion.
@@ -2556,8 +2546,7 @@ __device__ __noinline__ void write_out_masks(const uint32_t *planes, const uint3
 // `queue`: 8 counters, zero at launch: the last 64 bytes of the CALLER's workspace, cleared in stream order right before the launch (the
 // library owns no device memory besides the map handles).  A workgroup reads the XCD it runs on from the XCC_ID hardware register.
 // Without a workspace there is no queue and the same kernel runs one workgroup per item (claim_work).
-constexpr int BITS_FIXED_DW = 20;             // [0..14] ascending key table, [15] next chunk of the grid scan, [16] the work item taken next,
-                                              // [17] queues this workgroup has found empty
+// (the words a workgroup keeps beside its planes, BITS_FIXED_DW: tds_raster_plan.h)
 // one thread: take the next item -- own queue first, then the others in cyclic order -- and leave it in state[0] (-1: nothing left);
 // state[1] = queues of that order already found empty by this workgroup.  Everything a workgroup carries from item to item lives in
 // LDS: the kernel has no register to spare
@@ -2987,59 +2976,6 @@ __global__ void __launch_bounds__(BWAVES * 64) raster_list_bits_kernel(CommonArg
     }
 }
 
-inline int bits_index_bits(int K) { return K <= 3 ? 2 : (K <= 7 ? 3 : 4); }
-inline size_t bits_lds_bytes(int K, int res, int twp, int nwaves, int out_mode) {
-    size_t plane_dw = ((size_t)K * res * (twp / 32) + 3) & ~(size_t)3;
-    size_t P = (size_t)1 << (2 * bits_index_bits(K));
-    size_t tab_dw = 3 * P * (out_mode == TDS_OUT_F32 ? 2 : 1);
-    return (plane_dw + tab_dw + BITS_FIXED_DW + (size_t)nwaves * BITS_WAVE_LDS_DW) * 4;
-}
-// The knobs of K3 that the testing hooks set (include/tdship.h, "testing hooks"), constants in the product: the strip width (0: automatic),
-// waves per workgroup of the bit-plane kernel and of K3r (0: by image size), K3r's LDS budget in KiB (it takes the widest strip that fits), and
-// the TDS_RASTER_DBG_* flags.
-struct RasterKnobs { int force_tw, bits_waves, list_waves, list_lds_kb, debug; };
-#ifndef TDS_TESTING
-constexpr
-#endif
-RasterKnobs g_knobs = {0, 4, 0, 40, 0};
-
-// The work queues of a persistent bit-plane launch: 8 counters (64 bytes) that must be zero when the kernel starts.  They live at the
-// END of the caller's workspace (tds_raster_scene_workspace_bytes provides for them) and are cleared in stream order right before the
-// launch.  Two launches that may overlap in time must not share a workspace; that already holds for the face lists.  The library allocates
-// nothing per call.  (They are cleared by tds::zero_async, a kernel: see there why not hipMemsetAsync.)
-constexpr int64_t QUEUE_BYTES = 64;
-// where the queues start in a workspace of `bytes` (what lies before is left for the lists); -1: no room for them
-inline int64_t queue_offset(int64_t bytes) { return bytes < QUEUE_BYTES + 64 ? -1 : (bytes - QUEUE_BYTES) & ~(int64_t)63; }
-// the workspace that leaves `lists` bytes for the lists and room for the queues after them
-inline int64_t with_queue_tail(int64_t lists) { return ((lists + 63) & ~(int64_t)63) + QUEUE_BYTES + 64; }
-// what the lists may use of a workspace of `bytes` (0: none): all that lies before the queues -- and, in a mask call, before the channel table
-// (MASK_TABLE_BYTES right in front of the queues)
-inline int64_t lists_room(int64_t bytes, bool masks) {
-    const int64_t q = queue_offset(bytes);
-    return q < 0 ? 0 : (masks ? std::max<int64_t>(q - MASK_TABLE_BYTES, 0) : q);
-}
-
-// The workspace of the split form: a marker list (`poisoned`, n_img + 1 words) at 0, a count per camera, then `caps` poly records per camera,
-// each 16 bytes in `lists` (flags, P0, P1, P2) and 4 in `lists3` (P3).  The recommended workspace (tds_raster_scene_workspace_bytes*)
-// counts LIST_CAPS records of 16 bytes while the launch divides what it gets by 20, so LIST_CAPS = 2048 yields about 1636 records per
-// camera.  Kept as it was measured: a change moves which cameras overflow to the fused kernel.
-struct SplitLayout { int64_t counts, lists, lists3, caps; };        // byte offsets; records per camera
-// caps < 0: as many as `bytes` hold (a multiple of 4, at most 8192; 0 when none fit)
-inline SplitLayout split_layout(int64_t n_img, int64_t caps, int64_t bytes = 0) {
-    const int64_t counts = ((n_img + 1) * 4 + 255) & ~(int64_t)255, lists = (counts + n_img * 4 + 255) & ~(int64_t)255;
-    if (caps < 0) caps = bytes > lists ? std::min<int64_t>(((bytes - lists) / (n_img * 20)) & ~(int64_t)3, 8192) : 0;
-    return {counts, lists, lists + n_img * caps * 16, caps};
-}
-
-// workgroups of a persistent launch: exactly as many as are resident at a time -- three per CU (168 VGPRs: three waves per SIMD), fewer when
-// the LDS of one exceeds a third of the CU's 160 KiB.  (A surplus of waiting workgroups costs: DESIGN_HISTORY.md, appendix R6; fewer than the
-// resident number, or head / tail items in strips, do not pay either: profiles/r06_tail_attempts.log.)
-inline int64_t resident_workgroups(int cus, size_t lds_bytes, const RasterKnobs &k) {
-    const size_t granted = (lds_bytes + 2047) & ~(size_t)2047;                  // LDS is granted in 2 KiB steps
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / std::max<size_t>(granted, 1)));
-    // (testing build, GRID8 / GRID4: 8 / 4 workgroups per CU -- the surplus of round 3)
-    return (int64_t)cus * ((k.debug & TDS_RASTER_DBG_GRID8) ? 8 : ((k.debug & TDS_RASTER_DBG_GRID4) ? 4 : per_cu));
-}
 // the CUs a launch on `stream` may use
 int launch_cus(hipStream_t stream) {
     constexpr int MAX_DEVICES = 64;
@@ -3103,167 +3039,6 @@ __global__ void __launch_bounds__(RBLOCK, 4) raster_mesh_kernel(MeshArgs a, Comm
     if (!(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_STORE)) write_out<TW, OutT>(tile, (OutT *)c.out, img, res, X0, tid);
 }
 
-inline size_t lds_bytes(int tw, int res) { return ((size_t)tw * res + (size_t)RWAVES * WAVE_LDS_DW) * sizeof(uint32_t); }
-
-// strip width: the widest of {64,32,16,8} whose tile leaves room for two workgroups per CU (160 KiB LDS), else one
-inline int pick_tw(int res) {
-    const int cands[4] = {64, 32, 16, 8};
-    for (int tw : cands)
-        if (lds_bytes(tw, res) <= 80 * 1024) return tw;
-    for (int tw : cands)
-        if (lds_bytes(tw, res) <= 160 * 1024) return tw;
-    return 0;
-}
-// strip width of the packed-key kernels (0: the resolution does not fit)
-inline int strip_width(int res, const RasterKnobs &k) { return (k.force_tw && k.force_tw <= 64) ? k.force_tw : pick_tw(res); }
-
-constexpr int DEFAULT_CAPS = 512;         // faces per strip list that the recommended workspace provides
-constexpr int LIST_CAPS = 2048;           // faces per camera list of the split bit-plane path that the recommended workspace provides
-// The split form (K3s + K3r) serves resolutions up to these; above, the fused launch hides the scan behind its write stream or its row loops.
-// ONE sweep on one build and box (round 6, tools/split_threshold_sweep.sh, B = 1024 x 64, ms per call, fused / split -- each pair from one process;
-// profiles/r06_split_threshold_sweep.log):
-//   float32   96 4.00 / 2.72   104 4.09 / 3.02   112 4.13 / 3.24   116 4.14 / 3.98   120 4.19 / 4.46   124 4.18 / 4.20   128 4.12 / 3.24   136 4.33 / 5.38
-//            144 4.36 / 3.93   152 4.46 / 5.03   160 4.48 / 4.28   168 5.11 / 6.20   176 4.80 / 5.02   192 4.97 / 5.48
-//   uint8    128 3.99 / 2.91   160 4.16 / 3.38   176 4.51 / 3.70   192 4.50 / 4.14   208 4.69 / 4.33   216 4.65 / 4.38   224 4.94 / 5.18 (7.35 once the strip no longer
-//            holds the whole image)   256 5.09 / 5.64
-// float32: K3r is bound by its write stream from about 116 x 116 on and pays for output columns (res x 4 bytes) that straddle 64-byte sectors, so above
-// SPLIT_ANY_RES_F32 the split form is taken only where res is a multiple of 16 (split_serves).
-constexpr int SPLIT_MAX_RES_F32 = 160, SPLIT_ANY_RES_F32 = 116, SPLIT_MAX_RES_U8 = 216;
-inline bool split_serves(int res, bool f32) {
-    if (!f32) return res <= SPLIT_MAX_RES_U8;
-    return res <= SPLIT_ANY_RES_F32 || (res <= SPLIT_MAX_RES_F32 && (res & 15) == 0);
-}
-
-// Bits: the bit-plane kernel (raster_scene_bits_kernel), the whole image or strips of it; Split: K3s (scan_faces_kernel) + K3r
-// (raster_list_bits_kernel) + the bit-plane kernel over the cameras whose list overflowed; packed keys Binned (K3a bin_faces_kernel + K3b
-// raster_scene_list_kernel) or Fused (raster_scene_kernel); Error: TDS_ELIMIT
-enum class RasterForm { Bits, Split, Binned, Fused, Error };
-
-struct PlanInput {
-    int64_t n_img;
-    int res, out_mode, n_keys;  // n_keys: distinct keys of the scene (its map(s) and the listed actor keys); -1: more than MAX_KEYS
-    bool keys_listed, actors, extra, want_slices;   // the caller listed the actors' keys; N > 0; n_extra > 0; index slices wanted
-    int64_t workspace_bytes;    // what the lists may use, the queue tail cut off; 0: no workspace, or no room for the queues
-    int cus;                    // CUs the launch may use
-};
-
-struct RasterPlan {
-    RasterForm form;
-    const char *error;          // Error: the message (a format that may take MAX_KEYS)
-    int tw, strips;             // strip width of the packed-key kernels; strips per image of the raster launch
-    int twp, nwv, nb;           // bit planes: strip width (32-padded), waves per workgroup, index bits,
-    size_t lds;                 // LDS per workgroup,
-    bool four_per_cu, persist;  // the MINWG = 4 instantiation (one workgroup per item) instead of MINWG = 3, a persistent launch over the queues
-    int64_t grid, caps;         // workgroups of the raster launch; faces per list (Split: per camera, Binned: per strip)
-    SplitLayout ws;             // Split: the workspace layout; Binned: the strip lists at ws.lists, their counts at 0
-    int tws, lw; size_t lds_s;  // Split: strip width, waves and LDS per workgroup of K3r
-};
-
-// A pure function of the call's shape and the knobs: no HIP call, no global.  tests/test_raster_plan.py pins its choices.
-inline bool is_mask_mode(int out_mode) { return out_mode == TDS_OUT_MASK_U8 || out_mode == TDS_OUT_MASK_BITS; }
-
-RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
-    // the masks take the plan of the uint8 image of the same shape; only their LDS is smaller (no pair table).  They are streamed out of the
-    // bit-plane kernels only.
-    if (is_mask_mode(in.out_mode)) {
-        PlanInput u8 = in;
-        u8.out_mode = TDS_OUT_U8;
-        RasterPlan p = plan_raster_scene(u8, k);
-        if (p.form == RasterForm::Bits || p.form == RasterForm::Split) {
-            const size_t tab = (size_t)3 * ((size_t)1 << (2 * p.nb)) * 4;
-            p.lds -= tab;
-            if (p.form == RasterForm::Split) p.lds_s -= tab;
-        } else if (p.form != RasterForm::Error) {
-            p.form = RasterForm::Error;
-            p.error = "tds_raster_scene_masks: the masks come from the bit-plane kernels only (at most %d distinct keys, listed by the caller)";
-        }
-        return p;
-    }
-    RasterPlan p{};
-    const int res = in.res, full = (res + 31) & ~31;
-    p.tw = strip_width(res, k);
-    p.strips = (res + p.tw - 1) / p.tw;
-    p.grid = in.n_img * p.strips;
-    // fastest path: bit planes, when the scene uses at most MAX_KEYS distinct keys and the caller listed the actors' keys
-    if ((in.keys_listed || !(in.actors || in.extra)) && in.n_keys > 0 && !(k.debug & TDS_RASTER_DBG_NO_BITS)) {
-        auto lds_of = [&](int twp, int nwv) { return bits_lds_bytes(in.n_keys, res, twp, nwv, in.out_mode); };
-        // strip width: the whole (32-padded) image if the planes fit 64 KiB, else the widest multiple of 32 that does
-        int twp = full;
-        while (twp > 32 && (size_t)in.n_keys * res * (twp / 8) > 64 * 1024) twp -= 32;
-        // ... in strips of EQUAL width (nine keys at 256 x 256: 192 + 64 columns left the second strip's workgroups a third of the work and the first
-        // one's two per CU -- 10.4 ms; 128 + 128 at three per CU: profiles/r06_more_keys.log)
-        // and, where one more strip lets three workgroups share a CU instead of two, in one more (ten keys: 3 x 96 columns).
-        if (twp < full && !(k.debug & TDS_RASTER_DBG_WIDEST_STRIPS)) {
-            const int n_strips = (res + twp - 1) / twp;
-            auto equal_width = [&](int n) { return (((res + n - 1) / n) + 31) & ~31; };
-            twp = equal_width(n_strips);
-            if (lds_of(twp, k.bits_waves) > 52 * 1024 && equal_width(n_strips + 1) >= 64 && lds_of(equal_width(n_strips + 1), k.bits_waves) <= 52 * 1024 &&
-                !(k.debug & TDS_RASTER_DBG_NO_EXTRA_STRIP))
-                twp = equal_width(n_strips + 1);
-        }
-        int nwv = k.bits_waves;
-        // Three workgroups per CU need at most 52 KiB each (160 KiB of LDS, allocated in 2 KiB steps): five keys at 256 x 256 just fit.
-        // A whole image that does not (six keys and more: two agent types, traffic lights, waypoints) -- measured at B = 1024 x 64, 256 x 256,
-        // six / seven keys, float32 | uint8 ms (profiles/r06_more_keys.log):
-        //     two half-image strips, four 128-VGPR workgroups per CU (each strip scans the grid for itself)   7.79 / 7.86 | 6.88 / 6.98
-        //     the whole image, two 4-wave workgroups per CU (persistent)                                       7.62 / 7.71 | 6.90 / 6.99
-        //     the whole image, two 8-WAVE workgroups per CU (sixteen waves per CU instead of eight)            7.61 / 7.63 | 6.25 / 6.32
-        // so: eight waves on the whole image where two such workgroups fit a CU (80 KiB each: up to seven keys at 256 x 256), else half strips
-        // (eight keys: 7.72 against 7.75 for the whole image in 4-wave workgroups; five keys at 320 x 320: 2.76 against 2.84; and differentiable
-        // calls, whose index slices the 4-wave kernel writes).  Eight waves also rule out the split form below (uint8, 192 - 216 px, 8 - 10 keys).
-        if (twp == full && twp >= 128 && lds_of(twp, nwv) > 52 * 1024 && !(k.debug & TDS_RASTER_DBG_WHOLE_4WAVES)) {
-            const int half = ((twp / 2) + 31) & ~31;
-            if (nwv == 4 && !in.want_slices && lds_of(twp, 8) <= 80 * 1024 && !(k.debug & TDS_RASTER_DBG_NO_8WAVES)) nwv = 8;
-            else if (lds_of(half, nwv) <= 52 * 1024) twp = half;
-        }
-        if (k.force_tw >= 32 && k.force_tw < twp) twp = k.force_tw;     // tuning hook
-        if (lds_of(twp, nwv) <= 150 * 1024) {
-            p.form = RasterForm::Bits; p.twp = twp; p.nwv = nwv; p.nb = bits_index_bits(in.n_keys); p.lds = lds_of(twp, nwv);
-            p.strips = (res + twp - 1) / twp; p.grid = in.n_img * p.strips;
-            // differentiable calls: float32, four waves; the instantiation that also stores the index slices
-            if (in.want_slices && nwv != 4) { p.form = RasterForm::Error; p.error = "tds_raster_scene: index slices need the 4-wave bit-plane kernel"; return p; }
-            // ---- the split form (K3s + K3r) where the launch is not bound by the write stream (where it pays: the sweep beside SPLIT_MAX_RES_*) ----
-            const bool f32 = in.out_mode == TDS_OUT_F32;
-            bool split = !in.want_slices && nwv == 4 && in.workspace_bytes > 0 && split_serves(res, f32);
-            if (k.debug & TDS_RASTER_DBG_NO_SPLIT) split = false;
-            if (k.debug & TDS_RASTER_DBG_SPLIT) split = !in.want_slices && nwv == 4 && in.workspace_bytes > 0;
-            if (split) p.ws = split_layout(in.n_img, -1, in.workspace_bytes);
-            if (split && p.ws.caps >= 128) {
-                // strip width of K3r: the widest multiple of 32 columns whose workgroup stays within the LDS budget (four workgroups per CU);
-                // waves: two up to 104 x 104 float32 / 128 x 128 uint8 pixels of a strip, four above (the sweep is DESIGN_HISTORY.md, appendix R7)
-                int lw = k.list_waves, tws = full;
-                if (lw == 0) lw = (int64_t)res * tws <= (f32 ? 104 * 104 : 128 * 128) ? 2 : 4;
-                while (tws > 32 && lds_of(tws, lw) > (size_t)k.list_lds_kb * 1024) tws -= 32;
-                // (more keys than the sweep's five can push a large image over the LDS budget: K3r in several strips per camera loses to
-                // the fused kernel from about 160 x 160 on -- uint8 224: 7.35 against 4.94 ms -- unless the testing build forces the form)
-                const bool narrowed = tws < full && res >= 160 && !(k.debug & TDS_RASTER_DBG_SPLIT);
-                if (lds_of(tws, lw) <= 150 * 1024 && !narrowed) { p.form = RasterForm::Split; p.tws = tws; p.lw = lw; p.lds_s = lds_of(tws, lw); p.caps = p.ws.caps; }
-            }
-            // the instantiations for three workgroups per CU are persistent launches: their workgroups take (camera, strip) items from per-XCD
-            // queues (see claim_work); the others get one workgroup per item, and so do all without a workspace (there is no queue).  The launch
-            // over the cameras K3s marked (normally none) takes its items from a queue: a persistent instantiation.
-            p.four_per_cu = nwv == 4 && !in.want_slices && p.form != RasterForm::Split && p.lds <= 40 * 1024 && !(k.debug & TDS_RASTER_DBG_MINWG3);
-            p.persist = nwv == 4 && !p.four_per_cu && in.workspace_bytes > 0;
-            if (p.persist) p.grid = std::min(p.form == RasterForm::Split ? 512 : p.grid, resident_workgroups(in.cus, p.lds, k));
-            return p;
-        }
-    }
-    if (in.want_slices) {
-        p.form = RasterForm::Error; p.error = "tds_raster_scene: index slices are produced by the bit-plane kernel only (at most %d distinct keys, listed by the caller)";
-        return p;
-    }
-    // general path: bin once per camera (K3a), then rasterise per strip from the lists (K3b)
-    if (in.workspace_bytes > 0 && !(k.debug & TDS_RASTER_DBG_NO_BINNED) && p.strips <= MAX_STRIPS) {
-        int64_t caps = std::min<int64_t>((in.workspace_bytes / p.grid - (int64_t)sizeof(uint32_t)) / (int64_t)sizeof(uint4), 4096);
-        if (caps >= 64) {
-            p.ws.lists = (p.grid * (int64_t)sizeof(uint32_t) + 255) & ~(int64_t)255;
-            if (p.ws.lists + p.grid * caps * (int64_t)sizeof(uint4) > in.workspace_bytes) --caps;
-            p.form = RasterForm::Binned; p.caps = caps; return p;
-        }
-    }
-    p.form = RasterForm::Fused; return p;
-}
-
 // (auto: instantiated where they are called, so the kernels are instantiated -- and laid out in the code object -- in the order they are named)
 template <int N> using IntC = std::integral_constant<int, N>;
 template <class F> auto with_nb(int nb, F &&f) { if (nb == 2) f(IntC<2>()); else if (nb == 3) f(IntC<3>()); else f(IntC<4>()); }
@@ -3279,81 +3054,6 @@ void launch(void (*kern)(P...), int64_t grid, int block, size_t lds, hipStream_t
 
 }  // namespace
 
-#if defined(TDS_TESTING) && !defined(TDS_RASTER_MASKS_TU)
-// ---- testing build only (include/tdship.h, section "testing hooks"): absent from libtdship.so --------------------------------
-// force the strip width (0 = automatic)
-TDS_EXPORT int tds_raster_set_strip_width(int tw) {
-    TDS_CHECK_ARG(tw == 0 || tw == 8 || tw == 16 || tw == 32 || tw == 64 || tw == 96 || tw == 128, "strip width must be 0, 8, 16, 32, 64, 96 or 128");
-    g_knobs.force_tw = tw;
-    return TDS_OK;
-}
-
-// waves per workgroup of the bit-plane kernel (4 or 8)
-TDS_EXPORT int tds_raster_set_bits_waves(int n) {
-    TDS_CHECK_ARG(n == 4 || n == 8, "waves per workgroup must be 4 or 8");
-    g_knobs.bits_waves = n;
-    return TDS_OK;
-}
-
-// read and reset the work counters of the bit-plane kernel (debug flag TDS_RASTER_DBG_STATS)
-TDS_EXPORT int tds_raster_get_stats(unsigned long long *out16) {
-    TDS_CHECK_ARG(out16, "tds_raster_get_stats: null output");
-    unsigned long long zero[16] = {0};
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stats), sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: copy failed"); return TDS_EHIP; }
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: reset failed"); return TDS_EHIP; }
-    return TDS_OK;
-}
-
-// read and reset the two counters of the prepared scan set-ups (debug flag TDS_RASTER_DBG_STATS): work items of the persistent bit-plane
-// launches that used their record, and that computed their set-up in the kernel
-TDS_EXPORT int tds_raster_get_prep_stats(unsigned long long *out2) {
-    TDS_CHECK_ARG(out2, "tds_raster_get_prep_stats: null output");
-    unsigned long long zero[2] = {0, 0};
-    if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_stats), sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: copy failed"); return TDS_EHIP; }
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: reset failed"); return TDS_EHIP; }
-    return TDS_OK;
-}
-
-// K3r (the list rasteriser of the split bit-plane path): the LDS a workgroup may take in KiB, which sets the strip width
-TDS_EXPORT int tds_raster_set_list_lds(int lds_kb) {
-    TDS_CHECK_ARG(lds_kb >= 16 && lds_kb <= 150, "tds_raster_set_list_lds: 16..150 KiB");
-    g_knobs.list_lds_kb = lds_kb;
-    return TDS_OK;
-}
-
-// K3r: waves per workgroup (2 or 4; 0 = chosen by the size of a strip)
-TDS_EXPORT int tds_raster_set_list_waves(int waves) {
-    TDS_CHECK_ARG(waves == 0 || waves == 2 || waves == 4, "tds_raster_set_list_waves: 0, 2 or 4");
-    g_knobs.list_waves = waves;
-    return TDS_OK;
-}
-
-// ablation switches, see CommonArgs::debug
-TDS_EXPORT int tds_raster_set_debug(int flags) {
-    g_knobs.debug = flags;
-    return TDS_OK;
-}
-
-// plan_raster_scene with explicit knobs; workspace_bytes as a caller passes it (the queue tail is cut off here, as in the launch)
-TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices,
-                               int64_t workspace_bytes, int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug,
-                               tds_raster_plan_t *out) {
-    TDS_CHECK_ARG(out && n_img > 0 && res > 0 && res <= 4096 && n_keys >= -1 && n_keys <= MAX_KEYS && cus > 0 &&
-                  (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode)), "tds_raster_plan: bad arguments");
-    const PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, lists_room(workspace_bytes, is_mask_mode(out_mode)), cus};
-    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug});
-    *out = tds_raster_plan_t{(int)p.form, p.tw, p.strips, p.twp, p.nwv, p.nb, p.nwv == 4 ? (p.four_per_cu ? 4 : 3) : 0, want_slices && p.form == RasterForm::Bits,
-                             p.four_per_cu, p.persist, p.tws, p.lw, (int64_t)p.lds, (int64_t)p.lds_s, p.grid, p.caps, p.ws.counts, p.ws.lists, p.ws.lists3};
-    return TDS_OK;
-}
-
-#endif  // TDS_TESTING
-
-// bytes of the coverage record of n_img float32 images of res x res (0: no record at this resolution -- lines are tracked where res is a multiple of 32)
-static int64_t coverage_bytes(int64_t n_img, int res) {
-    return (res & 31) ? 0 : (int64_t)COV_HEADER_DW * 4 + n_img * (int64_t)(res >> 5) * (int64_t)(res >> 5) * 4;
-}
-
 static int common_checks(const char *fn, int64_t n_img, int res, int out_mode, const void *out, int &tw) {
     TDS_CHECK_ARG(n_img >= 0, "%s: negative image count", fn);
     TDS_CHECK_ARG(res > 0 && res <= 4096, "%s: resolution %d out of range (1..4096)", fn, res);
@@ -3364,78 +3064,6 @@ static int common_checks(const char *fn, int64_t n_img, int res, int out_mode, c
     TDS_CHECK_ARG(n_img * ((res + tw - 1) / tw) < ((int64_t)1 << 31), "%s: too many strips", fn);
     return TDS_OK;
 }
-
-#ifndef TDS_RASTER_MASKS_TU
-TDS_EXPORT int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes) {
-    TDS_CHECK_ARG(bytes, "tds_raster_index_slices_bytes: null output");
-    TDS_CHECK_ARG(n_img >= 0 && res > 0 && res <= 4096, "tds_raster_index_slices_bytes: bad sizes");
-    *bytes = (res & 3) ? 0 : n_img * (int64_t)((res + 31) / 32) * (int64_t)(res / 4) * 64;
-    return TDS_OK;
-}
-
-TDS_EXPORT int tds_raster_coverage_bytes(int64_t n_img, int res, int64_t *bytes) {
-    TDS_CHECK_ARG(bytes, "tds_raster_coverage_bytes: null output");
-    TDS_CHECK_ARG(n_img >= 0 && res > 0 && res <= 4096, "tds_raster_coverage_bytes: bad sizes");
-    *bytes = coverage_bytes(n_img, res);
-    return TDS_OK;
-}
-
-TDS_EXPORT int tds_raster_scene_workspace_bytes(int64_t n_img, int res, int64_t *bytes) {
-    TDS_CHECK_ARG(bytes, "tds_raster_scene_workspace_bytes: null output");
-    TDS_CHECK_ARG(res > 0 && res <= 4096 && n_img >= 0, "tds_raster_scene_workspace_bytes: bad arguments");
-    const int tw = strip_width(res, g_knobs);
-    int64_t lists = 0;
-    if (tw != 0 && (res + tw - 1) / tw <= MAX_STRIPS) lists = n_img * ((res + tw - 1) / tw) * (DEFAULT_CAPS * 16 + 4);
-    // the split bit-plane path, LIST_CAPS faces per camera, where the split form can be chosen for either output type (testing: anywhere)
-#ifndef TDS_TESTING
-    if (split_serves(res, true) || split_serves(res, false))
-#endif
-    lists = std::max(lists, split_layout(n_img, LIST_CAPS).lists3);
-    *bytes = with_queue_tail(lists);
-    return TDS_OK;
-}
-
-TDS_EXPORT int tds_raster_scene_workspace_bytes_for(int64_t n_img, int res, int out_mode, int n_keys, int64_t *bytes) {
-    TDS_CHECK_ARG(bytes, "tds_raster_scene_workspace_bytes_for: null output");
-    TDS_CHECK_ARG(res > 0 && res <= 4096 && n_img >= 0, "tds_raster_scene_workspace_bytes_for: bad arguments");
-    if (is_mask_mode(out_mode)) {                // the uint8 image's workspace and the channel table in front of the queues
-        const int rc = tds_raster_scene_workspace_bytes_for(n_img, res, TDS_OUT_U8, n_keys, bytes);
-        if (rc == TDS_OK) *bytes += MASK_TABLE_BYTES;
-        return rc;
-    }
-    TDS_CHECK_ARG(out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8, "tds_raster_scene_workspace_bytes_for: unknown output mode %d", out_mode);
-    if (n_keys < 0 || n_keys > MAX_KEYS) return tds_raster_scene_workspace_bytes(n_img, res, bytes);
-    // the bit-plane kernels: face lists where the split form can run for this output type, the work queues of the persistent launch always
-    int64_t lists = 0;
-#ifndef TDS_TESTING
-    if (split_serves(res, out_mode == TDS_OUT_F32))
-#endif
-        lists = split_layout(n_img, LIST_CAPS).lists3;
-    *bytes = with_queue_tail(lists);
-    return TDS_OK;
-}
-
-// The table of prepared scan set-ups (tds_raster_aux_t::camera_prep): one record per work item (camera, strip) of the launch that takes it -- the
-// fused bit-plane kernel in persistent 4-wave workgroups; 0 where the call is served by another launch.  The strips are the plan's: of a plain
-// and of a differentiable call (which may cut the image in two where the plain call takes eight waves) the larger count.
-TDS_EXPORT int tds_raster_camera_prep_bytes(int64_t n_img, int res, int out_mode, int n_keys, int64_t *bytes) {
-    TDS_CHECK_ARG(bytes, "tds_raster_camera_prep_bytes: null output");
-    *bytes = 0;
-    TDS_CHECK_ARG(n_img >= 0 && n_img < ((int64_t)1 << 31) && res > 0 && res <= 4096, "tds_raster_camera_prep_bytes: bad sizes");
-    TDS_CHECK_ARG(out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode), "tds_raster_camera_prep_bytes: unknown output mode %d", out_mode);
-    TDS_CHECK_ARG(n_keys >= -1 && n_keys <= MAX_KEYS, "tds_raster_camera_prep_bytes: n_keys must be -1 (not known) .. %d", MAX_KEYS);
-    if (is_mask_mode(out_mode) || n_keys <= 0 || n_img == 0) return TDS_OK;
-    int64_t items = 0, ws_bytes = 0;            // (with the workspace the library recommends: where that makes the plan the split form, no table)
-    (void)tds_raster_scene_workspace_bytes_for(n_img, res, out_mode, n_keys, &ws_bytes);
-    for (int slices = 0; slices < (out_mode == TDS_OUT_F32 ? 2 : 1); ++slices) {
-        const PlanInput in = {n_img, res, out_mode, n_keys, true, true, false, slices != 0, lists_room(ws_bytes, false), 256};
-        const RasterPlan p = plan_raster_scene(in, g_knobs);
-        if (p.form == RasterForm::Bits && p.persist) items = std::max<int64_t>(items, n_img * p.strips);
-    }
-    *bytes = items * (int64_t)sizeof(PrepRecord);
-    return TDS_OK;
-}
-#endif  // !TDS_RASTER_MASKS_TU
 
 namespace {
 // what the scene kernels need to know about the static map(s) of a launch
@@ -3601,8 +3229,7 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     TDS_CHECK_ARG(n_extra >= 0 && n_extra < (1 << 20) && (n_extra == 0 || (extra_tri && extra_key)), "tds_raster_scene: bad per-camera triangle arrays");
     const bool want_slices = aux && aux->index_slices;
     if (want_slices) {
-        int64_t need = 0;
-        (void)tds_raster_index_slices_bytes(n_img, res, &need);
+        const int64_t need = index_slices_bytes(n_img, res);
         TDS_CHECK_ARG(need > 0 && out_mode == TDS_OUT_F32, "tds_raster_scene: index slices need a float32 image whose resolution is a multiple of 4");
         TDS_CHECK_ARG(aux->index_slices_bytes >= need, "tds_raster_scene: index slices buffer too small (%lld < %lld bytes)",
                       (long long)aux->index_slices_bytes, (long long)need);
@@ -3671,7 +3298,7 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     // prepared scan set-ups, written in stream order right in front of it.  No table, or one too small or misaligned: as before -- never an error.
     // (The two fields were appended to the struct: they are read only from a caller that says its struct has them.)
     if (p.form == RasterForm::Bits && p.persist && aux && (aux->flags & TDS_RASTER_HAS_CAMERA_PREP) && aux->camera_prep && ((uintptr_t)aux->camera_prep & 15) == 0 &&
-        aux->camera_prep_bytes >= n_img * p.strips * (int64_t)sizeof(PrepRecord)) {
+        aux->camera_prep_bytes >= n_img * p.strips * PREP_RECORD_BYTES) {
         const int64_t items = n_img * p.strips;
         hipLaunchKernelGGL(camera_prepare_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const SceneArgs &)a, cm, p.twp, (PrepRecord *)aux->camera_prep);
         TDS_LAUNCH_CHECK("camera_prepare_kernel");
@@ -3724,4 +3351,26 @@ TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int
     TDS_LAUNCH_CHECK("raster_mesh_kernel");
     return TDS_OK;
 }
+
+#ifdef TDS_TESTING
+// ---- testing build only (include/tdship.h, section "testing hooks"; the knobs and tds_raster_plan are raster_host.hip's) ----
+// read and reset the work counters of the bit-plane kernel (debug flag TDS_RASTER_DBG_STATS)
+TDS_EXPORT int tds_raster_get_stats(unsigned long long *out16) {
+    TDS_CHECK_ARG(out16, "tds_raster_get_stats: null output");
+    unsigned long long zero[16] = {0};
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stats), sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+
+// read and reset the two counters of the prepared scan set-ups (debug flag TDS_RASTER_DBG_STATS): work items of the persistent bit-plane
+// launches that used their record, and that computed their set-up in the kernel
+TDS_EXPORT int tds_raster_get_prep_stats(unsigned long long *out2) {
+    TDS_CHECK_ARG(out2, "tds_raster_get_prep_stats: null output");
+    unsigned long long zero[2] = {0, 0};
+    if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_stats), sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+#endif  // TDS_TESTING
 #endif  // !TDS_RASTER_MASKS_TU

@@ -18,6 +18,7 @@
 // t_a -> t_b moves with (1 - u) dt_a + u dt_b, so the same weights A0, A1 give d/dt_a and d/dt_b; the host chains them to the actor's
 // length and width through the template's construction.
 #include "tds_common.h"
+#include "tds_raster_plan.h"
 #include <algorithm>
 
 namespace {
@@ -705,7 +706,7 @@ TDS_EXPORT int tds_raster_scene_bwd_idx_f32(const float *state, const float *age
     a.gstride = grad_out_stride;
     a.n_keys = n_keys;
     for (int i = 0; i < 16; ++i) a.keys[i] = i < n_keys ? keys[i] : 0u;
-    a.nb = n_keys <= 3 ? 2 : (n_keys <= 7 ? 3 : 4);                 // as bits_index_bits of the forward
+    a.nb = tds_raster::bits_index_bits(n_keys);                     // the forward's
     // camera pass: per wave 64 owner records (NB * 5 + 1 words each, padded to 16 bytes) + 2048 uint16 cells; colour pass: 48 x BW_BLOCK floats
     const size_t lds_cam = (size_t)(BW_BLOCK / 64) * (64 * ((a.nb * 5 + 1 + 3) & ~3) + BW_QCELLS / 2) * sizeof(uint32_t);
     const size_t lds = std::max(lds_cam, grad_color ? (size_t)48 * BW_BLOCK * sizeof(float) : (size_t)0);
