@@ -6,6 +6,7 @@ lane map); the "policy" is random.
 
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
+    python examples/step_loop.py --neighbors 8      # a non-visual loop: the 8 nearest other agents in each agent's frame, with their relative velocity
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
     python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
     python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
@@ -61,11 +62,14 @@ def main():
     ap.add_argument('--res', type=int, default=128)
     ap.add_argument('--scan', type=int, default=0, metavar='RAYS', help='observe RAYS-ray range scans (compute_range_scan) instead of images')
     ap.add_argument('--scan-range', type=float, default=50.0)
+    ap.add_argument('--neighbors', type=int, default=0, metavar='K', help='observe the K nearest other agents (compute_neighbors) instead of images')
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
     ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
     args = ap.parse_args()
+    if args.scan and args.neighbors:
+        ap.error('--scan and --neighbors are two observations in place of the image: choose one')
     if args.route and args.route_to:
         ap.error('--route and --route-to are two ways to deal the one route an agent has')
     dev = torch.device('cuda', 0)
@@ -123,6 +127,9 @@ def main():
         if args.scan:
             scan = sim.compute_range_scan(n_rays=args.scan, max_range=args.scan_range)
             obs = torch.stack([scan.agents, scan.road], dim=-1) / args.scan_range        # (B, A, R, 2) in [0, 1]: distance to the nearest other agent, to the road edge
+        elif args.neighbors:
+            near = sim.compute_neighbors(k=args.neighbors, max_distance=args.scan_range)
+            obs = near.features                                              # (B, A, K, 8): Neighbors.FEATURES per slot, zeros where near.mask is False
         else:
             obs = sim.render_egocentric(res=res, fov=35.0)                   # (B, A, 3, H, W): what a policy would consume
         if routed:
@@ -143,6 +150,9 @@ def main():
     dt = time.perf_counter() - t0
     print(f'{args.steps} steps of {args.batch} x {args.agents} agents, observations {tuple(obs.shape)}: {1e3 * dt / args.steps:.2f} ms per step, '
           f'{args.batch * args.agents * args.steps / dt / 1e6:.2f} M agent-steps/s')
+    if args.neighbors:
+        print(f'{args.neighbors} neighbour slots within {args.scan_range:g} m: {float(near.mask.float().mean()):.3f} filled, nearest at '
+              f'{float(near.features[..., :2].norm(dim=-1)[near.mask[..., 0], 0].mean()):.1f} m on average')
     if args.npcs:
         c = sim.npc_controller
         print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '

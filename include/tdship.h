@@ -699,6 +699,35 @@ int tds_range_scan_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, 
                              const float *ray_sc, float *agent_range, float *road_range, int32_t *hit, int64_t B, int64_t A, int64_t E, int R,
                              float max_range, float gap_tolerance, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K6  neighbour observations (no reference counterpart: the definition is this library's own; binary32 model, equal bit for
+ * bit: tests/neighbors_model.py).  For every exposed agent the K nearest other entities within max_distance, nearest first, in its own frame.
+ * Entities are those of tds_range_scan_f32: the A exposed agents followed by E - A NPCs.
+ *   boxes    B x E x 5      [x, y, length, width, psi]; psi is not read
+ *   sc       B x E x 2      [sin, cos] of psi;  speed B x E;  present B x E uint8
+ *   visible  B x A x E      uint8, optional: non-zero = observer a may see entity e; NULL = everything is visible
+ *   features B x A x K x 8  float32;  index B x A x K int32
+ * Arithmetic: binary32 throughout, every + - * rounded once (the build passes -ffp-contract=off), so a numpy-float32 model that does the same
+ * operations in the same order reproduces the outputs bit for bit.
+ * Candidates of observer a (a < A, present[b, a] set) in scene b: every e != a with present[b, e] set, visible[b, a, e] != 0 where visible is
+ * given, and d2 <= r2, where dx = x_e - x_a, dy = y_e - y_a, d2 = dx*dx + dy*dy and r2 = max_distance * max_distance, computed once on the
+ * host in float32.  A NaN d2 fails the comparison: no candidate.  max_distance = +inf is allowed: every finite pose is then a candidate.
+ * Selection: the K candidates with the smallest (d2, e) -- equal d2 is broken by the lower entity index; slot 0 is the nearest.
+ * Slot k, 8 floats (32 bytes: two aligned 16-byte stores), with (s, c) the observer's [sin, cos], (se, ce) the neighbour's, v_a / v_e the speeds:
+ *   0, 1  x = dx*c + dy*s,  y = dy*c - dx*s                      (the convention of the route lookahead)
+ *   2, 3  sin_rel = se*c - ce*s,  cos_rel = ce*c + se*s
+ *   4, 5  vx = v_e*cos_rel - v_a,  vy = v_e*sin_rel              (the neighbour's velocity minus the observer's, in the observer's frame)
+ *   6, 7  the neighbour's length and width, copied
+ * index holds the entity of the slot, -1 for an empty slot; the features of an empty slot are all 0; the row of an observer that is not
+ * present is entirely empty; every output is written in full.
+ * 1 <= K <= TDS_NEIGHBORS_MAX_K, max_distance not negative and not NaN, A <= E: else TDS_EINVAL before any launch; E > TDS_NEIGHBORS_MAX_ENTITIES
+ * (the entities of a scene live in LDS, 32 bytes each) is TDS_ELIMIT; B * A == 0 is a successful no-op.  One launch; nothing is allocated and
+ * nothing synchronises; every loop of the kernel is bounded by E and K whatever the tensors hold. */
+#define TDS_NEIGHBORS_MAX_K 32
+#define TDS_NEIGHBORS_MAX_ENTITIES 1024
+int tds_neighbors_f32(const float *boxes, const float *sc, const float *speed, const uint8_t *present, const uint8_t *visible,
+                      float *features, int32_t *index, int64_t B, int64_t A, int64_t E, int K, float max_distance, void *stream);
+
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */

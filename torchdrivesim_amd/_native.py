@@ -179,6 +179,7 @@ tds_range_scan_f32(handle map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f3
     float gap_tolerance, stream stream)
 tds_range_scan_multi_f32(handle set, i32* scene_map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E,
     int R, float max_range, float gap_tolerance, stream stream)
+tds_neighbors_f32(f32* boxes, f32* sc, f32* speed, u8* present, u8* visible, f32* features, i32* index, int64 B, int64 A, int64 E, int K, float max_distance, stream stream)
 '''
 
 #: entry points that only libtdship_testing.so exports (include/tdship.h, "testing hooks")
@@ -281,6 +282,7 @@ SPAWN_MAX_BOXES = 2048           # TDS_SPAWN_MAX_BOXES
 FOLLOW_MAX_HOPS, FOLLOW_MAX_ENTITIES = 8, 1024       # TDS_FOLLOW_MAX_HOPS, TDS_FOLLOW_MAX_ENTITIES
 ROUTE_MAX_LANES, ROUTE_MAX_LOOKAHEAD = 16, 32        # TDS_ROUTE_MAX_LANES, TDS_ROUTE_MAX_LOOKAHEAD
 ROUTE_MAX_GRAPH = 2048                               # TDS_ROUTE_MAX_GRAPH
+NEIGHBORS_MAX_K, NEIGHBORS_MAX_ENTITIES = 32, 1024   # TDS_NEIGHBORS_MAX_K, TDS_NEIGHBORS_MAX_ENTITIES
 
 
 class TdsError(RuntimeError):

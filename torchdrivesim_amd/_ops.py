@@ -648,6 +648,46 @@ def range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_toler
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# K6 neighbour observations
+# ---------------------------------------------------------------------------------------------------------------
+def check_neighbors_args(k, max_distance):
+    """the argument rules of tds_neighbors_f32, on the host: raised before anything is computed or launched"""
+    if int(k) != k or int(k) < 1 or int(k) > nat.NEIGHBORS_MAX_K:
+        raise ValueError(f'neighbors: k must be 1 .. {nat.NEIGHBORS_MAX_K} (got {k})')
+    if not float(max_distance) >= 0.0:                  # (NaN fails the comparison; +inf is allowed)
+        raise ValueError(f'neighbors: max_distance must not be negative or NaN (got {max_distance})')
+
+
+def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=None):
+    """The k nearest other entities of every exposed agent (tds_neighbors_f32, include/tdship.h "K6"): boxes (B,E,5) [x,y,length,width,psi],
+    sc (B,E,2) [sin, cos] of psi, speed (B,E), present (B,E), visible None or (B,A,E) bool / uint8 -> features (B,A,k,8) float32,
+    index (B,A,k) int32.  No gradient; CPU tensors raise (there is no CPU fallback)."""
+    check_neighbors_args(k, max_distance)
+    if boxes.dim() != 3 or boxes.shape[-1] != 5:
+        raise ValueError(f'neighbors: boxes must be (B, E, 5), got {tuple(boxes.shape)}')
+    B, E = int(boxes.shape[0]), int(boxes.shape[1])
+    A, K = int(n_exposed), int(k)
+    if A < 0 or A > E:
+        raise ValueError(f'neighbors: {n_exposed} exposed agents, {E} entities')
+    if tuple(sc.shape) != (B, E, 2) or tuple(speed.shape) != (B, E) or tuple(present.shape) != (B, E):
+        raise ValueError(f'neighbors: sc must be ({B}, {E}, 2), speed and present ({B}, {E}), got {tuple(sc.shape)}, {tuple(speed.shape)} and '
+                         f'{tuple(present.shape)}')
+    if visible is not None:
+        if tuple(visible.shape) != (B, A, E):
+            raise ValueError(f'neighbors: visible must be ({B}, {A}, {E}), got {tuple(visible.shape)}')
+        if visible.dtype not in (torch.bool, u8):
+            raise ValueError(f'neighbors: visible must be bool or uint8, got {visible.dtype}')
+    boxes, sc, speed = _c(boxes.detach()), _c(sc.detach()), _c(speed.detach())
+    present = _u8(present)
+    visible = None if visible is None else _u8(visible)
+    dev = boxes.device
+    features = torch.empty((B, A, K, 8), dtype=f32, device=dev)
+    index = torch.empty((B, A, K), dtype=i32, device=dev)
+    nat.call('tds_neighbors_f32', dev, boxes, sc, speed, present, visible, features, index, B, A, E, K, float(max_distance))
+    return features, index
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # K3 rasteriser
 # ---------------------------------------------------------------------------------------------------------------
 #: scratch for the binned fast path of K3, one per (device, stream, cameras, resolution): two renders of one shape on different streams

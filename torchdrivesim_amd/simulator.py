@@ -9,6 +9,7 @@
     compute_collision  -> K2a, all agents of all scenes in one launch        reference: simulator.py:1064-1194 (A launches)
     compute_offroad    -> K2b over the device-resident map grid              reference: simulator.py:1035-1044
 
+    compute_neighbors  -> K6 (csrc/neighbors.hip), the K nearest entities per agent   reference: -- (get_all_agents_relative, all pairs)
     compute_wrong_way  -> lane tables of `lanelet_map` (lanelet2.py), one launch  reference: simulator.py:607-630 (Python triple loop)
 
 Also carried: traffic controls, waypoint goals (state + rendering), observation noise and lane features (plumbing only).  Out of scope
@@ -60,6 +61,31 @@ class RangeScan:
     agents: Tensor
     road: Tensor
     hit: Tensor
+
+
+@dataclass
+class Neighbors:
+    """What `Simulator.compute_neighbors` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`) and `index` BxAxK int32, the entity
+    in [0, A + Npc) of every slot, -1 for an empty one (its features are all 0)."""
+    features: Tensor
+    index: Tensor
+
+    FEATURES = ('x', 'y', 'sin', 'cos', 'vx', 'vy', 'length', 'width')
+
+    @property
+    def mask(self) -> Tensor:
+        """BxAxK bool: the slot holds a neighbour"""
+        return self.index >= 0
+
+    def take(self, per_entity: Tensor, fill=0) -> Tensor:
+        """Gathers a per-entity tensor Bx(A+Npc)x... (`get_all_agent_type()` and the like) at `index` -> BxAxKx..., `fill` in the empty slots."""
+        B, A, K = self.index.shape
+        if per_entity.dim() < 2 or per_entity.shape[0] != B:
+            raise ValueError(f'take: expected a ({B}, E, ...) tensor, got {tuple(per_entity.shape)}')
+        rest = tuple(per_entity.shape[2:])
+        idx = self.index.clamp(min=0).to(torch.int64).reshape((B, A * K) + (1,) * len(rest)).expand((B, A * K) + rest)
+        got = torch.gather(per_entity, 1, idx).reshape((B, A, K) + rest)
+        return torch.where(self.mask.reshape((B, A, K) + (1,) * len(rest)), got, torch.full((), fill, dtype=got.dtype, device=got.device))
 
 
 def _enlarge(x: Tensor, n: int) -> Tensor:
@@ -1222,6 +1248,34 @@ class Simulator:
             ray_sc = _ops.heading_sc(state[..., 2].detach().unsqueeze(-1) + self.range_scan_angles(R, fov, device=state.device))
             out = _ops.range_scan(smap, boxes, sc, self.get_all_agent_present_mask(), ray_sc, A, max_range, gap_tolerance, want_agents=agents)
         return RangeScan(*out)
+
+    # ------------------------------------------------------------------------------------------------- neighbour observations
+    def compute_neighbors(self, k: int = 8, max_distance: float = 50.0, visible: Optional[Tensor] = None) -> Neighbors:
+        """The `k` nearest OTHER present entities (exposed agents and NPCs) of every exposed agent within `max_distance` metres between centres
+        (+inf: no limit), nearest first, equal distances by the lower entity index:
+
+        features  BxAxkx8  per slot `Neighbors.FEATURES`: x, y of the neighbour's centre in the observer's frame (x ahead, y to the left), [sin, cos]
+                           of its heading relative to the observer's, vx, vy its velocity minus the observer's in the observer's frame, its length
+                           and width; all 0 in an empty slot;
+        index     BxAxk    int32: the entity in [0, A + Npc) of the slot, -1 for an empty slot (`Neighbors.mask`; `Neighbors.take` gathers any
+                           per-entity tensor at it).
+
+        `visible`: an optional BxAx(A+Npc) bool or uint8 tensor, non-zero where observer a may see entity e -- `get_noisy_present_mask()` of an
+        occlusion noise model is one.  Rows of exposed agents that are not present are empty.  1 <= k <= 32, at most 1024 entities per scene.
+        One HIP kernel in binary32 (csrc/neighbors.hip; the definition is in include/tdship.h, tests/neighbors_model.py equals it bit for bit).
+        No gradient.  Runs on the current stream and allocates its outputs only, so it can be captured into a graph."""
+        _ops.check_neighbors_args(k, max_distance)
+        state = self.get_state()
+        if not state.is_cuda:
+            raise RuntimeError(f'compute_neighbors runs on an MI355X; the simulator is on {state.device} (no CPU fallback)')
+        B, A, K = state.shape[0], self.agent_count, int(k)
+        if A == 0:
+            return Neighbors(torch.empty((B, 0, K, 8), dtype=torch.float32, device=state.device), torch.empty((B, 0, K), dtype=torch.int32, device=state.device))
+        with torch.no_grad():
+            all_state = self.get_all_agent_state().detach()
+            boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
+            out = _ops.neighbors(boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, max_distance, visible=visible)
+        return Neighbors(*out)
 
     def compute_wrong_way(self) -> Tensor:
         """Wrong-way metric per agent, -cos of the angle between the agent and the lane it is on where that angle exceeds
