@@ -7,6 +7,8 @@ lane map); the "policy" is random.
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
     python examples/step_loop.py --neighbors 8      # a non-visual loop: the 8 nearest other agents in each agent's frame, with their relative velocity
+    python examples/step_loop.py --lights device --stop-lines 4     # the light programmes run on the device, a clock per scene; a non-visual loop sees
+                                                                    # the 4 nearest stop lines ahead with their colour and the seconds until it changes
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
     python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
     python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
@@ -24,7 +26,7 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402  (scene construction shared with the benchmark)
 from torchdrivesim_amd import lanelet2  # noqa: E402
-from torchdrivesim_amd.map import load_map_config, traffic_controls_from_map_config  # noqa: E402
+from torchdrivesim_amd.map import load_map_config, programmed_traffic_lights_from_map_config, traffic_controls_from_map_config  # noqa: E402
 from torchdrivesim_amd.traffic_lights import current_light_state_tensor_from_controller  # noqa: E402
 from torchdrivesim_amd.utils import Resolution  # noqa: E402
 
@@ -63,13 +65,16 @@ def main():
     ap.add_argument('--scan', type=int, default=0, metavar='RAYS', help='observe RAYS-ray range scans (compute_range_scan) instead of images')
     ap.add_argument('--scan-range', type=float, default=50.0)
     ap.add_argument('--neighbors', type=int, default=0, metavar='K', help='observe the K nearest other agents (compute_neighbors) instead of images')
+    ap.add_argument('--lights', choices=('host', 'device'), default='host', help='where the light programmes run: one host controller for the whole batch '
+                    '(the index tensor is copied over every step), or on the device with a clock per scene (traffic_controls.ProgrammedTrafficLightControl)')
+    ap.add_argument('--stop-lines', type=int, default=0, metavar='K', help='observe the K nearest stop lines ahead (compute_stop_lines) instead of images')
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
     ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
     args = ap.parse_args()
-    if args.scan and args.neighbors:
-        ap.error('--scan and --neighbors are two observations in place of the image: choose one')
+    if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) > 1:
+        ap.error('--scan, --neighbors and --stop-lines are observations in place of the image: choose one')
     if args.route and args.route_to:
         ap.error('--route and --route-to are two ways to deal the one route an agent has')
     dev = torch.device('cuda', 0)
@@ -77,8 +82,14 @@ def main():
     lanes = lanelet2.load_lanelet_map(os.path.join(gold, 'carla_Town01.osm.gz'), origin=(0.0, 0.0))
     cfg = load_map_config(os.path.join(gold, 'maps', 'carla_Town01', 'metadata.json'))
     sim, _, _ = bench.build_simulator(args.batch, args.agents, dev, seed=0, lanelet_map=lanes)
-    # traffic lights: the programmes run on the host, the device sees one index per light and step
+    # traffic lights: by default the programmes run on the host, the device sees one index per light and step
     controls = {k: v.extend(args.batch).to(dev) for k, v in traffic_controls_from_map_config(cfg).items()}
+    if args.lights == 'device':
+        # ... with --lights device they run on the device: sim.step ticks every scene's own clocks in one launch, and a scene's lights are reset with
+        # the scene, from (seed, scene id) like its spawn -- here once, for the episodes the batch starts with
+        episode_ids = torch.arange(args.batch, device=dev)
+        controls['traffic_light'] = programmed_traffic_lights_from_map_config(cfg, args.batch, dev, dt=0.1, seed=0)
+        controls['traffic_light'].reset(scene_ids=episode_ids)
     sim.traffic_controls = controls
     if args.npcs:
         # NPC traffic: placed on the lanes clear of the agents (one launch), then on rails along the lane graph, one launch per step.  They drive on
@@ -121,8 +132,9 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
         action = torch.rand((args.batch, args.agents, 2), device=dev, generator=g) * 2 - 1
-        programme.tick(0.1)
-        controls['traffic_light'].set_state(current_light_state_tensor_from_controller(programme, light_ids).unsqueeze(0).expand(args.batch, -1).to(dev))
+        if args.lights == 'host':
+            programme.tick(0.1)
+            controls['traffic_light'].set_state(current_light_state_tensor_from_controller(programme, light_ids).unsqueeze(0).expand(args.batch, -1).to(dev))
         sim.step(action)
         if args.scan:
             scan = sim.compute_range_scan(n_rays=args.scan, max_range=args.scan_range)
@@ -130,6 +142,10 @@ def main():
         elif args.neighbors:
             near = sim.compute_neighbors(k=args.neighbors, max_distance=args.scan_range)
             obs = near.features                                              # (B, A, K, 8): Neighbors.FEATURES per slot, zeros where near.mask is False
+        elif args.stop_lines:
+            lines = sim.compute_stop_lines(k=args.stop_lines, max_distance=args.scan_range)
+            colour = torch.nn.functional.one_hot((lines.state + 1).long(), 4)[..., 1:]                  # red / yellow / green, all 0 in an empty slot
+            obs = torch.cat([lines.features, colour.to(lines.features.dtype)], dim=-1)                 # (B, A, K, 11): StopLines.FEATURES + the colour
         else:
             obs = sim.render_egocentric(res=res, fov=35.0)                   # (B, A, 3, H, W): what a policy would consume
         if routed:
@@ -153,6 +169,10 @@ def main():
     if args.neighbors:
         print(f'{args.neighbors} neighbour slots within {args.scan_range:g} m: {float(near.mask.float().mean()):.3f} filled, nearest at '
               f'{float(near.features[..., :2].norm(dim=-1)[near.mask[..., 0], 0].mean()):.1f} m on average')
+    if args.stop_lines:
+        red = (lines.state == 0) & lines.mask
+        print(f'{args.stop_lines} stop-line slots within {args.scan_range:g} m ahead: {float(lines.mask.float().mean()):.3f} filled, {float(red.float().mean()):.3f} '
+              f'red; the nearest changes in {float(lines.features[..., 0, 6][lines.mask[..., 0]].mean()):.1f} s on average')
     if args.npcs:
         c = sim.npc_controller
         print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '

@@ -728,6 +728,65 @@ int tds_range_scan_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, 
 int tds_neighbors_f32(const float *boxes, const float *sc, const float *speed, const uint8_t *present, const uint8_t *visible,
                       float *features, int32_t *index, int64_t B, int64_t A, int64_t E, int K, float max_distance, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K7  traffic lights on the device (models, equal bit for bit: tests/lights_model.py).
+ *
+ * (a) The programmes.  M machines of at most P phases drive N lights; the tables are shared by the B scenes of a batch, the clocks are per scene:
+ *   duration    M x P float64     seconds of phase p of machine m (rows of shorter machines are padded)
+ *   next_phase  M x P int32       LIST POSITION of the phase that follows (what TrafficLightStateMachine.tick indexes its list with)
+ *   n_phases    M int32           phases of machine m, 1 .. P
+ *   colour      M x P x N uint8   the state light n shows in that phase, 255 where the phase does not name the light
+ *   phase       B x M int32       in and out: list position of the current phase;  remaining B x M float64, in and out: seconds left in it
+ *   state       B x N int64, time_to_change B x N float32: out;  mask B uint8 or NULL: scenes with a zero are left exactly as they are
+ * tds_lights_step, for every masked scene:
+ *   1. with `advance` non-zero every machine does, in float64 with + - and comparisons only, p its phase and r its remaining time:
+ *        left = r - dt;  if left > 0: r = left.  Otherwise at most TDS_LIGHTS_MAX_SKIPS times:
+ *          nxt = next_phase[m][p], span = duration[m][nxt];
+ *          if left == 0: p = nxt, r = span, stop;
+ *          left += span;  if left > 0: p = nxt, r = left if left <= span else span, stop;
+ *          p = nxt;
+ *        and when the cap is exhausted p = nxt, r = span.  This is TrafficLightStateMachine.tick operation for operation (the one copy of it that
+ *        host and device compile is csrc/tds_lights.h).
+ *   2. then every light n takes colour[m][p_m][n] of the LAST machine m (the highest index) whose current phase names it -- the order of the
+ *      host's merged.update -- and time_to_change[b, n] is that machine's remaining time rounded to binary32.  A light that no current phase
+ *      names keeps what it had.  advance == 0 does step 2 alone.
+ * dt points to ONE double in host memory, read before the launch (a scalar of the call; the kernel gets the value).
+ * tds_lights_reset puts every machine of the masked scenes at the beginning of phase (r0 * n_phases[m]) >> 32, r0 the first word of
+ * Philox4x32-10 with key (seed low ^ 0x4C494748, seed high ^ 0x54535452) and counter (scene id low, scene id high, m, 0), and sets remaining to
+ * that phase's duration; state and time_to_change follow with tds_lights_step(advance = 0).
+ * M > TDS_LIGHTS_MAX_MACHINES, P > TDS_LIGHTS_MAX_PHASES or N > TDS_LIGHTS_MAX_LIGHTS is TDS_ELIMIT; a negative or non-finite dt is TDS_EINVAL
+ * before any launch; B == 0 is a successful no-op.  One launch each, nothing is allocated, nothing synchronises; every index read from device
+ * memory (phase, next_phase, n_phases) is clamped to its table before use and every loop is bounded whatever the tables hold. */
+#define TDS_LIGHTS_MAX_MACHINES 256
+#define TDS_LIGHTS_MAX_PHASES 64
+#define TDS_LIGHTS_MAX_LIGHTS 1024
+#define TDS_LIGHTS_MAX_SKIPS 1024
+int tds_lights_step(const double *duration, const int32_t *next_phase, const int32_t *n_phases, const uint8_t *colour, int32_t *phase,
+                    double *remaining, int64_t *state, float *time_to_change, const uint8_t *mask, int64_t B, int64_t M, int64_t P, int64_t N,
+                    const double *dt, int advance, void *stream);
+int tds_lights_reset(const int32_t *n_phases, const double *duration, int32_t *phase, double *remaining, const uint8_t *mask,
+                     const int64_t *scene_ids, int64_t B, int64_t M, int64_t P, uint64_t seed, void *stream);
+
+/* (b) Stop-line observations (no reference counterpart).  For every exposed agent the K nearest stop lines of one traffic control within
+ * max_distance between centres, nearest first, in the agent's frame; K6's conventions.
+ *   agent_xy B x A x 2, agent_sc B x A x 2 [sin, cos], agent_present B x A uint8
+ *   lines B x N x 5 [x, y, length, width, psi] (psi is not read), line_sc B x N x 2 [sin, cos] of psi, mask B x N uint8 (0: padding)
+ *   state B x N int64 (the control's state), time_to_change B x N float32 or NULL (read as 0)
+ *   features B x A x K x 8 float32, index B x A x K int32, slot_state B x A x K int32
+ * Binary32 throughout, every operation rounded once.  With (s, c) the observer's [sin, cos] and (sl, cl) the line's:
+ *   dx = x_n - x_a, dy = y_n - y_a, d2 = dx*dx + dy*dy;  x = dx*c + dy*s, y = dy*c - dx*s;  sin_rel = sl*c - cl*s, cos_rel = cl*c + sl*s.
+ * Candidates of a present observer: the lines n with mask[b, n] set, d2 <= r2 (r2 = max_distance * max_distance, computed once on the host in
+ * float32), with ahead_only x >= 0, and cos_rel >= min_cos (-inf: no such filter).  A NaN fails every test.  Selection: the K smallest (d2, n).
+ * Slot k: x, y, sin_rel, cos_rel, length, width, time_to_change[b, n], sqrt(d2) (correctly rounded); index = n; slot_state = state[b, n] as
+ * int32.  Empty slots are all 0 with index -1 and slot_state -1; the row of an absent observer is all empty; every output is written in full.
+ * 1 <= K <= TDS_STOP_LINES_MAX_K, max_distance not negative and not NaN, min_cos not NaN: else TDS_EINVAL; N > TDS_LIGHTS_MAX_LIGHTS (the lines of
+ * a scene live in LDS, 32 bytes each) is TDS_ELIMIT; B * A == 0 is a successful no-op.  One launch, nothing allocated, nothing synchronises. */
+#define TDS_STOP_LINES_MAX_K 32
+int tds_stop_lines_f32(const float *agent_xy, const float *agent_sc, const uint8_t *agent_present, const float *lines, const float *line_sc,
+                       const uint8_t *mask, const int64_t *state, const float *time_to_change, float *features, int32_t *index,
+                       int32_t *slot_state, int64_t B, int64_t A, int64_t N, int K, float max_distance, int ahead_only, float min_cos,
+                       void *stream);
+
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */

@@ -180,6 +180,11 @@ tds_range_scan_f32(handle map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f3
 tds_range_scan_multi_f32(handle set, i32* scene_map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E,
     int R, float max_range, float gap_tolerance, stream stream)
 tds_neighbors_f32(f32* boxes, f32* sc, f32* speed, u8* present, u8* visible, f32* features, i32* index, int64 B, int64 A, int64 E, int K, float max_distance, stream stream)
+tds_lights_step(f64* duration, i32* next_phase, i32* n_phases, u8* colour, i32* phase, f64* remaining, i64* state, f32* time_to_change, u8* mask, int64 B, int64 M, int64 P,
+    int64 N, host* dt, int advance, stream stream)
+tds_lights_reset(i32* n_phases, f64* duration, i32* phase, f64* remaining, u8* mask, i64* scene_ids, int64 B, int64 M, int64 P, uint64 seed, stream stream)
+tds_stop_lines_f32(f32* agent_xy, f32* agent_sc, u8* agent_present, f32* lines, f32* line_sc, u8* mask, i64* state, f32* time_to_change, f32* features, i32* index,
+    i32* slot_state, int64 B, int64 A, int64 N, int K, float max_distance, int ahead_only, float min_cos, stream stream)
 '''
 
 #: entry points that only libtdship_testing.so exports (include/tdship.h, "testing hooks")
@@ -283,6 +288,8 @@ FOLLOW_MAX_HOPS, FOLLOW_MAX_ENTITIES = 8, 1024       # TDS_FOLLOW_MAX_HOPS, TDS_
 ROUTE_MAX_LANES, ROUTE_MAX_LOOKAHEAD = 16, 32        # TDS_ROUTE_MAX_LANES, TDS_ROUTE_MAX_LOOKAHEAD
 ROUTE_MAX_GRAPH = 2048                               # TDS_ROUTE_MAX_GRAPH
 NEIGHBORS_MAX_K, NEIGHBORS_MAX_ENTITIES = 32, 1024   # TDS_NEIGHBORS_MAX_K, TDS_NEIGHBORS_MAX_ENTITIES
+LIGHTS_MAX_MACHINES, LIGHTS_MAX_PHASES, LIGHTS_MAX_LIGHTS = 256, 64, 1024      # TDS_LIGHTS_MAX_MACHINES, TDS_LIGHTS_MAX_PHASES, TDS_LIGHTS_MAX_LIGHTS
+LIGHTS_MAX_SKIPS, STOP_LINES_MAX_K = 1024, 32        # TDS_LIGHTS_MAX_SKIPS, TDS_STOP_LINES_MAX_K
 
 
 class TdsError(RuntimeError):

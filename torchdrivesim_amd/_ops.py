@@ -688,6 +688,72 @@ def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=Non
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# K7 traffic lights on the device (csrc/lights.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def lights_step(tables, phase, remaining, state, time_to_change, dt, advance=True, mask=None):
+    """tds_lights_step (include/tdship.h "K7"): tables = (duration MxP float64, next_phase MxP int32, n_phases M int32, colour MxPxN uint8); phase
+    (B,M) int32, remaining (B,M) float64, state (B,N) int64 and time_to_change (B,N) float32 are updated IN PLACE and must be dense tensors of
+    exactly those types; mask None or (B,) bool / uint8.  One launch on the current stream, no allocation, no synchronisation."""
+    duration, next_phase, n_phases, colour = tables
+    B, M = phase.shape
+    P, N = duration.shape[1], state.shape[1]
+    if tuple(duration.shape) != (M, P) or tuple(next_phase.shape) != (M, P) or tuple(n_phases.shape) != (M,) or tuple(colour.shape) != (M, P, N):
+        raise ValueError(f'lights_step: tables of {tuple(duration.shape)}, {tuple(next_phase.shape)}, {tuple(n_phases.shape)} and {tuple(colour.shape)} '
+                         f'for {M} machines and {N} lights')
+    if tuple(remaining.shape) != (B, M) or tuple(state.shape) != (B, N) or tuple(time_to_change.shape) != (B, N):
+        raise ValueError(f'lights_step: remaining must be ({B}, {M}), state and time_to_change ({B}, {N}), got {tuple(remaining.shape)}, '
+                         f'{tuple(state.shape)} and {tuple(time_to_change.shape)}')
+    if mask is not None and tuple(mask.shape) != (B,):
+        raise ValueError(f'lights_step: mask must be ({B},), got {tuple(mask.shape)}')
+    nat.call('tds_lights_step', phase.device, duration, next_phase, n_phases, colour, phase, remaining, state, time_to_change,
+             None if mask is None else _u8(mask), B, M, P, N, ctypes.byref(ctypes.c_double(float(dt))), int(bool(advance)))
+
+
+def lights_reset(tables, phase, remaining, scene_ids, seed, mask=None):
+    """tds_lights_reset: every machine of the masked scenes to the beginning of its Philox-picked phase, in place; follow it with
+    lights_step(advance=False).  scene_ids (B,) int64."""
+    duration, _, n_phases, _ = tables
+    B, M = phase.shape
+    if tuple(remaining.shape) != (B, M) or tuple(scene_ids.shape) != (B,) or (mask is not None and tuple(mask.shape) != (B,)):
+        raise ValueError(f'lights_reset: remaining must be ({B}, {M}), scene_ids and mask ({B},)')
+    nat.call('tds_lights_reset', phase.device, n_phases, duration, phase, remaining, None if mask is None else _u8(mask), scene_ids, B, M,
+             duration.shape[1], _seed64(seed))
+
+
+def check_stop_lines_args(k, max_distance, min_cos):
+    """the argument rules of tds_stop_lines_f32, on the host: raised before anything is computed or launched"""
+    if int(k) != k or int(k) < 1 or int(k) > nat.STOP_LINES_MAX_K:
+        raise ValueError(f'stop lines: k must be 1 .. {nat.STOP_LINES_MAX_K} (got {k})')
+    if not float(max_distance) >= 0.0:                  # (NaN fails the comparison; +inf is allowed)
+        raise ValueError(f'stop lines: max_distance must not be negative or NaN (got {max_distance})')
+    if min_cos is not None and float(min_cos) != float(min_cos):
+        raise ValueError('stop lines: min_cos must not be NaN')
+
+
+def stop_lines(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, time_to_change, k, max_distance, ahead_only=True, min_cos=None):
+    """The k nearest stop lines of every exposed agent (tds_stop_lines_f32, include/tdship.h "K7"): agent_xy (B,A,2), agent_sc (B,A,2) [sin, cos],
+    agent_present (B,A); lines (B,N,5) [x,y,length,width,psi], line_sc (B,N,2), mask (B,N), state (B,N) int64, time_to_change None or (B,N)
+    -> features (B,A,k,8) float32, index (B,A,k) int32, state (B,A,k) int32.  No gradient; CPU tensors raise (there is no CPU fallback)."""
+    check_stop_lines_args(k, max_distance, min_cos)
+    if agent_xy.dim() != 3 or agent_xy.shape[-1] != 2 or lines.dim() != 3 or lines.shape[-1] != 5 or lines.shape[0] != agent_xy.shape[0]:
+        raise ValueError(f'stop lines: agent_xy must be (B, A, 2) and lines (B, N, 5), got {tuple(agent_xy.shape)} and {tuple(lines.shape)}')
+    B, A, N, K = int(agent_xy.shape[0]), int(agent_xy.shape[1]), int(lines.shape[1]), int(k)
+    if tuple(agent_sc.shape) != (B, A, 2) or tuple(agent_present.shape) != (B, A):
+        raise ValueError(f'stop lines: agent_sc must be ({B}, {A}, 2) and agent_present ({B}, {A}), got {tuple(agent_sc.shape)} and {tuple(agent_present.shape)}')
+    if tuple(line_sc.shape) != (B, N, 2) or tuple(mask.shape) != (B, N) or tuple(state.shape) != (B, N) or \
+            (time_to_change is not None and tuple(time_to_change.shape) != (B, N)):
+        raise ValueError(f'stop lines: line_sc must be ({B}, {N}, 2), mask, state and time_to_change ({B}, {N})')
+    dev = agent_xy.device
+    features = torch.empty((B, A, K, 8), dtype=f32, device=dev)
+    index = torch.empty((B, A, K), dtype=i32, device=dev)
+    slot_state = torch.empty((B, A, K), dtype=i32, device=dev)
+    nat.call('tds_stop_lines_f32', dev, _c(agent_xy.detach()), _c(agent_sc.detach()), _u8(agent_present), _c(lines.detach()), _c(line_sc.detach()), _u8(mask),
+             _c(state, torch.int64), None if time_to_change is None else _c(time_to_change), features, index, slot_state, B, A, N, K, float(max_distance),
+             int(bool(ahead_only)), float('-inf') if min_cos is None else float(min_cos))
+    return features, index, slot_state
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # K3 rasteriser
 # ---------------------------------------------------------------------------------------------------------------
 #: scratch for the binned fast path of K3, one per (device, stream, cameras, resolution): two renders of one shape on different streams

@@ -2,13 +2,12 @@
 // first, in the observer's frame, with relative velocity and size.  No reference counterpart: the definition is this project's own
 // (include/tdship.h "K6"; binary32 model, bit for bit: tests/neighbors_model.py).
 // One workgroup = a slice of NB_AGENTS observers of one scene; the scene's E entities are staged in LDS once, 32 bytes each; one wave per
-// observer, the waves of a workgroup taking the observers of the slice in turn.  Every candidate has the 64-bit key (bits of d2) << 32 | e --
-// d2 >= 0, so its bits order as an unsigned integer; the keys are unique -- and the K smallest keys are the answer:
-//   E <= 64   a lane per entity; a lane's rank is the number of smaller keys, counted over the CANDIDATE lanes' d2 read as wave-uniform values
-//             (v_readlane: no LDS traffic, one step per candidate whatever K is); the lane whose rank is below K writes its own slot;
-//   E  > 64   the d2 bits of the observer go to the wave's own LDS row, then K rounds of a wave-wide minimum over the keys above the last winner.
+// observer, the waves of a workgroup taking the observers of the slice in turn.  The wave selects the K smallest keys (bits of d2) << 32 | e of the
+// candidates (tds_select.h, shared with the stop lines of lights.hip): by rank among the candidate lanes up to 64 entities, in K rounds of a wave-wide
+// minimum over keys in LDS above.
 // All arithmetic is binary32 + - *, rounded once each (-ffp-contract=off).
 #include "tds_common.h"
+#include "tds_select.h"
 #include <algorithm>
 
 namespace {
@@ -17,7 +16,7 @@ constexpr int NB_BLOCK = 256;           // 4 waves
 constexpr int NB_WAVES = NB_BLOCK / 64;
 constexpr int NB_AGENTS = 16;           // observers per workgroup: four per wave
 constexpr int NB_WORDS = 8;             // LDS words per entity: x, y, length, width, sin, cos, speed, present (0 / 1)
-constexpr uint32_t NO_KEY = 0xffffffffu; // the d2 bits of an entity that is no candidate (a NaN pattern: no candidate's d2 is a NaN)
+using tds::NO_KEY;                      // the d2 bits of an entity that is no candidate
 
 struct NeighborArgs {
     const float *boxes, *sc, *speed;
@@ -56,15 +55,6 @@ __device__ __forceinline__ void store_slot(const NeighborArgs &g, const float *b
     g.index[row + k] = e;
 }
 
-__device__ __forceinline__ uint64_t wave_min(uint64_t v) {
-    for (int m = 32; m > 0; m >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // grid = (B, ceil(A / NB_AGENTS)); dynamic LDS = E * NB_WORDS floats, and for E > 64 another NB_WAVES * E words of keys
 __global__ void __launch_bounds__(NB_BLOCK) neighbors_kernel(NeighborArgs g) {
     extern __shared__ __attribute__((aligned(16))) float bx[];
@@ -89,35 +79,11 @@ __global__ void __launch_bounds__(NB_BLOCK) neighbors_kernel(NeighborArgs g) {
             continue;
         }
         const uint8_t *vis = g.visible ? g.visible + (b * A + a) * E : nullptr;
-        if (E <= 64) {
-            const uint32_t key = lane < E ? key_of(bx, vis, a, lane, me.x, me.y, g.r2) : NO_KEY;
-            const uint64_t cand = __ballot(key != NO_KEY);              // lanes >= E hold NO_KEY: at most E bits
-            int rank = 0;
-            for (uint64_t m = cand; m != 0; m &= m - 1) {                // one step per candidate (wave-uniform): only they can be smaller
-                const int i = __builtin_ctzll(m);
-                const uint32_t ki = __builtin_amdgcn_readlane(key, i);
-                rank += (ki < key || (ki == key && i < lane)) ? 1 : 0;
-            }
-            const int found = __popcll(cand);
-            if (key != NO_KEY && rank < K) store_slot(g, bx, row, rank, lane, me, me2);
-            if (lane >= found && lane < K) store_slot(g, bx, row, lane, -1, me, me2);
-        } else {
-            for (int e = lane; e < E; e += 64) wk[e] = key_of(bx, vis, a, e, me.x, me.y, g.r2);     // read back by the same lane only
-            int mine = -1;
-            uint64_t above = 0;                                          // the keys still to be dealt: those >= above
-            for (int k = 0; k < K; ++k) {
-                uint64_t best = ~(uint64_t)0;
-                for (int e = lane; e < E; e += 64) {
-                    const uint64_t key = ((uint64_t)wk[e] << 32) | (uint32_t)e;
-                    if (key >= above && key < best) best = key;
-                }
-                best = wave_min(best);
-                if ((uint32_t)(best >> 32) == NO_KEY) break;             // no candidate is left (wave-uniform)
-                if (lane == k) mine = (int)(uint32_t)best;
-                above = best + 1;
-            }
-            if (lane < K) store_slot(g, bx, row, lane, mine, me, me2);
-        }
+        const auto store = [&](int k, int e) { store_slot(g, bx, row, k, e, me, me2); };
+        if (E <= 64)
+            tds::select_by_rank(lane < E ? key_of(bx, vis, a, lane, me.x, me.y, g.r2) : NO_KEY, lane, K, store);
+        else
+            tds::select_by_rounds(wk, E, lane, K, [&](int e) { return key_of(bx, vis, a, e, me.x, me.y, g.r2); }, store);
     }
 }
 

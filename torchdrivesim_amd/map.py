@@ -135,6 +135,18 @@ def traffic_controls_from_map_config(cfg: MapConfig) -> Dict[str, BaseTrafficCon
     return {k: kinds[k](torch.tensor(v).unsqueeze(0)) for k, v in poses.items() if v}
 
 
+def programmed_traffic_lights_from_map_config(cfg: MapConfig, batch_size: int, device, dt: float = 0.1, seed: int = 0, scene_ids=None):
+    """The map's traffic lights with their programmes on the device, a clock per scene: a `ProgrammedTrafficLightControl` for `batch_size` scenes
+    from the package's traffic-light stop lines and its `traffic_light_controller`."""
+    from .traffic_controls import ProgrammedTrafficLightControl
+    lights = [s for s in cfg.stoplines if s.agent_type == 'traffic_light']
+    controller = cfg.traffic_light_controller
+    if not lights or controller is None:
+        raise ValueError(f'map {cfg.name}: no traffic-light stop lines or no traffic_light_controller file')
+    pos = torch.tensor([[s.x, s.y, s.length, s.width, s.orientation] for s in lights]).unsqueeze(0).expand(batch_size, -1, -1).contiguous().to(device)
+    return ProgrammedTrafficLightControl(pos, controller, [s.actor_id for s in lights], dt=dt, seed=seed, scene_ids=scene_ids)
+
+
 def find_wrong_way_stoplines(map_cfg: MapConfig, angle_threshold: float = 3.141592653589793 / 6, device=None) -> List[int]:
     """Ids of the stop lines that face against every lanelet they lie on (map.py:231-245): a consistency check of a map package.
     All stop lines are answered by ONE launch of the lane-direction query (the reference asks Lanelet2 stop line by stop line)."""

@@ -10,6 +10,7 @@
     compute_offroad    -> K2b over the device-resident map grid              reference: simulator.py:1035-1044
 
     compute_neighbors  -> K6 (csrc/neighbors.hip), the K nearest entities per agent   reference: -- (get_all_agents_relative, all pairs)
+    compute_stop_lines -> K7 (csrc/lights.hip), the K nearest stop lines per agent    reference: --
     compute_wrong_way  -> lane tables of `lanelet_map` (lanelet2.py), one launch  reference: simulator.py:607-630 (Python triple loop)
 
 Also carried: traffic controls, waypoint goals (state + rendering), observation noise and lane features (plumbing only).  Out of scope
@@ -86,6 +87,27 @@ class Neighbors:
         idx = self.index.clamp(min=0).to(torch.int64).reshape((B, A * K) + (1,) * len(rest)).expand((B, A * K) + rest)
         got = torch.gather(per_entity, 1, idx).reshape((B, A, K) + rest)
         return torch.where(self.mask.reshape((B, A, K) + (1,) * len(rest)), got, torch.full((), fill, dtype=got.dtype, device=got.device))
+
+
+@dataclass
+class StopLines:
+    """What `Simulator.compute_stop_lines` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`), `index` BxAxK int32, the stop line
+    of every slot, and `state` BxAxK int32, its index into the control's `allowed_states`; -1 in both for an empty slot (its features are all 0:
+    the state is kept out of them so that an empty slot cannot read as 'red' = 0)."""
+    features: Tensor
+    index: Tensor
+    state: Tensor
+
+    FEATURES = ('x', 'y', 'sin', 'cos', 'length', 'width', 'time_to_change', 'distance')
+
+    @property
+    def mask(self) -> Tensor:
+        """BxAxK bool: the slot holds a stop line"""
+        return self.index >= 0
+
+    def take(self, per_line: Tensor, fill=0) -> Tensor:
+        """Gathers a per-line tensor BxNx... (the control's `state`, `time_to_change`, ...) at `index` -> BxAxKx..., `fill` in the empty slots."""
+        return Neighbors.take(self, per_line, fill)
 
 
 def _enlarge(x: Tensor, n: int) -> Tensor:
@@ -1276,6 +1298,44 @@ class Simulator:
             boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
             out = _ops.neighbors(boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, max_distance, visible=visible)
         return Neighbors(*out)
+
+    # ------------------------------------------------------------------------------------------------- stop-line observations
+    def compute_stop_lines(self, k: int = 4, max_distance: float = 60.0, ahead_only: bool = True, min_cos: Optional[float] = None,
+                           kind: str = 'traffic_light') -> StopLines:
+        """The `k` nearest present stop lines of `traffic_controls[kind]` of every exposed agent within `max_distance` metres between centres
+        (+inf: no limit), nearest first, equal distances by the lower index:
+
+        features  BxAxkx8  per slot `StopLines.FEATURES`: x, y of the line's centre in the agent's frame (x ahead, y to the left), [sin, cos] of the
+                           line's orientation relative to the agent's heading, its length and width, the seconds until its light changes (0 for a
+                           control without a programme) and the distance; all 0 in an empty slot;
+        index     BxAxk    int32: the stop line of the slot, -1 for an empty slot (`StopLines.mask`; `StopLines.take` gathers at it);
+        state     BxAxk    int32: the line's index into the control's `allowed_states`, -1 for an empty slot.
+
+        `ahead_only` keeps the lines with x >= 0; `min_cos` those whose relative orientation has at least that cosine.  Rows of agents that are not
+        present are empty.  1 <= k <= 32, at most 1024 lines per scene.  One HIP kernel in binary32 (csrc/lights.hip; the definition is in
+        include/tdship.h "K7", tests/lights_model.py equals it bit for bit).  No gradient.  Runs on the current stream and allocates its outputs
+        only, so it can be captured into a graph."""
+        _ops.check_stop_lines_args(k, max_distance, min_cos)
+        controls = self.get_traffic_controls()
+        if not controls or kind not in controls:
+            raise ValueError(f'compute_stop_lines: the simulator has no {kind!r} traffic controls')
+        control = controls[kind]
+        state = self.get_state()
+        if not state.is_cuda:
+            raise RuntimeError(f'compute_stop_lines runs on an MI355X; the simulator is on {state.device} (no CPU fallback)')
+        A = self.agent_count
+        with torch.no_grad():
+            pos = control.pos
+            key = (pos.data_ptr(), pos._version, tuple(pos.shape), str(pos.device))
+            cached = getattr(control, '_line_sc_cache', None)
+            if cached is None or cached[0] != key:                      # the stop lines do not move: their [sin, cos] is computed once
+                lines = _ops._c(pos.detach()).to(state.device)
+                cached = (key, lines, _ops.heading_sc(lines[..., 4]))
+                control._line_sc_cache = cached
+            agent = state.detach()
+            out = _ops.stop_lines(agent[..., :2], self._heading_sc().detach()[:, :A], self.get_present_mask(), cached[1], cached[2], control.mask,
+                                  control.state, getattr(control, 'time_to_change', None), k, max_distance, ahead_only=ahead_only, min_cos=min_cos)
+        return StopLines(*out)
 
     def compute_wrong_way(self) -> Tensor:
         """Wrong-way metric per agent, -cos of the angle between the agent and the lane it is on where that angle exceeds

@@ -141,3 +141,159 @@ class YieldControl(BaseTrafficControl):
 
 class StopSignControl(BaseTrafficControl):
     """Stop sign.  No violations are computed."""
+
+
+def light_programme_tables(controller, light_ids, allowed_states, dt=0.1):
+    """The device tables of `ProgrammedTrafficLightControl` from a host `traffic_lights.TrafficLightController`, as CPU tensors: a dict of
+    duration MxP float64, next_phase MxP int32 (the LIST POSITION `TrafficLightStateMachine.tick` indexes its phases with), n_phases M int32,
+    sequence_number MxP int32 (what `state_per_machine` reports) and colour MxPxN uint8 (index into `allowed_states` of light `light_ids[n]`,
+    255 where the phase does not name it).  Shorter machines are padded with phases of one second that lead to themselves and name nothing.
+    ValueError for what the kernel must never meet: see the class."""
+    import math
+    from torchdrivesim_amd import _native as nat
+    machines = [fsm.states for fsm in controller.traffic_fsms]
+    M, N = len(machines), len(light_ids)
+    if M == 0 or any(len(phases) == 0 for phases in machines):
+        raise ValueError('traffic lights: a controller needs at least one machine, and every machine a phase')
+    P = max(len(phases) for phases in machines)
+    duration = torch.ones((M, P), dtype=torch.float64)
+    next_phase = torch.arange(P, dtype=torch.int32).repeat(M, 1)
+    sequence_number = torch.zeros((M, P), dtype=torch.int32)
+    colour = torch.full((M, P, N), 255, dtype=torch.uint8)
+    column = {str(i): n for n, i in enumerate(light_ids)}
+    if len(column) != N:
+        raise ValueError('traffic lights: light_ids repeats an id')
+    always = torch.zeros(N, dtype=torch.bool)
+    for m, phases in enumerate(machines):
+        for p, phase in enumerate(phases):
+            d, nxt = float(phase.duration), int(phase.next_state)
+            if not (math.isfinite(d) and d > 0):
+                raise ValueError(f'traffic lights: machine {m}, phase {p}: the duration must be finite and > 0 (got {phase.duration})')
+            if not 0 <= nxt < len(phases):
+                raise ValueError(f'traffic lights: machine {m}, phase {p}: next_state {nxt} is outside the machine\'s {len(phases)} phases')
+            duration[m, p], next_phase[m, p], sequence_number[m, p] = d, nxt, int(phase.sequence_number)
+            for actor, state in phase.actor_states.items():
+                if actor in column:
+                    if state.name not in allowed_states:
+                        raise ValueError(f'traffic lights: machine {m}, phase {p}: light {actor} is {state.name!r}, which is none of {allowed_states}')
+                    colour[m, p, column[actor]] = allowed_states.index(state.name)
+        always |= (colour[m, :len(phases)] != 255).all(dim=0)
+    if not bool(always.all()):
+        missing = [light_ids[n] for n in torch.nonzero(~always).flatten().tolist()]
+        raise ValueError(f'traffic lights: no machine names light(s) {missing} in every one of its phases: they would have no colour at times')
+    shortest = min(float(phase.duration) for phases in machines for phase in phases)
+    if not (math.isfinite(dt) and 0 <= dt <= nat.LIGHTS_MAX_SKIPS * shortest):
+        raise ValueError(f'traffic lights: dt must be finite, not negative and at most {nat.LIGHTS_MAX_SKIPS} x the shortest phase ({shortest} s), got {dt}')
+    return dict(duration=duration, next_phase=next_phase, n_phases=torch.tensor([len(phases) for phases in machines], dtype=torch.int32),
+                sequence_number=sequence_number, colour=colour)
+
+
+class ProgrammedTrafficLightControl(TrafficLightControl):
+    """Traffic lights whose programmes run ON THE DEVICE, a clock per scene (csrc/lights.hip; the definition is in include/tdship.h "K7").
+    Built from a host `traffic_lights.TrafficLightController`, whose phases become tables shared by the batch; `light_ids[n]` is the id of stop
+    line n of `pos` (BxNx5).  Per scene it owns `phase` BxM int32 (list position), `remaining` BxM float64, `state` BxN int64 -- the attribute
+    every consumer of a TrafficLightControl reads, here written IN PLACE and never replaced --, `time_to_change` BxN float32 and `scene_ids`.
+    `step` (and so `Simulator.step`) advances every machine of every scene by `dt` in one launch; the arithmetic is
+    `TrafficLightStateMachine.tick`'s in float64, bit for bit.  `reset` deals the masked scenes a random phase that depends on (seed, scene id)
+    only.  ValueError at construction for a duration that is not finite and > 0, a next_state outside its machine, a colour outside
+    `allowed_states`, a light that no machine names in every phase, and a dt that is negative, non-finite or longer than 1024 shortest phases."""
+
+    _TABLES = ('duration', 'next_phase', 'n_phases', 'sequence_number', 'colour')
+
+    def __init__(self, pos: Tensor, controller, light_ids, dt: float = 0.1, seed: int = 0, scene_ids: Optional[Tensor] = None,
+                 mask: Optional[Tensor] = None):
+        super().__init__(pos, mask=mask)
+        light_ids = [int(i) for i in light_ids]
+        if pos.dim() != 3 or pos.shape[1] != len(light_ids):
+            raise ValueError(f'traffic lights: pos {tuple(pos.shape)} for {len(light_ids)} light ids')
+        tables = light_programme_tables(controller, light_ids, self.allowed_states, dt)
+        if not pos.is_cuda:
+            raise RuntimeError(f'ProgrammedTrafficLightControl runs on an MI355X; pos is on {pos.device} (no CPU fallback)')
+        dev, B, M = pos.device, pos.shape[0], tables['n_phases'].shape[0]
+        self.tables = {k: v.to(dev) for k, v in tables.items()}
+        self.light_ids, self.dt, self.seed = light_ids, float(dt), int(seed)
+        self.phase = torch.zeros((B, M), dtype=torch.int32, device=dev)
+        self.remaining = torch.zeros((B, M), dtype=torch.float64, device=dev)
+        self.time_to_change = torch.zeros((B, len(light_ids)), dtype=torch.float32, device=dev)
+        self.scene_ids = torch.arange(B, dtype=torch.int64, device=dev)
+        self.reset(scene_ids=scene_ids)
+
+    def _tensors(self):
+        return super()._tensors() + ('phase', 'remaining', 'time_to_change', 'scene_ids')
+
+    def _kernel_tables(self):
+        t = self.tables
+        return t['duration'], t['next_phase'], t['n_phases'], t['colour']
+
+    def _dense(self):
+        for n in ('state', 'phase', 'remaining', 'time_to_change', 'scene_ids'):
+            setattr(self, n, getattr(self, n).contiguous())
+        return self
+
+    def copy(self):
+        other = object.__new__(self.__class__)
+        other.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ('_lines_cache', '_line_sc_cache')})
+        other.allowed_states, other.light_ids = list(self.allowed_states), list(self.light_ids)
+        for n in self._tensors():
+            setattr(other, n, getattr(self, n).clone())
+        return other
+
+    def to(self, device):
+        super().to(device)
+        self.tables = {k: v.to(device) for k, v in self.tables.items()}
+        return self
+
+    def extend(self, n: int, in_place: bool = True):
+        return super().extend(n, in_place)._dense()
+
+    def select_batch_elements(self, idx, in_place: bool = True):
+        return super().select_batch_elements(idx, in_place)._dense()
+
+    def set_state(self, state: Tensor) -> None:
+        """the colours, copied INTO `state` (the programme overwrites them at its next tick)"""
+        if state is not self.state:
+            self.state.copy_(state)
+
+    def tick(self, dt: float) -> Tensor:
+        """every machine of every scene advanced by `dt` seconds, through as many phases as that spans: one launch"""
+        _ops.lights_step(self._kernel_tables(), self.phase, self.remaining, self.state, self.time_to_change, dt)
+        return self.state
+
+    def compute_state(self, time: int) -> Tensor:
+        return self.tick(self.dt)
+
+    def set_to(self, light_states) -> None:
+        """Jump to (phase index, seconds remaining) per machine: a B x m x 2 tensor, or the host's list form [[index, seconds], ...] for the first m
+        machines, applied to every scene.  Clamped as the host's `set_to`: the index into the machine, the time to at most the phase's duration.
+        `state` and `time_to_change` follow; no time passes."""
+        t = torch.as_tensor(light_states, dtype=torch.float64).to(self.phase.device)
+        if t.dim() == 2:
+            t = t.unsqueeze(0).expand(self.phase.shape[0], -1, -1)
+        m = t.shape[1]
+        if t.dim() != 3 or t.shape[0] != self.phase.shape[0] or m > self.phase.shape[1] or t.shape[2] != 2:
+            raise ValueError(f'set_to: expected ({self.phase.shape[0]}, m <= {self.phase.shape[1]}, 2), got {tuple(t.shape)}')
+        index = torch.minimum(t[..., 0].to(torch.int64).clamp(min=0), self.tables['n_phases'][:m].to(torch.int64) - 1)
+        span = torch.gather(self.tables['duration'][:m].expand(t.shape[0], -1, -1), 2, index.unsqueeze(-1)).squeeze(-1)
+        self.phase[:, :m] = index.to(torch.int32)
+        self.remaining[:, :m] = torch.where(t[..., 1] <= span, t[..., 1], span)
+        _ops.lights_step(self._kernel_tables(), self.phase, self.remaining, self.state, self.time_to_change, 0.0, advance=False)
+
+    def reset(self, mask: Optional[Tensor] = None, scene_ids: Optional[Tensor] = None) -> None:
+        """Every machine of the scenes where `mask` (B bool) is set -- all scenes without one -- to the beginning of a random phase, in place: two
+        launches, no allocation, no synchronisation.  The phase depends on (seed, scene id, machine) only, so a scene's lights are the same in
+        any batch or shard that holds it; new `scene_ids` (B int64) are stored first."""
+        if scene_ids is not None:
+            self.scene_ids.copy_(scene_ids)
+        _ops.lights_reset(self._kernel_tables(), self.phase, self.remaining, self.scene_ids, self.seed, mask=mask)
+        _ops.lights_step(self._kernel_tables(), self.phase, self.remaining, self.state, self.time_to_change, 0.0, advance=False, mask=mask)
+
+    @property
+    def state_per_machine(self) -> Tensor:
+        """BxM: the `sequence_number` of every machine's current phase (TrafficLightController.state_per_machine)"""
+        seq = self.tables['sequence_number'].expand(self.phase.shape[0], -1, -1)
+        return torch.gather(seq, 2, self.phase.to(torch.int64).unsqueeze(-1)).squeeze(-1)
+
+    @property
+    def time_remaining(self) -> Tensor:
+        """BxM float64: seconds left in every machine's current phase"""
+        return self.remaining
