@@ -6,6 +6,7 @@
 // The forward quantities are recomputed (float, same formulas as the forward kernels); results are compared with the
 // reference's autograd gradients (fixture G7) in tests/test_gpu_backward.py.
 #include "tds_common.h"
+#include "tds_nearest_face.h"
 
 using tds::GridEntry;
 using tds::MapView;
@@ -431,247 +432,36 @@ __global__ void __launch_bounds__(GBLOCK, 2) collision_scene_bwd_kernel(const fl
 // ---------------------------------------------------------------------------------------------------------------
 // offroad backward
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return (ax * bx + ay * by) + 0.0f; }
+constexpr int BL = tds::NF_LANES;       // lanes per corner
 
-// squared distance to a segment and its gradient w.r.t. the point (autograd of infractions.py:147-159)
-__device__ __forceinline__ float seg_d2_grad(float px, float py, float ax, float ay, float bx, float by, float &gx, float &gy) {
-    float ex = bx - ax, ey = by - ay;
-    float l2 = dot2(ex, ey, ex, ey);
-    float t = dot2(ex, ey, px - ax, py - ay) / (l2 + (float)1e-8);
-    float tc = fminf(fmaxf(t, 0.0f), 1.0f);
-    float qx = ax + tc * ex, qy = ay + tc * ey;
-    float rx = px - qx, ry = py - qy;
-    float d = dot2(rx, ry, rx, ry);
-    gx = 2.0f * rx; gy = 2.0f * ry;
-    if (t >= 0.0f && t <= 1.0f) {                                    // clamp passes the gradient on [0, 1]
-        float s = 2.0f * (rx * ex + ry * ey) / (l2 + (float)1e-8);
-        gx -= s * ex; gy -= s * ey;
-    }
-    if (l2 <= (float)1e-8) { d = dot2(px - bx, py - by, px - bx, py - by); gx = 2.0f * (px - bx); gy = 2.0f * (py - by); }
-    return d;
-}
-
-__device__ __forceinline__ float tri_d2_grad(float px, float py, const GridEntry &e, float &gx, float &gy) {
-    float cz = (e.x2 - e.x0) * (e.y1 - e.y0) - (e.y2 - e.y0) * (e.x1 - e.x0);
-    float norm_normal = sqrtf(cz * cz);
-    float p0x = e.x1 - e.x0, p0y = e.y1 - e.y0, p1x = e.x2 - e.x0, p1y = e.y2 - e.y0, p2x = px - e.x0, p2y = py - e.y0;
-    float d00 = dot2(p0x, p0y, p0x, p0y), d01 = dot2(p0x, p0y, p1x, p1y), d11 = dot2(p1x, p1y, p1x, p1y);
-    float d20 = dot2(p2x, p2y, p0x, p0y), d21 = dot2(p2x, p2y, p1x, p1y);
-    float denom = d00 * d11 - d01 * d01 + (float)1e-8;
-    float w1 = (d11 * d20 - d01 * d21) / denom, w2 = (d00 * d21 - d01 * d20) / denom, w0 = 1.0f - w1 - w2;
-    bool inside = (0.0f <= w0) && (w0 <= 1.0f) && (0.0f <= w1) && (w1 <= 1.0f) && (0.0f <= w2) && (w2 <= 1.0f);
-    float area = fabsf(p0x * p1y - p0y * p1x) / 2.0f;
-    inside = inside && !(area < (float)5e-3) && (norm_normal > (float)1e-8);
-    float g1x, g1y, g2x, g2y, g3x, g3y;
-    float e01 = seg_d2_grad(px, py, e.x0, e.y0, e.x1, e.y1, g1x, g1y);
-    float e02 = seg_d2_grad(px, py, e.x0, e.y0, e.x2, e.y2, g2x, g2y);
-    float e12 = seg_d2_grad(px, py, e.x1, e.y1, e.x2, e.y2, g3x, g3y);
-    float dist = e01; gx = g1x; gy = g1y;
-    if (e02 < dist) { dist = e02; gx = g2x; gy = g2y; }
-    if (e12 < dist) { dist = e12; gx = g3x; gy = g3y; }
-    if (inside) { dist = 0.0f; gx = 0.0f; gy = 0.0f; }
-    return dist;
-}
-
-// `stop`: below it the caller's gradient is zero (F.threshold), so the walk may end early (see nearest_face_d2 in map.hip)
-__device__ float nearest_face_d2_grad(const MapView &m, float px, float py, float &gx, float &gy, float stop) {
-    float best = __builtin_inff();
-    gx = gy = 0.0f;
-    if (m.nx <= 0 || !(px == px) || !(py == py) || __builtin_isinf(px) || __builtin_isinf(py)) return best;
-    float fx = fminf(fmaxf((px - m.ox) * m.inv_cell, -1.0e6f), 1.0e6f), fy = fminf(fmaxf((py - m.oy) * m.inv_cell, -1.0e6f), 1.0e6f);
-    int cx = (int)floorf(fx), cy = (int)floorf(fy);
-    auto visit = [&](int x, int y) {
-        float bx0 = m.ox + (float)x * m.cell, by0 = m.oy + (float)y * m.cell;
-        float ddx = fmaxf(fmaxf(bx0 - px, px - (bx0 + m.cell)), 0.0f), ddy = fmaxf(fmaxf(by0 - py, py - (by0 + m.cell)), 0.0f);
-        if ((ddx * ddx + ddy * ddy) * 0.998f - 1e-3f >= best) return;
-        int s = m.cell_start[y * m.nx + x], e = m.cell_start[y * m.nx + x + 1];
-        for (int i = s; i < e && best > stop; ++i) {
-            GridEntry ge = m.entries[i];
-            float tgx, tgy;
-            float d = tri_d2_grad(px, py, ge, tgx, tgy);
-            if (d < best) { best = d; gx = tgx; gy = tgy; }
-        }
-    };
-    int k = max(max(0, max(-cx, cx - (m.nx - 1))), max(-cy, cy - (m.ny - 1)));
-    for (;; ++k) {
-        int y0 = max(cy - k, 0), y1 = min(cy + k, m.ny - 1), x0 = max(cx - k, 0), x1 = min(cx + k, m.nx - 1);
-        for (int y = y0; y <= y1; ++y) {
-            if (y == cy - k || y == cy + k) {
-                for (int x = x0; x <= x1; ++x) visit(x, y);
-            } else {
-                if (cx - k >= 0 && cx - k < m.nx) visit(cx - k, y);
-                if (k > 0 && cx + k >= 0 && cx + k < m.nx) visit(cx + k, y);
-            }
-        }
-        if (best <= stop) break;
-        float bound = (float)k * m.cell * 0.999f;
-        if (best <= bound * bound) break;
-        if (cx - k <= 0 && cx + k >= m.nx - 1 && cy - k <= 0 && cy + k >= m.ny - 1) break;
-    }
-    return best;
-}
-
-// the same arg-min by the ordered descent of the hierarchy over the faces (see nearest_face_d2_bvh in map.hip): the group's BL lanes hold the
-// same point, weigh a child each at an inner node and a face each at a leaf; boxes AT the running minimum are still opened (a face in them may
-// tie it, and the lowest face index among ties gives the gradient); the gradient is taken once, from the winning face
-constexpr int BL = 8;             // lanes per corner (a power of two, <= 16: a wavefront holds whole agents)
-using tds::BVH_STACK;             // (tds_common.h; tds_map_create refuses to attach a hierarchy the stack cannot hold)
-__device__ float nearest_face_d2_grad_bvh(const tds::NearView &nv, float px, float py, float &gx, float &gy, float stop, int sub) {
-    static_assert(BL == 8, "nearest_face_d2_grad_bvh: a lane per child of a node");
-    __shared__ int2 stacks[GBLOCK / BL][BVH_STACK];
-    int2 *st = stacks[threadIdx.x / BL];
-    const float inf = __builtin_inff();
-    const int shift = (int)(threadIdx.x & 63 & ~(BL - 1));                              // the group's first lane within the wavefront
-    float best = inf;
-    int best_f = 0x7fffffff;                 // among faces at the same distance the one of lowest index gives the gradient (torch.min's choice)
-    gx = gy = 0.0f;
-    auto box_lb = [&](float x0, float y0, float x1, float y1) {
-        const float ex = fmaxf(fmaxf(x0 - px, px - x1), 0.0f), ey = fmaxf(fmaxf(y0 - py, py - y1), 0.0f);
-        return (ex * ex + ey * ey) * 0.998f - 1e-3f;
-    };
-    int sp = 0, cur = 0;
-    for (;;) {
-        if (cur >= 0) {
-            const float4 bx = nv.bvh[cur].box[sub];
-            const int ch = nv.bvh[cur].child[sub];
-            const float lb = box_lb(bx.x, bx.y, bx.z, bx.w);
-            const bool open = lb <= best && lb < inf;
-            const float key = open ? lb : inf;
-            int above = 0;                                                             // open children that will lie above this lane's on the stack
-#pragma unroll
-            for (int k = 1; k < BL; ++k) {
-                const float o = __shfl_xor(key, k);
-                above += (o < key || (o == key && (sub ^ k) < sub)) ? 1 : 0;
-            }
-            const int nopen = __popc((unsigned)(__ballot(open) >> shift) & 0xffu);
-            const int slot = sp + nopen - 1 - above;
-            if (open && slot < BVH_STACK) st[slot] = make_int2(ch, __float_as_int(lb));
-            sp = min(sp + nopen, BVH_STACK);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        } else {
-            const int code = -1 - cur, first = code >> 4, cnt = code & 15;
-            float d = inf;
-            int f = 0x7fffffff;
-            if (sub < cnt) {
-                const int fi = nv.bvh_idx[first + sub];
-                const GridEntry ge = nv.faces[fi];
-                const float fx0 = fminf(ge.x0, fminf(ge.x1, ge.x2)), fx1 = fmaxf(ge.x0, fmaxf(ge.x1, ge.x2));
-                const float fy0 = fminf(ge.y0, fminf(ge.y1, ge.y2)), fy1 = fmaxf(ge.y0, fmaxf(ge.y1, ge.y2));
-                if (!(box_lb(fx0, fy0, fx1, fy1) > best)) {                             // (a box AT the minimum may hold a face that ties it)
-                    float tgx, tgy;
-                    const float t = tri_d2_grad(px, py, ge, tgx, tgy);                // (the distance alone: the gradient is taken below)
-                    if (t < inf) { d = t; f = fi; }                                   // a NaN distance never becomes the minimum
-                }
-            }
-#pragma unroll
-            for (int k = 1; k < BL; k <<= 1) {
-                const float od = __shfl_xor(d, k);
-                const int of = __shfl_xor(f, k);
-                if (od < d || (od == d && of < f)) { d = od; f = of; }
-            }
-            if (d < best || (d == best && f < best_f)) { best = d; best_f = f; }
-        }
-        // the next subtree that can still hold a face as near
-        float lb = inf;
-        bool done = false;
-        do {
-            if (sp == 0 || best <= stop) { done = true; break; }
-            --sp;
-            cur = st[sp].x; lb = __int_as_float(st[sp].y);
-        } while (lb > best);
-        if (done) break;
-    }
-    if (best_f != 0x7fffffff) best = tri_d2_grad(px, py, nv.faces[best_f], gx, gy);
-    return best;
-}
-
-// the same arg-min from the candidate list of the point's cell (tds::NearView, see nearest_face_d2_lists in map.hip).  As in the forward
-// kernel a point is served by a GROUP of BL consecutive lanes that all hold it; `sub` is the lane's place in its group: a round evaluates BL
-// candidates' DISTANCES side by side (one lane per point walked the list four at a time, gradients and all: 0.12 ms at 16 384 agents against the
-// forward's 0.04), the group agrees on (minimum, lowest face index), and the gradient is taken once, from the winning face.
-__device__ float nearest_face_d2_grad_lists(const MapView &m, const tds::NearView &nv, float px, float py, float &gx, float &gy, float stop, int sub) {
-    if (nv.cand == nullptr || m.nx <= 0 || !(px == px) || !(py == py) || __builtin_isinf(px) || __builtin_isinf(py))
-        return nearest_face_d2_grad(m, px, py, gx, gy, stop);
-    // beyond the lists' grid: the hierarchy over the faces where the map has one (walked by the group together), else the walk over grid rings
-    // (every lane of the group for itself: the same point, the same answer)
-    auto beyond = [&]() { return nv.bvh != nullptr ? nearest_face_d2_grad_bvh(nv, px, py, gx, gy, stop, sub) : nearest_face_d2_grad(m, px, py, gx, gy, stop); };
-    const float fx = (px - nv.ox) * m.inv_cell, fy = (py - nv.oy) * m.inv_cell;
-    if (!(fx >= 0.0f && fy >= 0.0f && fx < (float)nv.nx && fy < (float)nv.ny)) return beyond();
-    const int cx = tds::cell_coord(px, nv.ox, m.inv_cell), cy = tds::cell_coord(py, nv.oy, m.inv_cell);
-    if (cx < 0 || cy < 0 || cx >= nv.nx || cy >= nv.ny) return beyond();
-    const int s = nv.cand_start[cy * nv.nx + cx], e = nv.cand_start[cy * nv.nx + cx + 1];
-    const float inf = __builtin_inff();
-    float best = inf;                        // the group's minimum so far, the same in all its lanes
-    int best_f = 0x7fffffff;                 // among faces at the same distance the one of lowest index gives the gradient (torch.min's choice)
-    gx = gy = 0.0f;
-    for (int i = s; i < e && best > stop; i += BL) {
-        const int j = i + sub;
-        tds::NearCand c;
-        c.face = 0; c.lb = inf;
-        if (j < e) c = nv.cand[j];
-        const float lb0 = __shfl(c.lb, (threadIdx.x & 63 & ~(BL - 1)));                // the round's first candidate
-        if (lb0 > best) break;                                                        // sorted by lb: nothing further can be as near
-        float d = inf;
-        int f = 0x7fffffff;
-        if (j < e && !(c.lb > best)) {
-            const GridEntry ge = nv.faces[c.face];
-            // a face whose bounding box is already farther than the running minimum is not evaluated
-            const float fx0 = fminf(ge.x0, fminf(ge.x1, ge.x2)), fx1 = fmaxf(ge.x0, fmaxf(ge.x1, ge.x2));
-            const float fy0 = fminf(ge.y0, fminf(ge.y1, ge.y2)), fy1 = fmaxf(ge.y0, fmaxf(ge.y1, ge.y2));
-            const float ex = fmaxf(fmaxf(fx0 - px, px - fx1), 0.0f), ey = fmaxf(fmaxf(fy0 - py, py - fy1), 0.0f);
-            if (!((ex * ex + ey * ey) * 0.998f - 1e-3f > best)) {
-                float tgx, tgy;
-                const float t = tri_d2_grad(px, py, ge, tgx, tgy);                    // (the distance alone: the gradient is taken below)
-                if (t < inf) { d = t; f = c.face; }                                   // a NaN distance never becomes the minimum
-            }
-        }
-#pragma unroll
-        for (int k = 1; k < BL; k <<= 1) {
-            const float od = __shfl_xor(d, k);
-            const int of = __shfl_xor(f, k);
-            if (od < d || (od == d && of < f)) { d = od; f = of; }
-        }
-        if (d < best || (d == best && f < best_f)) { best = d; best_f = f; }
-    }
-    if (best_f != 0x7fffffff) best = tri_d2_grad(px, py, nv.faces[best_f], gx, gy);
-    return best;
-}
-
-// BL lanes per agent corner, 4 consecutive groups = one agent; the 4 corners of an agent are reduced with shuffles
+// BL lanes per agent corner, 4 consecutive groups = one agent; the nearest face by tds_nearest_face.h as (distance, lowest face index), the
+// gradient of its distance once, from that face; the 4 corners of an agent are reduced with shuffles
 __global__ void __launch_bounds__(GBLOCK) offroad_bwd_kernel(MapView m, tds::NearView nv, const float4 *__restrict__ state, const float2 *__restrict__ lenwid,
                                                              const float2 *__restrict__ sc, const uint8_t *__restrict__ present,
                                                              const float *__restrict__ gout, float4 *__restrict__ gstate,
                                                              float2 *__restrict__ glenwid, float2 *__restrict__ gsc, int64_t n, float threshold,
                                                              const MapView *__restrict__ views, const tds::NearView *__restrict__ nears,
                                                              const int32_t *__restrict__ scene_map, int agents_per_scene) {
-    const int64_t t = (int64_t)blockIdx.x * GBLOCK + threadIdx.x;
-    const int64_t a = t / (4 * BL);
-    const int k = (int)((t / BL) & 3), sub = (int)(t & (BL - 1));
+    const tds::NearLane l = tds::near_lane<GBLOCK>();
+    const int64_t a = l.a;
     float gx = 0, gy = 0, gl = 0, gw = 0, gs = 0, gc = 0;
-    if (a < n && views != nullptr) {
-        const int im = scene_map[a / agents_per_scene];
-        m = views[im]; nv = nears[im];
-    }
+    if (a < n) tds::select_scene_map(m, nv, views, nears, scene_map, a, agents_per_scene);       // (tds_offroad_multi_bwd_f32)
     if (a < n && m.n_faces > 0) {
         float go = gout[a] * ((present && !present[a]) ? 0.0f : 1.0f);
         if (go != 0.0f) {                                                            // (uniform within the agent's 4 groups)
-            float4 s = state[a];
-            float2 lw = lenwid[a];
-            float2 scv = sc[a];
-            const float sx = (k == 0 || k == 3) ? 0.5f : -0.5f, sy = (k < 2) ? 0.5f : -0.5f;
-            float x4 = sx * lw.x, y4 = sy * lw.y;
-            float px = (x4 * scv.y + y4 * (-scv.x)) + s.x, py = (x4 * scv.x + y4 * scv.y) + s.y;
-            float dgx, dgy;
-            float d = nearest_face_d2_grad_lists(m, nv, px, py, dgx, dgy, fmaxf(threshold, 0.0f), sub);
-            if (d == d && !__builtin_isinf(d) && d > threshold) {
+            const float2 scv = sc[a];
+            const tds::BoxCorner c = tds::box_corner(l.k, state[a], lenwid[a], scv);
+            // below the threshold the gradient is zero (F.threshold), so the walk may end early there
+            const tds::NearestFace nf = tds::nearest_face<true>(m, nv, c.px, c.py, fmaxf(threshold, 0.0f), l.sub, tds::nearest_in_bvh<true, GBLOCK>);
+            if (nf.face != nullptr && nf.d2 > threshold) {                           // (a face's distance is finite)
+                float dgx, dgy;
+                tds::tri_d2_grad(c.px, c.py, *nf.face, dgx, dgy);
                 float ggx = go * dgx, ggy = go * dgy;
                 gx = ggx; gy = ggy;
-                gl = ggx * sx * scv.y + ggy * sx * scv.x;
-                gw = -ggx * sy * scv.x + ggy * sy * scv.y;
-                gc = ggx * x4 + ggy * y4;
-                gs = -ggx * y4 + ggy * x4;
+                gl = ggx * c.sx * scv.y + ggy * c.sx * scv.x;
+                gw = -ggx * c.sy * scv.x + ggy * c.sy * scv.y;
+                gc = ggx * c.x4 + ggy * c.y4;
+                gs = -ggx * c.y4 + ggy * c.x4;
             }
         }
     }
@@ -680,11 +470,22 @@ __global__ void __launch_bounds__(GBLOCK) offroad_bwd_kernel(MapView m, tds::Nea
     for (int d = BL; d < 4 * BL; d <<= 1) {
         gx += __shfl_xor(gx, d); gy += __shfl_xor(gy, d); gl += __shfl_xor(gl, d); gw += __shfl_xor(gw, d); gs += __shfl_xor(gs, d); gc += __shfl_xor(gc, d);
     }
-    if (a < n && k == 0 && sub == 0) {
+    if (a < n && l.k == 0 && l.sub == 0) {
         if (gstate) gstate[a] = make_float4(gx, gy, 0.0f, 0.0f);
         if (glenwid) glenwid[a] = make_float2(gl, gw);
         if (gsc) gsc[a] = make_float2(gs, gc);
     }
+}
+
+// both entry points: one map (`views` null) or a set with a map index per scene
+int launch_offroad_bwd(const MapView &view, const tds::NearView &near, const MapView *views, const tds::NearView *nears, const int32_t *scene_map,
+                       int64_t agents_per_scene, const float *state, const float *lenwid, const float *sc, const uint8_t *present, const float *grad_out,
+                       float *grad_state, float *grad_lenwid, float *grad_sc, int64_t n_agents, float threshold, void *stream) {
+    hipLaunchKernelGGL(offroad_bwd_kernel, dim3(tds::near_blocks(n_agents, GBLOCK)), dim3(GBLOCK), 0, (hipStream_t)stream, view, near,
+                       (const float4 *)state, (const float2 *)lenwid, (const float2 *)sc, present, grad_out, (float4 *)grad_state, (float2 *)grad_lenwid,
+                       (float2 *)grad_sc, n_agents, threshold, views, nears, scene_map, (int)agents_per_scene);
+    TDS_LAUNCH_CHECK("offroad_bwd_kernel");
+    return TDS_OK;
 }
 
 }  // namespace
@@ -740,13 +541,8 @@ TDS_EXPORT int tds_offroad_bwd_f32(const tds_map_t *map, const float *state, con
     TDS_CHECK_ARG(n_agents >= 0, "tds_offroad_bwd_f32: bad agent count");
     if (n_agents == 0) return TDS_OK;
     TDS_CHECK_ARG(state && lenwid && sc && grad_out, "tds_offroad_bwd_f32: null pointer");
-    int64_t threads = n_agents * 4 * BL;
-    hipLaunchKernelGGL(offroad_bwd_kernel, dim3((unsigned)((threads + GBLOCK - 1) / GBLOCK)), dim3(GBLOCK), 0, (hipStream_t)stream, map->view,
-                       map->near, (const float4 *)state, (const float2 *)lenwid, (const float2 *)sc, present, grad_out, (float4 *)grad_state,
-                       (float2 *)grad_lenwid, (float2 *)grad_sc, n_agents, threshold, (const MapView *)nullptr, (const tds::NearView *)nullptr,
-                       (const int32_t *)nullptr, 1);
-    TDS_LAUNCH_CHECK("offroad_bwd_kernel");
-    return TDS_OK;
+    return launch_offroad_bwd(map->view, map->near, nullptr, nullptr, nullptr, 1, state, lenwid, sc, present, grad_out, grad_state, grad_lenwid, grad_sc,
+                              n_agents, threshold, stream);
 }
 
 TDS_EXPORT int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state,
@@ -757,11 +553,6 @@ TDS_EXPORT int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t 
     TDS_CHECK_ARG(n_agents >= 0, "tds_offroad_multi_bwd_f32: bad agent count");
     if (n_agents == 0) return TDS_OK;
     TDS_CHECK_ARG(state && lenwid && sc && grad_out, "tds_offroad_multi_bwd_f32: null pointer");
-    int64_t threads = n_agents * 4 * BL;
-    hipLaunchKernelGGL(offroad_bwd_kernel, dim3((unsigned)((threads + GBLOCK - 1) / GBLOCK)), dim3(GBLOCK), 0, (hipStream_t)stream, tds::MapView{},
-                       tds::NearView{nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, 0, nullptr, nullptr}, (const float4 *)state, (const float2 *)lenwid, (const float2 *)sc, present,
-                       grad_out, (float4 *)grad_state, (float2 *)grad_lenwid, (float2 *)grad_sc, n_agents, threshold, (const MapView *)set->d_views,
-                       (const tds::NearView *)set->d_near, scene_map, (int)agents_per_scene);
-    TDS_LAUNCH_CHECK("offroad_bwd_kernel");
-    return TDS_OK;
+    return launch_offroad_bwd(MapView{}, tds::NearView{}, set->d_views, set->d_near, scene_map, agents_per_scene, state, lenwid, sc, present, grad_out,
+                              grad_state, grad_lenwid, grad_sc, n_agents, threshold, stream);
 }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "tds_common.h"
+#include "tds_nearest_face.h"
 
 using tds::GridEntry;
 using tds::MapView;
@@ -675,125 +676,14 @@ TDS_EXPORT int tds_rows_equal_u8(const void *rows, int64_t n_rows, int64_t row_b
 namespace {
 
 constexpr int OBLOCK = 256;
+constexpr int OL = tds::NF_LANES;       // lanes per corner
 
-__device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return (ax * bx + ay * by) + 0.0f; }
-
-// point_line_distance, infractions.py:147-159 (squared)
-__device__ __forceinline__ float seg_d2(float px, float py, float ax, float ay, float bx, float by) {
-    float ex = bx - ax, ey = by - ay;
-    float l2 = dot2(ex, ey, ex, ey);
-    float t = dot2(ex, ey, px - ax, py - ay) / (l2 + (float)1e-8);
-    float tt = fminf(fmaxf(t, 0.0f), 1.0f);
-    tt = (t != t) ? t : tt;                                  // torch.clamp propagates NaN
-    float qx = ax + tt * ex, qy = ay + tt * ey;
-    float d = dot2(px - qx, py - qy, px - qx, py - qy);
-    if (l2 <= (float)1e-8) d = dot2(px - bx, py - by, px - bx, py - by);
-    return d;
-}
-
-// point_to_mesh_distance_pt for one (point, triangle) in the z = 0 plane, infractions.py:100-170
-__device__ __forceinline__ float tri_d2(float px, float py, const GridEntry &e) {
-    float cz = (e.x2 - e.x0) * (e.y1 - e.y0) - (e.y2 - e.y0) * (e.x1 - e.x0);
-    float norm_normal = sqrtf(cz * cz);
-    float p0x = e.x1 - e.x0, p0y = e.y1 - e.y0, p1x = e.x2 - e.x0, p1y = e.y2 - e.y0;
-    float p2x = px - e.x0, p2y = py - e.y0;
-    float d00 = dot2(p0x, p0y, p0x, p0y), d01 = dot2(p0x, p0y, p1x, p1y), d11 = dot2(p1x, p1y, p1x, p1y);
-    float d20 = dot2(p2x, p2y, p0x, p0y), d21 = dot2(p2x, p2y, p1x, p1y);
-    float denom = d00 * d11 - d01 * d01 + (float)1e-8;
-    float w1 = (d11 * d20 - d01 * d21) / denom;
-    float w2 = (d00 * d21 - d01 * d20) / denom;
-    float w0 = 1.0f - w1 - w2;
-    bool inside = (0.0f <= w0) && (w0 <= 1.0f) && (0.0f <= w1) && (w1 <= 1.0f) && (0.0f <= w2) && (w2 <= 1.0f);
-    float area = fabsf(p0x * p1y - p0y * p1x) / 2.0f;
-    inside = inside && !(area < (float)5e-3) && (norm_normal > (float)1e-8);
-    float e01 = seg_d2(px, py, e.x0, e.y0, e.x1, e.y1);
-    float e02 = seg_d2(px, py, e.x0, e.y0, e.x2, e.y2);
-    float e12 = seg_d2(px, py, e.x1, e.y1, e.x2, e.y2);
-    float dist = fminf(fminf(e01, e02), e12);
-    return inside ? 0.0f : dist;
-}
-
-// A point is served by a GROUP of OL consecutive lanes (all of them hold the same point); `sub` is the lane's place in its group.
-#ifndef TDS_OL
-#define TDS_OL 8
-#endif
-constexpr int OL = TDS_OL;        // lanes per corner (a power of two, <= 16: a wavefront holds whole agents)
-__device__ __forceinline__ float group_min(float v) {
-#pragma unroll
-    for (int d = 1; d < OL; d <<= 1) v = fminf(v, __shfl_xor(v, d));
-    return v;
-}
-
-// min over all faces of tri_d2, found by walking grid rings outwards from the point's cell.  A face is listed in every
-// cell its bounding box touches, so its closest point lies in a listed cell whose box is at least as close as the face:
-// cells whose box is not closer than the best distance so far can be skipped, and the walk stops once a whole ring is.
-// The lanes of the group share the entries of a cell (entry i + sub of every round) and agree on the minimum after every cell; the minimum
-// over faces does not depend on the order in which they are looked at, so the result is that of a sequential walk, bit for bit.
-// `stop`: the caller only needs the exact minimum if it exceeds `stop` (F.threshold zeroes everything else), so the walk ends as soon
-// as the running minimum is <= stop.
-__device__ __forceinline__ float nearest_face_d2(const MapView &m, float px, float py, float stop, int sub) {
-    const float inf = __builtin_inff();
-    float best = inf;                                        // the group's minimum so far: the same in all its lanes
-    if (m.nx <= 0 || !(px == px) || !(py == py) || __builtin_isinf(px) || __builtin_isinf(py)) return best;
-    // unclamped cell of the point (float -> int conversion saturates, keep it in a sane range first)
-    float fx = fminf(fmaxf((px - m.ox) * m.inv_cell, -1.0e6f), 1.0e6f), fy = fminf(fmaxf((py - m.oy) * m.inv_cell, -1.0e6f), 1.0e6f);
-    int cx = (int)floorf(fx), cy = (int)floorf(fy);
-    auto visit = [&](int x, int y) {
-        // squared distance from the point to the cell's box, shrunk a little so that rounding can only make us visit more
-        float bx0 = m.ox + (float)x * m.cell, by0 = m.oy + (float)y * m.cell;
-        float ddx = fmaxf(fmaxf(bx0 - px, px - (bx0 + m.cell)), 0.0f), ddy = fmaxf(fmaxf(by0 - py, py - (by0 + m.cell)), 0.0f);
-        float cd = (ddx * ddx + ddy * ddy) * 0.998f - 1e-3f;
-        if (cd >= best || best <= stop) return;
-        const int s = m.cell_start[y * m.nx + x], e = m.cell_start[y * m.nx + x + 1];
-        float mine = best;
-        for (int i = s + sub; i < e; i += OL) {
-            const GridEntry ge = m.entries[i];
-            // the face cannot beat the minimum if even its bounding box is farther (same safety shrink as for the cell)
-            float fx0 = fminf(ge.x0, fminf(ge.x1, ge.x2)), fx1 = fmaxf(ge.x0, fmaxf(ge.x1, ge.x2));
-            float fy0 = fminf(ge.y0, fminf(ge.y1, ge.y2)), fy1 = fmaxf(ge.y0, fmaxf(ge.y1, ge.y2));
-            float ex = fmaxf(fmaxf(fx0 - px, px - fx1), 0.0f), ey = fmaxf(fmaxf(fy0 - py, py - fy1), 0.0f);
-            if ((ex * ex + ey * ey) * 0.998f - 1e-3f >= mine) continue;
-            float d = tri_d2(px, py, ge);
-            mine = (d < mine) ? d : mine;                    // a NaN distance never becomes the minimum
-        }
-        best = group_min(mine);
-    };
-    int k = max(max(0, max(-cx, cx - (m.nx - 1))), max(-cy, cy - (m.ny - 1)));
-    for (;; ++k) {
-        // cells at Chebyshev distance exactly k from (cx, cy), clipped to the grid
-        int y0 = max(cy - k, 0), y1 = min(cy + k, m.ny - 1);
-        int x0 = max(cx - k, 0), x1 = min(cx + k, m.nx - 1);
-        for (int y = y0; y <= y1; ++y) {
-            if (y == cy - k || y == cy + k) {
-                for (int x = x0; x <= x1; ++x) visit(x, y);
-            } else {
-                if (cx - k >= 0 && cx - k < m.nx) visit(cx - k, y);
-                if (k > 0 && cx + k >= 0 && cx + k < m.nx) visit(cx + k, y);
-            }
-        }
-        if (best <= stop) break;
-        float bound = (float)k * m.cell * 0.999f;            // everything unvisited is at least this far away
-        if (best <= bound * bound) break;
-        if (cx - k <= 0 && cx + k >= m.nx - 1 && cy - k <= 0 && cy + k >= m.ny - 1) break;
-    }
-    return best;
-}
-
-// The same minimum by an ordered descent of the hierarchy over the faces (tds::BvhNode): for the points the candidate lists do not cover.
-// The group's lanes hold the same point.  At an inner node every lane weighs ONE of the eight children (a 16-byte box each: one 128-byte
-// line for the group); the children whose box can still beat the minimum go onto the group's stack (in LDS) farthest first -- a lane finds
-// its place by comparing its bound with the other seven -- and the nearest is taken up at once; at a leaf a face per lane.  Boxes are
-// shrunk like everywhere in K2b (x 0.998 - 1e-3): a subtree is left out only if every face in it is certainly farther than the minimum so
-// far, so the result is the minimum over ALL faces, bit for bit, and `stop` ends the descent as in the other walks.  (Round 5 began with
-// two children per node, both weighed by every lane: three times the depth, 0.60 ms for 65 536 strayed agents.)
-static_assert(OL == 8, "nearest_face_d2_bvh: a lane per child of a node");
-using tds::BVH_STACK;                   // (tds_common.h; tds_map_create refuses to attach a hierarchy the stack cannot hold)
-__device__ __forceinline__ float box_lb(float px, float py, float x0, float y0, float x1, float y1) {
-    const float ex = fmaxf(fmaxf(x0 - px, px - x1), 0.0f), ey = fmaxf(fmaxf(y0 - py, py - y1), 0.0f);
-    return (ex * ex + ey * ey) * 0.998f - 1e-3f;
-}
+// The forward's ordered descent of the hierarchy over the faces: tds::nearest_in_bvh<false> (tds_nearest_face.h, where the walk is
+// described) written out with its strict comparisons.  Kept beside the shared one because the instantiation of the template, the same
+// arithmetic, came out 1.4 % slower on agents that strayed from the map (profiles/nearest_face_timing.json); lists and rings are shared.
 __device__ float nearest_face_d2_bvh(const tds::NearView &nv, float px, float py, float stop, int sub) {
-    __shared__ int2 stacks[OBLOCK / OL][BVH_STACK];
+    static_assert(OL == 8, "nearest_face_d2_bvh: a lane per child of a node");
+    __shared__ int2 stacks[OBLOCK / OL][tds::BVH_STACK];
     int2 *st = stacks[threadIdx.x / OL];
     const float inf = __builtin_inff();
     const int shift = (int)(threadIdx.x & 63 & ~(OL - 1));                              // the group's first lane within the wavefront
@@ -803,7 +693,7 @@ __device__ float nearest_face_d2_bvh(const tds::NearView &nv, float px, float py
         if (cur >= 0) {
             const float4 bx = nv.bvh[cur].box[sub];
             const int ch = nv.bvh[cur].child[sub];
-            const float lb = box_lb(px, py, bx.x, bx.y, bx.z, bx.w);
+            const float lb = tds::box_lb(px, py, bx.x, bx.y, bx.z, bx.w);
             const bool open = lb < best;
             const float key = open ? lb : inf;
             int above = 0;                                                             // open children that will lie above this lane's on the stack
@@ -814,8 +704,8 @@ __device__ float nearest_face_d2_bvh(const tds::NearView &nv, float px, float py
             }
             const int nopen = __popc((unsigned)(__ballot(open) >> shift) & 0xffu);
             const int slot = sp + nopen - 1 - above;
-            if (open && slot < BVH_STACK) st[slot] = make_int2(ch, __float_as_int(lb));
-            sp = min(sp + nopen, BVH_STACK);
+            if (open && slot < tds::BVH_STACK) st[slot] = make_int2(ch, __float_as_int(lb));
+            sp = min(sp + nopen, tds::BVH_STACK);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -824,14 +714,12 @@ __device__ float nearest_face_d2_bvh(const tds::NearView &nv, float px, float py
             float d = inf;
             if (sub < cnt) {
                 const GridEntry ge = nv.faces[nv.bvh_idx[first + sub]];
-                const float fx0 = fminf(ge.x0, fminf(ge.x1, ge.x2)), fx1 = fmaxf(ge.x0, fmaxf(ge.x1, ge.x2));
-                const float fy0 = fminf(ge.y0, fminf(ge.y1, ge.y2)), fy1 = fmaxf(ge.y0, fmaxf(ge.y1, ge.y2));
-                if (!(box_lb(px, py, fx0, fy0, fx1, fy1) >= best)) {
-                    const float t = tri_d2(px, py, ge);
+                if (!(tds::face_lb(px, py, ge) >= best)) {
+                    const float t = tds::tri_d2(px, py, ge);
                     d = (t < inf) ? t : inf;                                          // a NaN distance never becomes the minimum
                 }
             }
-            best = fminf(best, group_min(d));
+            best = fminf(best, tds::group_min(d));
         }
         // the next subtree that can still hold a nearer face
         float lb;
@@ -843,87 +731,42 @@ __device__ float nearest_face_d2_bvh(const tds::NearView &nv, float px, float py
     }
 }
 
-// The same minimum from the candidate list of the point's cell (tds::NearView), walked by OL lanes together: candidate i + lane of every
-// round, the group's running minimum by three xor-shuffles, ended by the first round whose first candidate has a lower bound that is not
-// below it (the list is sorted by lower bound) or as soon as the minimum is <= stop.  The minimum over faces does not depend on the order
-// in which they are looked at, so the result is the sequential walk's, bit for bit.  One lane per point (the first version) was a chain of
-// dependent loads, candidate -> face -> next candidates, a few to a few dozen rounds long: 0.148 ms at B = 1024 x 64 however little
-// arithmetic it is; eight lanes per point: one or two rounds, 0.09 ms.  Points outside the grid take the ring walk.
-__device__ __forceinline__ float nearest_face_d2_lists(const MapView &m, const tds::NearView &nv, float px, float py, float stop, int sub) {
-    const float inf = __builtin_inff();
-    bool ring = nv.cand == nullptr || m.nx <= 0 || !(px == px) || !(py == py) || __builtin_isinf(px) || __builtin_isinf(py);
-    int cx = 0, cy = 0;
-    if (!ring) {
-        const float fx = (px - nv.ox) * m.inv_cell, fy = (py - nv.oy) * m.inv_cell;
-        ring = !(fx >= 0.0f && fy >= 0.0f && fx < (float)nv.nx && fy < (float)nv.ny);
-        if (!ring) {
-            cx = tds::cell_coord(px, nv.ox, m.inv_cell); cy = tds::cell_coord(py, nv.oy, m.inv_cell);
-            ring = cx < 0 || cy < 0 || cx >= nv.nx || cy >= nv.ny;
-        }
-    }
-    if (ring) {                                                                         // (uniform within the group: all its lanes hold the same point)
-        // beyond the lists' grid: the hierarchy over the faces where the map has one, else the walk over grid rings
-        if (nv.bvh != nullptr && px == px && py == py && !__builtin_isinf(px) && !__builtin_isinf(py)) return nearest_face_d2_bvh(nv, px, py, stop, sub);
-        return nearest_face_d2(m, px, py, stop, sub);
-    }
-    const int s = nv.cand_start[cy * nv.nx + cx], e = nv.cand_start[cy * nv.nx + cx + 1];
-    float best = inf;                                                                 // the group's minimum so far, the same in all its lanes
-    for (int i = s; i < e && best > stop; i += OL) {
-        const int j = i + sub;
-        tds::NearCand c;
-        c.face = 0; c.lb = inf;
-        if (j < e) c = nv.cand[j];
-        const float lb0 = __shfl(c.lb, (threadIdx.x & 63 & ~(OL - 1)));                // the round's first candidate
-        if (lb0 >= best) break;                                                       // sorted by lb: nothing further can be nearer
-        float d = inf;
-        if (c.lb < best) {
-            const GridEntry ge = nv.faces[c.face];
-            const float fx0 = fminf(ge.x0, fminf(ge.x1, ge.x2)), fx1 = fmaxf(ge.x0, fmaxf(ge.x1, ge.x2));
-            const float fy0 = fminf(ge.y0, fminf(ge.y1, ge.y2)), fy1 = fmaxf(ge.y0, fmaxf(ge.y1, ge.y2));
-            const float ex = fmaxf(fmaxf(fx0 - px, px - fx1), 0.0f), ey = fmaxf(fmaxf(fy0 - py, py - fy1), 0.0f);
-            if (!((ex * ex + ey * ey) * 0.998f - 1e-3f >= best)) {
-                const float t = tri_d2(px, py, ge);
-                d = (t < inf) ? t : inf;                                              // a NaN distance never becomes the minimum (as `d < best ? d : best`)
-            }
-        }
-        best = fminf(best, group_min(d));
-    }
-    return best;
-}
-
-// OL lanes per agent corner, 4 consecutive groups = one agent
+// OL lanes per agent corner, 4 consecutive groups = one agent; the nearest face by tds_nearest_face.h, the distance alone
 __global__ void __launch_bounds__(OBLOCK) offroad_kernel(MapView m, tds::NearView nv, const float4 *__restrict__ state, const float2 *__restrict__ lenwid,
                                                          const float2 *__restrict__ sc, const uint8_t *__restrict__ present,
                                                          float *__restrict__ out, int64_t n, float threshold, const MapView *__restrict__ views,
                                                          const tds::NearView *__restrict__ nears, const int32_t *__restrict__ scene_map, int agents_per_scene) {
-    const int64_t t = (int64_t)blockIdx.x * OBLOCK + threadIdx.x;
-    const int64_t a = t / (4 * OL);
-    const int k = (int)((t / OL) & 3), sub = (int)(t & (OL - 1));
+    const tds::NearLane l = tds::near_lane<OBLOCK>();
+    const int64_t a = l.a;
     float v = 0.0f;
-    if (a < n && views != nullptr) {                                                // one map per scene (tds_offroad_multi_f32)
-        const int im = scene_map[a / agents_per_scene];
-        m = views[im]; nv = nears[im];
-    }
+    if (a < n) tds::select_scene_map(m, nv, views, nears, scene_map, a, agents_per_scene);       // (tds_offroad_multi_f32)
     if (a < n && m.n_faces > 0) {
-        float4 s = state[a];
-        float2 lw = lenwid[a];
-        float2 scv = sc[a];
-        const float sx = (k == 0 || k == 3) ? 0.5f : -0.5f, sy = (k < 2) ? 0.5f : -0.5f;     // box2corners_th :285-288
-        float x4 = sx * lw.x, y4 = sy * lw.y;
-        float px = (x4 * scv.y + y4 * (-scv.x)) + s.x;
-        float py = (x4 * scv.x + y4 * scv.y) + s.y;
-        float d = nearest_face_d2_lists(m, nv, px, py, fmaxf(threshold, 0.0f), sub);
-        d = (d != d) ? 0.0f : d;                                     // nan_to_num :171
-        if (__builtin_isinf(d)) d = 3.4028234663852886e38f;
-        v = (d > threshold) ? d : 0.0f;                              // F.threshold(d, thr, 0) :172
+        const tds::BoxCorner c = tds::box_corner(l.k, state[a], lenwid[a], sc[a]);
+        auto in_bvh = [](const tds::NearView &nv, float px, float py, float stop, int sub) {
+            tds::Nearest<false> n;
+            n.d = nearest_face_d2_bvh(nv, px, py, stop, sub);
+            return n;
+        };
+        v = tds::offroad_corner_value(tds::nearest_face<false>(m, nv, c.px, c.py, fmaxf(threshold, 0.0f), l.sub, in_bvh).d2, threshold);
     }
     // sum of the 4 corners in order (infractions.py:228)
     float v1 = __shfl_down(v, OL), v2 = __shfl_down(v, 2 * OL), v3 = __shfl_down(v, 3 * OL);
-    if (a < n && k == 0 && sub == 0) {
+    if (a < n && l.k == 0 && l.sub == 0) {
         float tot = ((v + v1) + v2) + v3;
         if (present) tot = tot * (present[a] ? 1.0f : 0.0f);         // simulator.py:1044
         out[a] = tot;
     }
+}
+
+// both entry points: one map (`views` null) or a set with a map index per scene
+int launch_offroad(const MapView &view, const tds::NearView &near, const MapView *views, const tds::NearView *nears, const int32_t *scene_map,
+                   int64_t agents_per_scene, const float *state, const float *lenwid, const float *sc, const uint8_t *present, float *out,
+                   int64_t n_agents, float threshold, void *stream) {
+    hipLaunchKernelGGL(offroad_kernel, dim3(tds::near_blocks(n_agents, OBLOCK)), dim3(OBLOCK), 0, (hipStream_t)stream, view, near,
+                       (const float4 *)state, (const float2 *)lenwid, (const float2 *)sc, present, out, n_agents, threshold, views, nears, scene_map,
+                       (int)agents_per_scene);
+    TDS_LAUNCH_CHECK("offroad_kernel");
+    return TDS_OK;
 }
 
 }  // namespace
@@ -934,12 +777,7 @@ TDS_EXPORT int tds_offroad_f32(const tds_map_t *map, const float *state, const f
     TDS_CHECK_ARG(n_agents >= 0 && n_agents < ((int64_t)1 << 34), "tds_offroad_f32: bad agent count");
     if (n_agents == 0) return TDS_OK;
     TDS_CHECK_ARG(state && lenwid && sc && out, "tds_offroad_f32: null pointer");
-    int64_t threads = n_agents * 4 * OL;
-    hipLaunchKernelGGL(offroad_kernel, dim3((unsigned)((threads + OBLOCK - 1) / OBLOCK)), dim3(OBLOCK), 0, (hipStream_t)stream, map->view, map->near,
-                       (const float4 *)state, (const float2 *)lenwid, (const float2 *)sc, present, out, n_agents, threshold,
-                       (const MapView *)nullptr, (const tds::NearView *)nullptr, (const int32_t *)nullptr, 1);
-    TDS_LAUNCH_CHECK("offroad_kernel");
-    return TDS_OK;
+    return launch_offroad(map->view, map->near, nullptr, nullptr, nullptr, 1, state, lenwid, sc, present, out, n_agents, threshold, stream);
 }
 
 TDS_EXPORT int tds_offroad_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state, const float *lenwid,
@@ -949,12 +787,8 @@ TDS_EXPORT int tds_offroad_multi_f32(const tds_mapset_t *set, const int32_t *sce
     TDS_CHECK_ARG(n_agents >= 0 && n_agents < ((int64_t)1 << 34), "tds_offroad_multi_f32: bad agent count");
     if (n_agents == 0) return TDS_OK;
     TDS_CHECK_ARG(state && lenwid && sc && out, "tds_offroad_multi_f32: null pointer");
-    int64_t threads = n_agents * 4 * OL;
-    hipLaunchKernelGGL(offroad_kernel, dim3((unsigned)((threads + OBLOCK - 1) / OBLOCK)), dim3(OBLOCK), 0, (hipStream_t)stream, MapView{},
-                       tds::NearView{nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, 0, nullptr, nullptr}, (const float4 *)state, (const float2 *)lenwid, (const float2 *)sc, present, out, n_agents,
-                       threshold, (const MapView *)set->d_views, (const tds::NearView *)set->d_near, scene_map, (int)agents_per_scene);
-    TDS_LAUNCH_CHECK("offroad_kernel");
-    return TDS_OK;
+    return launch_offroad(MapView{}, tds::NearView{}, set->d_views, set->d_near, scene_map, agents_per_scene, state, lenwid, sc, present, out, n_agents,
+                          threshold, stream);
 }
 
 // ---- map sets: device array of the views of several maps, for launches whose scenes have different maps ----------------------------
