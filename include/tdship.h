@@ -271,6 +271,10 @@ int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t *scene_map,
  * The pixels never depend on it: no flag, NULL, a buffer that is too small or misaligned, or a call served by another launch (uint8 or float32 in 8-wave
  * workgroups or at four workgroups per CU, the split form, the masks, packed keys) renders exactly as before and leaves the buffer alone. */
 #define TDS_RASTER_HAS_CAMERA_PREP 4
+/*   flags              TDS_RASTER_NO_SMALL_FACES: every face goes through the face queue.  Without it the persistent 4-wave bit-plane launches paint
+ *                      the faces that lie inside the image and span at most TDS_RASTER_SMALL_ROWS rows on the lane that scanned them, where enough
+ *                      lanes of a scan step hold one; the pixels are the same either way. */
+#define TDS_RASTER_NO_SMALL_FACES 8
 typedef struct tds_raster_aux {
     uint32_t *index_slices;
     int64_t index_slices_bytes;
@@ -817,6 +821,13 @@ int tds_stop_lines_f32(const float *agent_xy, const float *agent_sc, const uint8
 #define TDS_RASTER_DBG_NO_EXTRA_STRIP 2097152  /* never one strip more than necessary (nine and more keys) */
 #define TDS_RASTER_DBG_PROLOGUE_TWICE 4194304  /* the fused bit-plane kernel runs its per-item prologue (trim polygon, scan window, grid rows) a second
                                                   time and drops the result: the difference to a plain launch is what the prologue costs */
+#define TDS_RASTER_DBG_DROP_SMALL 8388608      /* the fused bit-plane kernel drops, instead of queueing, every accepted face with all three vertices inside
+                                                  the image and at most TDS_RASTER_SMALL_ROWS rows: the difference to a plain launch is what these
+                                                  faces cost on the general path */
+#ifndef TDS_RASTER_SMALL_ROWS
+#define TDS_RASTER_SMALL_ROWS 7                /* rows (yb - yt + 1) of the largest face that is small: the persistent bit-plane kernel paints such faces
+                                                  on the lane that scanned them; the flag above and the counters below go by the same test */
+#endif
 
 #ifdef TDS_TESTING
 /* force the LDS strip width of K3 (0 = automatic, else 8 .. 128 output rows) */
@@ -834,6 +845,13 @@ int tds_raster_get_stats(unsigned long long *out16);
 /* read and reset the two counters of the prepared scan set-ups (TDS_RASTER_DBG_STATS): work items of the persistent bit-plane launches that used
  * their record of tds_raster_aux_t::camera_prep, and work items that computed their set-up in the kernel */
 int tds_raster_get_prep_stats(unsigned long long *out2);
+/* read and reset the 16 counters of small faces (TDS_RASTER_DBG_STATS; fused bit-plane kernels; a face is small as TDS_RASTER_DBG_DROP_SMALL says).
+ * A chunk is one step of a wave through the static map (up to 64 grid entries).  [0] chunks, [1] faces accepted in them, [2] small ones among those,
+ * [3] accepted faces of the other producers (actors, per-camera triangles), [4] small ones among those, [5..12] chunks by their number of small
+ * faces: 0, 1-8, 9-16, 17-24, 25-32, 33-40, 41-48, 49-64, [13] small faces in chunks that hold at least as many as the on-lane path asks for (25),
+ * [14] chunks without an accepted face,
+ * [15] faces painted on the lane that scanned them (persistent launches). */
+int tds_raster_get_small_stats(unsigned long long *out16);
 /* which launches tds_raster_scene makes for a call of this shape (its plan_raster_scene, with explicit knobs: those of the four setters above).
  * n_keys: distinct keys (-1: more than 15); workspace_bytes: as the caller passes it (0: none).
  * form: 0 bit planes, 1 split (K3s + K3r + the bit planes over overflowed cameras), 2 packed keys binned, 3 packed keys fused, 4 TDS_ELIMIT.
@@ -844,6 +862,11 @@ typedef struct {
 } tds_raster_plan_t;
 int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64_t workspace_bytes,
                     int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug, tds_raster_plan_t *out);
+/* the same call: does its launch paint small faces on the lane that scanned them?  small_faces: 0 = the caller passed TDS_RASTER_NO_SMALL_FACES.
+ * 1 exactly for the 4-wave bit-plane instantiations at three workgroups per CU (minwg 3) of a colour image, else 0. */
+int tds_raster_plan_small_lane(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices,
+                               int64_t workspace_bytes, int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug,
+                               int small_faces, int *small_lane);
 /* 0: maps created from now on carry no nearest-face candidate lists (K2b then walks grid rings) */
 int tds_testing_set_near_lists(int enabled);
 #endif

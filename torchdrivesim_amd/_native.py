@@ -26,6 +26,7 @@ OUT_MASK_U8, OUT_MASK_BITS = 2, 3     # semantic masks (tds_raster_scene_masks):
 RASTER_NO_TRIM = 1
 RASTER_REWRITE_ALL = 2
 RASTER_HAS_CAMERA_PREP = 4
+RASTER_NO_SMALL_FACES = 8
 
 
 class RasterDebug(enum.IntFlag):
@@ -53,6 +54,7 @@ class RasterDebug(enum.IntFlag):
     WIDEST_STRIPS = 1048576
     NO_EXTRA_STRIP = 2097152
     PROLOGUE_TWICE = 4194304
+    DROP_SMALL = 8388608
 
 _lib = None
 
@@ -196,8 +198,11 @@ tds_raster_set_list_waves(int waves)
 tds_raster_set_debug(int flags)
 tds_raster_get_stats(host* out16)
 tds_raster_get_prep_stats(host* out2)
+tds_raster_get_small_stats(host* out16)
 tds_raster_plan(int64 n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64 workspace_bytes, int cus, int force_tw,
     int bits_waves, int list_waves, int list_lds_kb, int debug, host* out)
+tds_raster_plan_small_lane(int64 n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64 workspace_bytes, int cus,
+    int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug, int small_faces, host* small_lane)
 tds_testing_set_near_lists(int enabled)
 '''
 

@@ -793,6 +793,9 @@ def _raster_workspace(dev, n_img, res, out_mode=None, n_keys=-1):
 #: per (device, stream, thread, shape of the launch), its size asked for on a cache miss only, the least recently used dropped, nothing carried between calls -- but not part of it.  False: every workgroup
 #: computes its camera's set-up itself, as before; the pixels are the same either way (tests/test_gpu_camera_prep.py).
 use_camera_prep = True
+#: the persistent bit-plane launches paint small map faces (inside the image, at most seven rows) on the lane that scanned them
+#: (TDS_RASTER_NO_SMALL_FACES of include/tdship.h switches it off per call); the pixels are the same with it switched off
+use_small_faces = True
 #: ... and for differentiable calls too.  Off by default: the launch that also stores the index slices writes every line and is bound by that
 #: stream, so the instructions saved buy nothing and the records' loads cost (config 5's forward launch at B = 256: 1.85 -> 1.87 - 1.89 ms with the
 #: table, three alternating runs each: profiles/camera_prep_timing.json); the native path takes the table all the same and is tested.
@@ -1141,7 +1144,7 @@ def _scene_call(fn, smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc
 
 
 def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, out_dtype=torch.float32, out=None, key_table=None,
-                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True, camera_prep=True):
+                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True, camera_prep=True, small_faces=True):
     """Fused Simulator.render: state (B,N,4), agent_sc (B,N,2), tmpl (B,N,7,2), actor_key (B,N,2) int32 bit patterns -- or (B,Nc,N,2)
     when every camera sees its own colours (custom_agent_colors) --, mask (B,Nc,N) bool/uint8, cam_xy / cam_sc (B,Nc,2)
     -> (B,Nc,3,res,res) float32 [0,255] or uint8.  extra_tri (B,Nc,K,3,2) world-space triangles with keys extra_key (B,Nc,K) int32
@@ -1184,6 +1187,9 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     if not trim:
         aux = aux if aux is not None else nat.RasterAuxPrep()
         aux.flags = nat.RASTER_NO_TRIM
+    if not (use_small_faces and small_faces):
+        aux = aux if aux is not None else nat.RasterAuxPrep()
+        aux.flags |= nat.RASTER_NO_SMALL_FACES
     cov_ent = cov_rec = None
     if caller_out is not None and _owned_buffers:
         if out_dtype == torch.float32 and slices is None and B * Nc > 0:

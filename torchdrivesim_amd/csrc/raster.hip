@@ -81,6 +81,7 @@ struct CommonArgs {
     int64_t n_img;
     void *out;
     int no_trim;                // trim_mesh_before_rendering = False (cv2.py:15,32): faces are kept whether or not a vertex is in view
+    int small_lane;             // the plan's: small faces are painted on the lane that scanned them (drain_bits; the instantiations that have the block)
     uint32_t *slices;           // optional: bit-slices of the winning key index per pixel, kept for the backward pass (bit-plane kernel
                                 // only; layout in include/tdship.h, tds_raster_aux_t) -- or, in a plain float32 colour launch of the fused
                                 // bit-plane kernel (no slices wanted), the COVERAGE RECORD of the output buffer (tds_raster_aux_t::coverage):
@@ -1628,6 +1629,7 @@ __device__ inline bool clip_line_small(int W, int H, int &x1, int &y1, int &x2, 
 // optional work counters (profiling hook tds_raster_get_stats of the testing build; active with debug flag TDS_RASTER_DBG_STATS)
 #ifdef TDS_TESTING
 __device__ unsigned long long g_stats[18];       // [16], [17]: work items that used their prepared record / computed their scan set-up (tds_raster_get_prep_stats)
+__device__ unsigned long long g_small_stats[16]; // small faces among the accepted ones (tds_raster_get_small_stats)
 #define TDS_STAT_LANES(W, I, V) do { if ((W).debug & TDS_RASTER_DBG_STATS) { const unsigned long long v_ = (unsigned long long)(V); if (v_) atomicAdd(&g_stats[I], v_); } } while (0)
 #define TDS_STAT(W, I, V) do { if (((W).debug & TDS_RASTER_DBG_STATS) && (W).lane == 0) atomicAdd(&g_stats[I], (unsigned long long)(V)); } while (0)
 #else
@@ -1987,12 +1989,13 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
 // edge_dx(xs, xe, 1) = trunc((xe - xs) * 65536 + 1/2) with C's truncation, is (xe - xs) << 16 for xe >= xs and ((xe - xs) << 16) + 1 below.
 // lane = face; `e` = the face's list entry (plane | outline edges << 4, three packed vertices); faces that miss the strip are skipped.
 __device__ __forceinline__ int slope_one_row(int xs, int xe) { const int d = xe - xs; return d >= 0 ? d << 16 : (int)(((unsigned)d << 16) + 1u); }
-// TALL = false: faces of one or two rows; TALL = true: up to four rows (yb - yt <= 3) -- the one or two rows between the top and the bottom
+// ROWS = 2: faces of one or two rows; ROWS > 2: up to ROWS rows (yb - yt <= ROWS - 1) -- the rows between the top and the bottom
 // vertex are painted by the lane too, each either the row of the middle vertex or a row of part 1 (chains T->M, T->B) / part 2 (M->B, T->B)
-// with the expressions of process_batch_bits' row items.  Which of the two serves a launch is decided by the resolution (wave-uniform): the
+// with the expressions of process_batch_bits' row items.  K3r: which of 2 and 4 serves a launch is decided by the resolution (wave-uniform): the
 // taller variant costs every chunk of faces about twice the instructions and pays where faces of three and four rows are many (128 x 128: 38 %
-// of the faces on top of the 32 % of one and two rows; 64 x 64: 8 % on top of 66 %).
-template <bool TALL>
+// of the faces on top of the 32 % of one and two rows; 64 x 64: 8 % on top of 66 %).  The fused persistent kernel takes ROWS = SMALL_ROWS for
+// the chunks of its scan in which enough lanes hold such a face (drain_bits).
+template <int ROWS>
 __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32_t plane, uint32_t v0, uint32_t v1, uint32_t v2) {
     const int H = w.H, X0 = w.X0, wpr = w.wpr;
     const int Xhi = min(w.W, X0 + w.TWp) - 1;
@@ -2013,7 +2016,7 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
     auto cls = [](int ax, int ay, int bx, int by) { return 5u | ((abs(bx - ax) >= abs(by - ay)) ? 2u : 0u); };
     const unsigned cTM = cls(xt, yt, xm, ym), cMB = cls(xm, ym, xb, yb), cTB = cls(xt, yt, xb, yb);
     int sTB, sTM, sMB;
-    if constexpr (TALL) {
+    if constexpr (ROWS > 2) {
         sTB = edge_dx(xt, xb, yb - yt);
         sTM = ym > yt ? edge_dx(xt, xm, ym - yt) : 0;
         sMB = yb > ym ? edge_dx(xm, xb, yb - ym) : 0;
@@ -2027,11 +2030,11 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
         edge_reach(cTB, xt, half_slope(sTB), L, R);
         paint_row(yt, L, R);
     }
-    if constexpr (TALL) {
+    if constexpr (ROWS > 2) {
         int oLb, oRb;
         edge_offsets(cTB, sTB, oLb, oRb);
 #pragma unroll
-        for (int j = 1; j <= 2; ++j) {
+        for (int j = 1; j <= ROWS - 2; ++j) {
             const int y = yt + j;
             if (y >= yb) break;
             const int xc = (xt << 16) + j * sTB;                     // the chain T->B in this row
@@ -2072,13 +2075,65 @@ __device__ __forceinline__ int key_plane(const uint32_t *keys, int K, uint32_t k
 }
 
 // BIG: faces outside the packed coordinate range may come along (they take the exact sequential path); the list kernel never sees one
-template <bool BIG = true>
-__device__ __forceinline__ void drain_bits(BitCtx &w, int k, bool acc, unsigned edges, const int (&px)[3], const int (&py)[3], bool more) {
+// map_chunk: the faces are one chunk of the static map's grid (testing build: the counters of small faces tell them from the other producers')
+// SROWS > 0 (the persistent kernel) and small_on (wave-uniform: the plan's RasterPlan::small_lane): SMALL faces -- all three vertices inside the image,
+// at most SROWS rows -- are painted at once by the lane that holds them (process_small_bits: no edge classes, no ring, no row items) whenever at
+// least SMALL_MIN_LANES lanes of the step hold one; they are not queued.  The planes are OR-ed, so the order of painting is free, and the pixels of
+// a face are the same on either path.  Which path a face takes depends on the faces beside it in the scan, never on the map.
+#ifndef TDS_SMALL_MIN_LANES
+#define TDS_SMALL_MIN_LANES 25
+#endif
+constexpr int SMALL_MIN_LANES = TDS_SMALL_MIN_LANES, SMALL_ROWS = TDS_RASTER_SMALL_ROWS;
+template <bool BIG = true, int SROWS = 0>
+__device__ __forceinline__ void drain_bits(BitCtx &w, int k, bool acc, unsigned edges, const int (&px)[3], const int (&py)[3], bool more, bool map_chunk = true,
+                                           bool small_on = false) {
+    static_assert(SROWS == 0 || SROWS == SMALL_ROWS, "one definition of a small face");
     if constexpr (BIG) {
         bool big = acc && (max(max(abs(px[0]), abs(px[1])), max(max(abs(px[2]), abs(py[0])), max(abs(py[1]), abs(py[2])))) >= COORD_LIMIT);
         if (__builtin_expect(__ballot(big) != 0, 0)) {
             if (big) fill_generic_bits(w.planes + (size_t)k * w.H * w.wpr, w.H, w.W, w.X0, w.TWp, w.wpr, px[0], py[0], px[1], py[1], px[2], py[2]);
             acc = acc && !big;
+        }
+    }
+    // Small faces: all three vertices inside the image, at most SMALL_ROWS rows -- what a lane paints on its own without edge classes, ring or
+    // row items.  One test serves the on-lane path and, in the testing build, the counters (TDS_RASTER_DBG_STATS: tds_raster_get_small_stats) and
+    // the ablation (TDS_RASTER_DBG_DROP_SMALL drops them: the difference to a plain launch is what they cost on the general path).
+    bool want_small = SROWS > 0 && small_on;
+#ifdef TDS_TESTING
+    want_small = want_small || (w.debug & (TDS_RASTER_DBG_STATS | TDS_RASTER_DBG_DROP_SMALL)) != 0;
+#endif
+    if (want_small) {
+        const unsigned oc = vertex_outcode(px[0], py[0], w.W, w.H) | vertex_outcode(px[1], py[1], w.W, w.H) | vertex_outcode(px[2], py[2], w.W, w.H);
+        const int yt = min(py[0], min(py[1], py[2])), yb = max(py[0], max(py[1], py[2]));
+        bool small = acc && oc == 0u && yb - yt <= SMALL_ROWS - 1;
+#ifdef TDS_TESTING
+        if (w.debug & (TDS_RASTER_DBG_STATS | TDS_RASTER_DBG_DROP_SMALL)) {
+            const int n_acc = __popcll(__ballot(acc)), n_all = __popcll(__ballot(small));
+            if ((w.debug & TDS_RASTER_DBG_STATS) && w.lane == 0) {
+                if (map_chunk) {
+                    atomicAdd(&g_small_stats[0], 1ull);
+                    atomicAdd(&g_small_stats[1], (unsigned long long)n_acc);
+                    atomicAdd(&g_small_stats[2], (unsigned long long)n_all);
+                    atomicAdd(&g_small_stats[5 + (n_all >= 49 ? 7 : (n_all + 7) / 8)], 1ull);
+                    if (n_all >= SMALL_MIN_LANES) atomicAdd(&g_small_stats[13], (unsigned long long)n_all);
+                    if (n_acc == 0) atomicAdd(&g_small_stats[14], 1ull);
+                } else {
+                    atomicAdd(&g_small_stats[3], (unsigned long long)n_acc);
+                    atomicAdd(&g_small_stats[4], (unsigned long long)n_all);
+                }
+            }
+            if ((w.debug & TDS_RASTER_DBG_DROP_SMALL) && map_chunk) { acc = acc && !small; small = false; }
+        }
+#endif
+        if constexpr (SROWS > 0) {
+            const int n_small = __popcll(__ballot(small));
+            if (small_on && n_small >= SMALL_MIN_LANES) {
+#ifdef TDS_TESTING
+                if ((w.debug & TDS_RASTER_DBG_STATS) && w.lane == 0) atomicAdd(&g_small_stats[15], (unsigned long long)n_small);
+#endif
+                process_small_bits<SROWS>(w, small, (uint32_t)k, pack_xy(px[0], py[0]), pack_xy(px[1], py[1]), pack_xy(px[2], py[2]));
+                acc = acc && !small;
+            }
         }
     }
     unsigned long long pending = __ballot(acc);
@@ -2589,6 +2644,7 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
     using E = typename PairTab<NB, OutT>::E;
     constexpr int BBLOCK = BWAVES * 64, P = 1 << (2 * NB);
     constexpr bool PERSIST = BWAVES == 4 && MINWG == 3;              // (the 8-wave instantiation as a persistent launch: 224 instead of 160 B of scratch, 6 % slower)
+    constexpr int SROWS = PERSIST && !is_mask<OutT>::value ? SMALL_ROWS : 0;       // small faces painted on the scan lane (drain_bits)
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int res = c.res, H = res, W = res, wpr = TWp >> 5, K = kt.n;
@@ -2714,8 +2770,11 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
             uint32_t key;
             int px[3] = {0, 0, 0}, py[3] = {0, 0, 0};
             unsigned edges;
+            // (read by the testing build's counters only; sampled before the step, so the step that ends a phase -- the masked agents' dot, one
+            // lane at the most -- is booked under the phase it belongs to)
+            const bool map_phase = st.phase == 2;
             const bool more = scan_step<BWAVES, SA>(st, a, ci, cam, img, lane, wave, X0, TWp, acc, key, px, py, edges);
-            drain_bits(w, key_plane(lkeys, K, key), acc, edges, px, py, more);
+            drain_bits<true, SROWS>(w, key_plane(lkeys, K, key), acc, edges, px, py, more, map_phase, c.small_lane != 0);
             if (!more) break;
         }
         // the next item is taken now (every wave read the current one two barriers ago): the round trip of the atomic hides behind the stream-out
@@ -2960,11 +3019,11 @@ __global__ void __launch_bounds__(BWAVES * 64) raster_list_bits_kernel(CommonArg
         bool small1, small2;
         const bool on1 = classify(P[0], P[1], P[2], acc, small1), on2 = classify(T[0], T[1], T[2], acc && has2, small2);
         if (res >= SMALL_TALL_RES) {
-            process_small_bits<true>(w, small1, e.x, P[0], P[1], P[2]);
-            process_small_bits<true>(w, small2, e.x, T[0], T[1], T[2]);
+            process_small_bits<4>(w, small1, e.x, P[0], P[1], P[2]);
+            process_small_bits<4>(w, small2, e.x, T[0], T[1], T[2]);
         } else {
-            process_small_bits<false>(w, small1, e.x, P[0], P[1], P[2]);
-            process_small_bits<false>(w, small2, e.x, T[0], T[1], T[2]);
+            process_small_bits<2>(w, small1, e.x, P[0], P[1], P[2]);
+            process_small_bits<2>(w, small2, e.x, T[0], T[1], T[2]);
         }
         drain_poly(w, on1 && !small1, on2 && !small2, e.x, P, more);
         if (!more) break;
@@ -3255,7 +3314,8 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     // the plan (the work queues of a persistent launch take the tail of the workspace: what the lists may use ends before them)
     const hipStream_t s = (hipStream_t)stream;
     const int64_t qoff = workspace ? queue_offset(workspace_bytes) : -1;
-    const PlanInput in = {n_img, res, out_mode, ok ? kt.n : -1, listed, N > 0, n_extra > 0, want_slices, workspace ? lists_room(workspace_bytes, masks) : 0, launch_cus(s)};
+    PlanInput in = {n_img, res, out_mode, ok ? kt.n : -1, listed, N > 0, n_extra > 0, want_slices, workspace ? lists_room(workspace_bytes, masks) : 0, launch_cus(s)};
+    in.small_faces = !(aux && (aux->flags & TDS_RASTER_NO_SMALL_FACES));
     const RasterPlan p = plan_raster_scene(in, g_knobs);
     if (aux && p.nb) { aux->n_keys = kt.n; aux->index_bits = p.nb; for (int i = 0; i < 16; ++i) aux->keys[i] = i < kt.n ? kt.key[i] : 0u; }
     if (p.form == RasterForm::Error) { tds::set_error(p.error, MAX_KEYS); return TDS_ELIMIT; }
@@ -3267,6 +3327,7 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
     cm.strips = p.strips; cm.n_img = n_img; cm.out = out; cm.slices = want_slices ? aux->index_slices : nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (aux && (aux->flags & TDS_RASTER_NO_TRIM)) ? 1 : 0;
+    cm.small_lane = p.small_lane ? 1 : 0;
     cm.prep = nullptr;
     char *const ws = (char *)workspace;
 #ifdef TDS_RASTER_MASKS_TU
@@ -3344,6 +3405,7 @@ TDS_EXPORT int tds_raster_mesh(const float *verts, const float *attrs, const int
     cm.cam_xy = (const float2 *)cam_xy; cm.cam_sc = (const float2 *)cam_sc; cm.scale = scale; cm.res = res;
     cm.strips = (res + tw - 1) / tw; cm.n_img = n_img; cm.out = out; cm.slices = nullptr; cm.debug = g_knobs.debug;
     cm.no_trim = (flags & TDS_RASTER_NO_TRIM) ? 1 : 0;
+    cm.small_lane = 0;
     cm.prep = nullptr;
     with_out(out_mode, [&](auto t) { with_tw(tw, [&](auto w) {
         launch(raster_mesh_kernel<w, decltype(t)>, n_img * cm.strips, RBLOCK, lds_bytes(w, res), (hipStream_t)stream, a, cm);
@@ -3370,6 +3432,15 @@ TDS_EXPORT int tds_raster_get_prep_stats(unsigned long long *out2) {
     unsigned long long zero[2] = {0, 0};
     if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_stats), sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: copy failed"); return TDS_EHIP; }
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+
+// read and reset the counters of small faces (debug flag TDS_RASTER_DBG_STATS; drain_bits)
+TDS_EXPORT int tds_raster_get_small_stats(unsigned long long *out16) {
+    TDS_CHECK_ARG(out16, "tds_raster_get_small_stats: null output");
+    unsigned long long zero[16] = {0};
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_small_stats), sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_small_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_small_stats), zero, sizeof(zero)) != hipSuccess) { tds::set_error("tds_raster_get_small_stats: reset failed"); return TDS_EHIP; }
     return TDS_OK;
 }
 #endif  // TDS_TESTING

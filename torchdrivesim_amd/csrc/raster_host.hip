@@ -55,6 +55,19 @@ TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys,
                              p.four_per_cu, p.persist, p.tws, p.lw, (int64_t)p.lds, (int64_t)p.lds_s, p.grid, p.caps, p.ws.counts, p.ws.lists, p.ws.lists3};
     return TDS_OK;
 }
+
+// whether the launch of that plan paints small faces on the scan lane (RasterPlan::small_lane), for a caller that allows it or not
+TDS_EXPORT int tds_raster_plan_small_lane(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices,
+                                          int64_t workspace_bytes, int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug,
+                                          int small_faces, int *small_lane) {
+    TDS_CHECK_ARG(small_lane && n_img > 0 && res > 0 && res <= 4096 && n_keys >= -1 && n_keys <= MAX_KEYS && cus > 0 &&
+                  (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode)), "tds_raster_plan_small_lane: bad arguments");
+    PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, lists_room(workspace_bytes, is_mask_mode(out_mode)), cus};
+    in.small_faces = small_faces != 0;
+    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug});
+    *small_lane = (p.form == RasterForm::Bits || p.form == RasterForm::Split) && p.small_lane ? 1 : 0;
+    return TDS_OK;
+}
 #endif  // TDS_TESTING
 
 TDS_EXPORT int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes) {

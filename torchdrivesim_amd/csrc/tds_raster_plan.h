@@ -125,6 +125,7 @@ struct PlanInput {
     bool keys_listed, actors, extra, want_slices;   // the caller listed the actors' keys; N > 0; n_extra > 0; index slices wanted
     int64_t workspace_bytes;    // what the lists may use, the queue tail cut off; 0: no workspace, or no room for the queues
     int cus;                    // CUs the launch may use
+    bool small_faces = true;    // the caller lets small faces be painted on the lane that scanned them (off: TDS_RASTER_NO_SMALL_FACES)
 };
 
 struct RasterPlan {
@@ -137,6 +138,7 @@ struct RasterPlan {
     int64_t grid, caps;         // workgroups of the raster launch; faces per list (Split: per camera, Binned: per strip)
     SplitLayout ws;             // Split: the workspace layout; Binned: the strip lists at ws.lists, their counts at 0
     int tws, lw; size_t lds_s;  // Split: strip width, waves and LDS per workgroup of K3r
+    bool small_lane;            // the bit-plane kernel paints small faces on the lane that scanned them (raster.hip: drain_bits)
 };
 
 // A pure function of the call's shape and the knobs: no HIP call, no global.  tests/test_raster_plan.py pins its choices,
@@ -154,6 +156,7 @@ inline RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
             const size_t tab = (size_t)3 * ((size_t)1 << (2 * p.nb)) * 4;
             p.lds -= tab;
             if (p.form == RasterForm::Split) p.lds_s -= tab;
+            p.small_lane = false;                       // the mask instantiations queue every face
         } else if (p.form != RasterForm::Error) {
             p.form = RasterForm::Error;
             p.error = "tds_raster_scene_masks: the masks come from the bit-plane kernels only (at most %d distinct keys, listed by the caller)";
@@ -226,6 +229,10 @@ inline RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
             p.four_per_cu = nwv == 4 && !in.want_slices && p.form != RasterForm::Split && p.lds <= 40 * 1024 && !(k.debug & TDS_RASTER_DBG_MINWG3);
             p.persist = nwv == 4 && !p.four_per_cu && in.workspace_bytes > 0;
             if (p.persist) p.grid = std::min(p.form == RasterForm::Split ? 512 : p.grid, resident_workgroups(in.cus, p.lds, k));
+            // Small faces on the scan lane: the 4-wave instantiations for three workgroups per CU have the block (issue-bound launches: 5.98 -> 5.76 ms
+            // at the headline, uint8 4.89 -> 4.69; the launch that stores every line of a float32 image is bound by HBM and neither gains nor loses
+            // beyond its spread: DESIGN.md section 6), the 8-wave and the 128-VGPR instantiations do not; the caller may switch it off.
+            p.small_lane = in.small_faces && nwv == 4 && !p.four_per_cu;
             return p;
         }
     }

@@ -30,6 +30,9 @@ class HipRendererConfig(RendererConfig):
     #: the persistent bit-plane launch computes each camera's scan set-up once, in a small kernel in front of it (`_ops.use_camera_prep`); the
     #: pixels are the same with it switched off
     camera_prep: bool = True
+    #: the persistent bit-plane launch paints small map faces (lane markings' slivers) on the lane that scanned them (`_ops.use_small_faces`); the
+    #: pixels are the same with it switched off
+    small_faces: bool = True
 
 
 @dataclass
@@ -136,7 +139,8 @@ class HipRenderer(BirdviewRenderer):
         return _ops.raster_scene(static_map, state, agent_sc, tmpl, actor_key, mask, camera_xy, camera_sc, fov, side, out_dtype=self.out_dtype,
                                  key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out,
                                  write_skipping=bool(getattr(self.cfg, 'write_skipping', True)),
-                                 camera_prep=bool(getattr(self.cfg, 'camera_prep', True)))
+                                 camera_prep=bool(getattr(self.cfg, 'camera_prep', True)),
+                                 small_faces=bool(getattr(self.cfg, 'small_faces', True)))
 
     def render_scene_masks(self, static_map, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor, camera_xy: Tensor,
                            camera_sc: Tensor, key_channels: Dict[int, int], n_channels: int, res: Optional[Resolution] = None,
