@@ -7,6 +7,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
     python examples/step_loop.py --neighbors 8      # a non-visual loop: the 8 nearest other agents in each agent's frame, with their relative velocity
+    python examples/step_loop.py --lanes 6          # a non-visual loop: the 6 nearest lanes in each agent's frame, each a foot point and a polyline ahead
     python examples/step_loop.py --lights device --stop-lines 4     # the light programmes run on the device, a clock per scene; a non-visual loop sees
                                                                     # the 4 nearest stop lines ahead with their colour and the seconds until it changes
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
@@ -68,13 +69,14 @@ def main():
     ap.add_argument('--lights', choices=('host', 'device'), default='host', help='where the light programmes run: one host controller for the whole batch '
                     '(the index tensor is copied over every step), or on the device with a clock per scene (traffic_controls.ProgrammedTrafficLightControl)')
     ap.add_argument('--stop-lines', type=int, default=0, metavar='K', help='observe the K nearest stop lines ahead (compute_stop_lines) instead of images')
+    ap.add_argument('--lanes', type=int, default=0, metavar='K', help='observe the K nearest lanes as polylines (compute_lanes) instead of images')
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
     ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
     args = ap.parse_args()
-    if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) > 1:
-        ap.error('--scan, --neighbors and --stop-lines are observations in place of the image: choose one')
+    if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) + (args.lanes > 0) > 1:
+        ap.error('--scan, --neighbors, --stop-lines and --lanes are observations in place of the image: choose one')
     if args.route and args.route_to:
         ap.error('--route and --route-to are two ways to deal the one route an agent has')
     dev = torch.device('cuda', 0)
@@ -146,6 +148,12 @@ def main():
             lines = sim.compute_stop_lines(k=args.stop_lines, max_distance=args.scan_range)
             colour = torch.nn.functional.one_hot((lines.state + 1).long(), 4)[..., 1:]                  # red / yellow / green, all 0 in an empty slot
             obs = torch.cat([lines.features, colour.to(lines.features.dtype)], dim=-1)                 # (B, A, K, 11): StopLines.FEATURES + the colour
+        elif args.lanes:
+            # the map of a vector policy: per slot Lanes.FEATURES and 8 points 4 m apart that follow the lane graph while the way is unambiguous.
+            # Directions are those of the simulator's lanelet map, which this package stores against the direction of travel (see --npcs): the
+            # agent's own lane reads cos < 0 here; Simulator(lanelet_map=revert_map(...)) gives the other reading.
+            near_lanes = sim.compute_lanes(k=args.lanes, max_distance=args.scan_range)
+            obs = torch.cat([near_lanes.features, near_lanes.points.flatten(-2)], dim=-1)             # (B, A, K, 8 + 16), zeros where near_lanes.mask is False
         else:
             obs = sim.render_egocentric(res=res, fov=35.0)                   # (B, A, 3, H, W): what a policy would consume
         if routed:
@@ -173,6 +181,9 @@ def main():
         red = (lines.state == 0) & lines.mask
         print(f'{args.stop_lines} stop-line slots within {args.scan_range:g} m ahead: {float(lines.mask.float().mean()):.3f} filled, {float(red.float().mean()):.3f} '
               f'red; the nearest changes in {float(lines.features[..., 0, 6][lines.mask[..., 0]].mean()):.1f} s on average')
+    if args.lanes:
+        print(f'{args.lanes} lane slots within {args.scan_range:g} m: {float(near_lanes.mask.float().mean()):.3f} filled, '
+              f'{float(near_lanes.n_valid[near_lanes.mask].float().mean()):.2f} of {near_lanes.points.shape[-2]} polyline points valid on average')
     if args.npcs:
         c = sim.npc_controller
         print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '

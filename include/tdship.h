@@ -791,6 +791,59 @@ int tds_stop_lines_f32(const float *agent_xy, const float *agent_sc, const uint8
                        int32_t *slot_state, int64_t B, int64_t A, int64_t N, int K, float max_distance, int ahead_only, float min_cos,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K8  lane observations (no reference counterpart: the definition is this library's own; float64 model, equal bit for bit:
+ * tests/lane_obs_model.py).  For every exposed agent the K nearest lanelets of its scene's lane table within max_distance of their centre
+ * lines, nearest first; each slot is the foot on the centre line in the agent's frame plus a polyline of P points ahead of the foot that
+ * follows the lane graph while the way is unambiguous.
+ *   agent_xy B x A x 2, agent_sc B x A x 2 [sin, cos], present B x A uint8
+ *   features B x A x K x 8 float32, points B x A x K x P x 2 float32, n_valid B x A x K int32, index B x A x K int32
+ * Arithmetic: binary64 on the lane table, every + - * / sqrt rounded once (the build passes -ffp-contract=off); the poses are read as float32
+ * and widened; every output float is the double result rounded once to binary32.
+ * Observer (b, a) with pose (x, y) and heading (s, c): its row is EMPTY if present[b, a] == 0, the scene has no lane table (scene_map[b]
+ * outside the set), or any of x, y, s, c is a NaN.
+ * Candidates: every lanelet l of the table that is eligible in the sense of tds_spawn_on_lanes_f32 (>= 2 centre-line points, a finite positive
+ * length) and carries no excluded tag (flag bit 0) -- the rule of tds_lane_snap.
+ * Foot: the closest point of the lanelet's 2-D centre line, found as tds_lane_snap finds it.  Segment i from (ax, ay) with (dx, dy) to the next point:
+ *   l2 = dx*dx + dy*dy;  u = l2 > 0 ? ((x - ax)*dx + (y - ay)*dy) / l2 : 0, clamped to [0, 1] (a NaN: 0);
+ *   fx = ax + u*dx - x, fy = ay + u*dy - y;  d2 = fx*fx + fy*fy.
+ * The segments in ascending order, the first d2 below +inf starts, a strictly smaller d2 replaces it: sb is the earliest segment of the smallest
+ * d2.  A lanelet none of whose d2 is below +inf (all NaN or +inf) is no candidate.
+ * In range: d2 <= r2, r2 = (double)max_distance * (double)max_distance.  max_distance = +inf is allowed.
+ * Selection: the K candidates in range with the smallest (bits of (float)d2, l) -- equal binary32 distance is broken by the lower lanelet index;
+ * slot 0 is the nearest.
+ * Slot features, 8 floats (two aligned 16-byte stores), with (tx, ty) = (dx, dy) / sqrt(l2) of segment sb, (0, 0) if l2 == 0, and cum the
+ * lanelet's cumulative 3-D lengths (cum[last] = its length):
+ *   0, 1  fx*c + fy*s,  fy*c - fx*s                  the foot in the observer's frame (the convention of the route lookahead and of K6)
+ *   2, 3  sin_rel = ty*c - tx*s,  cos_rel = tx*c + ty*s   the lane's direction at the foot against the heading (an oncoming lane: cos_rel < 0)
+ *   4     arc = cum[sb] + u*(cum[sb + 1] - cum[sb])  (the expression of tds_lane_snap)
+ *   5     remaining = cum[last] - arc
+ *   6     lateral = tx*(y - ay) - ty*(x - ax)        (left positive, as tds_lane_snap)
+ *   7     distance = sqrt(d2)
+ * Slot points: point j lies at q_j = arc + (double)j * (double)spacing along the lane.  The walk of point j starts on cur = l with base = 0 and
+ * no hops made; len(cur) = cum[last] of cur.  While q_j - base > len(cur): if cur has exactly ONE successor in the lane graph, that successor is
+ * a candidate in the sense above and fewer than TDS_LANE_OBS_MAX_HOPS hops were made, then base += len(cur), cur = the successor, one more
+ * hop; otherwise the point is invalid -- and so are all later ones, the walk of a later point passing through the same states.  A valid point:
+ *   pos = q_j - base;  k = clip(searchsorted(cum, pos, 'right') - 1, 0, n - 2);  w = cum[k + 1] - cum[k];  t = w > 0 ? (pos - cum[k]) / w : 0;
+ *   wx = px_k + t*(px_(k+1) - px_k), wy likewise (the convention of the route points);  ex = wx - x, ey = wy - y;
+ *   the point is (ex*c + ey*s, ey*c - ex*s).
+ * n_valid is the number of valid points: at least 1 in a filled slot (point 0 is the centre-line point at arc); invalid points are (0, 0).  A
+ * fork or a dead end ends the polyline; the branches are slots of their own where they are in range.  A table without a lane graph
+ * (tds_lanes_set_successors) has no successors.
+ * index is the lanelet of the slot in its scene's table, -1 for an empty slot, whose features and points are 0 and whose n_valid is 0.  Every
+ * output is written in full.
+ * 1 <= K <= TDS_LANE_OBS_MAX_K, 1 <= P <= TDS_LANE_OBS_MAX_POINTS, spacing finite and positive, max_distance not negative and not NaN: else
+ * TDS_EINVAL before any launch; a table of more than TDS_LANE_OBS_MAX_LANELETS lanelets (the limit of tds_lane_distances_f64) is TDS_ELIMIT;
+ * a set of several tables needs scene_map; B * A == 0 is a successful no-op.  One launch; nothing is allocated and nothing synchronises;
+ * every loop of the kernel is bounded by the table's sizes, K, P or the hop limit whatever the tensors hold. */
+#define TDS_LANE_OBS_MAX_K 32
+#define TDS_LANE_OBS_MAX_POINTS 32
+#define TDS_LANE_OBS_MAX_HOPS 8
+#define TDS_LANE_OBS_MAX_LANELETS 2048
+int tds_lane_observations_multi(const tds_laneset_t *set, const int32_t *scene_map, const float *agent_xy, const float *agent_sc,
+                                const uint8_t *present, float *features, float *points, int32_t *n_valid, int32_t *index, int64_t B,
+                                int64_t A, int K, int P, float spacing, float max_distance, void *stream);
+
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */

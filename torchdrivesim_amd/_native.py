@@ -187,6 +187,8 @@ tds_lights_step(f64* duration, i32* next_phase, i32* n_phases, u8* colour, i32* 
 tds_lights_reset(i32* n_phases, f64* duration, i32* phase, f64* remaining, u8* mask, i64* scene_ids, int64 B, int64 M, int64 P, uint64 seed, stream stream)
 tds_stop_lines_f32(f32* agent_xy, f32* agent_sc, u8* agent_present, f32* lines, f32* line_sc, u8* mask, i64* state, f32* time_to_change, f32* features, i32* index,
     i32* slot_state, int64 B, int64 A, int64 N, int K, float max_distance, int ahead_only, float min_cos, stream stream)
+tds_lane_observations_multi(handle set, i32* scene_map, f32* agent_xy, f32* agent_sc, u8* present, f32* features, f32* points, i32* n_valid, i32* index, int64 B, int64 A,
+    int K, int P, float spacing, float max_distance, stream stream)
 '''
 
 #: entry points that only libtdship_testing.so exports (include/tdship.h, "testing hooks")
@@ -295,6 +297,8 @@ ROUTE_MAX_GRAPH = 2048                               # TDS_ROUTE_MAX_GRAPH
 NEIGHBORS_MAX_K, NEIGHBORS_MAX_ENTITIES = 32, 1024   # TDS_NEIGHBORS_MAX_K, TDS_NEIGHBORS_MAX_ENTITIES
 LIGHTS_MAX_MACHINES, LIGHTS_MAX_PHASES, LIGHTS_MAX_LIGHTS = 256, 64, 1024      # TDS_LIGHTS_MAX_MACHINES, TDS_LIGHTS_MAX_PHASES, TDS_LIGHTS_MAX_LIGHTS
 LIGHTS_MAX_SKIPS, STOP_LINES_MAX_K = 1024, 32        # TDS_LIGHTS_MAX_SKIPS, TDS_STOP_LINES_MAX_K
+LANE_OBS_MAX_K, LANE_OBS_MAX_POINTS = 32, 32         # TDS_LANE_OBS_MAX_K, TDS_LANE_OBS_MAX_POINTS
+LANE_OBS_MAX_HOPS, LANE_OBS_MAX_LANELETS = 8, 2048   # TDS_LANE_OBS_MAX_HOPS, TDS_LANE_OBS_MAX_LANELETS
 
 
 class TdsError(RuntimeError):

@@ -754,6 +754,51 @@ def stop_lines(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, t
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# K8 lane observations (csrc/lane_obs.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def check_lanes_args(k, n_points, spacing, max_distance):
+    """the argument rules of tds_lane_observations_multi, on the host: raised before anything is computed or launched"""
+    if int(k) != k or int(k) < 1 or int(k) > nat.LANE_OBS_MAX_K:
+        raise ValueError(f'lanes: k must be 1 .. {nat.LANE_OBS_MAX_K} (got {k})')
+    if int(n_points) != n_points or int(n_points) < 1 or int(n_points) > nat.LANE_OBS_MAX_POINTS:
+        raise ValueError(f'lanes: n_points must be 1 .. {nat.LANE_OBS_MAX_POINTS} (got {n_points})')
+    if not 0.0 < float(spacing) < float('inf'):         # (NaN fails the comparison)
+        raise ValueError(f'lanes: spacing must be finite and positive (got {spacing})')
+    if not float(max_distance) >= 0.0:                  # (NaN fails the comparison; +inf is allowed)
+        raise ValueError(f'lanes: max_distance must not be negative or NaN (got {max_distance})')
+
+
+def empty_lane_observations(B, A, k, n_points, device):
+    """the outputs of `lane_observations` with every slot empty, built with torch: what a batch without any lane map gets"""
+    return (torch.zeros((B, A, k, 8), dtype=f32, device=device), torch.zeros((B, A, k, n_points, 2), dtype=f32, device=device),
+            torch.zeros((B, A, k), dtype=i32, device=device), torch.full((B, A, k), -1, dtype=i32, device=device))
+
+
+def lane_observations(lane_set, agent_xy, agent_sc, present, k, n_points, spacing, max_distance):
+    """The k nearest lanelets of every exposed agent (tds_lane_observations_multi, include/tdship.h "K8"): lane_set a LaneTableSet (its
+    scene_map, when there is one, has B entries), agent_xy (B,A,2), agent_sc (B,A,2) [sin, cos], present (B,A) -> features (B,A,k,8) float32,
+    points (B,A,k,n_points,2) float32, n_valid (B,A,k) int32, index (B,A,k) int32.  One launch on the current stream, no allocation besides
+    the outputs, no synchronisation.  No gradient; CPU tensors raise (there is no CPU fallback)."""
+    check_lanes_args(k, n_points, spacing, max_distance)
+    if agent_xy.dim() != 3 or agent_xy.shape[-1] != 2:
+        raise ValueError(f'lanes: agent_xy must be (B, A, 2), got {tuple(agent_xy.shape)}')
+    B, A, K, P = int(agent_xy.shape[0]), int(agent_xy.shape[1]), int(k), int(n_points)
+    if tuple(agent_sc.shape) != (B, A, 2) or tuple(present.shape) != (B, A):
+        raise ValueError(f'lanes: agent_sc must be ({B}, {A}, 2) and present ({B}, {A}), got {tuple(agent_sc.shape)} and {tuple(present.shape)}')
+    agent_xy, agent_sc, present = _c(agent_xy.detach()), _c(agent_sc.detach()), _u8(present)
+    dev = agent_xy.device
+    nat.dev_ptr(agent_xy, f32, 'agent_xy')                     # (a CPU tensor is refused before the lane set is looked at)
+    scene_map = _scene_map(lane_set, B, 'lane_observations')
+    features = torch.empty((B, A, K, 8), dtype=f32, device=dev)
+    points = torch.empty((B, A, K, P, 2), dtype=f32, device=dev)
+    n_valid = torch.empty((B, A, K), dtype=i32, device=dev)
+    index = torch.empty((B, A, K), dtype=i32, device=dev)
+    nat.call('tds_lane_observations_multi', dev, lane_set.handle, scene_map, agent_xy, agent_sc, present, features, points, n_valid, index, B, A, K, P,
+             float(spacing), float(max_distance))
+    return features, points, n_valid, index
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # K3 rasteriser
 # ---------------------------------------------------------------------------------------------------------------
 #: scratch for the binned fast path of K3, one per (device, stream, cameras, resolution): two renders of one shape on different streams

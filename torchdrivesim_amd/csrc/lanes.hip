@@ -290,15 +290,17 @@ TDS_EXPORT int tds_laneset_create(const tds_lanes_t *const *lanes, int n, tds_la
     TDS_CHECK_ARG(lanes && n > 0 && out, "tds_laneset_create: bad arguments");
     std::vector<LaneView> views(n);
     float max_tol = INFINITY;
+    int max_lanelets = 0;
     for (int i = 0; i < n; i++) {
         TDS_CHECK_ARG(lanes[i], "tds_laneset_create: lane table %d is null", i);
         TDS_CHECK_ARG(lanes[i]->device == lanes[0]->device, "tds_laneset_create: lane tables live on different devices");
         views[i] = lanes[i]->view;
         max_tol = std::min(max_tol, lanes[i]->view.max_tol);
+        max_lanelets = std::max(max_lanelets, lanes[i]->view.n);
     }
     tds_laneset *s = new (std::nothrow) tds_laneset();
     if (!s) return TDS_ENOMEM;
-    s->n = n, s->device = lanes[0]->device, s->max_tol = max_tol, s->d_views = nullptr;
+    s->n = n, s->device = lanes[0]->device, s->max_tol = max_tol, s->max_lanelets = max_lanelets, s->d_views = nullptr;
     hipError_t e = hipMalloc((void **)&s->d_views, n * sizeof(LaneView));
     if (e == hipSuccess) e = hipMemcpy(s->d_views, views.data(), n * sizeof(LaneView), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -564,12 +566,7 @@ __global__ __launch_bounds__(256) void lane_snap_kernel(LaneView single, const L
                 double bd = INFINITY;
                 int sb = 0x7fffffff;
                 for (int i = g; i + 1 < r.cl_n; i += GROUP) {
-                    double ax = cl[3 * i], ay = cl[3 * i + 1], dx = cl[3 * i + 3] - ax, dy = cl[3 * i + 4] - ay;
-                    double l2 = dx * dx + dy * dy;
-                    double u = l2 > 0 ? ((x - ax) * dx + (y - ay) * dy) / l2 : 0.0;
-                    u = fmin(fmax(u, 0.0), 1.0);
-                    double fx = ax + u * dx - x, fy = ay + u * dy - y;
-                    double d2 = fx * fx + fy * fy;
+                    const double d2 = tds::segment_foot(cl, i, x, y).d2;
                     if (d2 < bd) bd = d2, sb = i;
                 }
 #pragma unroll
@@ -579,17 +576,13 @@ __global__ __launch_bounds__(256) void lane_snap_kernel(LaneView single, const L
                     if (lex_less(od, oi, bd, sb)) bd = od, sb = oi;
                 }
                 if (sb == 0x7fffffff) continue;                          // every distance was NaN
-                double ax = cl[3 * sb], ay = cl[3 * sb + 1], dx = cl[3 * sb + 3] - ax, dy = cl[3 * sb + 4] - ay;
-                double l2 = dx * dx + dy * dy;
-                double u = l2 > 0 ? ((x - ax) * dx + (y - ay) * dy) / l2 : 0.0;
-                u = fmin(fmax(u, 0.0), 1.0);
-                double len = sqrt(l2);
-                double tx = len > 0 ? dx / len : 0.0, ty = len > 0 ? dy / len : 0.0;
-                double score = cs * tx + sn * ty;
+                const tds::SegmentFoot f = tds::segment_foot(cl, sb, x, y);
+                const tds::Unit2 t2 = tds::segment_unit(f);
+                double score = cs * t2.x + sn * t2.y;
                 if (score > best_score) {                                 // strictly: the lowest index wins ties, and a winner has a score > 0
                     best_score = score, best_lane = l;
-                    best_arc = cum[sb] + u * (cum[sb + 1] - cum[sb]);
-                    best_lat = tx * (y - ay) - ty * (x - ax);
+                    best_arc = tds::foot_arc(f, cum, sb);
+                    best_lat = tds::foot_lateral(f, t2, x, y);
                 }
             }
         }

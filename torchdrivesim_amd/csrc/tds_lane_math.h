@@ -1,6 +1,6 @@
-// The lane-graph arithmetic every lane kernel shares (spawn.hip, follow.hip, route.hip): the random stream, the search on a centre line's
-// cumulative lengths, the point at an arc length.  Nothing of HIP in here: a host compiler takes this file as it is, and
-// tests/lane_math_host.cpp holds these functions to the float64 models on the CPU.
+// The lane-graph arithmetic every lane kernel shares (lanes.hip, spawn.hip, follow.hip, route.hip, lane_obs.hip): the random stream, the search
+// on a centre line's cumulative lengths, the foot of a pose on a segment, the point at an arc length.  Nothing of HIP in here: a host compiler
+// takes this file as it is, and tests/lane_math_host.cpp and tests/lane_foot_host.cpp hold these functions to the float64 models on the CPU.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -49,6 +49,33 @@ TDS_HD inline int segment_of(const double *cum, int n, double s) {
     if (k > n - 2) k = n - 2;
     return k;
 }
+
+// the foot of (x, y) on segment i of a centre line in 2-D, what tds_lane_snap and K8 (lane_obs.hip) rank a lanelet's segments by: u = the
+// foot's parameter clamped to [0, 1] (0 on a segment without length, and for a NaN), (fx, fy) = foot - pose, d2 = its squared length.  (ax, ay) is
+// the segment's first point, (dx, dy) the segment, l2 = dx*dx + dy*dy.  tests/lane_foot_host.cpp holds it to tests/lane_obs_model.py bit for bit.
+struct SegmentFoot { double ax, ay, dx, dy, l2, u, fx, fy, d2; };
+TDS_HD inline SegmentFoot segment_foot(const double *cl, int i, double x, double y) {
+    SegmentFoot f;
+    f.ax = cl[3 * i], f.ay = cl[3 * i + 1], f.dx = cl[3 * i + 3] - f.ax, f.dy = cl[3 * i + 4] - f.ay;
+    f.l2 = f.dx * f.dx + f.dy * f.dy;
+    double u = f.l2 > 0 ? ((x - f.ax) * f.dx + (y - f.ay) * f.dy) / f.l2 : 0.0;
+    f.u = fmin(fmax(u, 0.0), 1.0);
+    f.fx = f.ax + f.u * f.dx - x, f.fy = f.ay + f.u * f.dy - y;
+    f.d2 = f.fx * f.fx + f.fy * f.fy;
+    return f;
+}
+
+// what a foot says of the pose against its lanelet: the segment's unit vector ((0, 0) without length), the foot's arc length on `cum` (the
+// lanelet's own cumulative lengths, cum[i] at the segment's first point), the pose's signed offset from the segment, left positive
+struct Unit2 { double x, y; };
+TDS_HD inline Unit2 segment_unit(const SegmentFoot &f) {
+    const double len = sqrt(f.l2);
+    Unit2 t;
+    t.x = len > 0 ? f.dx / len : 0.0, t.y = len > 0 ? f.dy / len : 0.0;
+    return t;
+}
+TDS_HD inline double foot_arc(const SegmentFoot &f, const double *cum, int i) { return cum[i] + f.u * (cum[i + 1] - cum[i]); }
+TDS_HD inline double foot_lateral(const SegmentFoot &f, Unit2 t, double x, double y) { return t.x * (y - f.ay) - t.y * (x - f.ax); }
 
 // the point at arc length s on segment k of a centre line (lanelet2.py:183-208 as torchdrivesim_amd/lanelet2.py restates it
 // [UNVERIFIED-UPSTREAM]): t = (s - cum[k]) / seg (0 on a segment of length 0), p = c[k] + t (c[k + 1] - c[k]), with (dx, dy) = the segment in 2-D.

@@ -91,6 +91,7 @@ struct tds_laneset {
     tds::LaneView *d_views;
     int n, device;
     float max_tol;
+    int max_lanelets;               // the lanelets of the largest table: what a launch sizes per-table LDS by (lane_obs.hip)
 };
 
 #define TDS_CHECK_SCENE_MAP(what, set, scene_map) \

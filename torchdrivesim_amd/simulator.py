@@ -11,6 +11,7 @@
 
     compute_neighbors  -> K6 (csrc/neighbors.hip), the K nearest entities per agent   reference: -- (get_all_agents_relative, all pairs)
     compute_stop_lines -> K7 (csrc/lights.hip), the K nearest stop lines per agent    reference: --
+    compute_lanes      -> K8 (csrc/lane_obs.hip), the K nearest lanes per agent as polylines  reference: --
     compute_wrong_way  -> lane tables of `lanelet_map` (lanelet2.py), one launch  reference: simulator.py:607-630 (Python triple loop)
 
 Also carried: traffic controls, waypoint goals (state + rendering), observation noise and lane features (plumbing only).  Out of scope
@@ -108,6 +109,29 @@ class StopLines:
     def take(self, per_line: Tensor, fill=0) -> Tensor:
         """Gathers a per-line tensor BxNx... (the control's `state`, `time_to_change`, ...) at `index` -> BxAxKx..., `fill` in the empty slots."""
         return Neighbors.take(self, per_line, fill)
+
+
+@dataclass
+class Lanes:
+    """What `Simulator.compute_lanes` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`), `points` BxAxKxPx2 float32, the centre
+    line ahead of the foot in the agent's frame, `n_valid` BxAxK int32, how many of a slot's points are valid (the others are 0), and `index`
+    BxAxK int32, the lanelet of every slot in its scene's `laneletLayer`, -1 for an empty one (its features and points are all 0)."""
+    features: Tensor
+    points: Tensor
+    n_valid: Tensor
+    index: Tensor
+
+    FEATURES = ('x', 'y', 'sin', 'cos', 'arc', 'remaining', 'lateral', 'distance')
+
+    @property
+    def mask(self) -> Tensor:
+        """BxAxK bool: the slot holds a lane"""
+        return self.index >= 0
+
+    @property
+    def points_mask(self) -> Tensor:
+        """BxAxKxP bool: the point is on the lane (the first `n_valid` of a slot are)"""
+        return torch.arange(self.points.shape[-2], device=self.n_valid.device) < self.n_valid.unsqueeze(-1)
 
 
 def _enlarge(x: Tensor, n: int) -> Tensor:
@@ -273,7 +297,7 @@ class Simulator:
                  waypoint_goals=None, agent_types: Optional[Tensor] = None, agent_type_names: Optional[List[str]] = None,
                  npc_controller: Optional[NPCController] = None, agent_lr: Optional[Tensor] = None, lane_features=None,
                  observation_noise_model=None, action_model_extras: Optional[Dict[str, Any]] = None, route_goals=None):
-        self._lane_set = None                            # device lane tables of `lanelet_map`, made on the first compute_wrong_way
+        self._lane_set = None                            # device lane tables of `lanelet_map`, made on the first compute_wrong_way / compute_lanes
         self.road_mesh = road_mesh
         self.lanelet_map = lanelet_map
         self.recenter_offset = recenter_offset
@@ -1337,6 +1361,47 @@ class Simulator:
                                   control.state, getattr(control, 'time_to_change', None), k, max_distance, ahead_only=ahead_only, min_cos=min_cos)
         return StopLines(*out)
 
+    # ------------------------------------------------------------------------------------------------- lane observations
+    def compute_lanes(self, k: int = 6, n_points: int = 8, spacing: float = 4.0, max_distance: float = 30.0) -> Lanes:
+        """The `k` nearest lanelets of `lanelet_map` of every exposed agent, by the distance to their centre lines, within `max_distance` metres
+        (+inf: no limit), nearest first, equal float32 distances by the lower lanelet index.  The lanelets are those `snap_to_lanes` looks at:
+        long enough to drive on and without an excluded tag.
+
+        features  BxAxkx8    per slot `Lanes.FEATURES`: x, y of the foot -- the closest point of the centre line -- in the agent's frame (x ahead, y
+                             to the left), [sin, cos] of the lane's direction there relative to the agent's heading (an oncoming lane has cos < 0),
+                             the foot's arc length on the lanelet, the length that remains after it, the agent's lateral offset from the line
+                             (left positive, as `snap_to_lanes`) and the distance; all 0 in an empty slot;
+        points    BxAxkxPx2  the centre line ahead of the foot in the agent's frame, point j `j * spacing` metres after it; the line goes on into
+                             the next lanelet while there is exactly one successor (at most 8 times) and ends at a fork or a dead end -- the
+                             branches are slots of their own where they are in range;
+        n_valid   BxAxk      int32: the points of the slot that are on the lane (`Lanes.points_mask`), the others are 0; at least 1 in a filled slot;
+        index     BxAxk      int32: the lanelet of the slot in its scene's `laneletLayer`, -1 for an empty slot (`Lanes.mask`).
+
+        Rows of agents that are not present, whose pose is NaN, or whose scene has no lanelet map (an entry `None`) are empty; without any lanelet
+        map everything is empty and nothing is launched.  1 <= k <= 32, 1 <= n_points <= 32, at most 2048 lanelets per map.  One HIP kernel in
+        binary64 (csrc/lane_obs.hip; the definition is in include/tdship.h "K8", tests/lane_obs_model.py equals it bit for bit).  No gradient.
+        Runs on the current stream and allocates its outputs only; the device lane tables are those of `compute_wrong_way`, built by the first
+        call of either -- which must happen outside a stream capture; after that the call can be captured into a graph."""
+        _ops.check_lanes_args(k, n_points, spacing, max_distance)
+        state = self.get_state()
+        if not state.is_cuda:
+            raise RuntimeError(f'compute_lanes runs on an MI355X; the simulator is on {state.device} (no CPU fallback)')
+        B, A = state.shape[0], self.agent_count
+        if A == 0 or self.lanelet_map is None or all(m is None for m in self.lanelet_map):
+            return Lanes(*_ops.empty_lane_observations(B, A, int(k), int(n_points), state.device))
+        with torch.no_grad():
+            agent = state.detach()
+            out = _ops.lane_observations(self._lane_tables(state.device), agent[..., :2], self._heading_sc().detach()[:, :A], self.get_present_mask(),
+                                         k, n_points, spacing, max_distance)
+        return Lanes(*out)
+
+    def _lane_tables(self, device) -> _ops.LaneTableSet:
+        """the device lane tables of `lanelet_map`, made on the first call and kept (allocations and copies: outside any stream capture)"""
+        tol = self.cfg.lanelet_inclusion_tolerance
+        if self._lane_set is None or self._lane_set[1] < tol or self._lane_set[0].device != device:
+            self._lane_set = (lane_table_set(self.lanelet_map, device, tol), tol)
+        return self._lane_set[0]
+
     def compute_wrong_way(self) -> Tensor:
         """Wrong-way metric per agent, -cos of the angle between the agent and the lane it is on where that angle exceeds
         `cfg.wrong_way_angle_threshold` (simulator.py:607-630 -> infractions.lanelet_orientation_loss), times the present mask.
@@ -1348,10 +1413,8 @@ class Simulator:
         if self.lanelet_map is None or all(m is None for m in self.lanelet_map):
             return torch.zeros(state.shape[0], state.shape[1], device=state.device)
         tol = self.cfg.lanelet_inclusion_tolerance
-        if self._lane_set is None or self._lane_set[1] < tol or self._lane_set[0].device != state.device:
-            self._lane_set = (lane_table_set(self.lanelet_map, state.device, tol), tol)
         assert self.cfg.wrong_way_angle_threshold >= np.pi / 2, 'direction_angle_threshold smaller than pi / 2 will produce false positives'
-        return _ops.wrong_way(self._lane_set[0], state, self.recenter_offset, self.get_present_mask(), self.cfg.wrong_way_angle_threshold, tol)
+        return _ops.wrong_way(self._lane_tables(state.device), state, self.recenter_offset, self.get_present_mask(), self.cfg.wrong_way_angle_threshold, tol)
 
     def compute_traffic_lights_violations(self) -> Tensor:
         """BxA: the agent is (mostly) past the stop line of a red light (simulator.py:1046-1062)."""
