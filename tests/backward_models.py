@@ -1,6 +1,6 @@
 """
 The yardsticks of the hand-derived backward kernels (csrc/backward.hip: offroad_bwd_kernel, discs_pair_bwd under both collision backward
-kernels; csrc/kinematic.hip: simple_step_bwd_kernel, unicycle_step_bwd_kernel): plain torch restatements of the DEFINITIONS (oracle/tds_oracle.c
+kernels; csrc/kinematic.hip: bicycle_step_bwd_kernel, simple_step_bwd_kernel, unicycle_step_bwd_kernel): plain torch restatements of the DEFINITIONS (oracle/tds_oracle.c
 R3d / R4, the kernels' comments), differentiated by torch autograd on the CPU.  Brute force over all faces and all pairs -- no grid, no lists,
 no hierarchy, no hand-written derivative, so they cannot share a bug with the kernels'.  Every function takes a `dtype`: float64 is the
 reference, float32 the yardstick (what ANY float32 evaluation of the same formulas may differ from float64 by; tests/test_backward_models.py
@@ -322,3 +322,86 @@ def unicycle_step_model(state, action, dt=0.1, max_acc=5.0, max_yaw_rate=1.0):
     x, y, psi, v = state.unbind(-1)
     v = v + action[..., 0] * max_acc * dt
     return torch.stack([x + v * torch.cos(psi) * dt, y + v * torch.sin(psi) * dt, psi + action[..., 1] * max_yaw_rate * dt, v], -1)
+
+
+def step_forward_rel(state, out, ref_out):
+    """The forward bar of the K1 tests (k1_check of tests/test_gpu_backward_float64.py explains it): the largest |out - ref_out| over
+    max(|ref_out|, 1e-3, 0.05 x the row's largest operand), the operands being the old coordinates and the increments.  numpy float64 arrays."""
+    operand = np.maximum(np.abs(state), np.abs(ref_out - state)).max(-1, keepdims=True)
+    return float(np.max(np.abs(out - ref_out) / np.maximum(np.maximum(np.abs(ref_out), 1e-3), 0.05 * operand)))
+
+
+def bicycle_step_model(state, action, lr, dt=0.1, max_acc=5.0, max_steer=math.pi / 2, left_handed=False, no_reversing=False):
+    """KinematicBicycle.step / BicycleNoReversing.step as the reference writes them (kinematic.py:462-477, :513-523), in the dtype of the inputs:
+    state (..., 4) [x, y, psi, v], action (..., 2) [acceleration, steering] normalised, lr (...).  The new speed drives the position along
+    psi + beta and the heading through sin(beta) / lr; no_reversing replaces an acceleration that would make the speed negative by the one that
+    stops the agent, -v / dt (the reference normalises and denormalises it on the way, and so does this)."""
+    x, y, psi, v = state.unbind(-1)
+    a, beta = action[..., 0] * max_acc, action[..., 1] * max_steer
+    if no_reversing:
+        a = torch.where(v + a * dt < 0, -v / dt, a)
+        a, beta = (a / max_acc) * max_acc, (beta / max_steer) * max_steer
+    if left_handed:
+        beta = -beta
+    v = v + a * dt
+    return torch.stack([x + v * torch.cos(psi + beta) * dt, y + v * torch.sin(psi + beta) * dt, psi + (v / lr) * torch.sin(beta) * dt, v], -1)
+
+
+def bicycle_clamp(state, action, dt=0.1, max_acc=5.0, **_):
+    """-> (clamped, borderline), both (...,) bool, from float64: the rows whose acceleration BicycleNoReversing replaces (v + a dt < 0), and
+    those within 1e-4 m/s of that switch -- a float32 evaluation may take either side there, and the two sides' gradients differ"""
+    s, a = _t(state, F64), _t(action, F64)
+    new = s[..., 3] + a[..., 0] * max_acc * dt
+    return new < 0, new.abs() < 1e-4
+
+
+def fit_action_model(future_xy, state, dt=0.1, max_acc=5.0, max_steer=math.pi / 2, left_handed=False):
+    """KinematicBicycle.fit_action (kinematic.py:479-506): the normalised bicycle action that takes `state` (..., 4) to the position future_xy
+    (..., 2) in one step of dt.  The steering is taken modulo 2 pi, and an agent that would have to turn by more than a right angle reverses."""
+    x, y, psi, v = state.unbind(-1)
+    vx, vy = (future_xy[..., 0] - x) / dt, (future_xy[..., 1] - y) / dt
+    speed = torch.sqrt(vx ** 2 + vy ** 2)
+    beta = torch.atan2(vy, vx) - psi * torch.sign(torch.abs(speed))
+    beta = torch.remainder(beta + math.pi, 2 * math.pi) - math.pi
+    reversing = torch.sign(torch.cos(beta)) == -1
+    speed = speed * torch.where(reversing, -1.0, 1.0).to(speed.dtype)
+    beta = torch.where(reversing, beta - math.pi * torch.sign(beta), beta)
+    if left_handed:
+        beta = -beta
+    return torch.stack([((speed - v) / dt) / max_acc, beta / max_steer], -1)
+
+
+def displacement_step_model(state, action, lr, max_dx=20.0, dt=0.1, oriented=False):
+    """BicycleByDisplacement / BicycleByOrientedDisplacement.step (kinematic.py:526-587): the action (dx, dy) * max_dx (oriented: in the agent's own
+    frame) names the position xy + (dx, dy) dt, fit_action_model turns it into a bicycle action and bicycle_step_model takes the step"""
+    d = action * max_dx
+    dx, dy = d[..., 0], d[..., 1]
+    if oriented:
+        c, s = torch.cos(state[..., 2]), torch.sin(state[..., 2])
+        dx, dy = c * dx - s * dy, s * dx + c * dy
+    target = torch.stack([state[..., 0] + dx * dt, state[..., 1] + dy * dt], -1)
+    return bicycle_step_model(state, fit_action_model(target, state, dt=dt), lr, dt=dt)
+
+
+#: the bicycle cases of the K1 tests: name -> keywords of _ops.bicycle_step and of bicycle_step_model alike
+K1_BICYCLE_CASES = {
+    'bicycle': dict(),
+    'bicycle_lh': dict(left_handed=True),
+    'bicycle_norev': dict(no_reversing=True),
+    'bicycle_lh_norev_dt': dict(dt=0.25, max_acc=3.0, max_steer=0.9, left_handed=True, no_reversing=True),
+}
+K1_SIZES, K1_STRIDED = (1, 255, 256, 257, 1000), (300, 77)                # agent counts of the parametrised test; (n, seed) of the strided one
+
+
+def k1_seed(n_action, n):
+    return 1000 * n_action + n
+
+
+def k1_inputs(n, n_action, seed, with_lr=False):
+    """state as in test_k1_backward_matches_torch_autograd: x, y, psi in [-3, 3), v in [-1.2, 2.8); action in [-1, 1); the incoming gradient in
+    [0, 1); lr in [1, 2), drawn last so that the other three do not depend on it.  With the speed on both sides of zero and |a dt| up to 0.5
+    (0.75 in the dt case) about 30 % of the rows of a no-reversing case clamp."""
+    gen = torch.Generator().manual_seed(seed)
+    state = torch.cat([(torch.rand(n, 3, generator=gen) - 0.5) * 6, (torch.rand(n, 1, generator=gen) - 0.3) * 4], -1)
+    action, wgt = (torch.rand(n, n_action, generator=gen) - 0.5) * 2, torch.rand(n, 4, generator=gen)
+    return (state, action, wgt, 1 + torch.rand(n, generator=gen)) if with_lr else (state, action, wgt)

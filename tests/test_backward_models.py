@@ -5,7 +5,10 @@ cap; and the table the GPU tolerance comes from -- the same models in float32 ag
 Printed here (largest |float32 model - float64 model| on the non-borderline rows, position / size / [sin, cos] gradient, beside the largest entry of
 each): near the road 2.2e-5 / 1.1e-5 / 6.9e-5 of 41 / 8.8 / 47; around the edge of the lists' grid 0.023 / 0.010 / 0.054 of 704 / 122 / 1 135; 50 - 300 m
 beyond the map 0.13 / 0.063 / 0.26 of 3 450 / 109 / 528 (short edges: the clamp term 2 (r . e) e / |e|^2 loses what r . e cancels); discs 4.1e-6 .. 2.8e-5 of
-3.5 .. 21."""
+3.5 .. 21.
+
+The bicycle step's model (bicycle_step_model, and fit_action_model for the displacement-driven bicycles) is anchored here too: to the reference's recorded
+outputs (G1, G1b), to the oracle on the very inputs of the K1 GPU tests, and its no-reversing inputs are shown to use both branches."""
 import functools
 
 import numpy as np
@@ -125,6 +128,106 @@ def test_step_models_against_hand_values():
     s, a = torch.from_numpy(g['state']).to(bm.F64), torch.from_numpy(g['action4']).to(bm.F64)
     assert rel(bm.simple_step_model(s, a).numpy(), g['out_simple']) <= 1e-5
     assert rel(bm.simple_step_model(s, a, oriented=True).numpy(), g['out_oriented']) <= 1e-5
+
+
+def rel_golden(x, y):
+    """the bar tests/test_oracle_golden.py holds the oracle to"""
+    return np.max(np.abs(x - y) / np.maximum(np.abs(y), 1e-3))
+
+
+def test_bicycle_model_reproduces_the_reference_outputs():
+    """G1: KinematicBicycle.step (plain, left-handed, dt = 0.25, two steps) and BicycleNoReversing.step as the reference computed them"""
+    g = load_golden('g1_kinematic.npz')
+    s, a, lr = (torch.from_numpy(g[k]).to(bm.F64) for k in ('state', 'action', 'lr'))
+    for kw, key in ((dict(), 'out_bicycle'), (dict(left_handed=True), 'out_bicycle_lh'), (dict(dt=0.25), 'out_bicycle_dt'), (dict(no_reversing=True), 'out_norev')):
+        assert rel_golden(bm.bicycle_step_model(s, a, lr, **kw).numpy(), g[key]) <= 1e-6, key
+    two = bm.bicycle_step_model(bm.bicycle_step_model(s, a, lr), a.flip(0), lr)
+    assert rel_golden(two.numpy(), g['out_bicycle_2steps']) <= 1e-6
+    assert not np.array_equal(g['out_norev'], g['out_bicycle']), 'the fixture has rows that clamp'
+
+
+def k1_bicycle_inputs():
+    """(case, n, state, action, wgt, lr) of every bicycle case the GPU tests run: the parametrised agent counts and the strided one"""
+    for name in bm.K1_BICYCLE_CASES:
+        for n, seed in [(n, bm.k1_seed(2, n)) for n in bm.K1_SIZES] + [bm.K1_STRIDED]:
+            yield (name, n) + bm.k1_inputs(n, 2, seed, with_lr=True)
+
+
+def test_bicycle_model_equals_the_oracle_on_the_gpu_tests_inputs(oracle):
+    """The model in the dtype of its inputs -- the float32 tensors of the K1 GPU tests, every case, agent count and the strided set -- against the float32
+    restatement the forward kernel is pinned to, at the golden bar: 1e-6 of max(|value|, 1e-3).  Both are then float32 evaluations of the reference's
+    expressions in the reference's order, clamped rows included, and differ in 1 - 26 of up to 4 000 coordinates by an ulp of sin / cos (measured: at most
+    6.6e-7).  (Cast to float64 first the model cannot meet this bar, and no evaluation could: within 3 m of the origin many new coordinates are small
+    differences of larger numbers, and the ORACLE's float32 rounding is 1.6e-5 .. 2.4e-5 of such a result, 1.2e-4 at a clamped row, where float32 leaves
+    1.2e-7 and float64 0.  The test below measures that comparison in what float32 can keep; G1 holds the float64 model at this bar.)"""
+    worst = 0.0
+    for name, n, state, action, _, lr in k1_bicycle_inputs():
+        kw = bm.K1_BICYCLE_CASES[name]
+        assert state.dtype == action.dtype == lr.dtype == bm.F32
+        want = oracle.bicycle_step(state.numpy(), action.numpy(), lr.numpy(), **kw)
+        got = bm.bicycle_step_model(state, action, lr, **kw)
+        assert got.dtype == bm.F32
+        worst = max(worst, rel_golden(got.numpy(), want))
+    print(f'bicycle model (float32, as its inputs) against the oracle on the K1 inputs: largest relative difference {worst:.3g}')
+    assert worst <= 1e-6
+
+
+def test_bicycle_model_equals_the_oracle_to_the_rounding_of_its_operands(oracle):
+    """The FLOAT64 model against the oracle, the error measured in what float32 can keep: every new coordinate is old + increment, the increment a product of
+    three or four rounded factors, so the oracle's result is within 4 float32 epsilons (2^-23) of the row's largest operand -- |old| or |increment| --
+    of the exact value: half an epsilon for each of the sum, the products and sin / cos, with a factor two to spare.  A wrong term or sign in the
+    model is 1e5 times that."""
+    worst = 0.0
+    for name, n, state, action, _, lr in k1_bicycle_inputs():
+        kw = bm.K1_BICYCLE_CASES[name]
+        want = oracle.bicycle_step(state.numpy(), action.numpy(), lr.numpy(), **kw)
+        s = state.to(bm.F64)
+        got = bm.bicycle_step_model(s, action.to(bm.F64), lr.to(bm.F64), **kw).numpy()
+        operand = np.maximum(np.abs(s.numpy()), np.abs(got - s.numpy())).max(-1, keepdims=True)
+        worst = max(worst, float(np.max(np.abs(want - got) / operand)) / 2.0 ** -23)
+    print(f'bicycle model against the oracle on the K1 inputs: largest difference {worst:.3g} float32 epsilons of the row\'s largest operand')
+    assert worst <= 4.0
+
+
+def test_bicycle_no_reversing_inputs_use_both_branches_and_few_are_borderline():
+    """from the float64 model alone, on the seeds of the GPU tests: 20 - 80 % of the rows clamp at every n >= 255, at most 1 % are within 1e-4 m/s of
+    the switch; at a clamped row the model's gradient with respect to v and to the acceleration is zero (to 1e-12: (-v / dt) dt + v)"""
+    seen = 0
+    for name, n, state, action, wgt, lr in k1_bicycle_inputs():
+        kw = bm.K1_BICYCLE_CASES[name]
+        if not kw.get('no_reversing'):
+            continue
+        clamped, border = bm.bicycle_clamp(state, action, **kw)
+        print(f'{name}, {n} agents: {int(clamped.sum())} rows clamp, {int(border.sum())} borderline')
+        assert int(border.sum()) <= 0.01 * n
+        if n >= 255:
+            assert 0.2 * n <= int(clamped.sum()) <= 0.8 * n
+        s, a, l = (t.to(bm.F64).requires_grad_(True) for t in (state, action, lr))
+        (bm.bicycle_step_model(s, a, l, **kw) * wgt.to(bm.F64)).sum().backward()
+        if bool(clamped.any()):
+            assert float(s.grad[clamped][:, 3].abs().max()) <= 1e-12 and float(a.grad[clamped][:, 0].abs().max()) <= 1e-12
+        free = ~clamped
+        assert bool((s.grad[free][:, 3] != 0).all()) and bool((a.grad[free][:, 0] != 0).all())
+        seen += int(clamped.sum())
+    assert seen > 1000
+
+
+def test_displacement_model_reproduces_the_reference_outputs():
+    """G1b: fit_action_model then bicycle_step_model in float64 against BicycleByDisplacement / BicycleByOrientedDisplacement of the reference, and
+    fit_action_model against the reference's fitted actions (G1), at the bars of tests/test_oracle_golden.py"""
+    g = load_golden('g1b_bicycle_displacement.npz')
+    s, a, lr = (torch.from_numpy(g[k]).to(bm.F64) for k in ('state', 'action', 'lr'))
+    # the reference names the target x + dx dt in float32, at up to 290 m: half an ulp of x (3e-5 m) in each coordinate is 0.71 ulp / dt in the
+    # fitted speed and, through the fitted steering (the arc v sin(beta) dt / lr, lr >= 1), less than one ulp in the new heading
+    ulp_x = float(np.spacing(np.float32(np.abs(g['state'][..., :2]).max())))
+    for name, kw in (('disp', {}), ('disp_max5', dict(max_dx=5.0, dt=0.2)), ('oriented', dict(oriented=True))):
+        got, want = bm.displacement_step_model(s, a, lr, **kw).numpy(), g[f'out_{name}']
+        assert rel_golden(got[..., :2], want[..., :2]) <= 1e-6, name
+        assert np.abs(got[..., 3] - want[..., 3]).max() <= ulp_x / kw.get('dt', 0.1) and np.abs(got[..., 2] - want[..., 2]).max() <= ulp_x, name
+    g = load_golden('g1_kinematic.npz')
+    s, f = torch.from_numpy(g['state']).to(bm.F64), torch.from_numpy(g['future']).to(bm.F64)
+    assert np.abs(bm.fit_action_model(f[..., :2], s).numpy() - g['fit_bicycle']).max() <= 1e-5
+    assert np.abs(bm.fit_action_model(f[..., :2], s, left_handed=True).numpy() - g['fit_bicycle_lh']).max() <= 1e-5
 
 
 # ------------------------------------------------------------------------------------------------------------------ caps and yardsticks

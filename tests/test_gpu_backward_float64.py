@@ -5,7 +5,7 @@ reference's own autograd and to the oracle in tests/test_backward_models.py).
                nearest-face searches (lists, hierarchy, grid rings), both entry points (one map, a map set), absent rows and rows without
                an incoming gradient, thresholds 0.5 / 0 / 25, agent counts that leave a wavefront half full
     discs      discs_pair_bwd under collision_scene_bwd_kernel (one chunk, several chunks, NPCs) and collision_bwd_kernel (rows)
-    K1         simple_step (plain, oriented), unicycle_step: forward and backward
+    K1         simple_step (plain, oriented), unicycle_step, bicycle_step (plain, left-handed, no reversing; lr's gradient too): forward and backward
 
 The bar, off-road and discs: on the rows the float64 model does not call borderline,
     |kernel - float64 model| <= 4 x the largest |float32 model - float64 model| on the same input set and tensor
@@ -245,39 +245,60 @@ K1_CASES = {
     'unicycle': ('unicycle_step', 2, dict()),
     'unicycle_limits_dt': ('unicycle_step', 2, dict(dt=0.25, max_acc=3.0, max_yaw_rate=0.7)),
 }
+K1_CASES.update({name: ('bicycle_step', 2, kw) for name, kw in bm.K1_BICYCLE_CASES.items()})        # these carry lr, and its gradient
 
 
-def k1_inputs(n, n_action, seed):
-    """state as in test_k1_backward_matches_torch_autograd"""
-    gen = torch.Generator().manual_seed(seed)
-    state = torch.cat([(torch.rand(n, 3, generator=gen) - 0.5) * 6, (torch.rand(n, 1, generator=gen) - 0.3) * 4], -1)
-    return state, (torch.rand(n, n_action, generator=gen) - 0.5) * 2, torch.rand(n, 4, generator=gen)
+def has_lr(name):
+    return K1_CASES[name][0] == 'bicycle_step'
 
 
-def k1_model(name, state, action, wgt):
+def k1_inputs(n, n_action, seed, with_lr=False):
+    """state as in test_k1_backward_matches_torch_autograd; with_lr: lr in [1, 2) as a fourth tensor"""
+    return bm.k1_inputs(n, n_action, seed, with_lr)
+
+
+def k1_model(name, state, action, wgt, lr=None):
+    """-> (new state, gradient of the state, of the action[, of lr]) of the float64 model"""
     fn, _, kw = K1_CASES[name]
-    s, a = state.to(torch.float64).requires_grad_(True), action.to(torch.float64).requires_grad_(True)
-    out = getattr(bm, fn + '_model')(s, a, **kw)
+    leaves = [t.detach().to(torch.float64).requires_grad_(True) for t in (state, action) + (() if lr is None else (lr,))]
+    out = getattr(bm, fn + '_model')(*leaves, **kw)
     (out * wgt.to(torch.float64)).sum().backward()
-    return out.detach(), s.grad, a.grad
+    return (out.detach(),) + tuple(t.grad for t in leaves)
 
 
-def k1_check(label, state, out, gs, ga, ref):
-    """The project's bars.  Gradients: rtol 2e-4, atol 2e-5 (test_k1_backward_matches_torch_autograd).  Forward: |kernel - model| <= 1e-5 of
+def k1_check(label, state, out, gs, ga, ref, glr=None, borderline=None):
+    """The project's bars.  Gradients: rtol 2e-4, atol 2e-5 (test_k1_backward_matches_torch_autograd), lr's too.  Forward: |kernel - model| <= 1e-5 of
     max(|model|, 1e-3) as in test_k1_bicycle_matches_oracle_and_golden -- where the new state is not a cancellation.  These states are a few
     metres from the origin and many of the 4 000 new coordinates are differences of two larger numbers; no float32 evaluation keeps 1e-5 of such a
     result (the float32 MODEL misses it by up to 1.2e-4 on these inputs), so the denominator is at least 0.05 x the row's largest operand: 1e-5 of
-    it are 8 float32 epsilons of that operand (the float32 model stays within 4.4e-6 of this bar over 100 draws)."""
-    ref_out, ref_gs, ref_ga = (t.numpy() for t in ref)
+    it are 8 float32 epsilons of that operand (the float32 model stays within 4.4e-6 of this bar over 100 draws).
+    borderline: rows at which the model's gradient is about to jump (bm.bicycle_clamp) -- left out of the gradient comparison, finite all the same;
+    the forward is continuous there and is compared on every row."""
+    ref_out, ref_gs, ref_ga = (t.numpy() for t in ref[:3])
     s = state.to(torch.float64).numpy()
-    operand = np.maximum(np.abs(s), np.abs(ref_out - s)).max(-1, keepdims=True)
-    rel = np.max(np.abs(f64(out).numpy() - ref_out) / np.maximum(np.maximum(np.abs(ref_out), 1e-3), 0.05 * operand))
-    dgs, dga = np.abs(f64(gs).numpy() - ref_gs).max(), np.abs(f64(ga).numpy() - ref_ga).max()
-    print(f'{label}: forward rel {rel:.3g} (bar 1e-5), gradient of the state {dgs:.3g} of {np.abs(ref_gs).max():.3g}, of the action {dga:.3g} of '
-          f'{np.abs(ref_ga).max():.3g} (bar rtol 2e-4, atol 2e-5)')
+    rel = bm.step_forward_rel(s, f64(out).numpy(), ref_out)
+    ok = np.ones(len(s), bool) if borderline is None else ~borderline.numpy()
+    pairs = [('state', f64(gs).numpy(), ref_gs), ('action', f64(ga).numpy(), ref_ga)] + ([] if glr is None else [('lr', f64(glr).numpy(), ref[3].numpy())])
+    print(f'{label}: forward rel {rel:.3g} (bar 1e-5), gradient ' + ', '.join(f'of the {k} {np.abs(got - want)[ok].max():.3g} of {np.abs(want).max():.3g}'
+                                                                            for k, got, want in pairs) +
+          f' (bar rtol 2e-4, atol 2e-5), borderline rows {int((~ok).sum())} of {len(ok)}')
     assert rel <= 1e-5
-    np.testing.assert_allclose(f64(gs).numpy(), ref_gs, rtol=2e-4, atol=2e-5)
-    np.testing.assert_allclose(f64(ga).numpy(), ref_ga, rtol=2e-4, atol=2e-5)
+    for k, got, want in pairs:
+        assert got.shape == want.shape and np.isfinite(got).all(), k
+        np.testing.assert_allclose(got[ok], want[ok], rtol=2e-4, atol=2e-5, err_msg=k)
+
+
+def k1_check_clamp(name, state, action, gs, ga, n):
+    """a no-reversing case: both branches at work (20 - 80 % of the rows clamp where n >= 255), and a clamped row passes nothing to its speed or its
+    acceleration -- exactly zero.  -> the borderline rows, from the float64 model alone"""
+    clamped, borderline = bm.bicycle_clamp(state, action, **K1_CASES[name][2])
+    if n >= 255:
+        assert 0.2 * n <= int(clamped.sum()) <= 0.8 * n
+    stop = (clamped & ~borderline).to(gs.device)
+    assert bool((gs[stop][:, 3] == 0).all()) and bool((ga[stop][:, 0] == 0).all())
+    go = (~clamped & ~borderline).to(gs.device)
+    assert bool((gs[go][:, 3] != 0).all()) and bool((ga[go][:, 0] != 0).all())
+    return borderline
 
 
 @pytest.mark.parametrize('n', [1, 255, 256, 257, 1000])
@@ -285,25 +306,36 @@ def k1_check(label, state, out, gs, ga, ref):
 def test_k1_step_forward_and_backward(ops, name, n):
     """agent counts around the workgroup size (KBLOCK = 256)"""
     fn, n_action, kw = K1_CASES[name]
-    state, action, wgt = k1_inputs(n, n_action, 1000 * n_action + n)
-    s, a = state.to(DEV).requires_grad_(True), action.to(DEV).requires_grad_(True)
-    out = getattr(ops, fn)(s, a, **kw)
+    state, action, wgt, *lr = k1_inputs(n, n_action, bm.k1_seed(n_action, n), has_lr(name))
+    s, a, *l = (t.to(DEV).requires_grad_(True) for t in [state, action] + lr)
+    out = getattr(ops, fn)(s, a, *l, **kw)
     (out * wgt.to(DEV)).sum().backward()
-    k1_check(f'{name}, {n} agents', state, out, s.grad, a.grad, k1_model(name, state, action, wgt))
-    assert float(s.grad.abs().min()) > 0 and float(a.grad.abs().max()) > 0
+    borderline = k1_check_clamp(name, state, action, s.grad, a.grad, n) if kw.get('no_reversing') else None
+    k1_check(f'{name}, {n} agents', state, out, s.grad, a.grad, k1_model(name, state, action, wgt, *lr), *(t.grad for t in l), borderline=borderline)
+    if kw.get('no_reversing'):
+        assert float(s.grad[:, :3].abs().min()) > 0 and float(a.grad.abs().max()) > 0
+    else:
+        assert float(s.grad.abs().min()) > 0 and float(a.grad.abs().max()) > 0
+    if l:
+        assert float(l[0].grad.abs().max()) > 0
 
 
-@pytest.mark.parametrize('name', ['oriented_norm_dt', 'unicycle_limits_dt'])
+@pytest.mark.parametrize('name', ['oriented_norm_dt', 'unicycle_limits_dt'] + list(bm.K1_BICYCLE_CASES))
 def test_k1_step_with_strided_views(ops, name):
-    """state and action as transposed views, the incoming gradient as every other row of a larger tensor"""
+    """state and action as transposed views, the incoming gradient as every other row of a larger tensor, lr as a column of a wider one"""
     fn, n_action, kw = K1_CASES[name]
-    n = 300
-    state, action, wgt = k1_inputs(n, n_action, 77)
+    n, seed = bm.K1_STRIDED
+    state, action, wgt, *lr = k1_inputs(n, n_action, seed, has_lr(name))
     s, a = state.t().contiguous().to(DEV).requires_grad_(True), action.t().contiguous().to(DEV).requires_grad_(True)
+    l2 = [torch.stack([t, -t], -1).to(DEV).requires_grad_(True) for t in lr]                   # (n, 2): lr and a column that is not used
+    lview = [t[:, 0] for t in l2]
     gout = torch.zeros(2 * n, 4)
     gout[::2] = wgt
     gview = gout.to(DEV)[::2]
-    assert not s.t().is_contiguous() and not a.t().is_contiguous() and not gview.is_contiguous()
-    out = getattr(ops, fn)(s.t(), a.t(), **kw)
+    assert not s.t().is_contiguous() and not a.t().is_contiguous() and not gview.is_contiguous() and not any(t.is_contiguous() for t in lview)
+    out = getattr(ops, fn)(s.t(), a.t(), *lview, **kw)
     out.backward(gview)
-    k1_check(f'{name}, strided views', state, out, s.grad.t(), a.grad.t(), k1_model(name, state, action, wgt))
+    borderline = k1_check_clamp(name, state, action, s.grad.t(), a.grad.t(), n) if kw.get('no_reversing') else None
+    k1_check(f'{name}, strided views', state, out, s.grad.t(), a.grad.t(), k1_model(name, state, action, wgt, *lr), *(t.grad[:, 0] for t in l2),
+             borderline=borderline)
+    assert all(bool((t.grad[:, 1] == 0).all()) for t in l2)

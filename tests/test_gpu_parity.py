@@ -123,6 +123,30 @@ def test_k1_bicycle_by_displacement_matches_golden(oracle, name, cls, kw):
     # (entry [0, 0] has zero displacement: d sqrt(vx^2 + vy^2) is undefined there, NaN in the reference's autograd as well)
     grad = act.grad.flatten(0, 1)[1:]
     assert torch.isfinite(grad).all() and grad.abs().sum() > 0
+    # ... and they are the gradients of the definition: float64 autograd of fit_action then the bicycle step (tests/backward_models.py), under the
+    # rule of tests/test_gpu_backward_float64.py -- |device - float64 model| <= 4 x the largest |float32 model - float64 model| on the same rows
+    import backward_models as bm
+    wgt = torch.rand(g['state'].shape, generator=torch.Generator().manual_seed(5))
+    mkw = dict(max_dx=float(kw.get('max_dx', 20)), dt=kw.get('dt', 0.1), oriented=cls.endswith('OrientedDisplacement'))
+
+    def model_grads(dtype):
+        s, a = (torch.from_numpy(g[k]).to(dtype).requires_grad_(True) for k in ('state', 'action'))
+        (bm.displacement_step_model(s, a, torch.from_numpy(g['lr']).to(dtype), **mkw) * wgt.to(dtype)).sum().backward()
+        return [t.grad.to(torch.float64).flatten(0, 1)[1:] for t in (s, a)]
+
+    st, act = dev(g['state']).requires_grad_(True), dev(g['action']).requires_grad_(True)
+    m.set_state(st)
+    m.step(act)
+    (m.get_state() * wgt.to(DEV)).sum().backward()
+    g64, g32 = model_grads(torch.float64), model_grads(torch.float32)
+    figures = []
+    for label, got, want, rough in zip(('state', 'action'), (st.grad, act.grad), g64, g32):
+        got = got.detach().cpu().to(torch.float64).flatten(0, 1)[1:]
+        figures.append((float((got - want).abs().max()), float((rough - want).abs().max())))
+        print(f'{name} gradient of the {label}: device against float64 {figures[-1][0]:.3g}, float32 model against float64 {figures[-1][1]:.3g} '
+              f'(bound {4 * figures[-1][1]:.3g}), largest entry {float(want.abs().max()):.3g}')
+        assert torch.isfinite(got).all() and float(want.abs().max()) > 0.5
+    assert all(diff <= 4.0 * yard for diff, yard in figures), figures
 
 
 def test_k1_large_random_and_state_not_mutated(ops, oracle):

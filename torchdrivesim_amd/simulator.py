@@ -1446,6 +1446,14 @@ class Simulator:
         if A == 0:
             return torch.zeros_like(self.get_state()[..., 0])
         if metric in (CollisionMetric.iou, CollisionMetric.discs):
+            state = self.get_state()
+            if self.npc_count == 0 and state.requires_grad and torch.is_grad_enabled():
+                # The shared [sin, cos] node comes into being BEFORE the boxes node, as it does when render() foresees the metrics (_mark_fork
+                # makes it ahead of the fork).  Autograd sums the gradients that reach a state in the order in which its consumers run, which
+                # is the reverse of the order in which they were made; a state inside a rollout has four (the next step, off-road, [sin, cos],
+                # boxes), three of them in the psi column, and a float sum of three depends on its order.  Made in one order on every path,
+                # a rollout's gradients have the same bits with overlap_infractions on and off (tests/test_gpu_rollout.py).
+                self._heading_sc()
             boxes = self._all_boxes()
             # a NaN heading is scrubbed inside the kernel, so the shared [sin, cos] of the raw headings serves the IoU metric
             sc = self._heading_sc() if metric == CollisionMetric.iou else None
