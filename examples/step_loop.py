@@ -11,6 +11,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py --lights device --stop-lines 4     # the light programmes run on the device, a clock per scene; a non-visual loop sees
                                                                     # the 4 nearest stop lines ahead with their colour and the seconds until it changes
     python examples/step_loop.py --npcs 32          # 32 NPCs per scene that follow the lanes (IDM), stop at red lights and for the agents
+    python examples/step_loop.py --npcs 32 --give-way       # ... and give way to each other at junctions (a second launch per step)
     python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
     python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
     python examples/step_loop.py --route-grad       # a few steps of gradient descent on the actions through the simulator, with a route loss
@@ -71,12 +72,15 @@ def main():
     ap.add_argument('--stop-lines', type=int, default=0, metavar='K', help='observe the K nearest stop lines ahead (compute_stop_lines) instead of images')
     ap.add_argument('--lanes', type=int, default=0, metavar='K', help='observe the K nearest lanes as polylines (compute_lanes) instead of images')
     ap.add_argument('--npcs', type=int, default=0, metavar='N', help='N lane-following NPCs per scene (behavior.LaneFollowingNPCController)')
+    ap.add_argument('--give-way', action='store_true', help='the NPCs give way to each other at junctions (LaneFollowingNPCController(give_way=True))')
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
     ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
     args = ap.parse_args()
     if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) + (args.lanes > 0) > 1:
         ap.error('--scan, --neighbors, --stop-lines and --lanes are observations in place of the image: choose one')
+    if args.give_way and not args.npcs:
+        ap.error('--give-way is an option of the NPCs: give --npcs N too')
     if args.route and args.route_to:
         ap.error('--route and --route-to are two ways to deal the one route an agent has')
     dev = torch.device('cuda', 0)
@@ -101,7 +105,7 @@ def main():
         npc_lanes = lanelet2.revert_map(lanes)
         agents = torch.cat([sim.get_state()[..., :2], sim.get_agent_size(), sim.get_state()[..., 2:3]], dim=-1)
         attributes, npc_state, placed = heuristic_initialize_batch(npc_lanes, args.batch, args.npcs, seed=1, occupied=agents, on_failure='mask', device=dev)
-        sim.npc_controller = LaneFollowingNPCController(npc_lanes, attributes[..., :2].contiguous(), npc_state, placed, seed=1)
+        sim.npc_controller = LaneFollowingNPCController(npc_lanes, attributes[..., :2].contiguous(), npc_state, placed, seed=1, give_way=args.give_way)
     if args.route:
         # route goals: every agent is snapped to the lane under it and dealt a route from there (two launches); then one launch per step.  On
         # revert_map of the town, like the NPCs: the file stores its lanelets against the direction of travel.
@@ -187,7 +191,8 @@ def main():
     if args.npcs:
         c = sim.npc_controller
         print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '
-              f'{float((c.leader != -1).float().mean()):.3f} behind a leader or a red light, {int(c.hops.sum())} lanelet changes')
+              f'{float((c.leader != -1).float().mean()):.3f} behind a leader or a red light, {int(c.hops.sum())} lanelet changes' +
+              (f', {float((c.yield_to >= 0).float().mean()):.3f} giving way at a junction' if args.give_way else ''))
     if args.route:
         r = sim.route_goals
         print(f'routes of {args.route:g} m: {float(r.valid.float().mean()):.3f} of the agents have one (mean {float(r.length.sum() / r.valid.sum().clamp(min=1)):.1f} m over '

@@ -522,7 +522,8 @@ int tds_lane_snap_multi(const tds_laneset_t *set, const int32_t *scene_map, int6
  *                 desired_speed B x N (v0 > 0); npc_present B x N uint8
  *   lane, arc, hops   B x N int32 / float64 / int32, IN AND OUT: lanelet, arc length on it, lanelet transitions made so far
  *   state         B x N x 4 [x, y, psi, speed], in and out (only speed is read); sc B x N x 2 [sin, cos] of the new pose = the unit vector of
- *                 its segment; leader B x N int32: the entity braked for, -1 none, -2 the end of the lane
+ *                 its segment; leader B x N int32: the entity braked for, -1 none, -2 the end of the lane, -3 the junction it gives way at
+ *                 (tds_lane_follow_step_stops_multi only)
  * Path: from (lane, arc) along the centre line (2-D) to the lanelet's end, then along the successor chosen for hop `hops`, `hops + 1`, ...:
  * succ[(r0 * n_succ) >> 32], r0 the first word of Philox4x32-10 with key (seed low ^ 0x4C414E45, seed high ^ 0x464F4C57) and counter (scene id
  * low, scene id high, NPC index, hop).  It ends with the segment in which `horizon` metres are covered, after TDS_FOLLOW_MAX_HOPS successors,
@@ -549,6 +550,58 @@ int tds_lane_follow_step_multi(const tds_laneset_t *set, const int32_t *scene_ma
                                const int32_t *self_index, const float *npc_size, const float *desired_speed, const uint8_t *npc_present,
                                int32_t *lane, double *arc, int32_t *hops, float *state, float *sc, int32_t *leader, uint64_t seed, float dt,
                                float horizon, float lateral_margin, const float *idm, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Giving way at junctions (no reference counterpart: the definition is this library's own; float64 model:
+ * tests/give_way_model.py; the expressions: csrc/tds_conflicts.h).  Float64 with + - * / sqrt only.  DRIVABLE = eligible in the sense of
+ * tds_spawn_on_lanes_f32; len(l) = the last `cum` of l's centre line.
+ *
+ * tds_lane_conflicts_f64 fills table, L x (L + 2) float64 owned by the caller (L = the table's lanelets), laid out as
+ *   exit      L x L   exit[a][b] at table[a * L + b]
+ *   zone_in   L       at table[L * L + a]
+ *   zone_out  L       at table[L * L + L + a]
+ * For every drivable lanelet a: samples k = 0 .. min(floor(len(a) / step), 2^20) at arcs s_k = (double)k * step, the point of each as in
+ * tds_lane_follow_step's pose (the segment that holds s_k on `cum`, t = (s_k - cum[i]) / its 3-D length), 2-D.  For every drivable b that is
+ * not EXCLUDED -- b == a, b a successor of a, a a successor of b, a and b successors of a common lanelet -- a sample HITS b iff the least
+ * squared distance from it to b's 2-D centre-line segments (the foot of tds_lane_snap) is <= clearance * clearance.  exit[a][b] = the last
+ * s_k that hits b, -1 without one (and for every other pair); zone_in[a] = the least over b of the first s_k that hits b, +inf without one;
+ * zone_out[a] = the greatest exit[a][b], -1 without one.  a and b CONFLICT iff exit[a][b] >= 0 and exit[b][a] >= 0.  One launch, a workgroup
+ * per lanelet.  clearance or step not finite or not > 0 is TDS_EINVAL before any launch, L > TDS_CONFLICT_MAX_LANELETS is TDS_ELIMIT, a table
+ * without a successor graph TDS_EINVAL.
+ *
+ * tds_lane_give_way_multi decides, for the N NPCs of every scene as they are BEFORE the step, who stops before which junction; one launch, a
+ * workgroup per scene.  lane, arc, hops, state (B x N x 4, only speed is read), npc_size, npc_present, scene_ids, seed: as for
+ * tds_lane_follow_step_multi, whose route stream is used, so that the successors drawn here are the ones that kernel takes.  tables: per lane
+ * table of the set the address of its conflict table (int64, 0 = none).  Stop lines (S >= 0 per scene): line_lane B x S int32 (-1: on no
+ * lane), line_arc B x S float64, line_red B x S uint8.  Outputs: stop_at B x N float64 (+inf: none), yield_to B x N int32 (-1: none).
+ *   Path: l_0 = lane, start_0 = -arc; l_(k+1) = the successor drawn for hop hops + k, start_(k+1) = start_k + len(l_k); it ends when
+ *   start_(k+1) >= horizon, after TDS_FOLLOW_MAX_HOPS successors, or at a successor that is not drivable.  With half = length / 2:
+ *   Junction: the first l_k with zone_out[l_k] >= 0, start_k + zone_out[l_k] + half > 0 and start_k + zone_in[l_k] <= horizon.  Then
+ *   D = start_k + zone_in[l_k], gap = D - half, COMMITTED iff gap <= 0 or v * v >= 2 * b_max * gap, t = max(gap, 0) / max(v, creep_speed).
+ *   Rows that are absent, whose lane is not drivable, whose scene has no table, or without a junction take no part.
+ *   HELD: not committed, and a stop line with line_red set, line_lane == l_k' for a k' <= k, 0 < start_k' + line_arc < start_k + zone_out[l_k].
+ *   NPC i (junction p, not committed) GIVES WAY to j != i (junction q) iff j is not held, exit[q][p] >= 0 and exit[p][q] >= 0,
+ *   start_j + exit[q][p] + half_j > 0, and j is committed or (t_j, j) < (t_i, i) lexicographically.  Then stop_at[i] = D_i and yield_to[i] =
+ *   the lowest such j.
+ * N > TDS_GIVE_WAY_MAX_NPCS is TDS_ELIMIT; horizon or b_max negative or not finite, creep_speed not finite or not > 0 is TDS_EINVAL before any
+ * launch.  Nothing is allocated, nothing synchronises, every loop is bounded, no atomics.
+ *
+ * tds_lane_follow_step_stops_multi is tds_lane_follow_step_multi with one more input, stop_at B x N float64 or NULL (NULL: that entry point
+ * bit for bit): after the leader and the dead end, a finite stop_at gives gap_s = stop_at - length / 2, and if there is no leader so far or
+ * gap_s < gap: leader = -3, gap = gap_s, v_lead = 0. */
+#define TDS_CONFLICT_MAX_LANELETS 2048
+#define TDS_GIVE_WAY_MAX_NPCS 1024
+int tds_lane_conflicts_f64(const tds_lanes_t *lanes, double *table, float clearance, float step, void *stream);
+int tds_lane_give_way_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, const int64_t *tables, int64_t B,
+                            int64_t N, const int32_t *lane, const double *arc, const int32_t *hops, const float *state, const float *npc_size,
+                            const uint8_t *npc_present, int64_t S, const int32_t *line_lane, const double *line_arc, const uint8_t *line_red,
+                            uint64_t seed, float horizon, float b_max, float creep_speed, double *stop_at, int32_t *yield_to, void *stream);
+int tds_lane_follow_step_stops_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t N,
+                                     int64_t E, const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present,
+                                     const int32_t *self_index, const float *npc_size, const float *desired_speed,
+                                     const uint8_t *npc_present, int32_t *lane, double *arc, int32_t *hops, float *state, float *sc,
+                                     int32_t *leader, const double *stop_at, uint64_t seed, float dt, float horizon, float lateral_margin,
+                                     const float *idm, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Route goals (no reference counterpart: the definition is this library's own; float64 model: tests/route_model.py).

@@ -164,6 +164,12 @@ tds_lane_follow_step(handle lanes, i64* scene_ids, int64 B, int64 N, int64 E, f3
 tds_lane_follow_step_multi(handle set, i32* scene_map, i64* scene_ids, int64 B, int64 N, int64 E, f32* boxes, f32* ent_sc, f32* ent_speed, u8* ent_present, i32* self_index,
     f32* npc_size, f32* desired_speed, u8* npc_present, i32* lane, f64* arc, i32* hops, f32* state, f32* sc, i32* leader, uint64 seed, float dt, float horizon,
     float lateral_margin, host* idm, stream stream)
+tds_lane_conflicts_f64(handle lanes, f64* table, float clearance, float step, stream stream)
+tds_lane_give_way_multi(handle set, i32* scene_map, i64* scene_ids, i64* tables, int64 B, int64 N, i32* lane, f64* arc, i32* hops, f32* state, f32* npc_size, u8* npc_present,
+    int64 S, i32* line_lane, f64* line_arc, u8* line_red, uint64 seed, float horizon, float b_max, float creep_speed, f64* stop_at, i32* yield_to, stream stream)
+tds_lane_follow_step_stops_multi(handle set, i32* scene_map, i64* scene_ids, int64 B, int64 N, int64 E, f32* boxes, f32* ent_sc, f32* ent_speed, u8* ent_present,
+    i32* self_index, f32* npc_size, f32* desired_speed, u8* npc_present, i32* lane, f64* arc, i32* hops, f32* state, f32* sc, i32* leader, f64* stop_at, uint64 seed,
+    float dt, float horizon, float lateral_margin, host* idm, stream stream)
 tds_route_sample_multi(handle set, i32* scene_map, i64* scene_ids, int64 B, int64 A, i32* lane, f64* arc, f64* distance, u8* present, u8* mask, uint64 seed, i32* route_lanes,
     i32* route_n, f64* start_arc, f64* end_arc, f64* offsets, f64* length, i32* cursor, f64* stored, u8* completed, stream stream)
 tds_route_progress_multi(handle set, i32* scene_map, int64 B, int64 A, f32* xy, int64 xy_stride, f32* sc, u8* present, i32* route_lanes, i32* route_n, f64* start_arc,
@@ -292,7 +298,8 @@ E_INVAL, E_HIP, E_NOMEM, E_LIMIT = -1, -2, -3, -4          # TDS_EINVAL, TDS_EHI
 BUFFER_DENSE = 1
 SPAWN_MAX_BOXES = 2048           # TDS_SPAWN_MAX_BOXES
 FOLLOW_MAX_HOPS, FOLLOW_MAX_ENTITIES = 8, 1024       # TDS_FOLLOW_MAX_HOPS, TDS_FOLLOW_MAX_ENTITIES
-ROUTE_MAX_LANES, ROUTE_MAX_LOOKAHEAD = 16, 32        # TDS_ROUTE_MAX_LANES, TDS_ROUTE_MAX_LOOKAHEAD
+CONFLICT_MAX_LANELETS, GIVE_WAY_MAX_NPCS = 2048, 1024    # TDS_CONFLICT_MAX_LANELETS, TDS_GIVE_WAY_MAX_NPCS
+ROUTE_MAX_LANES, ROUTE_MAX_LOOKAHEAD = 16, 32       # TDS_ROUTE_MAX_LANES, TDS_ROUTE_MAX_LOOKAHEAD
 ROUTE_MAX_GRAPH = 2048                               # TDS_ROUTE_MAX_GRAPH
 NEIGHBORS_MAX_K, NEIGHBORS_MAX_ENTITIES = 32, 1024   # TDS_NEIGHBORS_MAX_K, TDS_NEIGHBORS_MAX_ENTITIES
 LIGHTS_MAX_MACHINES, LIGHTS_MAX_PHASES, LIGHTS_MAX_LIGHTS = 256, 64, 1024      # TDS_LIGHTS_MAX_MACHINES, TDS_LIGHTS_MAX_PHASES, TDS_LIGHTS_MAX_LIGHTS

@@ -1453,6 +1453,7 @@ class LaneTableHandle(_Handle):
         self.max_tolerance = float(max_tolerance)
         self.n_lanelets = int(len(table.flags))
         self._to_go = None                           # the distance table of routes to a destination: built by `lane_distances` when first asked for
+        self._conflicts = {}                         # (clearance, step) -> the conflict table of junctions: built by `lane_conflicts`
         poly = np.ascontiguousarray(table.poly_xy, np.float64)
         cl = np.ascontiguousarray(table.cl_xyz, np.float64)
         ps, cs = np.ascontiguousarray(table.poly_start, np.int32), np.ascontiguousarray(table.cl_start, np.int32)
@@ -1489,6 +1490,7 @@ class LaneTableSet(_Handle):
         nat.call('tds_laneset_create', self.device, arr, len(self.tables), ctypes.byref(handle))
         self._h = handle
         self._distance_tables = None
+        self._conflict_tables = {}
 
     def distance_tables(self):
         """(n tables,) int64 on the device: the address of every table's `lane_distances`, what tds_route_to_multi reads them through.  Built
@@ -1498,6 +1500,38 @@ class LaneTableSet(_Handle):
             self._distance_tables = torch.tensor([lane_distances(t).data_ptr() for t in self.tables], dtype=torch.int64, device=self.device)
             torch.cuda.current_stream(self.device).synchronize()            # once: whatever stream deals routes later finds the tables complete
         return self._distance_tables
+
+    def conflict_tables(self, clearance=2.0, step=0.5):
+        """(n tables,) int64 on the device: the address of every table's `lane_conflicts(table, clearance, step)`, what
+        tds_lane_give_way_multi reads them through.  Built once per (clearance, step) (allocations and one launch per table not seen before:
+        outside any capture); the tensors themselves live on the table objects, which this set keeps alive."""
+        key = (float(clearance), float(step))
+        if key not in self._conflict_tables:
+            self._conflict_tables[key] = torch.tensor([lane_conflicts(t, *key)[3].data_ptr() for t in self.tables], dtype=torch.int64, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()            # once: whatever stream steps the NPCs later finds the tables complete
+        return self._conflict_tables[key]
+
+
+def check_lane_conflicts_args(n_lanelets, clearance, step):
+    """what tds_lane_conflicts_f64 refuses, refused before any tensor is touched: TdsError with the code the entry point would return"""
+    for k, x in (('clearance', clearance), ('step', step)):
+        if not (0.0 < float(x) < float('inf')):
+            raise nat.TdsError('lane_conflicts', nat.E_INVAL, f'{k} must be finite and greater than 0 (got {x})')
+    if n_lanelets > nat.CONFLICT_MAX_LANELETS:
+        raise nat.TdsError('lane_conflicts', nat.E_LIMIT, f'{n_lanelets} lanelets exceed the {nat.CONFLICT_MAX_LANELETS} whose exclusions a workgroup holds in LDS')
+
+
+def lane_conflicts(table, clearance=2.0, step=0.5):
+    """tds_lane_conflicts_f64 for a `LaneTableHandle`: (exit (L, L), zone_in (L,), zone_out (L,), the whole table) float64, the first three views
+    of the last (include/tdship.h "Giving way at junctions").  Built once per (table, clearance, step) and kept on the table."""
+    key = (float(clearance), float(step))
+    L = table.n_lanelets
+    check_lane_conflicts_args(L, *key)
+    if key not in table._conflicts:
+        whole = torch.empty((L * (L + 2),), dtype=torch.float64, device=table.device)
+        nat.call('tds_lane_conflicts_f64', table.device, table.handle, whole, *key)
+        table._conflicts[key] = (whole[:L * L].view(L, L), whole[L * L:L * L + L], whole[L * L + L:], whole)
+    return table._conflicts[key]
 
 
 def lane_distances(table):
@@ -1645,8 +1679,8 @@ def check_lane_follow_args(n_entities, dt, horizon, lateral_margin, idm):
 
 
 def lane_follow_step(lane_set, scene_ids, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size, desired_speed, npc_present, lane, arc,
-                     hops, state, sc, leader, seed, dt, horizon=60.0, lateral_margin=0.2, idm=(1.5, 2.0, 1.5, 2.0, 6.0)):
-    """tds_lane_follow_step_multi (include/tdship.h): entities boxes (B,E,5), ent_sc (B,E,2), ent_speed (B,E), ent_present (B,E); per NPC
+                     hops, state, sc, leader, seed, dt, horizon=60.0, lateral_margin=0.2, idm=(1.5, 2.0, 1.5, 2.0, 6.0), stop_at=None):
+    """tds_lane_follow_step_multi (include/tdship.h; with stop_at (B,N) float64, the output of `lane_give_way`: tds_lane_follow_step_stops_multi): entities boxes (B,E,5), ent_sc (B,E,2), ent_speed (B,E), ent_present (B,E); per NPC
     self_index (B,N) int32, npc_size (B,N,2), desired_speed (B,N), npc_present (B,N); lane / arc / hops / state (B,N,4) / sc (B,N,2) / leader are
     updated IN PLACE and must be dense tensors of exactly the kernel's types.  One launch on the current stream, no allocation, no
     synchronisation.  idm = (T, s0, a, b, b_max)."""
@@ -1671,9 +1705,56 @@ def lane_follow_step(lane_set, scene_ids, boxes, ent_sc, ent_speed, ent_present,
     if self_index is not None and tuple(self_index.shape) != (B, N):
         raise RuntimeError(f'lane_follow_step: self_index must be ({B},{N}), got {tuple(self_index.shape)}')
     params = (ctypes.c_float * 5)(*[float(x) for x in idm])
+    if stop_at is not None:
+        if tuple(stop_at.shape) != (B, N):
+            raise RuntimeError(f'lane_follow_step: stop_at must be ({B},{N}), got {tuple(stop_at.shape)}')
+        nat.call('tds_lane_follow_step_stops_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'lane_follow_step'), _scene_ids(scene_ids, B, 'lane_follow_step'),
+                 B, N, E, _c(boxes), _c(ent_sc), _c(ent_speed), _u8(ent_present), self_index, _c(npc_size), _c(desired_speed), _u8(npc_present), lane, arc, hops,
+                 state, sc, leader, stop_at, _seed64(seed), float(dt), float(horizon), float(lateral_margin), params)
+        return
     nat.call('tds_lane_follow_step_multi', dev, lane_set.handle, _scene_map(lane_set, B, 'lane_follow_step'), _scene_ids(scene_ids, B, 'lane_follow_step'),
              B, N, E, _c(boxes), _c(ent_sc), _c(ent_speed), _u8(ent_present), self_index, _c(npc_size), _c(desired_speed), _u8(npc_present), lane, arc, hops,
              state, sc, leader, _seed64(seed), float(dt), float(horizon), float(lateral_margin), params)
+
+
+def check_lane_give_way_args(n_npcs, horizon, b_max, creep_speed):
+    """what tds_lane_give_way_multi refuses, refused before any tensor is touched: TdsError with the code the entry point would return"""
+    if n_npcs > nat.GIVE_WAY_MAX_NPCS:
+        raise nat.TdsError('lane_give_way', nat.E_LIMIT, f'{n_npcs} NPCs exceed the {nat.GIVE_WAY_MAX_NPCS} of a scene\'s workgroup')
+    for k, x in (('horizon', horizon), ('b_max', b_max)):
+        if not (0.0 <= float(x) < float('inf')):
+            raise nat.TdsError('lane_give_way', nat.E_INVAL, f'{k} must be finite and not negative (got {x})')
+    if not (0.0 < float(creep_speed) < float('inf')):
+        raise nat.TdsError('lane_give_way', nat.E_INVAL, f'creep_speed must be finite and greater than 0 (got {creep_speed})')
+
+
+def lane_give_way(lane_set, scene_ids, tables, lane, arc, hops, state, npc_size, npc_present, lines, seed, stop_at, yield_to, horizon=60.0, b_max=6.0,
+                  creep_speed=1.0):
+    """tds_lane_give_way_multi (include/tdship.h): tables = `lane_set.conflict_tables(clearance, step)`; lane / arc / hops (B,N), state (B,N,4),
+    npc_size (B,N,2), npc_present (B,N) as `lane_follow_step` takes them; lines = None or (line_lane (B,S) int32, line_arc (B,S) float64, line_red
+    (B,S) bool or uint8); stop_at (B,N) float64 and yield_to (B,N) int32 are WRITTEN.  One launch on the current stream, no allocation besides the
+    uint8 views of bool masks, no synchronisation."""
+    if state.dim() != 3 or state.shape[-1] != 4:
+        raise RuntimeError(f'lane_give_way: state must be (B,N,4), got {tuple(state.shape)}')
+    B, N = state.shape[:2]
+    check_lane_give_way_args(N, horizon, b_max, creep_speed)
+    given = dict(lane=lane, arc=arc, hops=hops, npc_size=npc_size, npc_present=npc_present, stop_at=stop_at, yield_to=yield_to)
+    for k, t in given.items():
+        if tuple(t.shape) != ((B, N, 2) if k == 'npc_size' else (B, N)):
+            raise RuntimeError(f'lane_give_way: {k} must be {(B, N, 2) if k == "npc_size" else (B, N)}, got {tuple(t.shape)}')
+    if tuple(tables.shape) != (len(lane_set.tables),):
+        raise RuntimeError(f'lane_give_way: tables must hold one address per lane table of the set ({len(lane_set.tables)}), got {tuple(tables.shape)}')
+    S, line_lane, line_arc, line_red = 0, None, None, None
+    if lines is not None:
+        line_lane, line_arc, line_red = lines
+        S = line_lane.shape[1]
+        for k, t in (('line_lane', line_lane), ('line_arc', line_arc), ('line_red', line_red)):
+            if tuple(t.shape) != (B, S):
+                raise RuntimeError(f'lane_give_way: {k} must be ({B},{S}), got {tuple(t.shape)}')
+        line_red = _u8(line_red)
+    nat.call('tds_lane_give_way_multi', state.device, lane_set.handle, _scene_map(lane_set, B, 'lane_give_way'), _scene_ids(scene_ids, B, 'lane_give_way'),
+             tables, B, N, lane, arc, hops, _c(state), _c(npc_size), _u8(npc_present), S, line_lane, line_arc, line_red, _seed64(seed), float(horizon),
+             float(b_max), float(creep_speed), stop_at, yield_to)
 
 
 # ---------------------------------------------------------------------------------------------------------------

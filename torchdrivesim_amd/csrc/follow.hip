@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "tds_common.h"
+#include "tds_conflicts.h"
 #include "tds_lanes.h"
 
 using tds::LaneRec;
@@ -47,6 +48,7 @@ struct FollowArgs {
     float *state, *sc;
     uint32_t key0, key1;
     double dt, horizon, margin, T, s0, a, b, b_max;
+    const double *stop_at;          // per NPC or null: where the yield pass (conflicts.hip) has it stop, +inf for nowhere
 };
 
 // grid = (B, ceil(N / W)), W = blockDim.x / 64 waves; dynamic LDS = E * ENT_WORDS floats + W * FOLLOW_MAX_PIECES * PIECE_DOUBLES doubles + W * NEAR_SLOTS ints
@@ -216,6 +218,10 @@ __global__ void __launch_bounds__(FBLOCK) lane_follow_kernel(FollowArgs g) {
         const double end_gap = off - own_len / 2.0;
         if (leader == -1 || end_gap < gap) leader = -2, gap = end_gap, v_lead = 0.0;
     }
+    if (g.stop_at) {                                                         // the junction it gives way at: one more standing obstacle
+        double gap_s;
+        if (tds::stop_is_nearest(g.stop_at[row], own_len / 2.0, leader, gap, &gap_s)) leader = -3, gap = gap_s, v_lead = 0.0;
+    }
     const double v0 = (double)g.desired_speed[row];
     const double r1 = vel / v0, r2 = r1 * r1;
     double acc = 1.0 - r2 * r2;
@@ -263,7 +269,7 @@ int follow_launch(const char *what, FollowArgs &g, const int32_t *scene_map, con
                   const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present, const int32_t *self_index,
                   const float *npc_size, const float *desired_speed, const uint8_t *npc_present, int32_t *lane, double *arc, int32_t *hops,
                   float *state, float *sc, int32_t *leader, uint64_t seed, float dt, float horizon, float lateral_margin, const float *idm,
-                  void *stream) {
+                  void *stream, const double *stop_at = nullptr) {
     TDS_CHECK_ARG(B >= 0 && N >= 0 && E >= 0 && B < ((int64_t)1 << 31) && N <= 2 * 65535, "%s: bad sizes B=%lld N=%lld E=%lld", what, (long long)B,
                   (long long)N, (long long)E);
     if (E > TDS_FOLLOW_MAX_ENTITIES) {
@@ -281,7 +287,7 @@ int follow_launch(const char *what, FollowArgs &g, const int32_t *scene_map, con
     g.scene_map = scene_map, g.scene_ids = scene_ids, g.N = (int)N, g.E = (int)E;
     g.boxes = boxes, g.ent_sc = ent_sc, g.ent_speed = ent_speed, g.ent_present = ent_present, g.self_index = self_index;
     g.npc_size = npc_size, g.desired_speed = desired_speed, g.npc_present = npc_present;
-    g.lane = lane, g.arc = arc, g.hops = hops, g.state = state, g.sc = sc, g.leader = leader;
+    g.lane = lane, g.arc = arc, g.hops = hops, g.state = state, g.sc = sc, g.leader = leader, g.stop_at = stop_at;
     // the route stream: spawn's key for the same seed with two words folded in ("LANE", "FOLW"), so the two streams never coincide
     g.key0 = (uint32_t)seed ^ 0x4C414E45u, g.key1 = (uint32_t)(seed >> 32) ^ 0x464F4C57u;
     g.dt = dt, g.horizon = horizon, g.margin = lateral_margin;
@@ -320,4 +326,18 @@ TDS_EXPORT int tds_lane_follow_step_multi(const tds_laneset_t *set, const int32_
     g.views = set->d_views, g.n_views = set->n;
     return follow_launch("tds_lane_follow_step_multi", g, scene_map, scene_ids, B, N, E, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size,
                          desired_speed, npc_present, lane, arc, hops, state, sc, leader, seed, dt, horizon, lateral_margin, idm, stream);
+}
+
+TDS_EXPORT int tds_lane_follow_step_stops_multi(const tds_laneset_t *set, const int32_t *scene_map, const int64_t *scene_ids, int64_t B, int64_t N,
+                                                int64_t E, const float *boxes, const float *ent_sc, const float *ent_speed, const uint8_t *ent_present,
+                                                const int32_t *self_index, const float *npc_size, const float *desired_speed,
+                                                const uint8_t *npc_present, int32_t *lane, double *arc, int32_t *hops, float *state, float *sc,
+                                                int32_t *leader, const double *stop_at, uint64_t seed, float dt, float horizon, float lateral_margin,
+                                                const float *idm, void *stream) {
+    TDS_CHECK_ARG(set, "tds_lane_follow_step_stops_multi: the lane-table set is null");
+    TDS_CHECK_SCENE_MAP("tds_lane_follow_step_stops_multi", set, scene_map);
+    FollowArgs g = {};
+    g.views = set->d_views, g.n_views = set->n;
+    return follow_launch("tds_lane_follow_step_stops_multi", g, scene_map, scene_ids, B, N, E, boxes, ent_sc, ent_speed, ent_present, self_index, npc_size,
+                         desired_speed, npc_present, lane, arc, hops, state, sc, leader, seed, dt, horizon, lateral_margin, idm, stream, stop_at);
 }
