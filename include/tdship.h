@@ -930,6 +930,10 @@ int tds_lane_observations_multi(const tds_laneset_t *set, const int32_t *scene_m
 #define TDS_RASTER_DBG_DROP_SMALL 8388608      /* the fused bit-plane kernel drops, instead of queueing, every accepted face with all three vertices inside
                                                   the image and at most TDS_RASTER_SMALL_ROWS rows: the difference to a plain launch is what these
                                                   faces cost on the general path */
+#define TDS_RASTER_DBG_SMALL_FREE_SLOPES 16777216  /* the on-lane block for small faces takes the packed vertices for its three slopes instead of computing
+                                                  them: wrong pixels, timing and counters only -- the difference to a plain launch is what the slopes cost */
+#define TDS_RASTER_DBG_SMALL_NO_MIDDLE_ROW 33554432 /* ... paints the row of the middle vertex, where it lies between the others, as a row of part 1: wrong
+                                                  pixels -- the difference is what that row's own expressions cost */
 #ifndef TDS_RASTER_SMALL_ROWS
 #define TDS_RASTER_SMALL_ROWS 7                /* rows (yb - yt + 1) of the largest face that is small: the persistent bit-plane kernel paints such faces
                                                   on the lane that scanned them; the flag above and the counters below go by the same test */

@@ -55,6 +55,8 @@ class RasterDebug(enum.IntFlag):
     NO_EXTRA_STRIP = 2097152
     PROLOGUE_TWICE = 4194304
     DROP_SMALL = 8388608
+    SMALL_FREE_SLOPES = 16777216
+    SMALL_NO_MIDDLE_ROW = 33554432
 
 _lib = None
 

@@ -19,6 +19,7 @@
 // Roofline: HBM write, 3*H*W*4 B per camera (fp32) -- DESIGN.md.
 #include "tds_common.h"
 #include "tds_raster_plan.h"
+#include "tds_short_slope.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -177,32 +178,8 @@ __device__ inline long long div_trunc(long long n, long long d) {
 // ---------------------------------------------------------------------------------------------------------
 struct Chain { int xs1; int dx1; int ysw; int xs2; int dx2; };     // slopes fit int32 for |dx| < 2^15 pixels
 
-// n / d for n < 2^31, 1 <= d < 2^16 and a quotient of at most 2^16: the fp32 estimate (24-bit operand, v_rcp_f32, one product: relative
-// error below 2^-22) is within 0.02 of the exact quotient, so its floor is off by at most one and one correction step in integers makes
-// it exact (q and d fit the 24-bit multiplier, q d < 2^32)
-__device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned d) {
-    unsigned q = (unsigned)((float)n * __builtin_amdgcn_rcpf((float)d));
-    int r = (int)(n - __umul24(q, d));
-    if (r < 0) --q;
-    else if (r >= (int)d) ++q;
-    return q;
-}
-
-// OpenCV's edge slope ((xe - xs) * 2 + dy) / (2 * dy) in 16.16 fixed point, C truncating division.
-// With N = (xe - xs) << 16 this is trunc(N / dy + 1/2):
-//   N >= 0: a + (2 r >= dy);   N < 0: -(a - (2 r < dy)),   a, r = divmod(|N|, dy)
-// (for N < 0 the case 2|N| <= dy -> 0 of the general formula cannot occur: |N| >= 65536 > dy).  |xe - xs| and dy are below 2^15 (packed
-// coordinate range), so divmod(|N|, dy) is two short divisions: |xe - xs| = hi dy + r1, then (r1 << 16) = lo dy + r  ->  a = hi << 16 | lo.
-// A 32-bit unsigned division costs the compiler two quarter-rate multiplies and twenty instructions; there are four per face.
-__device__ inline int edge_dx(int xs, int xe, int dyy) {
-    const int dxs = xe - xs;
-    const unsigned D = (unsigned)abs(dxs), d = (unsigned)dyy;
-    const unsigned hi = udiv_small(D, d), r1 = D - __umul24(hi, d);
-    const unsigned lo = udiv_small(r1 << 16, d), r = (r1 << 16) - __umul24(lo, d);
-    const unsigned a = (hi << 16) + lo;
-    if (dxs >= 0) return (int)(a + ((2u * r >= d) ? 1u : 0u));
-    return -(int)(a - ((2u * r < d) ? 1u : 0u));
-}
+// udiv_small (n / d over the float unit) and edge_dx (OpenCV's 16.16 edge slope, two short divisions) live in tds_short_slope.h, beside the short
+// form for the edges of small faces
 
 // chain visiting a0 -> a1 -> a2 (a0 = first top vertex)
 __device__ inline Chain make_chain(const int *px, const int *py, int a0, int a1, int a2) {
@@ -1990,8 +1967,10 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
 // lane = face; `e` = the face's list entry (plane | outline edges << 4, three packed vertices); faces that miss the strip are skipped.
 __device__ __forceinline__ int slope_one_row(int xs, int xe) { const int d = xe - xs; return d >= 0 ? d << 16 : (int)(((unsigned)d << 16) + 1u); }
 // ROWS = 2: faces of one or two rows; ROWS > 2: up to ROWS rows (yb - yt <= ROWS - 1) -- the rows between the top and the bottom
-// vertex are painted by the lane too, each either the row of the middle vertex or a row of part 1 (chains T->M, T->B) / part 2 (M->B, T->B)
-// with the expressions of process_batch_bits' row items.  K3r: which of 2 and 4 serves a launch is decided by the resolution (wave-uniform): the
+// vertex are painted by the lane too: the row of the middle vertex once, apart, as process_batch_bits paints it, and the rows that hold no vertex
+// in a loop with ONE form -- a row of part 1 (chains T->M, T->B) or part 2 (M->B, T->B) selects its chain, with the expressions of
+// process_batch_bits' row items (neighbouring lanes differ in what a row is: a body with arms made every wave walk all of them in every row).
+// The slopes of these edges, at most ROWS - 1 rows high, come from the short form of tds_short_slope.h: no division, no correction step.  K3r: which of 2 and 4 serves a launch is decided by the resolution (wave-uniform): the
 // taller variant costs every chunk of faces about twice the instructions and pays where faces of three and four rows are many (128 x 128: 38 %
 // of the faces on top of the 32 % of one and two rows; 64 x 64: 8 % on top of 66 %).  The fused persistent kernel takes ROWS = SMALL_ROWS for
 // the chunks of its scan in which enough lanes hold such a face (drain_bits).
@@ -2017,9 +1996,16 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
     const unsigned cTM = cls(xt, yt, xm, ym), cMB = cls(xm, ym, xb, yb), cTB = cls(xt, yt, xb, yb);
     int sTB, sTM, sMB;
     if constexpr (ROWS > 2) {
-        sTB = edge_dx(xt, xb, yb - yt);
-        sTM = ym > yt ? edge_dx(xt, xm, ym - yt) : 0;
-        sMB = yb > ym ? edge_dx(xm, xb, yb - ym) : 0;
+        static_assert(ROWS - 1 <= TDS_SHORT_SLOPE_MAX_DY && 2 * COORD_LIMIT <= TDS_SHORT_SLOPE_MAX_DX, "every edge of a small face is in the short form's domain");
+        if (TDS_DBG(w.debug) & TDS_RASTER_DBG_SMALL_FREE_SLOPES) {
+            // ablation: a few shifts in place of the slopes (exact over one row, up to twice too flat else: the spans keep about their widths)
+            auto cheap = [](int xs, int xe, int dyy) { return (int)((unsigned)(xe - xs) << 16) >> (dyy >> 1); };
+            sTB = cheap(xt, xb, yb - yt); sTM = cheap(xt, xm, ym - yt); sMB = cheap(xm, xb, yb - ym);
+        } else {
+            sTB = edge_dx_short(xt, xb, yb - yt);
+            sTM = ym > yt ? edge_dx_short(xt, xm, ym - yt) : 0;
+            sMB = yb > ym ? edge_dx_short(xm, xb, yb - ym) : 0;
+        }
     } else {
         sTB = slope_one_row(xt, xb); sTM = ym > yt ? slope_one_row(xt, xm) : 0; sMB = yb > ym ? slope_one_row(xm, xb) : 0;
     }
@@ -2033,25 +2019,33 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
     if constexpr (ROWS > 2) {
         int oLb, oRb;
         edge_offsets(cTB, sTB, oLb, oRb);
+        const unsigned xt16 = (unsigned)xt << 16;                    // (chain positions in unsigned: a product may wrap, the sums do not)
+        // the row of the middle vertex when it lies strictly between the others, once, as process_batch_bits paints it: T->M ends, M->B starts,
+        // T->B passes
+        if (ym > yt && ym < yb && !(TDS_DBG(w.debug) & TDS_RASTER_DBG_SMALL_NO_MIDDLE_ROW)) {
+            const int xc = (int)(xt16 + (unsigned)(ym - yt) * (unsigned)sTB);
+            int L = min(xm, (xc + oLb) >> 16), R = max(xm, (xc + oRb) >> 16);
+            edge_reach(cTM, xm, -half_slope(sTM), L, R);
+            edge_reach(cMB, xm, half_slope(sMB), L, R);
+            paint_row(ym, L, R);
+        }
+        // the rows that hold no vertex, one form for all: row yt + j lies on T->B and on T->M (part 1, above the middle vertex) or M->B (part 2);
+        // both chains' row ends are set up once, relative to the top row, and a row selects its chain
+        int oL1, oR1, oL2, oR2;
+        edge_offsets(cTM, sTM, oL1, oR1);
+        edge_offsets(cMB, sMB, oL2, oR2);
+        const unsigned x2 = ((unsigned)xm << 16) - (unsigned)(ym - yt) * (unsigned)sMB;     // M->B continued up to the top row
+        const unsigned l1 = xt16 + (unsigned)oL1, r1 = xt16 + (unsigned)oR1, l2 = x2 + (unsigned)oL2, r2 = x2 + (unsigned)oR2;
+        const unsigned lb = xt16 + (unsigned)oLb, rb = xt16 + (unsigned)oRb;
 #pragma unroll
         for (int j = 1; j <= ROWS - 2; ++j) {
             const int y = yt + j;
             if (y >= yb) break;
-            const int xc = (xt << 16) + j * sTB;                     // the chain T->B in this row
-            if (y == ym) {
-                // the row of the middle vertex: T->M ends, M->B starts, T->B passes
-                int L = min(xm, (xc + oLb) >> 16), R = max(xm, (xc + oRb) >> 16);
-                edge_reach(cTM, xm, -half_slope(sTM), L, R);
-                edge_reach(cMB, xm, half_slope(sMB), L, R);
-                paint_row(y, L, R);
-            } else {
-                const bool second = y > ym;                          // part 2: the other chain is M->B, else T->M
-                const int sA = second ? sMB : sTM, xA = second ? xm : xt, yA = second ? ym : yt;
-                int oLa, oRa;
-                edge_offsets(second ? cMB : cTM, sA, oLa, oRa);
-                const int xa = (xA << 16) + (y - yA) * sA;
-                paint_row(y, min(xa + oLa, xc + oLb) >> 16, max(xa + oRa, xc + oRb) >> 16);
-            }
+            const bool second = y > ym;
+            const unsigned sA = (unsigned)(second ? sMB : sTM) * (unsigned)j, sB = (unsigned)sTB * (unsigned)j;
+            const int L = min((int)((second ? l2 : l1) + sA), (int)(lb + sB)) >> 16, R = max((int)((second ? r2 : r1) + sA), (int)(rb + sB)) >> 16;
+            const int s0 = max(L, X0), s1 = min(R, Xhi);
+            if (y != ym && s0 <= s1) paint_span_bits(pl + y, H, s0 - X0, s1 - X0);
         }
     }
     {
