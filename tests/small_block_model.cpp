@@ -1,10 +1,10 @@
-/* Test infrastructure: a sequential model of the block that paints a SMALL face on the lane that scanned it, in the form it has since the
- * slopes of its short edges come without a division and the rows between the vertices have one form (torchdrivesim_amd/csrc/raster.hip:
- * process_small_bits<ROWS>, ROWS > 2), checked against the oracle's restatement of cv::fillConvexPoly (oracle/tds_oracle.c) triangle by
- * triangle.  The slopes are the kernel's own (tds_short_slope.h: edge_dx_short); the statements below follow the kernel's line by line:
- * the row of the top vertex, the row of the middle vertex once where it lies strictly between the others, the rows that hold no vertex from
- * row ends set up once relative to the top row (32-bit unsigned arithmetic: a product may wrap, the sums do not), the row of the bottom vertex.
- * tests/small_rows_model.c is the block's earlier form, and stays.
+/* Test infrastructure: the block that paints a SMALL face on the lane that scanned it (torchdrivesim_amd/csrc/raster.hip:
+ * process_small_bits<ROWS>, ROWS > 2) run on the CPU, checked against the oracle's restatement of cv::fillConvexPoly (oracle/tds_oracle.c)
+ * triangle by triangle.  The row rule is the kernel's own code, compiled for the host: the sort by row, the classes of the short edges, the
+ * rows of the three vertices and the row ends of the chains (tds_face_rows.h), the slopes (tds_short_slope.h: edge_dx_short).  What the
+ * model states itself is what the kernel keeps beside its stores: the order of the rows and the loop over the rows that hold no vertex, from
+ * row ends set up once relative to the top row (32-bit unsigned arithmetic: a product may wrap, the sums do not).
+ * tests/small_rows_model.c is the block's earlier form, written independently, and stays.
  *
  * usage: small_block_model ROWS exhaustive RES OFFSET N | ROWS random RES COUNT SEED | ROWS wide RES
  *        ("oldrows-..." paints the middle vertex's row as a row of part 1, which the check must notice)
@@ -14,35 +14,14 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "tds_face_rows.h"
 #include "tds_short_slope.h"
 
 extern "C" void orc_fill_convex_poly(float *img, int W, int H, const int32_t *pts, int npts, const float *col);
 
-static const int MERGE_BIAS = 160;
 static int BROKEN = 0;
 static int imin(int a, int b) { return a < b ? a : b; }
 static int imax(int a, int b) { return a > b ? a : b; }
-
-static int half_slope(int s) { return s >= 0 ? (s >> 1) : -((-s) >> 1); }
-static void edge_offsets(unsigned cls, int s, int *offL, int *offR) {
-    const int bias = (cls & 4u) ? MERGE_BIAS : 0;
-    const int h = abs(s) >> 1;
-    const int mx = (cls & 3u) == 3u;
-    const int yl = 32768 - ((cls & 1u) ? bias : 0);
-    const int xl = imin(32768, 65536 - h + bias), xr = imax(32768, h + bias);
-    *offL = mx ? xl : yl;
-    *offR = mx ? xr : 32768;
-}
-static void edge_reach(unsigned cls, int x0, int d, int *L, int *R) {
-    if (cls & 1u) {
-        *L = imin(*L, x0); *R = imax(*R, x0);
-        if (cls & 2u) {
-            const int v = (int)(((uint32_t)x0 << 16) + (uint32_t)d + ((cls & 4u) ? MERGE_BIAS : 0)) >> 16;
-            if (d >= 0) *R = imax(*R, v); else *L = imin(*L, v + 1);
-        }
-    }
-}
-static unsigned cls_of(int ax, int ay, int bx, int by) { return 5u | ((abs(bx - ax) >= abs(by - ay)) ? 2u : 0u); }
 
 static uint8_t *g_mask; static int g_W, g_H, ROWS;
 static void paint_row(int y, int L, int R) {
@@ -59,35 +38,28 @@ static int is_small(const int32_t *p) {
 }
 
 static void model_small(const int32_t *p) {
-    const int i0 = (p[0] & 0xffff) | (p[1] << 16), i1 = (p[2] & 0xffff) | (p[3] << 16), i2 = (p[4] & 0xffff) | (p[5] << 16);
-    const int pT = imin(i0, imin(i1, i2)), pB = imax(i0, imax(i1, i2)), pM = imax(imin(i0, i1), imin(imax(i0, i1), i2));
-    const int xt = (int16_t)(pT & 0xffff), yt = pT >> 16, xm = (int16_t)(pM & 0xffff), ym = pM >> 16, xb = (int16_t)(pB & 0xffff), yb = pB >> 16;
-    const int xmin = imin(xt, imin(xm, xb)), xmax = imax(xt, imax(xm, xb));
-    if (yt == yb) { paint_row(yt, xmin, xmax); return; }
-    const unsigned cTM = cls_of(xt, yt, xm, ym), cMB = cls_of(xm, ym, xb, yb), cTB = cls_of(xt, yt, xb, yb);
+    const uint32_t v0 = pack_xy(p[0], p[1]), v1 = pack_xy(p[2], p[3]), v2 = pack_xy(p[4], p[5]);
+    const int pT = top_vertex(v0, v1, v2), pB = bottom_vertex(v0, v1, v2), pM = middle_vertex(v0, v1, v2);
+    const int xt = unpack_x((uint32_t)pT), yt = unpack_y((uint32_t)pT), xm = unpack_x((uint32_t)pM), ym = unpack_y((uint32_t)pM);
+    const int xb = unpack_x((uint32_t)pB), yb = unpack_y((uint32_t)pB);
+    if (yt == yb) { paint_row(yt, imin(xt, imin(xm, xb)), imax(xt, imax(xm, xb))); return; }
+    const unsigned cTM = short_edge_class(xt, yt, xm, ym), cMB = short_edge_class(xm, ym, xb, yb), cTB = short_edge_class(xt, yt, xb, yb);
     const int sTB = edge_dx_short(xt, xb, yb - yt);
     const int sTM = ym > yt ? edge_dx_short(xt, xm, ym - yt) : 0;
     const int sMB = yb > ym ? edge_dx_short(xm, xb, yb - ym) : 0;
-    {
-        int L = xt, R = xt;
-        if (ym > yt) edge_reach(cTM, xt, half_slope(sTM), &L, &R);
-        else { L = imin(xt, xm); R = imax(xt, xm); edge_reach(cMB, xm, half_slope(sMB), &L, &R); }
-        edge_reach(cTB, xt, half_slope(sTB), &L, &R);
-        paint_row(yt, L, R);
-    }
-    int oLb, oRb;
-    edge_offsets(cTB, sTB, &oLb, &oRb);
-    const unsigned xt16 = (unsigned)xt << 16;
+    const FaceEdges f{xt, yt, xm, ym, xb, yb, cTM, cMB, cTB, sTM, sMB, sTB};
+    int L, R;
+    face_row_top(f, L, R);
+    paint_row(yt, L, R);
     if (ym > yt && ym < yb && !BROKEN) {
-        const int xc = (int)(xt16 + (unsigned)(ym - yt) * (unsigned)sTB);
-        int L = imin(xm, (xc + oLb) >> 16), R = imax(xm, (xc + oRb) >> 16);
-        edge_reach(cTM, xm, -half_slope(sTM), &L, &R);
-        edge_reach(cMB, xm, half_slope(sMB), &L, &R);
+        face_row_middle(f, L, R);
         paint_row(ym, L, R);
     }
-    int oL1, oR1, oL2, oR2;
-    edge_offsets(cTM, sTM, &oL1, &oR1);
-    edge_offsets(cMB, sMB, &oL2, &oR2);
+    int oLb, oRb, oL1, oR1, oL2, oR2;
+    edge_offsets(cTB, sTB, oLb, oRb);
+    edge_offsets(cTM, sTM, oL1, oR1);
+    edge_offsets(cMB, sMB, oL2, oR2);
+    const unsigned xt16 = (unsigned)xt << 16;
     const unsigned x2 = ((unsigned)xm << 16) - (unsigned)(ym - yt) * (unsigned)sMB;
     const unsigned l1 = xt16 + (unsigned)oL1, r1 = xt16 + (unsigned)oR1, l2 = x2 + (unsigned)oL2, r2 = x2 + (unsigned)oR2;
     const unsigned lb = xt16 + (unsigned)oLb, rb = xt16 + (unsigned)oRb;
@@ -96,19 +68,10 @@ static void model_small(const int32_t *p) {
         if (y >= yb) break;
         const int second = y > ym;
         const unsigned sA = (unsigned)(second ? sMB : sTM) * (unsigned)j, sB = (unsigned)sTB * (unsigned)j;
-        const int L = imin((int)((second ? l2 : l1) + sA), (int)(lb + sB)) >> 16, R = imax((int)((second ? r2 : r1) + sA), (int)(rb + sB)) >> 16;
-        if (y != ym || BROKEN) paint_row(y, L, R);
+        if (y != ym || BROKEN) paint_row(y, imin((int)((second ? l2 : l1) + sA), (int)(lb + sB)) >> 16, imax((int)((second ? r2 : r1) + sA), (int)(rb + sB)) >> 16);
     }
-    {
-        int L = 0x7fffffff, R = -0x7fffffff;
-        edge_reach(cTB, xb, -half_slope(sTB), &L, &R);
-        if (ym < yb) edge_reach(cMB, xb, -half_slope(sMB), &L, &R);
-        else {
-            edge_reach(cTM, xm, -half_slope(sTM), &L, &R);
-            L = imin(L, imin(xm, xb)); R = imax(R, imax(xm, xb));
-        }
-        paint_row(yb, L, R);
-    }
+    face_row_bottom(f, L, R);
+    paint_row(yb, L, R);
 }
 
 static long g_checked, g_bad, g_skipped;
@@ -186,6 +149,7 @@ int main(int argc, char **argv) {
             check(p, img);
         }
     } else { fprintf(stderr, "unknown mode %s\n", mode); return 2; }
+    free(img); free(g_mask);
     printf("%ld triangles, %ld differ, %ld not small\n", g_checked, g_bad, g_skipped);
     return g_bad || g_skipped ? 1 : 0;
 }

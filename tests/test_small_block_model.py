@@ -1,9 +1,9 @@
 """
 The block that paints a SMALL face on the lane that scanned it (raster.hip: process_small_bits<ROWS>, ROWS > 2: the persistent kernel's 7 rows,
 the list rasteriser's 4) in the form it has with division-free slopes and one form for the rows between the vertices, as sequential C++
-(tests/small_block_model.cpp, the slopes from the kernel's own tds_short_slope.h), held to the oracle's cv::fillConvexPoly restatement
-triangle by triangle: the exhaustive 7 x 7 vertex grid, flat wide faces of every height, middle row, width and edge direction, random small
-faces.  CPU only; the kernel itself is compared with the oracle under -m gpu (tests/test_gpu_small_block.py).
+(tests/small_block_model.cpp, the row rule and the slopes from the kernel's own tds_face_rows.h and tds_short_slope.h), held to the oracle's
+cv::fillConvexPoly restatement triangle by triangle: the exhaustive 7 x 7 vertex grid, flat wide faces of every height, middle row, width and
+edge direction, random small faces; once more under the address and undefined-behaviour sanitizers.  CPU only; the kernel itself is compared with the oracle under -m gpu (tests/test_gpu_small_block.py).
 """
 import os
 import re
@@ -19,13 +19,17 @@ ROWS = int(re.search(r'#define TDS_RASTER_SMALL_ROWS (\d+)', open(os.path.join(R
 LIST_ROWS = 4                    # the list rasteriser's instantiation (raster.hip: process_small_bits<4>)
 
 
+def build(out, *flags):
+    libdir = os.path.join(ROOT, 'oracle', '_build')
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.run(['g++', '-std=c++17', '-O2', '-ffp-contract=off', '-Wall', '-Werror', *flags, '-I', INC, '-o', out, SRC, '-L', libdir, '-ltds_oracle',
+                    f'-Wl,-rpath,{libdir}'], check=True)
+    return out
+
+
 @pytest.fixture(scope='module')
 def model(oracle):
-    libdir = os.path.join(ROOT, 'oracle', '_build')
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    subprocess.run(['g++', '-std=c++17', '-O2', '-ffp-contract=off', '-Wall', '-Werror', '-I', INC, '-o', OUT, SRC, '-L', libdir, '-ltds_oracle',
-                    f'-Wl,-rpath,{libdir}'], check=True)
-    return OUT
+    return build(OUT)
 
 
 def run(model, *args):
@@ -74,3 +78,13 @@ def test_the_check_can_fail(model):
     assert r.returncode == 1 and ' 0 differ' not in r.stdout
     r = run(model, ROWS - 1, 'exhaustive', 16, 4, 7)
     assert r.returncode == 1 and ' 0 not small' not in r.stdout
+
+
+def test_clean_under_the_sanitizers(model):
+    """the same program with AddressSanitizer and UndefinedBehaviorSanitizer linked in (the oracle library as it is), run on its own: any report
+    ends it with an error.  The chain products that may wrap stay in unsigned types, so there is nothing for it to say."""
+    san = build(OUT + '_san', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-static-libasan', '-static-libubsan')
+    for args in [(ROWS, 'exhaustive', 16, 4, 7), (LIST_ROWS, 'exhaustive', 16, 5, 4)]:
+        r = run(san, *args)
+        assert r.returncode == 0 and r.stderr == '', r.stdout + r.stderr
+        assert r.stdout == run(model, *args).stdout and ' 0 differ, 0 not small' in r.stdout

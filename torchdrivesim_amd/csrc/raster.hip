@@ -18,6 +18,7 @@
 //     explicit per-camera RGB mesh.
 // Roofline: HBM write, 3*H*W*4 B per camera (fp32) -- DESIGN.md.
 #include "tds_common.h"
+#include "tds_face_rows.h"
 #include "tds_raster_plan.h"
 #include "tds_short_slope.h"
 #include <algorithm>
@@ -314,9 +315,7 @@ __device__ inline void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-__device__ inline uint32_t pack_xy(int x, int y) { return ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16); }
-__device__ inline int unpack_x(uint32_t p) { return (int)(short)(p & 0xffffu); }
-__device__ inline int unpack_y(uint32_t p) { return (int)p >> 16; }
+// pack_xy, unpack_x, unpack_y (x & 0xffff | y << 16) and the sort of three packed vertices by row live in tds_face_rows.h
 
 // Faces whose pixel coordinates do not fit the packed fast path (|coord| >= COORD_LIMIT): the sequential OpenCV
 // algorithm executed by a single lane, painting only the strip.  Practically never taken (a vertex more than 16000
@@ -1629,20 +1628,15 @@ constexpr int HCHUNK = TDS_HCHUNK;    // rows per item: x-major outline edges (o
 // ---- outline edges merged into the rows -------------------------------------------------------------------------------------
 // cv::fillConvexPoly paints Line(v2,v0) + Line(v0,v1) + Line(v1,v2) + the scan-converted rows.  For an edge that lies inside the image
 // (cv::Line does not clip it) the pixels of the edge in a row and the scan-converted span of that row are ONE run of pixels, and its
-// ends follow from the 16.16 edge chain of the scan conversion by an add and a shift -- the edge is never walked:
-//   y-major (|dy| > |dx|): cv::Line paints x(tau) = x0 + dx tau / |dy| rounded to nearest, a tie going to the LEFT pixel (either direction
-//     of the walk); the span ends at floor(chain + 1/2).  Left end: floor(chain + 1/2 - BIAS), right end unchanged.
-//   x-major: row tau holds the pixels x with x(tau - 1/2) < x <= x(tau + 1/2), cut at the edge's end points:
-//     floor(chain - slope/2 + BIAS) + 1 .. floor(chain + slope/2 + BIAS), merged with the span by min / max.
-// The chain strays from the exact line: OpenCV's slope is trunc(q + 1/2) in units of 2^-16, i.e. within 1/2 unit of q for q >= 0 but
-// between 1/2 and 3/2 units ABOVE it for q < 0, per row.  The half-row positions of the exact line are multiples of 1/(2|dy|): BIAS must
-// exceed the accumulated error and, with it, stay below 1/(2|dy|) -- 160 units for |dy| <= 100 (3/2 * 100 < 160, 160 + 150 < 32768 / 100).
-// Edges of up to 147 rows whose half-row positions are never integers (no ties) need no bias (3/2 * 147 < 32768 / 147).  Everything
-// else -- edges that cv::clipLine would touch, longer edges -- is walked exactly (edge ring below).  The rows of the three vertices are
-// painted apart, by the face's own lane (the runs are cut at the end points there); the rows in between are work items.
-// tests/fill_rows_model.c is this rule as sequential C, checked triangle by triangle against the oracle's cv::fillConvexPoly
+// ends follow from the 16.16 edge chain of the scan conversion by an add and a shift -- the edge is never walked.  The rule is stated once, in
+// tds_face_rows.h (MERGE_BIAS, edge_offsets, edge_reach, half_slope, the rows of the three vertices): the bias holds for edges of up to
+// 100 rows.  Edges of up to 147 rows whose half-row positions are never integers (no ties) need no bias
+// (3/2 * 147 < 32768 / 147).  Everything else -- edges that cv::clipLine would touch, longer edges -- is walked exactly (edge ring below).
+// The rows of the three vertices are painted apart, by the face's own lane (the runs are cut at the end points there); the rows in between
+// are work items.  On the CPU, against the oracle's cv::fillConvexPoly triangle by triangle: tests/small_block_model.cpp paints small faces
+// with the header's own functions; tests/fill_rows_model.c and tests/small_rows_model.c are the rule written again, independently, as sequential C
 // (exhaustively on small grids, millions of random triangles at 64..1024 pixels).
-constexpr int MERGE_BIAS = 160, MERGE_DY_BIAS = 100, MERGE_DY_NOBIAS = 147;
+constexpr int MERGE_DY_BIAS = 100, MERGE_DY_NOBIAS = 147;
 
 // bit 0: the edge is merged into the rows, bit 1: x-major, bit 2: biased
 // oca, ocb: outcodes of the end points (vertex_outcode), 0 = inside the image
@@ -1663,29 +1657,6 @@ __device__ __forceinline__ unsigned edge_class(int ax, int ay, int bx, int by, u
     }
     return (merge ? 1u : 0u) | (xmaj ? 2u : 0u) | (shortish ? 4u : 0u);
 }
-// row ends of a chain that follows an edge of class `cls` with 16.16 slope s: left = (x + offL) >> 16, right = (x + offR) >> 16
-__device__ __forceinline__ void edge_offsets(unsigned cls, int s, int &offL, int &offR) {
-    // selects, no branches: neighbouring lanes hold edges of every class
-    const int bias = (cls & 4u) ? MERGE_BIAS : 0;
-    const int h = abs(s) >> 1;
-    const bool mx = (cls & 3u) == 3u;
-    const int yl = 32768 - ((cls & 1u) ? bias : 0);
-    const int xl = min(32768, 65536 - h + bias), xr = max(32768, h + bias);
-    offL = mx ? xl : yl;
-    offR = mx ? xr : 32768;
-}
-// the pixels of a merged edge in the row of its end point x0: x0 itself and, x-major, the run from x0 towards x0 + d (d = half a row's
-// advance along the edge, 16.16, signed)
-__device__ __forceinline__ void edge_reach(unsigned cls, int x0, int d, int &L, int &R) {
-    if (cls & 1u) {
-        L = min(L, x0); R = max(R, x0);
-        if (cls & 2u) {
-            const int v = ((x0 << 16) + d + ((cls & 4u) ? MERGE_BIAS : 0)) >> 16;
-            if (d >= 0) R = max(R, v); else L = min(L, v + 1);
-        }
-    }
-}
-__device__ __forceinline__ int half_slope(int s) { return s >= 0 ? (s >> 1) : -((-s) >> 1); }
 
 __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush) {
     const int lane = w.lane, H = w.H, W = w.W, X0 = w.X0, TWp = w.TWp, wpr = w.wpr;
@@ -1702,11 +1673,9 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
         const uint32_t v0 = w.q[QCAP + lane], v1 = w.q[2 * QCAP + lane], v2 = w.q[3 * QCAP + lane];
         const uint32_t kidx = q0 & 15u, em = (q0 >> 4) & 7u;
         flags = (int)kidx;
-        // packed vertices (x & 0xffff | y << 16) compare like (y, x): sorted by row with three instructions
-        const int i0 = (int)v0, i1 = (int)v1, i2 = (int)v2;
-        pT = min(i0, min(i1, i2));
-        const int pB = max(i0, max(i1, i2));
-        pM = max(min(i0, i1), min(max(i0, i1), i2));
+        pT = top_vertex(v0, v1, v2);
+        const int pB = bottom_vertex(v0, v1, v2);
+        pM = middle_vertex(v0, v1, v2);
         const int xt = unpack_x((uint32_t)pT), yt = unpack_y((uint32_t)pT), xm = unpack_x((uint32_t)pM), ym = unpack_y((uint32_t)pM);
         const int xb = unpack_x((uint32_t)pB), yb = unpack_y((uint32_t)pB);
         const int xmin = min(xt, min(xm, xb)), xmax = max(xt, max(xm, xb));
@@ -1746,33 +1715,21 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
                 sTM = ym > yt ? edge_dx(xt, xm, ym - yt) : 0;
                 sMB = yb > ym ? edge_dx(xm, xb, yb - ym) : 0;
                 if (!(TDS_DBG(w.debug) & TDS_RASTER_DBG_NO_SCAN)) {
-                    // the row of the top vertex (two of them: the span between them): both chains start here
+                    // the rows of the three vertices (tds_face_rows.h), the middle one where it lies strictly between the others
+                    const FaceEdges f{xt, yt, xm, ym, xb, yb, cTM, cMB, cTB, sTM, sMB, sTB};
                     {
-                        int L = xt, R = xt;
-                        if (ym > yt) edge_reach(cTM, xt, half_slope(sTM), L, R);
-                        else { L = min(xt, xm); R = max(xt, xm); edge_reach(cMB, xm, half_slope(sMB), L, R); }
-                        edge_reach(cTB, xt, half_slope(sTB), L, R);
+                        int L, R;
+                        face_row_top(f, L, R);
                         paint_row(yt, L, R);
                     }
-                    // the row of the middle vertex when it lies strictly between the others: T->M ends, M->B starts, T->B passes
                     if (ym > yt && ym < yb) {
-                        int oL, oR;
-                        edge_offsets(cTB, sTB, oL, oR);
-                        const int xc = (xt << 16) + (ym - yt) * sTB;
-                        int L = min(xm, (xc + oL) >> 16), R = max(xm, (xc + oR) >> 16);
-                        edge_reach(cTM, xm, -half_slope(sTM), L, R);
-                        edge_reach(cMB, xm, half_slope(sMB), L, R);
+                        int L, R;
+                        face_row_middle(f, L, R);
                         paint_row(ym, L, R);
                     }
-                    // the row of the bottom vertex is never scan-converted: the last pixels of the merged edges that end there
                     {
-                        int L = 0x7fffffff, R = -0x7fffffff;
-                        edge_reach(cTB, xb, -half_slope(sTB), L, R);
-                        if (ym < yb) edge_reach(cMB, xb, -half_slope(sMB), L, R);
-                        else {
-                            edge_reach(cTM, xm, -half_slope(sTM), L, R);
-                            if (cMB & 1u) { L = min(L, min(xm, xb)); R = max(R, max(xm, xb)); }      // the horizontal bottom edge
-                        }
+                        int L, R;
+                        face_row_bottom(f, L, R);
                         paint_row(yb, L, R);
                     }
                     // the rows in between: part 1 = rows yt+1 .. ym-1, part 2 = rows ym+1 .. yb-1, cut to the image
@@ -1961,11 +1918,9 @@ __device__ __forceinline__ void process_batch_bits(BitCtx &w, int n, bool flush)
 
 // The short set-up for SMALL faces (K3r sorts them out chunk by chunk: all three vertices inside the image, in one row or in two adjacent rows).  Such a
 // face has nothing between its vertex rows to scan-convert, every outline edge lies inside the image and is short, i.e. merged into the rows
-// (edge_class: 1 | x-major << 1 | 4) and nothing goes to the edge ring -- what is left of process_batch_bits is the painting of the vertex
-// rows, with the SAME expressions (edge_reach over the half slopes of OpenCV's 16.16 chains); the slope over one row,
-// edge_dx(xs, xe, 1) = trunc((xe - xs) * 65536 + 1/2) with C's truncation, is (xe - xs) << 16 for xe >= xs and ((xe - xs) << 16) + 1 below.
-// lane = face; `e` = the face's list entry (plane | outline edges << 4, three packed vertices); faces that miss the strip are skipped.
-__device__ __forceinline__ int slope_one_row(int xs, int xe) { const int d = xe - xs; return d >= 0 ? d << 16 : (int)(((unsigned)d << 16) + 1u); }
+// (short_edge_class: 1 | x-major << 1 | 4) and nothing goes to the edge ring -- what is left of process_batch_bits is the painting of the vertex
+// rows, by the SAME functions (tds_face_rows.h: face_row_top, face_row_middle, face_row_bottom); the slope over one row is slope_one_row.
+// lane = face; faces that miss the strip are skipped.
 // ROWS = 2: faces of one or two rows; ROWS > 2: up to ROWS rows (yb - yt <= ROWS - 1) -- the rows between the top and the bottom
 // vertex are painted by the lane too: the row of the middle vertex once, apart, as process_batch_bits paints it, and the rows that hold no vertex
 // in a loop with ONE form -- a row of part 1 (chains T->M, T->B) or part 2 (M->B, T->B) selects its chain, with the expressions of
@@ -1979,8 +1934,7 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
     const int H = w.H, X0 = w.X0, wpr = w.wpr;
     const int Xhi = min(w.W, X0 + w.TWp) - 1;
     if (!valid) return;
-    const int i0 = (int)v0, i1 = (int)v1, i2 = (int)v2;
-    const int pT = min(i0, min(i1, i2)), pB = max(i0, max(i1, i2)), pM = max(min(i0, i1), min(max(i0, i1), i2));
+    const int pT = top_vertex(v0, v1, v2), pB = bottom_vertex(v0, v1, v2), pM = middle_vertex(v0, v1, v2);
     const int xt = unpack_x((uint32_t)pT), yt = unpack_y((uint32_t)pT), xm = unpack_x((uint32_t)pM), ym = unpack_y((uint32_t)pM);
     const int xb = unpack_x((uint32_t)pB), yb = unpack_y((uint32_t)pB);
     const int xmin = min(xt, min(xm, xb)), xmax = max(xt, max(xm, xb));
@@ -1991,9 +1945,7 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
         if (s0 <= s1) paint_span_bits(pl + y, H, s0 - X0, s1 - X0);
     };
     if (yt == yb) { paint_row(yt, xmin, xmax); return; }         // one row: the three (horizontal, merged) edges are one span
-    // classes of the merged short edges: 1 | x-major << 1 | biased (edge_class with both end points inside the image and |dy| <= 100)
-    auto cls = [](int ax, int ay, int bx, int by) { return 5u | ((abs(bx - ax) >= abs(by - ay)) ? 2u : 0u); };
-    const unsigned cTM = cls(xt, yt, xm, ym), cMB = cls(xm, ym, xb, yb), cTB = cls(xt, yt, xb, yb);
+    const unsigned cTM = short_edge_class(xt, yt, xm, ym), cMB = short_edge_class(xm, ym, xb, yb), cTB = short_edge_class(xt, yt, xb, yb);
     int sTB, sTM, sMB;
     if constexpr (ROWS > 2) {
         static_assert(ROWS - 1 <= TDS_SHORT_SLOPE_MAX_DY && 2 * COORD_LIMIT <= TDS_SHORT_SLOPE_MAX_DX, "every edge of a small face is in the short form's domain");
@@ -2009,24 +1961,20 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
     } else {
         sTB = slope_one_row(xt, xb); sTM = ym > yt ? slope_one_row(xt, xm) : 0; sMB = yb > ym ? slope_one_row(xm, xb) : 0;
     }
+    const FaceEdges f{xt, yt, xm, ym, xb, yb, cTM, cMB, cTB, sTM, sMB, sTB};
     {
-        int L = xt, R = xt;
-        if (ym > yt) edge_reach(cTM, xt, half_slope(sTM), L, R);
-        else { L = min(xt, xm); R = max(xt, xm); edge_reach(cMB, xm, half_slope(sMB), L, R); }
-        edge_reach(cTB, xt, half_slope(sTB), L, R);
+        int L, R;
+        face_row_top(f, L, R);
         paint_row(yt, L, R);
     }
     if constexpr (ROWS > 2) {
         int oLb, oRb;
         edge_offsets(cTB, sTB, oLb, oRb);
         const unsigned xt16 = (unsigned)xt << 16;                    // (chain positions in unsigned: a product may wrap, the sums do not)
-        // the row of the middle vertex when it lies strictly between the others, once, as process_batch_bits paints it: T->M ends, M->B starts,
-        // T->B passes
+        // the row of the middle vertex when it lies strictly between the others, once, as process_batch_bits paints it
         if (ym > yt && ym < yb && !(TDS_DBG(w.debug) & TDS_RASTER_DBG_SMALL_NO_MIDDLE_ROW)) {
-            const int xc = (int)(xt16 + (unsigned)(ym - yt) * (unsigned)sTB);
-            int L = min(xm, (xc + oLb) >> 16), R = max(xm, (xc + oRb) >> 16);
-            edge_reach(cTM, xm, -half_slope(sTM), L, R);
-            edge_reach(cMB, xm, half_slope(sMB), L, R);
+            int L, R;
+            face_row_middle(f, L, R);
             paint_row(ym, L, R);
         }
         // the rows that hold no vertex, one form for all: row yt + j lies on T->B and on T->M (part 1, above the middle vertex) or M->B (part 2);
@@ -2049,13 +1997,8 @@ __device__ __forceinline__ void process_small_bits(BitCtx &w, bool valid, uint32
         }
     }
     {
-        int L = 0x7fffffff, R = -0x7fffffff;
-        edge_reach(cTB, xb, -half_slope(sTB), L, R);
-        if (ym < yb) edge_reach(cMB, xb, -half_slope(sMB), L, R);
-        else {
-            edge_reach(cTM, xm, -half_slope(sTM), L, R);
-            L = min(L, min(xm, xb)); R = max(R, max(xm, xb));          // the horizontal bottom edge (merged)
-        }
+        int L, R;
+        face_row_bottom(f, L, R);
         paint_row(yb, L, R);
     }
 }
