@@ -7,6 +7,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
     python examples/step_loop.py --neighbors 8      # a non-visual loop: the 8 nearest other agents in each agent's frame, with their relative velocity
+    python examples/step_loop.py --ttc 5            # beside whatever is observed: when each agent would first hit another one within 5 s at constant velocity
     python examples/step_loop.py --lanes 6          # a non-visual loop: the 6 nearest lanes in each agent's frame, each a foot point and a polyline ahead
     python examples/step_loop.py --lights device --stop-lines 4     # the light programmes run on the device, a clock per scene; a non-visual loop sees
                                                                     # the 4 nearest stop lines ahead with their colour and the seconds until it changes
@@ -67,6 +68,8 @@ def main():
     ap.add_argument('--scan', type=int, default=0, metavar='RAYS', help='observe RAYS-ray range scans (compute_range_scan) instead of images')
     ap.add_argument('--scan-range', type=float, default=50.0)
     ap.add_argument('--neighbors', type=int, default=0, metavar='K', help='observe the K nearest other agents (compute_neighbors) instead of images')
+    ap.add_argument('--ttc', type=float, default=0.0, metavar='SECONDS', help='also compute every agent\'s time to collision within SECONDS each step '
+                    '(compute_time_to_collision): an anticipatory safety term of a reward, beside whatever is observed')
     ap.add_argument('--lights', choices=('host', 'device'), default='host', help='where the light programmes run: one host controller for the whole batch '
                     '(the index tensor is copied over every step), or on the device with a clock per scene (traffic_controls.ProgrammedTrafficLightControl)')
     ap.add_argument('--stop-lines', type=int, default=0, metavar='K', help='observe the K nearest stop lines ahead (compute_stop_lines) instead of images')
@@ -129,12 +132,14 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     totals = {k: torch.zeros((), device=dev) for k in ('collision', 'offroad', 'wrong_way', 'red_light')}     # summed on the device: no sync per step
     advanced = torch.zeros((), device=dev)
+    ttc_sums = torch.zeros(3, device=dev)           # agents with a time to collision below 2 s (as a share, per step), the finite times, how many
     warmup = 3                                   # the first steps build the device maps, lane tables and workspaces (once per simulator): not timed
     for it in range(warmup + args.steps):
         if it == warmup:
             for v in totals.values():
                 v.zero_()
             advanced.zero_()
+            ttc_sums.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
         action = torch.rand((args.batch, args.agents, 2), device=dev, generator=g) * 2 - 1
@@ -170,6 +175,11 @@ def main():
             again = route.off_route | (sim.route_goals.completed & sim.route_goals.truncated)
             replanned += again.sum()
             sim.route_goals.resample_to(sim.get_state(), mask=again, present_mask=sim.get_present_mask())
+        if args.ttc:
+            # where compute_collision says that it has happened, this says that it is about to: +inf for an agent with nothing on its course
+            first = sim.compute_time_to_collision(k=1, horizon=args.ttc).min                          # (B, A) seconds
+            finite = torch.isfinite(first)
+            ttc_sums += torch.stack([(first < 2.0).float().mean(), torch.where(finite, first, torch.zeros_like(first)).sum(), finite.float().sum()])
         totals['collision'] += (sim.compute_collision() > 0).float().mean()
         totals['offroad'] += (sim.compute_offroad() > 0).float().mean()
         totals['wrong_way'] += (sim.compute_wrong_way() > 0).float().mean()
@@ -188,6 +198,10 @@ def main():
     if args.lanes:
         print(f'{args.lanes} lane slots within {args.scan_range:g} m: {float(near_lanes.mask.float().mean()):.3f} filled, '
               f'{float(near_lanes.n_valid[near_lanes.mask].float().mean()):.2f} of {near_lanes.points.shape[-2]} polyline points valid on average')
+    if args.ttc:
+        below, total, count = ttc_sums.tolist()
+        print(f'time to collision within {args.ttc:g} s: {below / args.steps:.3f} of the agents per step below 2 s, '
+              f'{count / (args.steps * args.batch * args.agents):.3f} with one at all, ' + (f'{total / count:.2f} s on average' if count else 'none to average'))
     if args.npcs:
         c = sim.npc_controller
         print(f'{args.npcs} NPCs per scene: {float((c.lane >= 0).float().mean()):.3f} on a lane, mean speed {float(c.npc_state[..., 3].mean()):.2f} m/s, '

@@ -897,6 +897,37 @@ int tds_lane_observations_multi(const tds_laneset_t *set, const int32_t *scene_m
                                 const uint8_t *present, float *features, float *points, int32_t *n_valid, int32_t *index, int64_t B,
                                 int64_t A, int K, int P, float spacing, float max_distance, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K9  time to collision (no reference counterpart: the definition is this library's own; float64 model, equal bit for bit:
+ * tests/ttc_model.py; the pair test is stated once, in csrc/tds_ttc.h).  For every exposed agent the K other entities it would touch first
+ * within `horizon` seconds, soonest first, and when -- every entity keeping its velocity v * [cos psi, sin psi] and its heading.
+ * Inputs are those of tds_neighbors_f32 (K6): boxes B x E x 5 (psi is not read), sc B x E x 2 [sin, cos], speed B x E, present B x E uint8,
+ * visible B x A x E uint8 or NULL.  Outputs: ttc B x A x K float32, index B x A x K int32.
+ * Arithmetic: the float32 inputs are widened exactly; binary64 throughout; only + - * /, fabs and comparisons, each rounded once (the build
+ * passes -ffp-contract=off); a result is rounded to binary32 once, at the end.
+ * Observer a (a < A) against entity e, with (x, y, l, w, s, c, v) of each: e != a; present[b, a] and present[b, e] set; visible[b, a, e] != 0
+ * where visible is given; all seven values of both finite -- tested first: a non-finite entity is no candidate, a non-finite observer has an
+ * empty row.  Then
+ *   hla = 0.5*l_a + margin, hwa = 0.5*w_a + margin   (the observer grows by the margin on every side);  hle = 0.5*l_e, hwe = 0.5*w_e
+ *   dx = x_e - x_a, dy = y_e - y_a;  rvx = v_e*c_e - v_a*c_a, rvy = v_e*s_e - v_a*s_a;  lo = -inf, hi = +inf
+ * and for the four axes (nx, ny) = (c_a, s_a), (-s_a, c_a), (c_e, s_e), (-s_e, c_e), in this order:
+ *   p = dx*nx + dy*ny;  w = rvx*nx + rvy*ny
+ *   R = hla*|c_a*nx + s_a*ny| + hwa*|c_a*ny - s_a*nx| + hle*|c_e*nx + s_e*ny| + hwe*|c_e*ny - s_e*nx|     summed left to right
+ *   w == 0:  no candidate if |p| > R, else the axis constrains nothing
+ *   else:    t0 = (-R - p)/w, t1 = (R - p)/w, swapped if t0 > t1;  if (t0 > lo) lo = t0;  if (t1 < hi) hi = t1
+ * The pair is a candidate iff lo <= hi && hi >= 0 && lo <= (double)horizon; its time is t = lo > 0 ? lo : 0.0 (never -0.0; 0 for a pair that
+ * overlaps already) and ttc = (float)t.
+ * Selection: the K candidates with the smallest (bits of ttc, e) -- equal float32 times are broken by the lower entity index; slot 0 is the
+ * soonest.  Empty slots hold +inf and -1; the row of an observer that is absent or not finite is entirely empty; every output is written in full.
+ * 1 <= K <= TDS_TTC_MAX_K, horizon not negative and not NaN (+inf is allowed), margin finite, A <= E: else TDS_EINVAL before any launch;
+ * E > TDS_TTC_MAX_ENTITIES (the entities of a scene live in LDS, 32 bytes each) is TDS_ELIMIT; B * A == 0 is a successful no-op.  Negative
+ * sizes or margins get no special case: the arithmetic decides.  One launch; nothing is allocated and nothing synchronises; every loop of the
+ * kernel is bounded by E and K whatever the tensors hold. */
+#define TDS_TTC_MAX_K 32
+#define TDS_TTC_MAX_ENTITIES 1024
+int tds_time_to_collision_f32(const float *boxes, const float *sc, const float *speed, const uint8_t *present, const uint8_t *visible,
+                              float *ttc, int32_t *index, int64_t B, int64_t A, int64_t E, int K, float horizon, float margin, void *stream);
+
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */

@@ -197,6 +197,8 @@ tds_stop_lines_f32(f32* agent_xy, f32* agent_sc, u8* agent_present, f32* lines, 
     i32* slot_state, int64 B, int64 A, int64 N, int K, float max_distance, int ahead_only, float min_cos, stream stream)
 tds_lane_observations_multi(handle set, i32* scene_map, f32* agent_xy, f32* agent_sc, u8* present, f32* features, f32* points, i32* n_valid, i32* index, int64 B, int64 A,
     int K, int P, float spacing, float max_distance, stream stream)
+tds_time_to_collision_f32(f32* boxes, f32* sc, f32* speed, u8* present, u8* visible, f32* ttc, i32* index, int64 B, int64 A, int64 E, int K, float horizon,
+    float margin, stream stream)
 '''
 
 #: entry points that only libtdship_testing.so exports (include/tdship.h, "testing hooks")
@@ -308,6 +310,7 @@ LIGHTS_MAX_MACHINES, LIGHTS_MAX_PHASES, LIGHTS_MAX_LIGHTS = 256, 64, 1024      #
 LIGHTS_MAX_SKIPS, STOP_LINES_MAX_K = 1024, 32        # TDS_LIGHTS_MAX_SKIPS, TDS_STOP_LINES_MAX_K
 LANE_OBS_MAX_K, LANE_OBS_MAX_POINTS = 32, 32         # TDS_LANE_OBS_MAX_K, TDS_LANE_OBS_MAX_POINTS
 LANE_OBS_MAX_HOPS, LANE_OBS_MAX_LANELETS = 8, 2048   # TDS_LANE_OBS_MAX_HOPS, TDS_LANE_OBS_MAX_LANELETS
+TTC_MAX_K, TTC_MAX_ENTITIES = 32, 1024               # TDS_TTC_MAX_K, TDS_TTC_MAX_ENTITIES
 
 
 class TdsError(RuntimeError):

@@ -6,6 +6,7 @@ rendering/ and simulator.py are thin layers over these.
 import atexit
 import collections
 import ctypes
+import math
 import sys
 import threading
 
@@ -685,6 +686,49 @@ def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=Non
     index = torch.empty((B, A, K), dtype=i32, device=dev)
     nat.call('tds_neighbors_f32', dev, boxes, sc, speed, present, visible, features, index, B, A, E, K, float(max_distance))
     return features, index
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# K9 time to collision
+# ---------------------------------------------------------------------------------------------------------------
+def check_ttc_args(k, horizon, margin):
+    """the argument rules of tds_time_to_collision_f32, on the host: raised before anything is computed or launched"""
+    if int(k) != k or int(k) < 1 or int(k) > nat.TTC_MAX_K:
+        raise ValueError(f'time_to_collision: k must be 1 .. {nat.TTC_MAX_K} (got {k})')
+    if not float(horizon) >= 0.0:                       # (NaN fails the comparison; +inf is allowed)
+        raise ValueError(f'time_to_collision: horizon must not be negative or NaN (got {horizon})')
+    if not math.isfinite(float(margin)):
+        raise ValueError(f'time_to_collision: margin must be finite (got {margin})')
+
+
+def time_to_collision(boxes, sc, speed, present, n_exposed, k, horizon, margin=0.0, visible=None):
+    """The k entities every exposed agent would touch first within `horizon` seconds at constant velocity and heading, and when
+    (tds_time_to_collision_f32, include/tdship.h "K9"): boxes (B,E,5) [x,y,length,width,psi], sc (B,E,2) [sin, cos] of psi, speed (B,E),
+    present (B,E), visible None or (B,A,E) bool / uint8 -> ttc (B,A,k) float32 (+inf in an empty slot), index (B,A,k) int32 (-1 there).
+    No gradient; CPU tensors raise (there is no CPU fallback)."""
+    check_ttc_args(k, horizon, margin)
+    if boxes.dim() != 3 or boxes.shape[-1] != 5:
+        raise ValueError(f'time_to_collision: boxes must be (B, E, 5), got {tuple(boxes.shape)}')
+    B, E = int(boxes.shape[0]), int(boxes.shape[1])
+    A, K = int(n_exposed), int(k)
+    if A < 0 or A > E:
+        raise ValueError(f'time_to_collision: {n_exposed} exposed agents, {E} entities')
+    if tuple(sc.shape) != (B, E, 2) or tuple(speed.shape) != (B, E) or tuple(present.shape) != (B, E):
+        raise ValueError(f'time_to_collision: sc must be ({B}, {E}, 2), speed and present ({B}, {E}), got {tuple(sc.shape)}, {tuple(speed.shape)} and '
+                         f'{tuple(present.shape)}')
+    if visible is not None:
+        if tuple(visible.shape) != (B, A, E):
+            raise ValueError(f'time_to_collision: visible must be ({B}, {A}, {E}), got {tuple(visible.shape)}')
+        if visible.dtype not in (torch.bool, u8):
+            raise ValueError(f'time_to_collision: visible must be bool or uint8, got {visible.dtype}')
+    boxes, sc, speed = _c(boxes.detach()), _c(sc.detach()), _c(speed.detach())
+    present = _u8(present)
+    visible = None if visible is None else _u8(visible)
+    dev = boxes.device
+    ttc = torch.empty((B, A, K), dtype=f32, device=dev)
+    index = torch.empty((B, A, K), dtype=i32, device=dev)
+    nat.call('tds_time_to_collision_f32', dev, boxes, sc, speed, present, visible, ttc, index, B, A, E, K, float(horizon), float(margin))
+    return ttc, index
 
 
 # ---------------------------------------------------------------------------------------------------------------

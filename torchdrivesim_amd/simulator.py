@@ -12,6 +12,7 @@
     compute_neighbors  -> K6 (csrc/neighbors.hip), the K nearest entities per agent   reference: -- (get_all_agents_relative, all pairs)
     compute_stop_lines -> K7 (csrc/lights.hip), the K nearest stop lines per agent    reference: --
     compute_lanes      -> K8 (csrc/lane_obs.hip), the K nearest lanes per agent as polylines  reference: --
+    compute_time_to_collision -> K9 (csrc/ttc.hip), when each agent would first touch another entity  reference: --
     compute_wrong_way  -> lane tables of `lanelet_map` (lanelet2.py), one launch  reference: simulator.py:607-630 (Python triple loop)
 
 Also carried: traffic controls, waypoint goals (state + rendering), observation noise and lane features (plumbing only).  Out of scope
@@ -88,6 +89,28 @@ class Neighbors:
         idx = self.index.clamp(min=0).to(torch.int64).reshape((B, A * K) + (1,) * len(rest)).expand((B, A * K) + rest)
         got = torch.gather(per_entity, 1, idx).reshape((B, A, K) + rest)
         return torch.where(self.mask.reshape((B, A, K) + (1,) * len(rest)), got, torch.full((), fill, dtype=got.dtype, device=got.device))
+
+
+@dataclass
+class TimeToCollision:
+    """What `Simulator.compute_time_to_collision` returns: `ttc` BxAxK float32, the seconds until the agent first touches the entity of the slot
+    (0: they overlap already), soonest first, +inf in an empty slot; `index` BxAxK int32, that entity in [0, A + Npc), -1 for an empty slot."""
+    ttc: Tensor
+    index: Tensor
+
+    @property
+    def mask(self) -> Tensor:
+        """BxAxK bool: the slot holds an entity the agent would touch within the horizon"""
+        return self.index >= 0
+
+    @property
+    def min(self) -> Tensor:
+        """BxA: the agent's time to its first collision, +inf if there is none within the horizon"""
+        return self.ttc[..., 0]
+
+    def take(self, per_entity: Tensor, fill=0) -> Tensor:
+        """Gathers a per-entity tensor Bx(A+Npc)x... at `index` -> BxAxKx..., `fill` in the empty slots (as `Neighbors.take`)."""
+        return Neighbors.take(self, per_entity, fill)
 
 
 @dataclass
@@ -1322,6 +1345,32 @@ class Simulator:
             boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
             out = _ops.neighbors(boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, max_distance, visible=visible)
         return Neighbors(*out)
+
+    # ------------------------------------------------------------------------------------------------- time to collision
+    def compute_time_to_collision(self, k: int = 1, horizon: float = 5.0, margin: float = 0.0, visible: Optional[Tensor] = None) -> TimeToCollision:
+        """When every exposed agent would first touch another present entity (exposed agents and NPCs) if everybody kept its current velocity
+        `v * [cos psi, sin psi]` and heading: the `k` soonest within `horizon` seconds (+inf: no limit), equal times by the lower entity index:
+
+        ttc    BxAxk  float32 seconds, 0 for a pair whose rectangles overlap already, +inf in an empty slot (`TimeToCollision.min` is slot 0);
+        index  BxAxk  int32: the entity in [0, A + Npc) of the slot, -1 for an empty slot (`TimeToCollision.mask`, `TimeToCollision.take`).
+
+        `margin` metres are added to the observing agent's rectangle on every side.  `visible` is that of `compute_neighbors`.  Rows of exposed
+        agents that are not present, or whose pose, size or speed is not finite, are empty.  1 <= k <= 32, at most 1024 entities per scene.
+        One HIP kernel in binary64 (csrc/ttc.hip; the definition is in include/tdship.h "K9", tests/ttc_model.py equals it bit for bit).
+        No gradient.  Runs on the current stream and allocates its outputs only, so it can be captured into a graph."""
+        _ops.check_ttc_args(k, horizon, margin)
+        state = self.get_state()
+        if not state.is_cuda:
+            raise RuntimeError(f'compute_time_to_collision runs on an MI355X; the simulator is on {state.device} (no CPU fallback)')
+        B, A, K = state.shape[0], self.agent_count, int(k)
+        if A == 0:
+            return TimeToCollision(torch.empty((B, 0, K), dtype=torch.float32, device=state.device), torch.empty((B, 0, K), dtype=torch.int32, device=state.device))
+        with torch.no_grad():
+            all_state = self.get_all_agent_state().detach()
+            boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
+            out = _ops.time_to_collision(boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, horizon, margin,
+                                         visible=visible)
+        return TimeToCollision(*out)
 
     # ------------------------------------------------------------------------------------------------- stop-line observations
     def compute_stop_lines(self, k: int = 4, max_distance: float = 60.0, ahead_only: bool = True, min_cos: Optional[float] = None,
