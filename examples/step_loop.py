@@ -16,6 +16,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py --route 200        # every agent gets a 200 m route on the lane graph: progress as a reward term, lookahead as observation
     python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
     python examples/step_loop.py --route-grad       # a few steps of gradient descent on the actions through the simulator, with a route loss
+    python examples/step_loop.py --ttc-grad         # one step: a time-to-collision penalty differentiated to the actions through the simulator
 """
 import argparse
 import os
@@ -59,6 +60,24 @@ def route_grad_loop(args, sim, lanes, dev):
                   f'|d loss / d action| {float(grad.abs().mean()):.4f}, mean acceleration command {float(action[..., 0].mean()):+.3f}')
 
 
+def ttc_grad_step(args, sim, dev):
+    """--ttc-grad: "do not be on course to overlap" by backpropagation.  One step: the actions are applied, every agent with a finite time to
+    collision within the horizon pays (horizon - ttc).clamp(min=0), and that penalty is differentiated to the actions through the backward launch of
+    time to collision and the kinematic step.  compute_collision() has no gradient for these agents: nothing overlaps yet."""
+    horizon = args.ttc or 5.0
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    sim.kinematic_model.set_state(sim.get_state().detach())
+    sim.step(action)
+    first = sim.compute_time_to_collision(k=1, horizon=horizon, differentiable=True).min      # (B, A) seconds, with the graph
+    finite = torch.isfinite(first)
+    penalty = torch.where(finite, (horizon - first).clamp(min=0), torch.zeros_like(first)).sum()
+    grad, = torch.autograd.grad(penalty, action)
+    on_course = finite & (first.detach() > 0)
+    print(f'{int(finite.sum())} of {finite.numel()} agents have a time to collision within {horizon:g} s ({int(on_course.sum())} not overlapping yet), penalty '
+          f'{float(penalty.detach()):.2f} s; |d penalty / d action| {float(grad.abs().sum(-1)[on_course].mean()) if bool(on_course.any()) else 0.0:.4f} on '
+          f'average over those agents, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -79,6 +98,8 @@ def main():
     ap.add_argument('--route', type=float, default=0.0, metavar='METRES', help='deal every agent a route of METRES on the lane graph (goals.RouteGoal)')
     ap.add_argument('--route-to', action='store_true', help='deal every agent the shortest route to a random on-lane destination (goals.RouteGoal.to)')
     ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
+    ap.add_argument('--ttc-grad', action='store_true', help='one step: differentiate a time-to-collision penalty (within --ttc seconds, default 5) to the '
+                    'actions through the simulator (compute_time_to_collision(differentiable=True))')
     args = ap.parse_args()
     if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) + (args.lanes > 0) > 1:
         ap.error('--scan, --neighbors, --stop-lines and --lanes are observations in place of the image: choose one')
@@ -124,6 +145,8 @@ def main():
         sim.route_goals = RouteGoal.to(route_lanes, sim.get_state(), destination[..., :3].contiguous(), present_mask=sim.get_present_mask() & found)
     if args.route_grad:
         return route_grad_loop(args, sim, lanes, dev)
+    if args.ttc_grad:
+        return ttc_grad_step(args, sim, dev)
     routed = bool(args.route) or args.route_to
     replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller

@@ -928,6 +928,38 @@ int tds_lane_observations_multi(const tds_laneset_t *set, const int32_t *scene_m
 int tds_time_to_collision_f32(const float *boxes, const float *sc, const float *speed, const uint8_t *present, const uint8_t *visible,
                               float *ttc, int32_t *index, int64_t B, int64_t A, int64_t E, int K, float horizon, float margin, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K9b  differentiable time to collision: the backward of K9 (float64 torch-autograd model: tests/ttc_grad_model.py; the pair
+ * gradient is stated once, in csrc/tds_ttc_grad.h, and its numpy restatement in that model equals it bit for bit).
+ * Inputs: boxes, sc, speed as K9 read them; index B x A x K int32 as K9 wrote it; g_ttc B x A x K float32, the incoming gradient of ttc.
+ * Outputs: g_boxes B x E x 5 (the psi column is 0: psi is not read, it gets its gradient through [sin, cos]), g_sc B x E x 2, g_speed B x E.
+ * s and c are independent inputs; margin and horizon get no gradient.
+ * Slot (b, a, k) with e = index[b, a, k] CONTRIBUTES iff 0 <= e < E and e != a, all seven values of both boxes are finite, and lo > 0, where
+ * lo is K9's, recomputed with K9's binary64 expressions over the axes with w != 0 (the observer grown by margin).  Every other slot -- empty,
+ * a pair that overlaps already (t = 0), an index that is garbage -- contributes exactly zero whatever its g_ttc holds (a NaN, an infinity).
+ * The forward's discrete choices are constants: the binding axis n = (nx, ny) is the FIRST of the four axes, in K9's order, whose t0 (after the
+ * swap) equals lo -- K9's strict t0 > lo update; sigma = sign(w) on it; the signs of the four fabs arguments of R, with sign(0) = 0.  Then
+ * t = lo = (-sigma*R - p)/w, and with N = sigma*R + p + t*w:  d t = -dN/w at constant t, that is with q = d + t*rv
+ *   dt = -( sigma*dR + n.dd + t*(n.drv) + q.dn ) / w.
+ * The 14 partials, every operation binary64 and rounded once, in this order (a: observer, e: other; hl, hw as in K9):
+ *   a1 = c_a*nx + s_a*ny, a2 = c_a*ny - s_a*nx, e1 = c_e*nx + s_e*ny, e2 = c_e*ny - s_e*nx;  inv = -1/w
+ *   ka1 = sigma*(hla*sign(a1)), ka2 = sigma*(hwa*sign(a2)), ke1 = sigma*(hle*sign(e1)), ke2 = sigma*(hwe*sign(e2))
+ *   qx = dx + t*rvx, qy = dy + t*rvy
+ *   gnx = ((ka1*c_a - ka2*s_a) + (ke1*c_e - ke2*s_e)) + qx;  gny = ((ka1*s_a + ka2*c_a) + (ke1*s_e + ke2*c_e)) + qy
+ *   nca = (ka1*nx + ka2*ny) - t*(v_a*nx), nsa = (ka1*ny - ka2*nx) - t*(v_a*ny), nce = (ke1*nx + ke2*ny) + t*(v_e*nx), nse = (ke1*ny - ke2*nx) + t*(v_e*ny)
+ *   axis 0: nca += gnx, nsa += gny;  axis 1: nsa -= gnx, nca += gny;  axis 2: nce += gnx, nse += gny;  axis 3: nse -= gnx, nce += gny
+ *   x_e: nx*inv, y_e: ny*inv, x_a: -(nx*inv), y_a: -(ny*inv);  length_a: (sigma*(0.5*|a1|))*inv, width_a: (sigma*(0.5*|a2|))*inv, length_e and
+ *   width_e likewise with e1, e2;  sin_a: nsa*inv, cos_a: nca*inv, sin_e: nse*inv, cos_e: nce*inv;  speed_a: -((t*a1)*inv), speed_e: (t*e1)*inv.
+ * Per entity j each of its seven gradients is the binary64 sum of g_ttc[slot] * partial over the contributing slots of j's own row (observer
+ * side, j < A) and of every slot of the scene whose index is j (other side), rounded to binary32 once.  The order of the sum is fixed (per lane
+ * in slot order, then a butterfly over the lanes); no atomics: two runs give the same bits.  Every output is written in full; the row of an
+ * entity with no contribution is exactly 0.
+ * Argument rules, limits and codes are K9's (horizon is not an argument); B * E == 0 is a successful no-op; with A == 0 index and g_ttc may be
+ * NULL.  One launch; nothing is allocated and nothing synchronises; every loop of the kernel is bounded by A, E and K whatever index holds, and
+ * an index outside [0, E) is never dereferenced. */
+int tds_time_to_collision_bwd_f32(const float *boxes, const float *sc, const float *speed, const int32_t *index, const float *g_ttc,
+                                  float *g_boxes, float *g_sc, float *g_speed, int64_t B, int64_t A, int64_t E, int K, float margin, void *stream);
+
 /* ---- testing hooks ------------------------------------------------------------------------------------------------------------
  * NOT part of the product: libtdship.so exports none of these.  They exist in libtdship_testing.so, the same sources compiled with
  * -DTDS_TESTING, which tools/ (ablations, work counters) and a few tests (forcing the slow code paths) load instead. */

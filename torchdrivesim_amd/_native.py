@@ -199,6 +199,8 @@ tds_lane_observations_multi(handle set, i32* scene_map, f32* agent_xy, f32* agen
     int K, int P, float spacing, float max_distance, stream stream)
 tds_time_to_collision_f32(f32* boxes, f32* sc, f32* speed, u8* present, u8* visible, f32* ttc, i32* index, int64 B, int64 A, int64 E, int K, float horizon,
     float margin, stream stream)
+tds_time_to_collision_bwd_f32(f32* boxes, f32* sc, f32* speed, i32* index, f32* g_ttc, f32* g_boxes, f32* g_sc, f32* g_speed, int64 B, int64 A, int64 E, int K,
+    float margin, stream stream)
 '''
 
 #: entry points that only libtdship_testing.so exports (include/tdship.h, "testing hooks")

@@ -731,6 +731,46 @@ def time_to_collision(boxes, sc, speed, present, n_exposed, k, horizon, margin=0
     return ttc, index
 
 
+class _TimeToCollisionGrad(torch.autograd.Function):
+    """K9 as an autograd node: forward = time_to_collision, backward = tds_time_to_collision_bwd_f32 (csrc/ttc_bwd.hip), one launch"""
+
+    @staticmethod
+    def forward(ctx, boxes, sc, speed, present, n_exposed, k, horizon, margin, visible):
+        ttc, index = time_to_collision(boxes, sc, speed, present, n_exposed, k, horizon, margin, visible=visible)
+        ctx.mark_non_differentiable(index)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(boxes, sc, speed, index)
+        ctx.margin = float(margin)
+        return ttc, index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_ttc, _g_index):
+        if g_ttc is None or not any(ctx.needs_input_grad[:3]):
+            return (None,) * 9
+        boxes, sc, speed, index = ctx.saved_tensors
+        B, A, K = index.shape
+        E = boxes.shape[1]
+        dev = boxes.device
+        g_boxes = torch.empty((B, E, 5), dtype=f32, device=dev)
+        g_sc = torch.empty((B, E, 2), dtype=f32, device=dev)
+        g_speed = torch.empty((B, E), dtype=f32, device=dev)
+        nat.call('tds_time_to_collision_bwd_f32', dev, _c(boxes.detach()), _c(sc.detach()), _c(speed.detach()), index, _c(g_ttc), g_boxes, g_sc, g_speed,
+                 B, A, E, K, ctx.margin)
+        need = ctx.needs_input_grad
+        return (g_boxes.to(boxes.dtype) if need[0] else None, g_sc.to(sc.dtype) if need[1] else None, g_speed.to(speed.dtype) if need[2] else None) + \
+            (None,) * 6
+
+
+def time_to_collision_grad(boxes, sc, speed, present, n_exposed, k, horizon, margin=0.0, visible=None):
+    """`time_to_collision`, differentiable (include/tdship.h "K9b"): the same launch and the same bits; `ttc` carries the graph to
+    `boxes` ([x, y, length, width]; the psi column gets zeros -- psi has its gradient through `sc`), to `sc` = [sin psi, cos psi] and to `speed`,
+    `index` never does.  The backward is ONE launch (tds_time_to_collision_bwd_f32).  The forward's discrete choices -- which entity is in a slot,
+    the axis that binds, the signs -- are constants.  A slot contributes iff it is filled and its time is above 0; an empty slot and a pair that
+    overlaps already contribute exactly zero whatever their incoming gradient holds.  No gradient to `margin` or `horizon`, no double backward."""
+    return _TimeToCollisionGrad.apply(boxes, sc, speed, present, n_exposed, k, horizon, margin, visible)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # K7 traffic lights on the device (csrc/lights.hip; DESIGN.md 5.5h)
 # ---------------------------------------------------------------------------------------------------------------

@@ -1347,7 +1347,8 @@ class Simulator:
         return Neighbors(*out)
 
     # ------------------------------------------------------------------------------------------------- time to collision
-    def compute_time_to_collision(self, k: int = 1, horizon: float = 5.0, margin: float = 0.0, visible: Optional[Tensor] = None) -> TimeToCollision:
+    def compute_time_to_collision(self, k: int = 1, horizon: float = 5.0, margin: float = 0.0, visible: Optional[Tensor] = None,
+                                  differentiable: bool = False) -> TimeToCollision:
         """When every exposed agent would first touch another present entity (exposed agents and NPCs) if everybody kept its current velocity
         `v * [cos psi, sin psi]` and heading: the `k` soonest within `horizon` seconds (+inf: no limit), equal times by the lower entity index:
 
@@ -1357,7 +1358,15 @@ class Simulator:
         `margin` metres are added to the observing agent's rectangle on every side.  `visible` is that of `compute_neighbors`.  Rows of exposed
         agents that are not present, or whose pose, size or speed is not finite, are empty.  1 <= k <= 32, at most 1024 entities per scene.
         One HIP kernel in binary64 (csrc/ttc.hip; the definition is in include/tdship.h "K9", tests/ttc_model.py equals it bit for bit).
-        No gradient.  Runs on the current stream and allocates its outputs only, so it can be captured into a graph."""
+        Runs on the current stream and allocates its outputs only, so it can be captured into a graph.
+
+        `differentiable=True`, with grad mode on and a state or size that requires grad: the same launch and the same bits, and `ttc` carries the
+        graph to x, y, psi (through the shared [sin psi, cos psi] node), the speed and the sizes of both entities of every slot; `index` never
+        does.  The backward is one HIP kernel (csrc/ttc_bwd.hip; include/tdship.h "K9b", held to the float64 model tests/ttc_grad_model.py).
+        Constants of differentiation: which entity is in a slot, the separating axis that binds, the sign of the closing speed on it and the
+        signs inside the projected extents; `margin` and `horizon` get no gradient.  A slot contributes iff it is filled and its time is above
+        0: an empty slot (+inf) and a pair that overlaps already (0) contribute exactly zero whatever gradient comes in.  Otherwise -- the flag
+        off, under `no_grad`, nothing requiring grad -- nothing is recorded and nothing is saved."""
         _ops.check_ttc_args(k, horizon, margin)
         state = self.get_state()
         if not state.is_cuda:
@@ -1365,6 +1374,12 @@ class Simulator:
         B, A, K = state.shape[0], self.agent_count, int(k)
         if A == 0:
             return TimeToCollision(torch.empty((B, 0, K), dtype=torch.float32, device=state.device), torch.empty((B, 0, K), dtype=torch.int32, device=state.device))
+        if differentiable and torch.is_grad_enabled():
+            all_state, size = self.get_all_agent_state(), self.get_all_agent_size()
+            if all_state.requires_grad or size.requires_grad:
+                boxes = _ops.state_boxes(all_state, size)
+                return TimeToCollision(*_ops.time_to_collision_grad(boxes, self._heading_sc(), all_state[..., 3], self.get_all_agent_present_mask(), A, K,
+                                                                    horizon, margin, visible))
         with torch.no_grad():
             all_state = self.get_all_agent_state().detach()
             boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
