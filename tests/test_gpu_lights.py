@@ -406,6 +406,17 @@ def test_wave_and_stride_boundaries(N):
     assert filled > 0
 
 
+@pytest.mark.parametrize('A', [16, 17, 33])
+def test_slices_of_observers_and_the_later_turns_of_a_wave(A):
+    """a workgroup takes 16 observers, four per wave: one full slice, a second slice with one observer, a third; B = 2, K = 4, 40 lines (by rank)
+    and 70 (in rounds), a fifth of the observers and of the lines absent"""
+    for N in (40, 70):
+        s = lm.random_scenes(5000 + 100 * A + N, 2, A, N, absent=0.2)
+        want = lm.stop_lines(**s, k=4, max_distance=60.0, ahead_only=False)
+        assert not s['agent_present'].all() and (want[1][:, 16 * ((A - 1) // 16):] >= 0).any()         # absent observers; the last slice sees a line
+        assert_slots(run(s, 4, 60.0, ahead_only=False), want, f'A={A} N={N}')
+
+
 def test_the_line_limit_and_the_arguments():
     from torchdrivesim_amd import _native as nat
     s = lm.random_scenes(9, 1, 2, 1024, duplicates=0.02)

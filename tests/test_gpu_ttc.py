@@ -74,6 +74,17 @@ def test_wave_and_stride_boundaries(E):
     assert filled > 0
 
 
+@pytest.mark.parametrize('A', [16, 17, 33])
+def test_slices_of_observers_and_the_later_turns_of_a_wave(A):
+    """a workgroup takes 16 observers, four per wave: one full slice, a second slice with one observer, a third; B = 2, K = 4, 40 entities (by
+    rank) and 70 (in rounds), a fifth of the entities absent, observers among them"""
+    for E in (40, 70):
+        s = tm.random_scenes(4000 + 100 * A + E, 2, A, E, absent=0.2)
+        want = model(s, A, 4, INF, 0.25)
+        assert not s['present'][:, :A].all() and (want[1][:, 16 * ((A - 1) // 16):A] >= 0).any()       # absent observers; the last slice meets somebody
+        assert_bits(run(s, A, 4, INF, 0.25), want, f'A={A} E={E}')
+
+
 def test_the_entity_limit():
     """E = 1024, K = 32 equals the model; E = 1025 is refused with TDS_ELIMIT"""
     from torchdrivesim_amd import _native as nat

@@ -115,6 +115,17 @@ def test_random_scenes(name, least):
     assert absent.any() and not out['g_boxes'][absent].any() and not out['g_sc'][absent].any() and not out['g_speed'][absent].any()
 
 
+def test_three_slices_of_receiving_entities():
+    """E = 33: a workgroup takes 16 receiving entities, four per wave, so two full slices and a third with entity 32 alone, which in scene 0 has a
+    speed again and is met; A = 17 observers, the forward's second slice with one"""
+    s = tm.random_scenes(3318, 2, 17, 33)
+    s['speed'][0, 32] = F32(7.5)
+    out = run(s, 17, K, HORIZON, MARGIN, seed=33)
+    forward_bits_are_todays(s, 17, K, HORIZON, MARGIN, out)
+    contributes = hold('E33', s, out, MARGIN, least=47)
+    assert (out['index'][0][contributes[0]] == 32).any() and contributes[:, 16].any()
+
+
 def test_the_visible_mask():
     s, A = tm.scenes('mask40')
     visible = np.random.default_rng(22).random((3, A, 40)) < 0.6

@@ -8,6 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from test_neighbors_resources import frame  # noqa: E402
 KERNELS = ('lights_step_kernel', 'lights_reset_kernel', 'stop_lines_kernel')
 
 
@@ -42,7 +43,7 @@ def test_the_kernels_keep_their_occupancy(table, name):
 def test_the_lds_is_what_the_design_states(table):
     """the step kernel: an int32 phase and a float32 remaining time per machine, 2 KiB for TDS_LIGHTS_MAX_MACHINES, static; the stop lines: 32 bytes
     per line, and above 64 lines a row of 4-byte keys per wave -- 48 KiB at the limit of TDS_LIGHTS_MAX_LIGHTS, within the 64 KiB a launch gets
-    without asking for more.  Read from the constants the launches are sized by."""
+    without asking for more.  Read from the constants the launches are sized by (the stop lines': csrc/tds_observers.h, with the key rows)."""
     src = open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'lights.hip')).read()
     const = {k: int(v) for k, v in re.findall(r'constexpr int (\w+) = (\d+);', src)}
     header = open(os.path.join(ROOT, 'include', 'tdship.h')).read()
@@ -50,7 +51,6 @@ def test_the_lds_is_what_the_design_states(table):
     assert limit == dict(MACHINES=256, PHASES=64, LIGHTS=1024, SKIPS=1024)
     assert const['LT_BLOCK'] == limit['MACHINES'] and table['lights_step_kernel']['group_segment_fixed_size'] == 8 * limit['MACHINES']
     assert table['lights_reset_kernel']['group_segment_fixed_size'] == 0 and table['stop_lines_kernel']['group_segment_fixed_size'] == 0
-    assert (const['SL_BLOCK'], const['SL_AGENTS'], const['SL_WORDS']) == (256, 16, 8)
-    assert 'SL_WAVES = SL_BLOCK / 64' in src and '(N > 64 ? (size_t)SL_WAVES * N * sizeof(uint32_t) : 0)' in src
-    lds = lambda N: N * const['SL_WORDS'] * 4 + (const['SL_BLOCK'] // 64 * N * 4 if N > 64 else 0)
-    assert lds(36) == 1152 and lds(65) == 65 * 48 and lds(limit['LIGHTS']) == 48 * 1024 <= 64 * 1024
+    lds = frame()
+    assert 'tds::slice_grid(B, A), dim3(tds::OBS_BLOCK), tds::lds_bytes(N, true)' in src and 'TDS_LIGHTS_MAX_LIGHTS' in src
+    assert lds(36, True) == 1152 and lds(64, True) == 2 * 1024 and lds(65, True) == 65 * 48 and lds(limit['LIGHTS'], True) == 48 * 1024 <= 64 * 1024

@@ -97,8 +97,12 @@ def test_mask_and_take_on_hand_made_tensors():
 
 
 def test_the_kernel_source_neither_allocates_nor_synchronises():
-    src = re.sub(r'//.*', '', open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'neighbors.hip')).read())
-    for word in ('hipMalloc', 'hipFree', 'hipMemset', 'hipMemcpy', 'Synchronize', 'hipHostMalloc', 'asm'):
-        assert word not in src, f'neighbors.hip mentions {word}'
-    make = open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'Makefile')).read()
-    assert '-ffp-contract=off' in make and 'neighbors.hip' in make
+    csrc = os.path.join(ROOT, 'torchdrivesim_amd', 'csrc')
+    for name in ('neighbors.hip', 'tds_observers.h'):                        # the kernel and the frame it launches in
+        src = re.sub(r'//.*', '', open(os.path.join(csrc, name)).read())
+        for word in ('hipMalloc', 'hipFree', 'hipMemset', 'hipMemcpy', 'Synchronize', 'hipHostMalloc', 'asm', 'atomic'):
+            assert word not in src, f'{name} mentions {word}'
+    assert open(os.path.join(csrc, 'neighbors.hip')).read().count('hipLaunchKernelGGL') == 1                             # one launch,
+    assert 'hipLaunchKernelGGL' not in open(os.path.join(csrc, 'tds_observers.h')).read()                                # and none in the frame
+    make = open(os.path.join(csrc, 'Makefile')).read()
+    assert '-ffp-contract=off' in make and 'neighbors.hip' in make and make.count('tds_observers.h') == 2

@@ -10,6 +10,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 
+def frame():
+    """the constants and the LDS rule of the frame the kernel launches in, asserted on csrc/tds_observers.h -> lds(n, with_key_rows) in bytes"""
+    src = open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'tds_observers.h')).read()
+    const = {k: int(v) for k, v in re.findall(r'constexpr int (\w+) = (\d+);', src)}
+    assert (const['OBS_BLOCK'], const['OBS_SLICE'], const['OBS_WORDS']) == (256, 16, 8) and 'OBS_WAVES = OBS_BLOCK / 64' in src
+    assert 'return (size_t)n * OBS_WORDS * sizeof(float) + (with_key_rows && n > 64 ? (size_t)OBS_WAVES * n * sizeof(uint32_t) : 0);' in src
+    return lambda n, with_key_rows: n * const['OBS_WORDS'] * 4 + (const['OBS_BLOCK'] // 64 * n * 4 if with_key_rows and n > 64 else 0)
+
+
 @pytest.fixture(scope='module')
 def kernel():
     import kernel_resources
@@ -36,12 +45,11 @@ def test_the_neighbor_kernel_keeps_its_occupancy(kernel):
 
 def test_the_dynamic_lds_of_a_launch_is_what_the_design_states():
     """32 bytes per entity, and above 64 entities a row of 4-byte keys per wave: 2 KiB for the workload's 64 entities, 48 KiB at the limit of
-    TDS_NEIGHBORS_MAX_ENTITIES -- within the 64 KiB a launch gets without asking for more.  Read from the constants the launch is sized by."""
+    TDS_NEIGHBORS_MAX_ENTITIES -- within the 64 KiB a launch gets without asking for more.  Read from the constants the launch is sized by
+    (csrc/tds_observers.h), with the key rows."""
     src = open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'neighbors.hip')).read()
-    const = {k: int(v) for k, v in re.findall(r'constexpr int (\w+) = (\d+);', src)}
+    lds = frame()
     header = open(os.path.join(ROOT, 'include', 'tdship.h')).read()
     limit = int(re.search(r'#define TDS_NEIGHBORS_MAX_ENTITIES (\d+)', header).group(1))
-    assert (const['NB_BLOCK'], const['NB_AGENTS'], const['NB_WORDS'], limit) == (256, 16, 8, 1024)
-    assert 'NB_WAVES = NB_BLOCK / 64' in src and '(E > 64 ? (size_t)NB_WAVES * E * sizeof(uint32_t) : 0)' in src
-    lds = lambda E: E * const['NB_WORDS'] * 4 + (const['NB_BLOCK'] // 64 * E * 4 if E > 64 else 0)
-    assert lds(64) == 2 * 1024 and lds(65) == 65 * 48 and lds(limit) == 48 * 1024 <= 64 * 1024
+    assert limit == 1024 and 'tds::slice_grid(B, A), dim3(tds::OBS_BLOCK), tds::lds_bytes(E, true)' in src and 'TDS_NEIGHBORS_MAX_ENTITIES' in src
+    assert lds(64, True) == 2 * 1024 and lds(65, True) == 65 * 48 and lds(limit, True) == 48 * 1024 <= 64 * 1024

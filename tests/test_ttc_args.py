@@ -105,11 +105,12 @@ def test_mask_min_and_take_on_hand_made_tensors():
 
 def test_the_kernel_source_neither_allocates_nor_synchronises():
     csrc = os.path.join(ROOT, 'torchdrivesim_amd', 'csrc')
-    for name in ('ttc.hip', 'tds_ttc.h'):
+    for name in ('ttc.hip', 'tds_ttc.h', 'tds_observers.h'):
         src = re.sub(r'//.*', '', open(os.path.join(csrc, name)).read())
         for word in ('hipMalloc', 'hipFree', 'hipMemset', 'hipMemcpy', 'Synchronize', 'hipHostMalloc', 'asm', 'atomic'):
             assert word not in src, f'{name} mentions {word}'
     assert 'hip' not in re.sub(r'//.*', '', open(os.path.join(csrc, 'tds_ttc.h')).read()).replace('__HIPCC__', '')      # nothing of HIP in the header
-    assert open(os.path.join(csrc, 'ttc.hip')).read().count('hipLaunchKernelGGL') == 1                                   # one launch
+    assert open(os.path.join(csrc, 'ttc.hip')).read().count('hipLaunchKernelGGL') == 1                                   # one launch,
+    assert 'hipLaunchKernelGGL' not in open(os.path.join(csrc, 'tds_observers.h')).read()                                # and none in the frame
     make = open(os.path.join(csrc, 'Makefile')).read()
-    assert '-ffp-contract=off' in make and ' ttc.hip' in make and 'tds_ttc.h' in make
+    assert '-ffp-contract=off' in make and ' ttc.hip' in make and 'tds_ttc.h' in make and make.count('tds_observers.h') == 2

@@ -9,6 +9,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from test_neighbors_resources import frame  # noqa: E402
 KERNEL = 'time_to_collision_bwd_kernel'
 
 
@@ -38,15 +39,13 @@ def test_the_kernel_keeps_its_occupancy(kernel):
 
 def test_the_dynamic_lds_of_a_launch_is_what_the_design_states():
     """32 bytes per entity and nothing else: 2 KiB for the workload's 64 entities, 32 KiB at the limit of TDS_TTC_MAX_ENTITIES -- within the
-    64 KiB a launch gets without asking for more.  Read from the constants the launch is sized by."""
+    64 KiB a launch gets without asking for more.  Read from the constants the launch is sized by (csrc/tds_observers.h), without key rows."""
     src = open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'ttc_bwd.hip')).read()
-    const = {k: int(v) for k, v in re.findall(r'constexpr int (\w+) = (\d+);', src)}
+    lds = frame()
     header = open(os.path.join(ROOT, 'include', 'tdship.h')).read()
     limit = int(re.search(r'#define TDS_TTC_MAX_ENTITIES (\d+)', header).group(1))
-    assert (const['TTCB_BLOCK'], const['TTCB_ENTITIES'], const['TTCB_WORDS'], limit) == (256, 16, 8, 1024)
-    assert 'const size_t lds = (size_t)E * TTCB_WORDS * sizeof(float);' in src
-    lds = lambda E: E * const['TTCB_WORDS'] * 4
-    assert lds(64) == 2 * 1024 and lds(limit) == 32 * 1024 <= 64 * 1024
+    assert limit == 1024 and 'tds::slice_grid(B, E), dim3(tds::OBS_BLOCK), tds::lds_bytes(E, false)' in src and 'TDS_TTC_MAX_ENTITIES' in src
+    assert all(lds(E, False) == E * 32 for E in (1, 64, 65, limit)) and lds(64, False) == 2 * 1024 and lds(limit, False) == 32 * 1024 <= 64 * 1024
     design = open(os.path.join(ROOT, 'DESIGN.md')).read()
     section = design[design.index('### 5.5l'):]
     assert '32 bytes' in section and '32 KiB' in section and '2 KiB' in section and '90 VGPRs' in section

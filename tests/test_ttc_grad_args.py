@@ -82,10 +82,11 @@ def test_the_flag_is_off_by_default_and_the_docstring_states_the_rules():
 
 def test_the_kernel_source_neither_allocates_nor_synchronises():
     csrc = os.path.join(ROOT, 'torchdrivesim_amd', 'csrc')
-    for name in ('ttc_bwd.hip', 'tds_ttc_grad.h'):
+    for name in ('ttc_bwd.hip', 'tds_ttc_grad.h', 'tds_observers.h'):
         src = re.sub(r'//.*', '', open(os.path.join(csrc, name)).read())
         for word in ('hipMalloc', 'hipFree', 'hipMemset', 'hipMemcpy', 'Synchronize', 'hipHostMalloc', 'asm', 'atomic'):
             assert word not in src, f'{name} mentions {word}'
-    assert open(os.path.join(csrc, 'ttc_bwd.hip')).read().count('hipLaunchKernelGGL') == 1                               # one launch
+    assert open(os.path.join(csrc, 'ttc_bwd.hip')).read().count('hipLaunchKernelGGL') == 1                               # one launch,
+    assert 'hipLaunchKernelGGL' not in open(os.path.join(csrc, 'tds_observers.h')).read()                                # and none in the frame
     make = open(os.path.join(csrc, 'Makefile')).read()
-    assert '-ffp-contract=off' in make and ' ttc_bwd.hip' in make and make.count('tds_ttc_grad.h') == 2
+    assert '-ffp-contract=off' in make and ' ttc_bwd.hip' in make and make.count('tds_ttc_grad.h') == 2 and make.count('tds_observers.h') == 2

@@ -8,6 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from test_neighbors_resources import frame  # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -37,15 +38,14 @@ def test_the_kernel_keeps_its_occupancy(kernel):
 
 def test_the_dynamic_lds_of_a_launch_is_what_the_design_states():
     """32 bytes per entity, and above 64 entities a row of 4-byte keys per wave: 2 KiB for the workload's 64 entities, 48 KiB at the limit of
-    TDS_TTC_MAX_ENTITIES -- within the 64 KiB a launch gets without asking for more.  Read from the constants the launch is sized by."""
+    TDS_TTC_MAX_ENTITIES -- within the 64 KiB a launch gets without asking for more.  Read from the constants the launch is sized by
+    (csrc/tds_observers.h), with the key rows."""
     src = open(os.path.join(ROOT, 'torchdrivesim_amd', 'csrc', 'ttc.hip')).read()
-    const = {k: int(v) for k, v in re.findall(r'constexpr int (\w+) = (\d+);', src)}
+    lds = frame()
     header = open(os.path.join(ROOT, 'include', 'tdship.h')).read()
     limit = int(re.search(r'#define TDS_TTC_MAX_ENTITIES (\d+)', header).group(1))
-    assert (const['TTC_BLOCK'], const['TTC_AGENTS'], const['TTC_WORDS'], limit) == (256, 16, 8, 1024)
-    assert 'TTC_WAVES = TTC_BLOCK / 64' in src and '(E > 64 ? (size_t)TTC_WAVES * E * sizeof(uint32_t) : 0)' in src
-    lds = lambda E: E * const['TTC_WORDS'] * 4 + (const['TTC_BLOCK'] // 64 * E * 4 if E > 64 else 0)
-    assert lds(64) == 2 * 1024 and lds(65) == 65 * 48 and lds(limit) == 48 * 1024 <= 64 * 1024
+    assert limit == 1024 and 'tds::slice_grid(B, A), dim3(tds::OBS_BLOCK), tds::lds_bytes(E, true)' in src and 'TDS_TTC_MAX_ENTITIES' in src
+    assert lds(64, True) == 2 * 1024 and lds(65, True) == 65 * 48 and lds(limit, True) == 48 * 1024 <= 64 * 1024
     design = open(os.path.join(ROOT, 'DESIGN.md')).read()
     section = design[design.index('### 5.5k'):]
     assert '32 bytes' in section and '48 KiB' in section and '2 KiB' in section

@@ -651,12 +651,39 @@ def range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_toler
 # ---------------------------------------------------------------------------------------------------------------
 # K6 neighbour observations
 # ---------------------------------------------------------------------------------------------------------------
+def _check_k(what, k, limit):
+    if int(k) != k or int(k) < 1 or int(k) > limit:
+        raise ValueError(f'{what}: k must be 1 .. {limit} (got {k})')
+
+
+def _check_reach(what, name, value):
+    if not float(value) >= 0.0:                         # (NaN fails the comparison; +inf is allowed)
+        raise ValueError(f'{what}: {name} must not be negative or NaN (got {value})')
+
+
+def _entity_inputs(what, boxes, sc, speed, present, n_exposed, visible):
+    """the entities of K6 and K9, checked and as the kernels read them -> boxes, sc, speed, present, visible, B, A, E"""
+    if boxes.dim() != 3 or boxes.shape[-1] != 5:
+        raise ValueError(f'{what}: boxes must be (B, E, 5), got {tuple(boxes.shape)}')
+    B, E = int(boxes.shape[0]), int(boxes.shape[1])
+    A = int(n_exposed)
+    if A < 0 or A > E:
+        raise ValueError(f'{what}: {n_exposed} exposed agents, {E} entities')
+    if tuple(sc.shape) != (B, E, 2) or tuple(speed.shape) != (B, E) or tuple(present.shape) != (B, E):
+        raise ValueError(f'{what}: sc must be ({B}, {E}, 2), speed and present ({B}, {E}), got {tuple(sc.shape)}, {tuple(speed.shape)} and '
+                         f'{tuple(present.shape)}')
+    if visible is not None:
+        if tuple(visible.shape) != (B, A, E):
+            raise ValueError(f'{what}: visible must be ({B}, {A}, {E}), got {tuple(visible.shape)}')
+        if visible.dtype not in (torch.bool, u8):
+            raise ValueError(f'{what}: visible must be bool or uint8, got {visible.dtype}')
+    return _c(boxes.detach()), _c(sc.detach()), _c(speed.detach()), _u8(present), None if visible is None else _u8(visible), B, A, E
+
+
 def check_neighbors_args(k, max_distance):
     """the argument rules of tds_neighbors_f32, on the host: raised before anything is computed or launched"""
-    if int(k) != k or int(k) < 1 or int(k) > nat.NEIGHBORS_MAX_K:
-        raise ValueError(f'neighbors: k must be 1 .. {nat.NEIGHBORS_MAX_K} (got {k})')
-    if not float(max_distance) >= 0.0:                  # (NaN fails the comparison; +inf is allowed)
-        raise ValueError(f'neighbors: max_distance must not be negative or NaN (got {max_distance})')
+    _check_k('neighbors', k, nat.NEIGHBORS_MAX_K)
+    _check_reach('neighbors', 'max_distance', max_distance)
 
 
 def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=None):
@@ -664,23 +691,8 @@ def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=Non
     sc (B,E,2) [sin, cos] of psi, speed (B,E), present (B,E), visible None or (B,A,E) bool / uint8 -> features (B,A,k,8) float32,
     index (B,A,k) int32.  No gradient; CPU tensors raise (there is no CPU fallback)."""
     check_neighbors_args(k, max_distance)
-    if boxes.dim() != 3 or boxes.shape[-1] != 5:
-        raise ValueError(f'neighbors: boxes must be (B, E, 5), got {tuple(boxes.shape)}')
-    B, E = int(boxes.shape[0]), int(boxes.shape[1])
-    A, K = int(n_exposed), int(k)
-    if A < 0 or A > E:
-        raise ValueError(f'neighbors: {n_exposed} exposed agents, {E} entities')
-    if tuple(sc.shape) != (B, E, 2) or tuple(speed.shape) != (B, E) or tuple(present.shape) != (B, E):
-        raise ValueError(f'neighbors: sc must be ({B}, {E}, 2), speed and present ({B}, {E}), got {tuple(sc.shape)}, {tuple(speed.shape)} and '
-                         f'{tuple(present.shape)}')
-    if visible is not None:
-        if tuple(visible.shape) != (B, A, E):
-            raise ValueError(f'neighbors: visible must be ({B}, {A}, {E}), got {tuple(visible.shape)}')
-        if visible.dtype not in (torch.bool, u8):
-            raise ValueError(f'neighbors: visible must be bool or uint8, got {visible.dtype}')
-    boxes, sc, speed = _c(boxes.detach()), _c(sc.detach()), _c(speed.detach())
-    present = _u8(present)
-    visible = None if visible is None else _u8(visible)
+    boxes, sc, speed, present, visible, B, A, E = _entity_inputs('neighbors', boxes, sc, speed, present, n_exposed, visible)
+    K = int(k)
     dev = boxes.device
     features = torch.empty((B, A, K, 8), dtype=f32, device=dev)
     index = torch.empty((B, A, K), dtype=i32, device=dev)
@@ -693,10 +705,8 @@ def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=Non
 # ---------------------------------------------------------------------------------------------------------------
 def check_ttc_args(k, horizon, margin):
     """the argument rules of tds_time_to_collision_f32, on the host: raised before anything is computed or launched"""
-    if int(k) != k or int(k) < 1 or int(k) > nat.TTC_MAX_K:
-        raise ValueError(f'time_to_collision: k must be 1 .. {nat.TTC_MAX_K} (got {k})')
-    if not float(horizon) >= 0.0:                       # (NaN fails the comparison; +inf is allowed)
-        raise ValueError(f'time_to_collision: horizon must not be negative or NaN (got {horizon})')
+    _check_k('time_to_collision', k, nat.TTC_MAX_K)
+    _check_reach('time_to_collision', 'horizon', horizon)
     if not math.isfinite(float(margin)):
         raise ValueError(f'time_to_collision: margin must be finite (got {margin})')
 
@@ -707,23 +717,8 @@ def time_to_collision(boxes, sc, speed, present, n_exposed, k, horizon, margin=0
     present (B,E), visible None or (B,A,E) bool / uint8 -> ttc (B,A,k) float32 (+inf in an empty slot), index (B,A,k) int32 (-1 there).
     No gradient; CPU tensors raise (there is no CPU fallback)."""
     check_ttc_args(k, horizon, margin)
-    if boxes.dim() != 3 or boxes.shape[-1] != 5:
-        raise ValueError(f'time_to_collision: boxes must be (B, E, 5), got {tuple(boxes.shape)}')
-    B, E = int(boxes.shape[0]), int(boxes.shape[1])
-    A, K = int(n_exposed), int(k)
-    if A < 0 or A > E:
-        raise ValueError(f'time_to_collision: {n_exposed} exposed agents, {E} entities')
-    if tuple(sc.shape) != (B, E, 2) or tuple(speed.shape) != (B, E) or tuple(present.shape) != (B, E):
-        raise ValueError(f'time_to_collision: sc must be ({B}, {E}, 2), speed and present ({B}, {E}), got {tuple(sc.shape)}, {tuple(speed.shape)} and '
-                         f'{tuple(present.shape)}')
-    if visible is not None:
-        if tuple(visible.shape) != (B, A, E):
-            raise ValueError(f'time_to_collision: visible must be ({B}, {A}, {E}), got {tuple(visible.shape)}')
-        if visible.dtype not in (torch.bool, u8):
-            raise ValueError(f'time_to_collision: visible must be bool or uint8, got {visible.dtype}')
-    boxes, sc, speed = _c(boxes.detach()), _c(sc.detach()), _c(speed.detach())
-    present = _u8(present)
-    visible = None if visible is None else _u8(visible)
+    boxes, sc, speed, present, visible, B, A, E = _entity_inputs('time_to_collision', boxes, sc, speed, present, n_exposed, visible)
+    K = int(k)
     dev = boxes.device
     ttc = torch.empty((B, A, K), dtype=f32, device=dev)
     index = torch.empty((B, A, K), dtype=i32, device=dev)
@@ -806,10 +801,8 @@ def lights_reset(tables, phase, remaining, scene_ids, seed, mask=None):
 
 def check_stop_lines_args(k, max_distance, min_cos):
     """the argument rules of tds_stop_lines_f32, on the host: raised before anything is computed or launched"""
-    if int(k) != k or int(k) < 1 or int(k) > nat.STOP_LINES_MAX_K:
-        raise ValueError(f'stop lines: k must be 1 .. {nat.STOP_LINES_MAX_K} (got {k})')
-    if not float(max_distance) >= 0.0:                  # (NaN fails the comparison; +inf is allowed)
-        raise ValueError(f'stop lines: max_distance must not be negative or NaN (got {max_distance})')
+    _check_k('stop lines', k, nat.STOP_LINES_MAX_K)
+    _check_reach('stop lines', 'max_distance', max_distance)
     if min_cos is not None and float(min_cos) != float(min_cos):
         raise ValueError('stop lines: min_cos must not be NaN')
 
@@ -842,14 +835,12 @@ def stop_lines(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, t
 # ---------------------------------------------------------------------------------------------------------------
 def check_lanes_args(k, n_points, spacing, max_distance):
     """the argument rules of tds_lane_observations_multi, on the host: raised before anything is computed or launched"""
-    if int(k) != k or int(k) < 1 or int(k) > nat.LANE_OBS_MAX_K:
-        raise ValueError(f'lanes: k must be 1 .. {nat.LANE_OBS_MAX_K} (got {k})')
+    _check_k('lanes', k, nat.LANE_OBS_MAX_K)
     if int(n_points) != n_points or int(n_points) < 1 or int(n_points) > nat.LANE_OBS_MAX_POINTS:
         raise ValueError(f'lanes: n_points must be 1 .. {nat.LANE_OBS_MAX_POINTS} (got {n_points})')
     if not 0.0 < float(spacing) < float('inf'):         # (NaN fails the comparison)
         raise ValueError(f'lanes: spacing must be finite and positive (got {spacing})')
-    if not float(max_distance) >= 0.0:                  # (NaN fails the comparison; +inf is allowed)
-        raise ValueError(f'lanes: max_distance must not be negative or NaN (got {max_distance})')
+    _check_reach('lanes', 'max_distance', max_distance)
 
 
 def empty_lane_observations(B, A, k, n_points, device):

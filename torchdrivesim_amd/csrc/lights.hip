@@ -3,12 +3,12 @@
 //   lights_step_kernel   one workgroup per scene: a thread per machine advances its clock (tds_lights.h: TrafficLightStateMachine.tick in float64),
 //                        then, after a barrier, a thread per light takes the colour of the LAST machine whose current phase names it.
 //   lights_reset_kernel  a thread per (scene, machine): a Philox-picked phase at its beginning.
-//   stop_lines_kernel    the K nearest stop lines of every exposed agent, in K6's layout (neighbors.hip): the scene's lines staged in LDS, one wave
-//                        per observer, which selects as K6 does (tds_select.h).  Binary32 + - * and one correctly rounded square root, every
-//                        operation rounded once (-ffp-contract=off).
+//   stop_lines_kernel    the K nearest stop lines of every exposed agent, in K6's layout (neighbors.hip): the frame of tds_observers.h over the
+//                        scene's lines.  Binary32 + - * and one correctly rounded square root, every operation rounded once
+//                        (-ffp-contract=off).
 #include "tds_common.h"
 #include "tds_lights.h"
-#include "tds_select.h"
+#include "tds_observers.h"
 #include <math.h>
 
 static_assert(TDS_LIGHTS_MAX_SKIPS == TDS_LIGHTS_MAX_SKIPS_, "tds_lights.h and tdship.h disagree");
@@ -77,11 +77,7 @@ __global__ void __launch_bounds__(LT_BLOCK) lights_reset_kernel(const int32_t *n
 }
 
 // ---------------------------------------------------------------------------------------------------------------- stop lines
-constexpr int SL_BLOCK = 256;           // 4 waves
-constexpr int SL_WAVES = SL_BLOCK / 64;
-constexpr int SL_AGENTS = 16;           // observers per workgroup: four per wave
-constexpr int SL_WORDS = 8;             // LDS words per line: x, y, length, width, sin, cos, time to change, state (int32 bits)
-using tds::NO_KEY;                      // the d2 bits of a line that is no candidate
+constexpr int SL_WORDS = tds::OBS_WORDS;        // LDS words per line: x, y, length, width, sin, cos, time to change, state (int32 bits)
 
 struct StopLineArgs {
     const float *agent_xy, *agent_sc, *lines, *line_sc, *time_to_change;
@@ -95,7 +91,7 @@ struct StopLineArgs {
 
 struct Observer { float x, y, s, c; };
 
-// the d2 bits of line n as the observer sees it, NO_KEY if it is no candidate (a NaN fails every comparison)
+// the d2 bits of line n as the observer sees it, tds::NO_KEY if it is no candidate (a NaN fails every comparison)
 __device__ __forceinline__ uint32_t key_of(const StopLineArgs &g, const float *ln, const uint8_t *mask, int n, const Observer me) {
     const float4 q = *(const float4 *)(ln + SL_WORDS * n);
     const float2 h = *(const float2 *)(ln + SL_WORDS * n + 4);
@@ -105,7 +101,7 @@ __device__ __forceinline__ uint32_t key_of(const StopLineArgs &g, const float *l
     const float cos_rel = h.y * me.c + h.x * me.s;
     bool ok = mask[n] != 0 && d2 <= g.r2 && cos_rel >= g.min_cos;
     if (g.ahead_only) ok = ok && x >= 0.0f;
-    return ok ? __float_as_uint(d2) : NO_KEY;
+    return ok ? __float_as_uint(d2) : tds::NO_KEY;
 }
 
 // slot k of the row that starts at `row` (in slots): line n (-1: an empty slot)
@@ -128,37 +124,27 @@ __device__ __forceinline__ void store_slot(const StopLineArgs &g, const float *l
     g.slot_state[row + k] = st;
 }
 
-// grid = (B, ceil(A / SL_AGENTS)); dynamic LDS = N * SL_WORDS floats, and for N > 64 another SL_WAVES * N words of keys
-__global__ void __launch_bounds__(SL_BLOCK) stop_lines_kernel(StopLineArgs g) {
+// the launch of tds_observers.h: grid = (B, ceil(A / OBS_SLICE)), dynamic LDS = lds_bytes(N, true)
+__global__ void __launch_bounds__(tds::OBS_BLOCK) stop_lines_kernel(StopLineArgs g) {
     extern __shared__ __attribute__((aligned(16))) float ln[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const tds::SliceThread t;
     const int64_t b = blockIdx.x;
     const int A = g.A, N = g.N, K = g.K;
-    for (int j = tid; j < N; j += SL_BLOCK) {
+    t.stage_items(ln, N, [&](int j) {
         const float *p = g.lines + (b * N + j) * 5;
         const float2 sc = *(const float2 *)(g.line_sc + (b * N + j) * 2);
-        *(float4 *)(ln + SL_WORDS * j) = make_float4(p[0], p[1], p[2], p[3]);
-        *(float4 *)(ln + SL_WORDS * j + 4) = make_float4(sc.x, sc.y, g.time_to_change ? g.time_to_change[b * N + j] : 0.0f,
-                                                         __int_as_float((int32_t)g.state[b * N + j]));
-    }
-    __syncthreads();
+        return tds::Item{make_float4(p[0], p[1], p[2], p[3]), make_float4(sc.x, sc.y, g.time_to_change ? g.time_to_change[b * N + j] : 0.0f,
+                                                                           __int_as_float((int32_t)g.state[b * N + j]))};
+    });
     const uint8_t *mask = g.mask + b * N;
-    uint32_t *wk = (uint32_t *)(ln + SL_WORDS * N) + wave * N;            // (N > 64 only) this wave's row of d2 bits
-    const int a0 = blockIdx.y * SL_AGENTS, a1 = min(a0 + SL_AGENTS, A);
-    for (int a = a0 + wave; a < a1; a += SL_WAVES) {                     // wave-uniform: all 64 lanes stay together below
+    t.for_slice(A, [&](int a) {
         const int64_t row = (b * A + a) * K;
         const float2 xy = *(const float2 *)(g.agent_xy + (b * A + a) * 2), sc = *(const float2 *)(g.agent_sc + (b * A + a) * 2);
         const Observer me{xy.x, xy.y, sc.x, sc.y};
-        if (g.agent_present[b * A + a] == 0) {                           // an observer that is not present: an empty row
-            if (lane < K) store_slot(g, ln, row, lane, -1, me);
-            continue;
-        }
-        const auto store = [&](int k, int n) { store_slot(g, ln, row, k, n, me); };
-        if (N <= 64)
-            tds::select_by_rank(lane < N ? key_of(g, ln, mask, lane, me) : NO_KEY, lane, K, store);
-        else
-            tds::select_by_rounds(wk, N, lane, K, [&](int n) { return key_of(g, ln, mask, n, me); }, store);
-    }
+        const auto store = [&](int k, int n, uint32_t) { store_slot(g, ln, row, k, n, me); };
+        if (g.agent_present[b * A + a] == 0) return t.empty_row(K, store);       // an observer that is not present
+        t.select_row(ln, N, K, [&](int n) { return key_of(g, ln, mask, n, me); }, store);
+    });
 }
 
 int check_lights_sizes(const char *what, int64_t B, int64_t M, int64_t P, int64_t N) {
@@ -215,16 +201,10 @@ TDS_EXPORT int tds_stop_lines_f32(const float *agent_xy, const float *agent_sc, 
                                   int32_t *slot_state, int64_t B, int64_t A, int64_t N, int K, float max_distance, int ahead_only, float min_cos,
                                   void *stream) {
     const char *what = "tds_stop_lines_f32";
-    TDS_CHECK_ARG(B >= 0 && A >= 0 && N >= 0 && B < ((int64_t)1 << 31) && A < ((int64_t)1 << 20), "%s: bad sizes B=%lld A=%lld N=%lld", what, (long long)B,
-                  (long long)A, (long long)N);
-    TDS_CHECK_ARG(K >= 1 && K <= TDS_STOP_LINES_MAX_K, "%s: K must be 1 .. %d (got %d)", what, TDS_STOP_LINES_MAX_K, K);
+    TDS_CHECK_ARG(A < ((int64_t)1 << 20), "%s: bad sizes B=%lld A=%lld N=%lld", what, (long long)B, (long long)A, (long long)N);
     TDS_CHECK_ARG(max_distance >= 0.0f, "%s: max_distance must not be negative or NaN (got %g)", what, (double)max_distance);
     TDS_CHECK_ARG(min_cos == min_cos, "%s: min_cos must not be NaN", what);
-    if (N > TDS_LIGHTS_MAX_LIGHTS) {
-        tds::set_error("%s: %lld stop lines per scene (the lines of a scene live in LDS: at most %d)", what, (long long)N, TDS_LIGHTS_MAX_LIGHTS);
-        return TDS_ELIMIT;
-    }
-    if (B == 0 || A == 0) return TDS_OK;
+    if (int rc = tds::check_frame(what, B, A, N, K, TDS_STOP_LINES_MAX_K, tds::frame_stop_lines(TDS_LIGHTS_MAX_LIGHTS), A); rc != tds::FRAME_LAUNCH) return rc;
     TDS_CHECK_ARG(agent_xy && agent_sc && agent_present && features && index && slot_state, "%s: null pointer", what);
     TDS_CHECK_ARG(N == 0 || (lines && line_sc && mask && state), "%s: null pointer", what);
     StopLineArgs g{};
@@ -233,8 +213,7 @@ TDS_EXPORT int tds_stop_lines_f32(const float *agent_xy, const float *agent_sc, 
     g.A = (int)A; g.N = (int)N; g.K = K; g.ahead_only = ahead_only != 0;
     g.r2 = max_distance * max_distance;
     g.min_cos = min_cos;
-    const size_t lds = (size_t)N * SL_WORDS * sizeof(float) + (N > 64 ? (size_t)SL_WAVES * N * sizeof(uint32_t) : 0);
-    hipLaunchKernelGGL(stop_lines_kernel, dim3((unsigned)B, (unsigned)((A + SL_AGENTS - 1) / SL_AGENTS)), dim3(SL_BLOCK), lds, (hipStream_t)stream, g);
+    hipLaunchKernelGGL(stop_lines_kernel, tds::slice_grid(B, A), dim3(tds::OBS_BLOCK), tds::lds_bytes(N, true), (hipStream_t)stream, g);
     TDS_LAUNCH_CHECK("stop_lines_kernel");
     return TDS_OK;
 }

@@ -1,4 +1,5 @@
-// The K nearest of a scene's items, selected by ONE WAVE: what neighbors.hip (K6) and lights.hip (K7, stop lines) share.  Every candidate has the
+// The K nearest of a scene's items, selected by ONE WAVE: what neighbors.hip (K6), lights.hip (K7, stop lines) and ttc.hip (K9, whose "d2" is a
+// time) share, called from the frame of tds_observers.h.  Every candidate has the
 // 64-bit key (bits of d2) << 32 | item -- d2 >= +0, so its bits order as an unsigned integer; the keys are unique -- and the K smallest keys are the
 // answer, slot 0 the nearest.  An item that is no candidate carries the d2 bits NO_KEY.  Two forms, by the number of items:
 //   up to 64    a lane per item; a lane's slot is its RANK, the number of smaller keys, counted over the CANDIDATE lanes' d2 read as wave-uniform

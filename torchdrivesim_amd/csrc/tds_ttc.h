@@ -19,6 +19,10 @@ struct TtcBox { double x, y, hl, hw, s, c, v; };
 
 // a float32 input that is a number: neither a NaN nor an infinity
 TDS_HD inline bool ttc_finite(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
+// ... all seven values of an entity: only such an entity observes, is a candidate (K9) or takes part in a pair's gradient (K9b)
+TDS_HD inline bool ttc_finite(float x, float y, float length, float width, float s, float c, float v) {
+    return ttc_finite(x) && ttc_finite(y) && ttc_finite(length) && ttc_finite(width) && ttc_finite(s) && ttc_finite(c) && ttc_finite(v);
+}
 
 // the seven float32 values of an entity, widened exactly; margin grows the box on every side (the observer's; 0 for the other entity)
 TDS_HD inline TtcBox ttc_box(float x, float y, float length, float width, float s, float c, float v, double margin) {

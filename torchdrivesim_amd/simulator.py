@@ -66,8 +66,28 @@ class RangeScan:
     hit: Tensor
 
 
+class _Slots:
+    """What the per-observer top-K results share: `index` BxAxK int32 names the item of every slot, -1 for an empty one."""
+
+    @property
+    def mask(self) -> Tensor:
+        """BxAxK bool: the slot is filled"""
+        return self.index >= 0
+
+    def take(self, per_item: Tensor, fill=0) -> Tensor:
+        """Gathers a tensor BxNx... with a row per item of a scene -- per entity, Bx(A+Npc)x..., `get_all_agent_type()` and the like; per stop
+        line, the control's `state`, `time_to_change`, ... -- at `index` -> BxAxKx..., `fill` in the empty slots."""
+        B, A, K = self.index.shape
+        if per_item.dim() < 2 or per_item.shape[0] != B:
+            raise ValueError(f'take: expected a ({B}, E, ...) tensor, got {tuple(per_item.shape)}')
+        rest = tuple(per_item.shape[2:])
+        idx = self.index.clamp(min=0).to(torch.int64).reshape((B, A * K) + (1,) * len(rest)).expand((B, A * K) + rest)
+        got = torch.gather(per_item, 1, idx).reshape((B, A, K) + rest)
+        return torch.where(self.mask.reshape((B, A, K) + (1,) * len(rest)), got, torch.full((), fill, dtype=got.dtype, device=got.device))
+
+
 @dataclass
-class Neighbors:
+class Neighbors(_Slots):
     """What `Simulator.compute_neighbors` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`) and `index` BxAxK int32, the entity
     in [0, A + Npc) of every slot, -1 for an empty one (its features are all 0)."""
     features: Tensor
@@ -75,46 +95,22 @@ class Neighbors:
 
     FEATURES = ('x', 'y', 'sin', 'cos', 'vx', 'vy', 'length', 'width')
 
-    @property
-    def mask(self) -> Tensor:
-        """BxAxK bool: the slot holds a neighbour"""
-        return self.index >= 0
-
-    def take(self, per_entity: Tensor, fill=0) -> Tensor:
-        """Gathers a per-entity tensor Bx(A+Npc)x... (`get_all_agent_type()` and the like) at `index` -> BxAxKx..., `fill` in the empty slots."""
-        B, A, K = self.index.shape
-        if per_entity.dim() < 2 or per_entity.shape[0] != B:
-            raise ValueError(f'take: expected a ({B}, E, ...) tensor, got {tuple(per_entity.shape)}')
-        rest = tuple(per_entity.shape[2:])
-        idx = self.index.clamp(min=0).to(torch.int64).reshape((B, A * K) + (1,) * len(rest)).expand((B, A * K) + rest)
-        got = torch.gather(per_entity, 1, idx).reshape((B, A, K) + rest)
-        return torch.where(self.mask.reshape((B, A, K) + (1,) * len(rest)), got, torch.full((), fill, dtype=got.dtype, device=got.device))
-
 
 @dataclass
-class TimeToCollision:
+class TimeToCollision(_Slots):
     """What `Simulator.compute_time_to_collision` returns: `ttc` BxAxK float32, the seconds until the agent first touches the entity of the slot
     (0: they overlap already), soonest first, +inf in an empty slot; `index` BxAxK int32, that entity in [0, A + Npc), -1 for an empty slot."""
     ttc: Tensor
     index: Tensor
 
     @property
-    def mask(self) -> Tensor:
-        """BxAxK bool: the slot holds an entity the agent would touch within the horizon"""
-        return self.index >= 0
-
-    @property
     def min(self) -> Tensor:
         """BxA: the agent's time to its first collision, +inf if there is none within the horizon"""
         return self.ttc[..., 0]
 
-    def take(self, per_entity: Tensor, fill=0) -> Tensor:
-        """Gathers a per-entity tensor Bx(A+Npc)x... at `index` -> BxAxKx..., `fill` in the empty slots (as `Neighbors.take`)."""
-        return Neighbors.take(self, per_entity, fill)
-
 
 @dataclass
-class StopLines:
+class StopLines(_Slots):
     """What `Simulator.compute_stop_lines` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`), `index` BxAxK int32, the stop line
     of every slot, and `state` BxAxK int32, its index into the control's `allowed_states`; -1 in both for an empty slot (its features are all 0:
     the state is kept out of them so that an empty slot cannot read as 'red' = 0)."""
@@ -124,18 +120,9 @@ class StopLines:
 
     FEATURES = ('x', 'y', 'sin', 'cos', 'length', 'width', 'time_to_change', 'distance')
 
-    @property
-    def mask(self) -> Tensor:
-        """BxAxK bool: the slot holds a stop line"""
-        return self.index >= 0
-
-    def take(self, per_line: Tensor, fill=0) -> Tensor:
-        """Gathers a per-line tensor BxNx... (the control's `state`, `time_to_change`, ...) at `index` -> BxAxKx..., `fill` in the empty slots."""
-        return Neighbors.take(self, per_line, fill)
-
 
 @dataclass
-class Lanes:
+class Lanes(_Slots):
     """What `Simulator.compute_lanes` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`), `points` BxAxKxPx2 float32, the centre
     line ahead of the foot in the agent's frame, `n_valid` BxAxK int32, how many of a slot's points are valid (the others are 0), and `index`
     BxAxK int32, the lanelet of every slot in its scene's `laneletLayer`, -1 for an empty one (its features and points are all 0)."""
@@ -145,11 +132,6 @@ class Lanes:
     index: Tensor
 
     FEATURES = ('x', 'y', 'sin', 'cos', 'arc', 'remaining', 'lateral', 'distance')
-
-    @property
-    def mask(self) -> Tensor:
-        """BxAxK bool: the slot holds a lane"""
-        return self.index >= 0
 
     @property
     def points_mask(self) -> Tensor:
@@ -1319,6 +1301,13 @@ class Simulator:
         return RangeScan(*out)
 
     # ------------------------------------------------------------------------------------------------- neighbour observations
+    def _entities_no_grad(self):
+        """all entities as K6 and K9 read them, off the graph -> boxes Bx(A+Npc)x5 [x, y, length, width, psi], [sin, cos] of psi, speed, present"""
+        with torch.no_grad():
+            all_state = self.get_all_agent_state().detach()
+            boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
+            return boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask()
+
     def compute_neighbors(self, k: int = 8, max_distance: float = 50.0, visible: Optional[Tensor] = None) -> Neighbors:
         """The `k` nearest OTHER present entities (exposed agents and NPCs) of every exposed agent within `max_distance` metres between centres
         (+inf: no limit), nearest first, equal distances by the lower entity index:
@@ -1340,11 +1329,7 @@ class Simulator:
         B, A, K = state.shape[0], self.agent_count, int(k)
         if A == 0:
             return Neighbors(torch.empty((B, 0, K, 8), dtype=torch.float32, device=state.device), torch.empty((B, 0, K), dtype=torch.int32, device=state.device))
-        with torch.no_grad():
-            all_state = self.get_all_agent_state().detach()
-            boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
-            out = _ops.neighbors(boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, max_distance, visible=visible)
-        return Neighbors(*out)
+        return Neighbors(*_ops.neighbors(*self._entities_no_grad(), A, K, max_distance, visible=visible))
 
     # ------------------------------------------------------------------------------------------------- time to collision
     def compute_time_to_collision(self, k: int = 1, horizon: float = 5.0, margin: float = 0.0, visible: Optional[Tensor] = None,
@@ -1380,12 +1365,7 @@ class Simulator:
                 boxes = _ops.state_boxes(all_state, size)
                 return TimeToCollision(*_ops.time_to_collision_grad(boxes, self._heading_sc(), all_state[..., 3], self.get_all_agent_present_mask(), A, K,
                                                                     horizon, margin, visible))
-        with torch.no_grad():
-            all_state = self.get_all_agent_state().detach()
-            boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
-            out = _ops.time_to_collision(boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, horizon, margin,
-                                         visible=visible)
-        return TimeToCollision(*out)
+        return TimeToCollision(*_ops.time_to_collision(*self._entities_no_grad(), A, K, horizon, margin, visible=visible))
 
     # ------------------------------------------------------------------------------------------------- stop-line observations
     def compute_stop_lines(self, k: int = 4, max_distance: float = 60.0, ahead_only: bool = True, min_cos: Optional[float] = None,
