@@ -17,6 +17,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py --route-to         # every agent gets the shortest route to a random on-lane destination, planned again when it strays
     python examples/step_loop.py --route-grad       # a few steps of gradient descent on the actions through the simulator, with a route loss
     python examples/step_loop.py --ttc-grad         # one step: a time-to-collision penalty differentiated to the actions through the simulator
+    python examples/step_loop.py --neighbors-grad   # one step: a keep-your-distance penalty on the neighbour features differentiated to the actions
 """
 import argparse
 import os
@@ -78,6 +79,27 @@ def ttc_grad_step(args, sim, dev):
           f'average over those agents, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
 
 
+def neighbors_grad_step(args, sim, dev):
+    """--neighbors-grad: the observation of a vector policy with its gradient.  One step: the actions are applied, every agent pays
+    (comfort - distance).clamp(min=0) for each of its K nearest neighbours closer than `comfort` metres plus a little for a closing speed, and that
+    penalty is differentiated to the actions through the backward launch of the neighbour observations and the kinematic step -- to the observer's
+    action and to the neighbour's."""
+    k, comfort = args.neighbors or 8, 15.0
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    sim.kinematic_model.set_state(sim.get_state().detach())
+    sim.step(action)
+    near = sim.compute_neighbors(k=k, max_distance=args.scan_range, differentiable=True)      # features (B, A, K, 8) with the graph, index without
+    x, y, vx = near.features[..., 0], near.features[..., 1], near.features[..., 4]
+    distance = (x * x + y * y + 1e-6).sqrt()
+    close = near.mask & (distance.detach() < comfort)                                         # an empty slot holds zeros: mask it, it is no neighbour at 0 m
+    penalty = torch.where(close, (comfort - distance).clamp(min=0) + 0.1 * (-vx * x / distance).clamp(min=0), torch.zeros_like(distance)).sum()
+    grad, = torch.autograd.grad(penalty, action)
+    involved = close.any(-1)
+    print(f'{int(near.mask.sum())} of {near.mask.numel()} neighbour slots filled within {args.scan_range:g} m, {int(close.sum())} closer than {comfort:g} m, penalty '
+          f'{float(penalty.detach()):.2f}; |d penalty / d action| {float(grad.abs().sum(-1)[involved].mean()) if bool(involved.any()) else 0.0:.4f} on average '
+          f'over the {int(involved.sum())} agents with such a neighbour, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -100,6 +122,8 @@ def main():
     ap.add_argument('--route-grad', action='store_true', help='descend a route loss (advance, lateral, heading) to the actions through the simulator')
     ap.add_argument('--ttc-grad', action='store_true', help='one step: differentiate a time-to-collision penalty (within --ttc seconds, default 5) to the '
                     'actions through the simulator (compute_time_to_collision(differentiable=True))')
+    ap.add_argument('--neighbors-grad', action='store_true', help='one step: differentiate a keep-your-distance penalty on the features of the --neighbors K '
+                    '(default 8) nearest agents to the actions through the simulator (compute_neighbors(differentiable=True))')
     args = ap.parse_args()
     if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) + (args.lanes > 0) > 1:
         ap.error('--scan, --neighbors, --stop-lines and --lanes are observations in place of the image: choose one')
@@ -147,6 +171,8 @@ def main():
         return route_grad_loop(args, sim, lanes, dev)
     if args.ttc_grad:
         return ttc_grad_step(args, sim, dev)
+    if args.neighbors_grad:
+        return neighbors_grad_step(args, sim, dev)
     routed = bool(args.route) or args.route_to
     replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller

@@ -786,6 +786,32 @@ int tds_neighbors_f32(const float *boxes, const float *sc, const float *speed, c
                       float *features, int32_t *index, int64_t B, int64_t A, int64_t E, int K, float max_distance, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * K6b  differentiable neighbour observations: the backward of K6 (float64 torch-autograd model: tests/neighbors_grad_model.py;
+ * the slot gradient is stated once, in csrc/tds_neighbors_grad.h, and its numpy restatement in tests/test_neighbors_grad_host.py equals it bit
+ * for bit).
+ * Inputs: boxes, sc, speed as K6 read them; index B x A x K int32 as K6 wrote it; g_features B x A x K x 8 float32, the incoming gradient.
+ * Outputs: g_boxes B x E x 5 (the psi column is 0: psi is not read, it gets its gradient through [sin, cos]), g_sc B x E x 2, g_speed B x E.
+ * s and c are independent inputs.  Constants of differentiation: which entity is in a slot and the max_distance cut, visible, the order of
+ * the slots.
+ * Slot (b, a, k) with e = index[b, a, k] is FILLED iff 0 <= e < E and e != a.  Every other slot -- empty, an index that is garbage --
+ * contributes exactly zero whatever its g_features holds (a NaN, an infinity), and nothing is read at its index.  A filled slot whose inputs
+ * or incoming gradients are not finite propagates what IEEE arithmetic gives.
+ * With K6's names, f2 = se*c - ce*s, f3 = ce*c + se*s, and g0 .. g7 the incoming gradient of the slot's features, every operation binary64 on
+ * the widened float32 values and rounded once, in this order:
+ *   G2 = g2 + g5*v_e, G3 = g3 + g4*v_e;  px = g0*c - g1*s, py = g0*s + g1*c
+ *   to entity e:    x: px, y: py, length: g6, width: g7, sin: G2*c + G3*s, cos: G3*c - G2*s, speed: g4*f3 + g5*f2
+ *   to observer a:  x: -px, y: -py, sin: ((g0*dy - g1*dx) - G2*ce) + G3*se, cos: ((g0*dx + g1*dy) + G2*se) + G3*ce, speed: -g4
+ * Per entity j each of its seven gradients is the binary64 sum over the filled slots of the scene whose index is j (entity side) and over the
+ * filled slots of j's own row (observer side, j < A), rounded to binary32 once.  The order of the sum is fixed (16 lanes per entity: per lane
+ * the slots that name j in slot order, then the lane's slots of j's own row, then a butterfly over the 16 lanes); no atomics: two runs give the same bits.  Every
+ * output is written in full; the row of an entity no filled slot touches is exactly 0.
+ * Argument rules, limits and codes are K6's (max_distance is not an argument); B * E == 0 is a successful no-op; with A == 0 index and
+ * g_features may be NULL and every row is written as zeros.  One launch; nothing is allocated and nothing synchronises; every loop of the
+ * kernel is bounded by A, E and K whatever index holds. */
+int tds_neighbors_bwd_f32(const float *boxes, const float *sc, const float *speed, const int32_t *index, const float *g_features,
+                          float *g_boxes, float *g_sc, float *g_speed, int64_t B, int64_t A, int64_t E, int K, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K7  traffic lights on the device (models, equal bit for bit: tests/lights_model.py).
  *
  * (a) The programmes.  M machines of at most P phases drive N lights; the tables are shared by the B scenes of a batch, the clocks are per scene:

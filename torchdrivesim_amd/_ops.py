@@ -700,6 +700,45 @@ def neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=Non
     return features, index
 
 
+class _NeighborsGrad(torch.autograd.Function):
+    """K6 as an autograd node: forward = neighbors, backward = tds_neighbors_bwd_f32 (csrc/neighbors_bwd.hip), one launch"""
+
+    @staticmethod
+    def forward(ctx, boxes, sc, speed, present, n_exposed, k, max_distance, visible):
+        features, index = neighbors(boxes, sc, speed, present, n_exposed, k, max_distance, visible=visible)
+        ctx.mark_non_differentiable(index)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(boxes, sc, speed, index)
+        return features, index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_features, _g_index):
+        if g_features is None or not any(ctx.needs_input_grad[:3]):
+            return (None,) * 8
+        boxes, sc, speed, index = ctx.saved_tensors
+        B, A, K = index.shape
+        E = boxes.shape[1]
+        dev = boxes.device
+        g_boxes = torch.empty((B, E, 5), dtype=f32, device=dev)
+        g_sc = torch.empty((B, E, 2), dtype=f32, device=dev)
+        g_speed = torch.empty((B, E), dtype=f32, device=dev)
+        nat.call('tds_neighbors_bwd_f32', dev, _c(boxes.detach()), _c(sc.detach()), _c(speed.detach()), index, _c(g_features), g_boxes, g_sc, g_speed,
+                 B, A, E, K)
+        need = ctx.needs_input_grad
+        return (g_boxes.to(boxes.dtype) if need[0] else None, g_sc.to(sc.dtype) if need[1] else None, g_speed.to(speed.dtype) if need[2] else None) + \
+            (None,) * 5
+
+
+def neighbors_grad(boxes, sc, speed, present, n_exposed, k, max_distance, visible=None):
+    """`neighbors`, differentiable (include/tdship.h "K6b"): the same launch and the same bits; `features` carries the graph to
+    `boxes` ([x, y, length, width]; the psi column gets zeros -- psi has its gradient through `sc`), to `sc` = [sin psi, cos psi] and to `speed`
+    of both entities of every filled slot, `index` never does.  The backward is ONE launch (tds_neighbors_bwd_f32).  Which entity is in a slot,
+    the `max_distance` cut, `visible` and the order of the slots are constants.  An empty slot contributes exactly zero whatever its incoming
+    gradient holds; a filled slot whose inputs are not finite propagates what IEEE arithmetic gives.  No double backward."""
+    return _NeighborsGrad.apply(boxes, sc, speed, present, n_exposed, k, max_distance, visible)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # K9 time to collision
 # ---------------------------------------------------------------------------------------------------------------

@@ -89,7 +89,8 @@ class _Slots:
 @dataclass
 class Neighbors(_Slots):
     """What `Simulator.compute_neighbors` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`) and `index` BxAxK int32, the entity
-    in [0, A + Npc) of every slot, -1 for an empty one (its features are all 0)."""
+    in [0, A + Npc) of every slot, -1 for an empty one (its features are all 0).  With `differentiable=True` `features` carries the graph to the
+    poses, speeds and sizes it was computed from; `index` never does."""
     features: Tensor
     index: Tensor
 
@@ -1308,7 +1309,7 @@ class Simulator:
             boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
             return boxes, self._heading_sc().detach(), all_state[..., 3], self.get_all_agent_present_mask()
 
-    def compute_neighbors(self, k: int = 8, max_distance: float = 50.0, visible: Optional[Tensor] = None) -> Neighbors:
+    def compute_neighbors(self, k: int = 8, max_distance: float = 50.0, visible: Optional[Tensor] = None, differentiable: bool = False) -> Neighbors:
         """The `k` nearest OTHER present entities (exposed agents and NPCs) of every exposed agent within `max_distance` metres between centres
         (+inf: no limit), nearest first, equal distances by the lower entity index:
 
@@ -1321,7 +1322,15 @@ class Simulator:
         `visible`: an optional BxAx(A+Npc) bool or uint8 tensor, non-zero where observer a may see entity e -- `get_noisy_present_mask()` of an
         occlusion noise model is one.  Rows of exposed agents that are not present are empty.  1 <= k <= 32, at most 1024 entities per scene.
         One HIP kernel in binary32 (csrc/neighbors.hip; the definition is in include/tdship.h, tests/neighbors_model.py equals it bit for bit).
-        No gradient.  Runs on the current stream and allocates its outputs only, so it can be captured into a graph."""
+        Runs on the current stream and allocates its outputs only, so it can be captured into a graph.
+
+        `differentiable=True`, with grad mode on and a state or size that requires grad: the same launch and the same bits, and `features`
+        carries the graph to x, y, psi (through the shared [sin psi, cos psi] node) and the speed of both entities of every filled slot and to
+        the size of the slot's entity; `index` never does.  The backward is one HIP kernel (csrc/neighbors_bwd.hip; include/tdship.h "K6b",
+        held to the float64 model tests/neighbors_grad_model.py).  Constants of differentiation: which entity is in a slot and the
+        `max_distance` cut, `visible`, the order of the slots.  An empty slot contributes exactly zero whatever gradient comes in, NaN and
+        inf included; a filled slot whose inputs are not finite propagates what IEEE arithmetic gives.  Otherwise -- the flag off, under
+        `no_grad`, nothing requiring grad -- nothing is recorded and nothing is saved."""
         _ops.check_neighbors_args(k, max_distance)
         state = self.get_state()
         if not state.is_cuda:
@@ -1329,6 +1338,12 @@ class Simulator:
         B, A, K = state.shape[0], self.agent_count, int(k)
         if A == 0:
             return Neighbors(torch.empty((B, 0, K, 8), dtype=torch.float32, device=state.device), torch.empty((B, 0, K), dtype=torch.int32, device=state.device))
+        if differentiable and torch.is_grad_enabled():
+            all_state, size = self.get_all_agent_state(), self.get_all_agent_size()
+            if all_state.requires_grad or size.requires_grad:
+                boxes = _ops.state_boxes(all_state, size)
+                return Neighbors(*_ops.neighbors_grad(boxes, self._heading_sc(), all_state[..., 3], self.get_all_agent_present_mask(), A, K, max_distance,
+                                                      visible))
         return Neighbors(*_ops.neighbors(*self._entities_no_grad(), A, K, max_distance, visible=visible))
 
     # ------------------------------------------------------------------------------------------------- time to collision
