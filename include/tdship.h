@@ -275,6 +275,27 @@ int tds_offroad_multi_bwd_f32(const tds_mapset_t *set, const int32_t *scene_map,
  *                      the faces that lie inside the image and span at most TDS_RASTER_SMALL_ROWS rows on the lane that scanned them, where enough
  *                      lanes of a scan step hold one; the pixels are the same either way. */
 #define TDS_RASTER_NO_SMALL_FACES 8
+/* Helper launch (optional): a second stream whose CUs the persistent bit-plane launch may use as well.  A caller that keeps the launch's stream off
+ * some CUs for other kernels (tds_stream_create with a CU mask: the infraction metrics beside the launch) passes the stream confined to those CUs; the
+ * call then enqueues the SAME kernel with the same arguments a second time, on that stream, sized for its CUs (three workgroups per CU).  Its workgroups
+ * take work items from the launch's queues like all the others -- whatever is left when they start, which is when the kernels enqueued on that stream
+ * before the call have ended -- and exit at once when nothing is.  The pixels never depend on it.
+ *   helper_stream      the hipStream_t (in).  Used only when ALL of this holds, else the call makes its one launch as before: the launch is the fused
+ *                      bit-plane kernel of a colour image (float32 or uint8) in persistent 4-wave workgroups over all the cameras (not the masks, not the
+ *                      split form or the launch over its overflowed cameras, not four workgroups per CU or eight waves, not a call with index_slices);
+ *                      a workspace was given (the queues live there); helper_stream and `stream` are two different, non-NULL streams and helper_stream
+ *                      may use at least one CU; the launch has at least 4 work items (camera, strip) per workgroup of its own grid (shorter launches
+ *                      would wait for the other stream longer than they gain); neither stream is capturing (a captured graph keeps the single launch).
+ *   helper_workgroups  filled by the call (HOST): workgroups of the second enqueue, 0 = none was made.
+ *   flags              TDS_RASTER_HAS_HELPER_STREAM: the struct the caller passes is a tds_raster_aux_helper_t (below): tds_raster_aux_t with these two
+ *                      fields behind it (the two of TDS_RASTER_HAS_CAMERA_PREP are still read only with their own flag).  Appended like those, so
+ *                      the shorter structs stay valid.
+ * Ordering, all inside the call: the helper stream waits for an event recorded on `stream` behind everything the call enqueues in front of the launch
+ * (queue clear, coverage header, prepared set-ups), and `stream` waits for an event recorded on the helper stream behind the second enqueue before the
+ * call returns -- so whatever follows the call in `stream`'s order (the next call's queue clear, a free of the workspace, of `out` or of an input)
+ * follows BOTH enqueues.  The call blocks nothing on the host.  The events are created once per (device, stream, helper stream) and kept for the life
+ * of the process.  A HIP error while forking or joining: TDS_EHIP (after a failed fork nothing is enqueued on the helper stream). */
+#define TDS_RASTER_HAS_HELPER_STREAM 16
 typedef struct tds_raster_aux {
     uint32_t *index_slices;
     int64_t index_slices_bytes;
@@ -288,6 +309,13 @@ typedef struct tds_raster_aux {
     void *camera_prep;          /* in; read only with TDS_RASTER_HAS_CAMERA_PREP */
     int64_t camera_prep_bytes;  /* in; read only with TDS_RASTER_HAS_CAMERA_PREP */
 } tds_raster_aux_t;
+/* tds_raster_aux_t with the two fields of the helper launch appended (offsets 128 and 136): what a caller that sets TDS_RASTER_HAS_HELPER_STREAM passes
+ * as `aux`, its address cast to tds_raster_aux_t *.  The library looks behind the 128 bytes only under that flag. */
+typedef struct tds_raster_aux_helper {
+    tds_raster_aux_t aux;
+    void *helper_stream;        /* in */
+    int64_t helper_workgroups;  /* out */
+} tds_raster_aux_helper_t;
 int tds_raster_index_slices_bytes(int64_t n_img, int res, int64_t *bytes);
 /* bytes of the coverage record of n_img images of res x res (0: no lines are tracked at this resolution -- res is no multiple of 32) */
 int tds_raster_coverage_bytes(int64_t n_img, int res, int64_t *bytes);
@@ -1023,6 +1051,8 @@ int tds_time_to_collision_bwd_f32(const float *boxes, const float *sc, const flo
                                                   them: wrong pixels, timing and counters only -- the difference to a plain launch is what the slopes cost */
 #define TDS_RASTER_DBG_SMALL_NO_MIDDLE_ROW 33554432 /* ... paints the row of the middle vertex, where it lies between the others, as a row of part 1: wrong
                                                   pixels -- the difference is what that row's own expressions cost */
+#define TDS_RASTER_DBG_HELPER 67108864         /* never set by a caller: the testing build sets it in the arguments of the helper enqueue (tds_raster_aux_helper_t::
+                                                  helper_stream), so that the work counters can tell its items (tds_raster_get_helper_stats) */
 #ifndef TDS_RASTER_SMALL_ROWS
 #define TDS_RASTER_SMALL_ROWS 7                /* rows (yb - yt + 1) of the largest face that is small: the persistent bit-plane kernel paints such faces
                                                   on the lane that scanned them; the flag above and the counters below go by the same test */
@@ -1039,6 +1069,11 @@ int tds_raster_set_list_lds(int lds_kb);
 int tds_raster_set_list_waves(int waves);
 /* ablation switches of K3: an OR of the TDS_RASTER_DBG_* flags above */
 int tds_raster_set_debug(int flags);
+/* the helper launch (tds_raster_aux_helper_t::helper_stream) is made from this many work items per workgroup of the launch's own grid on (product: 4; >= 0) */
+int tds_raster_set_helper_min_items(int items_per_workgroup);
+/* read and reset the counter of work items that workgroups of the helper enqueue rendered (TDS_RASTER_DBG_STATS); the two counters of
+ * tds_raster_get_prep_stats count every item, whichever enqueue took it */
+int tds_raster_get_helper_stats(unsigned long long *out1);
 /* read and reset the 16 work counters of the bit-plane kernel */
 int tds_raster_get_stats(unsigned long long *out16);
 /* read and reset the two counters of the prepared scan set-ups (TDS_RASTER_DBG_STATS): work items of the persistent bit-plane launches that used

@@ -27,6 +27,7 @@ RASTER_NO_TRIM = 1
 RASTER_REWRITE_ALL = 2
 RASTER_HAS_CAMERA_PREP = 4
 RASTER_NO_SMALL_FACES = 8
+RASTER_HAS_HELPER_STREAM = 16
 
 
 class RasterDebug(enum.IntFlag):
@@ -57,6 +58,7 @@ class RasterDebug(enum.IntFlag):
     DROP_SMALL = 8388608
     SMALL_FREE_SLOPES = 16777216
     SMALL_NO_MIDDLE_ROW = 33554432
+    HELPER = 67108864
 
 _lib = None
 
@@ -72,6 +74,13 @@ class RasterAuxPrep(RasterAux):
     """tds_raster_aux_t with the two fields appended to it for the table of prepared scan set-ups; the library reads them only when `flags` has
     RASTER_HAS_CAMERA_PREP, so the shorter RasterAux stays a valid argument"""
     _fields_ = [('camera_prep', ctypes.c_void_p), ('camera_prep_bytes', ctypes.c_int64)]
+
+
+class RasterAuxHelper(RasterAuxPrep):
+    """tds_raster_aux_helper_t: tds_raster_aux_t and, behind it, the two fields of the helper launch -- the stream whose CUs the persistent launch may
+    use as well (in) and the workgroups of the second enqueue (out, 0: none was made); read and written only when `flags` has
+    RASTER_HAS_HELPER_STREAM"""
+    _fields_ = [('helper_stream', ctypes.c_void_p), ('helper_workgroups', ctypes.c_int64)]
 
 
 # One declaration per entry point of include/tdship.h, its parameters under the header's names (tests/test_abi.py holds the table to the header).
@@ -211,6 +220,8 @@ tds_raster_set_bits_waves(int n)
 tds_raster_set_list_lds(int lds_kb)
 tds_raster_set_list_waves(int waves)
 tds_raster_set_debug(int flags)
+tds_raster_set_helper_min_items(int items_per_workgroup)
+tds_raster_get_helper_stats(host* out1)
 tds_raster_get_stats(host* out16)
 tds_raster_get_prep_stats(host* out2)
 tds_raster_get_small_stats(host* out16)

@@ -960,6 +960,15 @@ use_small_faces = True
 #: table, three alternating runs each: profiles/camera_prep_timing.json); the native path takes the table all the same and is tested.
 use_camera_prep_with_slices = False
 _camera_preps = collections.OrderedDict()
+#: The persistent bit-plane launch of a loop in `Simulator.overlap_infractions = 'reserved'` mode runs on a stream that is kept off four CUs per XCD, for
+#: the metric kernels; once those have ended (about 1.3 of the launch's 5 ms) the 32 CUs would stand idle while the launch -- bound by instruction issue
+#: since it skips the background lines -- is short of SIMDs.  With this switch on, raster_scene hands the metric stream down as the launch's helper
+#: stream (include/tdship.h, tds_raster_aux_helper_t): the same kernel is enqueued there a second time, its 96 workgroups start when the metrics end
+#: and take items from the launch's queues.  Same pixels (tests/test_gpu_helper_cus.py); not for differentiable calls, masks, the split form, or
+#: under stream capture -- the native rule is plan_raster_scene's (csrc/tds_raster_plan.h, helper_grid).
+use_helper_cus = True
+#: workgroups of the helper enqueue of the last raster_scene call of this process (0: the call made its one launch)
+last_helper_workgroups = 0
 
 
 def _camera_prep_table(dev, n_img, res, out_mode, n_keys):
@@ -1180,8 +1189,9 @@ def stream_places(stream, n: int = 8192):
 def reserved_streams(device, per_xcd: int = 4):
     """(raster_stream, metric_stream) of `device`: two torch.cuda.ExternalStream over tds_stream_create -- the first may use every CU but
     `per_xcd` per XCD, the second ONLY those (mask bit i is CU i / 8 of XCD i % 8 on MI355X, tools/cu_mask_probe.hip).  The persistent raster
-    launch holds every CU it may use until its last image is out; kept off 32 of the 256 it loses nothing (it is bound by the write stream)
-    and the metric kernels have somewhere to run beside it (Simulator.overlap_infractions = 'reserved').  Created once per device; the
+    launch holds every CU it may use until its last image is out; kept off 32 of the 256 it loses nothing where it is bound by the write stream
+    (every line stored), and where it is bound by instruction issue (background lines skipped) it gets the 32 back as soon as the metrics have
+    ended (`use_helper_cus`); the metric kernels have somewhere to run beside it (Simulator.overlap_infractions = 'reserved').  Created once per device; the
     layout is VERIFIED on the device when the streams are made (reserved_layout_ok)."""
     ent = _reserved_entry(device, per_xcd)
     if ent[0] is None:
@@ -1303,7 +1313,8 @@ def _scene_call(fn, smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc
 
 
 def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, fov, res, out_dtype=torch.float32, out=None, key_table=None,
-                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True, camera_prep=True, small_faces=True):
+                 extra_tri=None, extra_key=None, index_slices=False, trim=True, write_skipping=True, camera_prep=True, small_faces=True,
+                 helper_stream=None):
     """Fused Simulator.render: state (B,N,4), agent_sc (B,N,2), tmpl (B,N,7,2), actor_key (B,N,2) int32 bit patterns -- or (B,Nc,N,2)
     when every camera sees its own colours (custom_agent_colors) --, mask (B,Nc,N) bool/uint8, cam_xy / cam_sc (B,Nc,2)
     -> (B,Nc,3,res,res) float32 [0,255] or uint8.  extra_tri (B,Nc,K,3,2) world-space triangles with keys extra_key (B,Nc,K) int32
@@ -1313,7 +1324,10 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     cannot be served by the bit-plane kernel.
     `out` an `owned_image` buffer (float32): the lines that held background after the last render into it and hold background again are not
     stored a second time (see `use_write_skipping` for what the caller must not do to the buffer in between); write_skipping=False stores them.
-    camera_prep=False (or `use_camera_prep`): no table of prepared scan set-ups is passed -- same pixels, the set-up is computed per workgroup."""
+    camera_prep=False (or `use_camera_prep`): no table of prepared scan set-ups is passed -- same pixels, the set-up is computed per workgroup.
+    helper_stream (a torch stream confined to CUs the current stream is kept off, see `use_helper_cus`): the persistent launch is enqueued there a
+    second time, behind whatever that stream holds; the current stream waits for it before the call returns.  `last_helper_workgroups` says
+    whether the launch took it."""
     assert out_dtype in (torch.float32, torch.uint8)
     dev = cam_xy.device
     mode = nat.OUT_F32 if out_dtype == torch.float32 else nat.OUT_U8
@@ -1342,19 +1356,19 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
         nbytes = ctypes.c_int64(0)
         nat.call('tds_raster_index_slices_bytes', dev, B * Nc, int(res), ctypes.byref(nbytes))
         slices = torch.empty(nbytes.value // 4, dtype=i32, device=dev)
-        aux = nat.RasterAuxPrep(index_slices=slices.data_ptr(), index_slices_bytes=nbytes.value)
+        aux = nat.RasterAuxHelper(index_slices=slices.data_ptr(), index_slices_bytes=nbytes.value)
     if not trim:
-        aux = aux if aux is not None else nat.RasterAuxPrep()
+        aux = aux if aux is not None else nat.RasterAuxHelper()
         aux.flags = nat.RASTER_NO_TRIM
     if not (use_small_faces and small_faces):
-        aux = aux if aux is not None else nat.RasterAuxPrep()
+        aux = aux if aux is not None else nat.RasterAuxHelper()
         aux.flags |= nat.RASTER_NO_SMALL_FACES
     cov_ent = cov_rec = None
     if caller_out is not None and _owned_buffers:
         if out_dtype == torch.float32 and slices is None and B * Nc > 0:
             cov_ent, decision, cov_rec = _coverage_aux(caller_out, int(res), B * Nc, use_write_skipping and write_skipping)
             if cov_rec is not None:
-                aux = aux if aux is not None else nat.RasterAuxPrep()
+                aux = aux if aux is not None else nat.RasterAuxHelper()
                 aux.coverage, aux.coverage_bytes = cov_rec['cov'].data_ptr(), cov_rec['cov'].numel() * 4
                 if decision != 'skip':
                     aux.flags |= nat.RASTER_REWRITE_ALL
@@ -1364,16 +1378,21 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
     if use_camera_prep and camera_prep and ws is not None and B * Nc > 0 and (slices is None or use_camera_prep_with_slices):
         prep = _camera_prep_table(dev, B * Nc, int(res), mode, n_keys)
     if prep is not None:
-        aux = aux if aux is not None else nat.RasterAuxPrep()
+        aux = aux if aux is not None else nat.RasterAuxHelper()
         aux.camera_prep, aux.camera_prep_bytes = prep.data_ptr(), prep.numel()
-        aux.flags |= nat.RASTER_HAS_CAMERA_PREP          # (RasterAuxPrep: the struct has the two fields)
+        aux.flags |= nat.RASTER_HAS_CAMERA_PREP          # (the struct has the two fields)
+    if use_helper_cus and helper_stream is not None and ws is not None and slices is None and B * Nc > 0:        # (stream capture: the native call checks)
+        aux = aux if aux is not None else nat.RasterAuxHelper()
+        aux.helper_stream = helper_stream.cuda_stream
+        aux.flags |= nat.RASTER_HAS_HELPER_STREAM        # (RasterAuxHelper: the struct has the two fields)
 
     def launch(aux):
         call((ws, 0 if ws is None else ws.numel(), kt, 0 if kt is None else len(key_table), 1 if (N > 0 and actor_key.dim() == 4) else 0),
              (None if aux is None else ctypes.byref(aux),))
 
-    global raster_calls
+    global raster_calls, last_helper_workgroups
     raster_calls += 1
+    last_helper_workgroups = 0
     try:
         launch(aux)
     except nat.TdsError as e:
@@ -1392,6 +1411,8 @@ def raster_scene(smap, state, agent_sc, tmpl, actor_key, mask, cam_xy, cam_sc, f
             cov_ent['record'] = cov_rec
         except Exception:                                      # noqa: BLE001 -- no version counter after all
             pass
+    if isinstance(aux, nat.RasterAuxHelper) and aux.flags & nat.RASTER_HAS_HELPER_STREAM:
+        last_helper_workgroups = int(aux.helper_workgroups)
     if ev is not None:
         ev[1].record(torch.cuda.current_stream(dev))
         raster_events.append(ev)

@@ -1604,7 +1604,8 @@ __device__ inline bool clip_line_small(int W, int H, int &x1, int &y1, int &x2, 
 // (checked exhaustively against the iterative walk in tests/test_oracle_fill.py::test_line_rows_closed_form)
 // optional work counters (profiling hook tds_raster_get_stats of the testing build; active with debug flag TDS_RASTER_DBG_STATS)
 #ifdef TDS_TESTING
-__device__ unsigned long long g_stats[18];       // [16], [17]: work items that used their prepared record / computed their scan set-up (tds_raster_get_prep_stats)
+__device__ unsigned long long g_stats[19];       // [16], [17]: work items that used their prepared record / computed their scan set-up (tds_raster_get_prep_stats)
+                                                 // [18]: work items taken by workgroups of the helper enqueue (tds_raster_get_helper_stats)
 __device__ unsigned long long g_small_stats[16]; // small faces among the accepted ones (tds_raster_get_small_stats)
 #define TDS_STAT_LANES(W, I, V) do { if ((W).debug & TDS_RASTER_DBG_STATS) { const unsigned long long v_ = (unsigned long long)(V); if (v_) atomicAdd(&g_stats[I], v_); } } while (0)
 #define TDS_STAT(W, I, V) do { if (((W).debug & TDS_RASTER_DBG_STATS) && (W).lane == 0) atomicAdd(&g_stats[I], (unsigned long long)(V)); } while (0)
@@ -2638,6 +2639,7 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
             }
 #ifdef TDS_TESTING
             if ((c.debug & TDS_RASTER_DBG_STATS) && tid == 0) atomicAdd(&g_stats[rec != nullptr ? 16 : 17], 1ull);
+            if ((c.debug & TDS_RASTER_DBG_STATS) && (c.debug & TDS_RASTER_DBG_HELPER) && tid == 0) atomicAdd(&g_stats[18], 1ull);
 #endif
         } else {
             int strip;
@@ -3149,13 +3151,56 @@ __global__ void coverage_prepare_kernel(uint32_t *hdr, uint32_t res, uint64_t n_
     hdr[COV_MODE] = (same && !rewrite_all) ? COV_SKIP : 0u;
 }
 
+// ---- the helper enqueue of the persistent launch (include/tdship.h, tds_raster_aux_helper_t::helper_stream; the rule: plan_raster_scene, helper_grid) ----
+// The CUs of a helper stream the call may use: 0 unless it is a stream of its own, neither it nor the call's stream is the NULL stream (whose
+// implicit ordering with every other stream is not something to fork from) and neither is capturing (a captured graph keeps the single launch).
+// A capture query that fails counts as "capturing".
+int helper_stream_cus(hipStream_t s, hipStream_t helper) {
+    if (helper == nullptr || s == nullptr || helper == s) return 0;
+    for (hipStream_t q : {s, helper}) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(q, &st) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        if (st != hipStreamCaptureStatusNone) return 0;
+    }
+    return launch_cus(helper);
+}
+
+// The two events of a helper enqueue: created once per (device, call stream, helper stream) and never destroyed -- a wait on one may be in flight
+// whenever the process ends.  Each pair is recorded on one pair of streams only, so two threads that render on different streams never re-record
+// an event the other is about to wait for.  false: a HIP error (set_error has it); true with null events: the table is full, no helper launch.
+struct HelperEvents { int dev; hipStream_t s, helper; hipEvent_t fork, join; };
+bool helper_events(const char *fn, hipStream_t s, hipStream_t helper, hipEvent_t &fork, hipEvent_t &join) {
+    constexpr int MAX_PAIRS = 64;
+    static std::mutex mu;
+    static HelperEvents pairs[MAX_PAIRS];
+    static int n_pairs = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); tds::set_error("%s: no current device for the helper launch", fn); return false; }
+    std::lock_guard<std::mutex> lock(mu);
+    for (int i = 0; i < n_pairs; ++i)
+        if (pairs[i].dev == dev && pairs[i].s == s && pairs[i].helper == helper) { fork = pairs[i].fork; join = pairs[i].join; return true; }
+    fork = join = nullptr;
+    if (n_pairs == MAX_PAIRS) return true;                 // more pairs of streams than the table holds: those beyond it get no helper launch
+    hipEvent_t f = nullptr, j = nullptr;
+    if (hipEventCreateWithFlags(&f, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&j, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (f) (void)hipEventDestroy(f);                   // (never recorded: nothing waits for it)
+        tds::set_error("%s: creating the events of the helper launch failed", fn);
+        return false;
+    }
+    pairs[n_pairs++] = HelperEvents{dev, s, helper, f, j};
+    fork = f; join = j;
+    return true;
+}
+
 // The launches of a Bits or Split plan, the output tag F where `first`, else S: float / uint8_t for the image, MaskBits / MaskU8 for the masks.
 // Split: K3s lists each camera's faces, K3r rasterises the lists, and the bit-plane launch runs over the cameras whose list overflowed (normally
 // none).  cm.slices: where a float32 image's differentiable call stores its index slices (the 4-wave instantiation that does), or the masks'
-// channel table.  fn: the entry point, for the errors.
+// channel table.  fn: the entry point, for the errors.  hl (p.helper_grid > 0 only): the stream and the events of the helper enqueue.
+struct HelperLaunch { hipStream_t stream; hipEvent_t fork, join; int64_t *workgroups; };
 template <typename F, typename S>
 auto launch_bit_planes(const char *fn, const RasterPlan &p, const SceneArgsEx &a, const CommonArgs &cm, const KeyTable &kt, char *ws, int64_t qoff,
-                       bool first, bool emit_slices, hipStream_t s) {
+                       bool first, bool emit_slices, hipStream_t s, const HelperLaunch *hl = nullptr) {
     auto with_tag = [&](auto f) { if (first) f(F()); else f(S()); };
     const int64_t n_img = cm.n_img;
     const uint32_t *only = nullptr;
@@ -3178,7 +3223,24 @@ auto launch_bit_planes(const char *fn, const RasterPlan &p, const SceneArgsEx &a
     }
     uint32_t *const queue = p.persist ? (uint32_t *)(ws + qoff) : nullptr;
     if (p.persist && tds::zero_async(queue, (size_t)QUEUE_BYTES, s) != hipSuccess) { tds::set_error("%s: clearing the work queues failed", fn); return TDS_EHIP; }
-    auto go = [&](auto kern, const auto &args) { launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cm, kt, p.twp, queue, only); };
+    // The helper enqueue (persistent launches over all the cameras only: the plan says so).  FORK: everything this call and its caller enqueue in
+    // front of the launch -- the queue clear right above, the coverage header, the prepared set-ups -- lies in front of the event the helper stream
+    // waits for.  A fork that fails enqueues nothing on the helper stream.
+    const bool helped = hl != nullptr && p.helper_grid > 0 && p.persist && only == nullptr && queue != nullptr;
+    if (helped) {
+        if (hipEventRecord(hl->fork, s) != hipSuccess || hipStreamWaitEvent(hl->stream, hl->fork, 0) != hipSuccess) {
+            tds::set_error("%s: forking the helper launch failed: %s", fn, hipGetErrorString(hipGetLastError()));
+            return TDS_EHIP;
+        }
+    }
+    CommonArgs ch = cm;                     // the helper's arguments: the launch's own, bit for bit (the testing build marks them for its counters)
+#ifdef TDS_TESTING
+    ch.debug |= TDS_RASTER_DBG_HELPER;
+#endif
+    auto go = [&](auto kern, const auto &args) {
+        launch(kern, p.grid, p.nwv * 64, p.lds, s, args, cm, kt, p.twp, queue, only);
+        if (helped) launch(kern, p.helper_grid, p.nwv * 64, p.lds, hl->stream, args, ch, kt, p.twp, queue, only);
+    };
     with_tag([&](auto t) {
         using T = decltype(t);
         if constexpr (std::is_same<T, float>::value) {
@@ -3195,7 +3257,17 @@ auto launch_bit_planes(const char *fn, const RasterPlan &p, const SceneArgsEx &a
         else
             with_nb(p.nb, [&](auto nb) { go(raster_scene_bits_kernel<8, nb, T, SceneArgsEx>, a); });
     });
-    TDS_LAUNCH_CHECK("raster_scene_bits_kernel");
+    const hipError_t launched = hipGetLastError();
+    // JOIN, whatever the two enqueues returned: the call's stream goes on only behind what the helper stream was given, so nothing the helper
+    // workgroups touch (queues, prepared set-ups, coverage record, `out`, the inputs) is cleared, reused or freed in the stream's order under them
+    if (helped) {
+        if (hipEventRecord(hl->join, hl->stream) != hipSuccess || hipStreamWaitEvent(s, hl->join, 0) != hipSuccess) {
+            tds::set_error("%s: joining the helper launch failed: %s", fn, hipGetErrorString(hipGetLastError()));
+            return TDS_EHIP;
+        }
+        if (launched == hipSuccess) *hl->workgroups = p.helper_grid;
+    }
+    if (launched != hipSuccess) { tds::set_error("launch of %s failed: %s", "raster_scene_bits_kernel", hipGetErrorString(launched)); return TDS_EHIP; }
     return TDS_OK;
 }
 
@@ -3253,6 +3325,21 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
     const int64_t qoff = workspace ? queue_offset(workspace_bytes) : -1;
     PlanInput in = {n_img, res, out_mode, ok ? kt.n : -1, listed, N > 0, n_extra > 0, want_slices, workspace ? lists_room(workspace_bytes, masks) : 0, launch_cus(s)};
     in.small_faces = !(aux && (aux->flags & TDS_RASTER_NO_SMALL_FACES));
+    // the helper stream of a caller whose struct has the field (appended like the prepared set-ups'); the plan decides whether the launch takes it
+    hipStream_t helper = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int helper_cus = 0;
+    tds_raster_aux_helper_t *const auxh = (aux && (aux->flags & TDS_RASTER_HAS_HELPER_STREAM)) ? (tds_raster_aux_helper_t *)aux : nullptr;
+    if (auxh) {
+        auxh->helper_workgroups = 0;
+        helper = (hipStream_t)auxh->helper_stream;
+        if (!masks && qoff >= 0) helper_cus = helper_stream_cus(s, helper);
+        if (helper_cus > 0) {
+            if (!helper_events("tds_raster_scene", s, helper, ev_fork, ev_join)) return TDS_EHIP;
+            if (ev_fork == nullptr) helper_cus = 0;
+        }
+    }
+    in.helper_cus = helper_cus;
     const RasterPlan p = plan_raster_scene(in, g_knobs);
     if (aux && p.nb) { aux->n_keys = kt.n; aux->index_bits = p.nb; for (int i = 0; i < 16; ++i) aux->keys[i] = i < kt.n ? kt.key[i] : 0u; }
     if (p.form == RasterForm::Error) { tds::set_error(p.error, MAX_KEYS); return TDS_ELIMIT; }
@@ -3302,8 +3389,10 @@ int raster_scene_impl(const MapSource &ms, const float *state, const float *agen
         TDS_LAUNCH_CHECK("camera_prepare_kernel");
         cm.prep = aux->camera_prep;
     }
-    if (p.form == RasterForm::Split || p.form == RasterForm::Bits)
-        return launch_bit_planes<float, uint8_t>("tds_raster_scene", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_F32, want_slices, s);
+    if (p.form == RasterForm::Split || p.form == RasterForm::Bits) {
+        const HelperLaunch hl = {helper, ev_fork, ev_join, helper_cus > 0 ? &auxh->helper_workgroups : nullptr};
+        return launch_bit_planes<float, uint8_t>("tds_raster_scene", p, a, cm, kt, ws, qoff, out_mode == TDS_OUT_F32, want_slices, s, helper_cus > 0 ? &hl : nullptr);
+    }
     if (p.form == RasterForm::Binned) {
         uint32_t *counts = (uint32_t *)ws; uint4 *lists = (uint4 *)(ws + p.ws.lists);
         launch(bin_faces_kernel, (n_img + BIN_WAVES - 1) / BIN_WAVES, BIN_WAVES * 64, 0, s, a, cm, p.tw, counts, lists, (int)p.caps);
@@ -3369,6 +3458,15 @@ TDS_EXPORT int tds_raster_get_prep_stats(unsigned long long *out2) {
     unsigned long long zero[2] = {0, 0};
     if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_stats), sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: copy failed"); return TDS_EHIP; }
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 16 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_prep_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+
+// read and reset the counter of work items that workgroups of the helper enqueue took (debug flag TDS_RASTER_DBG_STATS)
+TDS_EXPORT int tds_raster_get_helper_stats(unsigned long long *out1) {
+    TDS_CHECK_ARG(out1, "tds_raster_get_helper_stats: null output");
+    unsigned long long zero[1] = {0};
+    if (hipMemcpyFromSymbol(out1, HIP_SYMBOL(g_stats), sizeof(zero), 18 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_helper_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 18 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_helper_stats: reset failed"); return TDS_EHIP; }
     return TDS_OK;
 }
 

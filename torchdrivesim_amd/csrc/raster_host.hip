@@ -43,6 +43,13 @@ TDS_EXPORT int tds_raster_set_debug(int flags) {
     return TDS_OK;
 }
 
+// work items per workgroup of the main grid from which the helper launch is made (tds_raster_aux_t::helper_stream)
+TDS_EXPORT int tds_raster_set_helper_min_items(int items_per_workgroup) {
+    TDS_CHECK_ARG(items_per_workgroup >= 0, "tds_raster_set_helper_min_items: a count >= 0");
+    g_knobs.helper_min_items_per_wg = items_per_workgroup;
+    return TDS_OK;
+}
+
 // plan_raster_scene with explicit knobs; workspace_bytes as a caller passes it (the queue tail is cut off here, as in the launch)
 TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices,
                                int64_t workspace_bytes, int cus, int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug,
@@ -50,7 +57,7 @@ TDS_EXPORT int tds_raster_plan(int64_t n_img, int res, int out_mode, int n_keys,
     TDS_CHECK_ARG(out && n_img > 0 && res > 0 && res <= 4096 && n_keys >= -1 && n_keys <= MAX_KEYS && cus > 0 &&
                   (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode)), "tds_raster_plan: bad arguments");
     const PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, lists_room(workspace_bytes, is_mask_mode(out_mode)), cus};
-    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug});
+    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug, HELPER_MIN_ITEMS_PER_WG});
     *out = tds_raster_plan_t{(int)p.form, p.tw, p.strips, p.twp, p.nwv, p.nb, p.nwv == 4 ? (p.four_per_cu ? 4 : 3) : 0, want_slices && p.form == RasterForm::Bits,
                              p.four_per_cu, p.persist, p.tws, p.lw, (int64_t)p.lds, (int64_t)p.lds_s, p.grid, p.caps, p.ws.counts, p.ws.lists, p.ws.lists3};
     return TDS_OK;
@@ -64,7 +71,7 @@ TDS_EXPORT int tds_raster_plan_small_lane(int64_t n_img, int res, int out_mode, 
                   (out_mode == TDS_OUT_F32 || out_mode == TDS_OUT_U8 || is_mask_mode(out_mode)), "tds_raster_plan_small_lane: bad arguments");
     PlanInput in = {n_img, res, out_mode, n_keys, keys_listed != 0, actors != 0, extra != 0, want_slices != 0, lists_room(workspace_bytes, is_mask_mode(out_mode)), cus};
     in.small_faces = small_faces != 0;
-    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug});
+    const RasterPlan p = plan_raster_scene(in, RasterKnobs{force_tw, bits_waves, list_waves, list_lds_kb, debug, HELPER_MIN_ITEMS_PER_WG});
     *small_lane = (p.form == RasterForm::Bits || p.form == RasterForm::Split) && p.small_lane ? 1 : 0;
     return TDS_OK;
 }

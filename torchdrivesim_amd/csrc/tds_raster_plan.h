@@ -36,9 +36,11 @@ inline size_t bits_lds_bytes(int K, int res, int twp, int nwaves, int out_mode) 
 }
 // The knobs of K3 that the testing hooks set (include/tdship.h, "testing hooks"), constants in the product: the strip width (0: automatic),
 // waves per workgroup of the bit-plane kernel and of K3r (0: by image size), K3r's LDS budget in KiB (it takes the widest strip that fits), and
-// the TDS_RASTER_DBG_* flags.
-struct RasterKnobs { int force_tw, bits_waves, list_waves, list_lds_kb, debug; };
-constexpr RasterKnobs DEFAULT_KNOBS = {0, 4, 0, 40, 0};
+// the TDS_RASTER_DBG_* flags; helper_min_items_per_wg: the helper launch is made from that many work items per workgroup of the main grid on
+// (plan_raster_scene, at helper_grid, says why 4).
+struct RasterKnobs { int force_tw, bits_waves, list_waves, list_lds_kb, debug, helper_min_items_per_wg; };
+constexpr int HELPER_MIN_ITEMS_PER_WG = 4;
+constexpr RasterKnobs DEFAULT_KNOBS = {0, 4, 0, 40, 0, HELPER_MIN_ITEMS_PER_WG};
 #ifdef TDS_TESTING
 extern __attribute__((visibility("hidden"))) RasterKnobs g_knobs;    // one per library, defined in raster_host.hip: every launch reads what the hooks set
 #else
@@ -126,6 +128,8 @@ struct PlanInput {
     int64_t workspace_bytes;    // what the lists may use, the queue tail cut off; 0: no workspace, or no room for the queues
     int cus;                    // CUs the launch may use
     bool small_faces = true;    // the caller lets small faces be painted on the lane that scanned them (off: TDS_RASTER_NO_SMALL_FACES)
+    int helper_cus = 0;         // CUs of a helper stream the launch may use as well (tds_raster_aux_helper_t::helper_stream); 0: there is none -- no such stream,
+                                // the call's own stream, a stream without a CU, or a stream that is capturing (raster.hip: helper_stream_cus)
 };
 
 struct RasterPlan {
@@ -139,6 +143,7 @@ struct RasterPlan {
     SplitLayout ws;             // Split: the workspace layout; Binned: the strip lists at ws.lists, their counts at 0
     int tws, lw; size_t lds_s;  // Split: strip width, waves and LDS per workgroup of K3r
     bool small_lane;            // the bit-plane kernel paints small faces on the lane that scanned them (raster.hip: drain_bits)
+    int64_t helper_grid;        // workgroups of the second enqueue of the persistent launch, on the helper stream; 0: none
 };
 
 // A pure function of the call's shape and the knobs: no HIP call, no global.  tests/test_raster_plan.py pins its choices,
@@ -157,6 +162,7 @@ inline RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
             p.lds -= tab;
             if (p.form == RasterForm::Split) p.lds_s -= tab;
             p.small_lane = false;                       // the mask instantiations queue every face
+            p.helper_grid = 0;                          // ... and are enqueued once
         } else if (p.form != RasterForm::Error) {
             p.form = RasterForm::Error;
             p.error = "tds_raster_scene_masks: the masks come from the bit-plane kernels only (at most %d distinct keys, listed by the caller)";
@@ -233,6 +239,16 @@ inline RasterPlan plan_raster_scene(const PlanInput &in, const RasterKnobs &k) {
             // at the headline, uint8 4.89 -> 4.69; the launch that stores every line of a float32 image is bound by HBM and neither gains nor loses
             // beyond its spread: DESIGN.md section 6), the 8-wave and the 128-VGPR instantiations do not; the caller may switch it off.
             p.small_lane = in.small_faces && nwv == 4 && !p.four_per_cu;
+            // The helper enqueue: the same kernel once more on a stream confined to CUs the launch's own stream is kept off (the metric stream of
+            // Simulator.overlap_infractions = 'reserved'), as many workgroups as are resident there.  They claim items from the same queues, so only
+            // the persistent launch over ALL the cameras of a colour image takes it: not the launch over the cameras K3s marked (one short queue),
+            // not a call that stores index slices, none without queues.  And only a launch long enough: the helper workgroups start when the helper
+            // stream's earlier kernels have ended and the call's stream waits for them at the end, so a launch of a few items per workgroup can only
+            // lose the cross-stream waits (tens of microseconds) -- from HELPER_MIN_ITEMS_PER_WG items per workgroup of the main grid on.
+            // (Why 4: DESIGN.md section 6, the table of launch times at B = 16, 64 and 256 with and without the helper.)
+            if (p.form == RasterForm::Bits && p.persist && !in.want_slices && in.helper_cus > 0 &&
+                in.n_img * p.strips >= (int64_t)k.helper_min_items_per_wg * p.grid)
+                p.helper_grid = resident_workgroups(in.helper_cus, p.lds, k);
             return p;
         }
     }

@@ -33,6 +33,9 @@ class HipRendererConfig(RendererConfig):
     #: the persistent bit-plane launch paints small map faces (lane markings' slivers) on the lane that scanned them (`_ops.use_small_faces`); the
     #: pixels are the same with it switched off
     small_faces: bool = True
+    #: in `Simulator.overlap_infractions = 'reserved'` mode the persistent launch is enqueued a second time on the metric stream, so that the CUs
+    #: reserved for the metrics render too once the metrics have ended (`_ops.use_helper_cus`); the pixels are the same with it switched off
+    helper_cus: bool = True
 
 
 @dataclass
@@ -121,12 +124,13 @@ class HipRenderer(BirdviewRenderer):
                      camera_xy: Tensor, camera_sc: Tensor, res: Optional[Resolution] = None, fov: Optional[float] = None,
                      key_table=None, differentiable: bool = False, extra_tri: Optional[Tensor] = None,
                      extra_key: Optional[Tensor] = None, key_colors: Optional[Tensor] = None, color_keys=None,
-                     out: Optional[Tensor] = None, ego_cameras: int = 0) -> Tensor:
+                     out: Optional[Tensor] = None, ego_cameras: int = 0, helper_stream=None) -> Tensor:
         """-> B x Nc x 3 x H x W.  `out`: a caller-owned contiguous B x Nc x 3 x H x W tensor of the renderer's output dtype to render into
         (the C ABI takes caller buffers, include/tdship.h; the reference allocates per call, rendering/cv2.py:52) -- not for differentiable calls.  `differentiable`: attach the K3 backward (gradients w.r.t. state[..., :2], agent_sc, camera_xy,
         camera_sc; float32 output only).  `extra_tri` (B,Nc,K,3,2) / `extra_key` (B,Nc,K): per-camera world-space triangles.
         `key_colors` (K,3) / `color_keys` (K packed keys): colour-gradient handle, see _ops.raster_scene_diff.
-        `ego_cameras` = Nc (differentiable calls): the cameras are the first Nc agents of `state` / `agent_sc` -- their gradient is folded into the agents'."""
+        `ego_cameras` = Nc (differentiable calls): the cameras are the first Nc agents of `state` / `agent_sc` -- their gradient is folded into the agents'.
+        `helper_stream` (plain calls; dropped when cfg.helper_cus is off): see _ops.raster_scene."""
         side, fov = self._side_and_fov(res, fov)
         if differentiable:
             if self.out_dtype != torch.float32:
@@ -140,7 +144,8 @@ class HipRenderer(BirdviewRenderer):
                                  key_table=key_table, extra_tri=extra_tri, extra_key=extra_key, trim=self.trim, out=out,
                                  write_skipping=bool(getattr(self.cfg, 'write_skipping', True)),
                                  camera_prep=bool(getattr(self.cfg, 'camera_prep', True)),
-                                 small_faces=bool(getattr(self.cfg, 'small_faces', True)))
+                                 small_faces=bool(getattr(self.cfg, 'small_faces', True)),
+                                 helper_stream=helper_stream if bool(getattr(self.cfg, 'helper_cus', True)) else None)
 
     def render_scene_masks(self, static_map, state: Tensor, agent_sc: Tensor, tmpl: Tensor, actor_key: Tensor, mask: Tensor, camera_xy: Tensor,
                            camera_sc: Tensor, key_channels: Dict[int, int], n_channels: int, res: Optional[Resolution] = None,

@@ -734,8 +734,11 @@ class Simulator:
     _side_streams: Dict[int, Any] = {}
     _side_priority = -1          # HIP stream priority of the side stream (-1: high)
     #: overlap_infractions = 'reserved' (round 4): the raster launch runs on a stream that is kept off `_reserved_per_xcd` CUs per XCD, the metrics on a
-    #: stream confined to exactly those (`_ops.reserved_streams`, hipExtStreamCreateWithCUMask).  The write-bound launch loses nothing on 224 of 256
-    #: CUs (tools/cu_mask_probe.hip) and the metrics -- served slowly beside the saturated write stream, but served -- finish well inside its 7 ms.
+    #: stream confined to exactly those (`_ops.reserved_streams`, hipExtStreamCreateWithCUMask).  The launch that stores every line is bound by the
+    #: write stream and loses nothing on 224 of 256 CUs (tools/cu_mask_probe.hip); the launch of a loop that renders into a ring of owned buffers
+    #: skips the background lines, is bound by instruction issue and DOES lose by them (4.9 ms alone on 256 CUs, 5.5 ms on 224: DESIGN.md section 6).
+    #: So the metric stream is handed to the launch as its helper stream (`_ops.use_helper_cus`): once the metrics have ended -- about 1.3 of the
+    #: 5 ms -- the reserved CUs run workgroups of the same launch.  The metrics lose nothing: they are enqueued first.
     _reserved_per_xcd = 4
 
     def _fork_sources(self):
@@ -1090,8 +1093,16 @@ class Simulator:
             # folds the cameras' gradient into the agents' (no slice nodes for camera_xy / camera_sc in the graph)
             ego_n = n_cam if (_ego and diff and scene['ctrl'] is None and n_cam <= state.shape[1]) else 0
             k, ktab, extra = self._launch_keys(scene, n_cam, custom_agent_colors, wp_tri)
+            # 'reserved' and a plain launch that goes to the stream kept off the reserved CUs (the loop's own stream, or the detour below): the
+            # metric stream -- the foreseen metrics are on it by now -- is the launch's helper stream (`_ops.use_helper_cus`)
+            helper = None
+            if self.overlap_infractions == 'reserved' and not diff and state.is_cuda and self._reserved_usable(state.device):
+                rs0, ms0 = _ops.reserved_streams(state.device, Simulator._reserved_per_xcd)
+                if torch.cuda.current_stream(state.device) == rs0 or (self._fork is not None and self._fork[2] != rs0):
+                    helper = ms0
             launch = lambda: self.renderer.render_scene(scene['map'], state, agent_sc, tmpl_all, k, mask.contiguous(), camera_xy, camera_sc,     # noqa: E731
-                                                        res=res, fov=fov, key_table=ktab, differentiable=diff, **extra, out=out, ego_cameras=ego_n)
+                                                        res=res, fov=fov, key_table=ktab, differentiable=diff, **extra, out=out, ego_cameras=ego_n,
+                                                        helper_stream=helper)
             if self.overlap_infractions == 'reserved' and not diff and self._fork is not None and state.is_cuda and \
                     self._fork[2] != _ops.reserved_streams(state.device, Simulator._reserved_per_xcd)[0]:
                 # the launch goes to the stream that is kept off the reserved CUs: it waits for what the caller's stream has enqueued so far
