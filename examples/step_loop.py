@@ -18,6 +18,7 @@ lane map); the "policy" is random.
     python examples/step_loop.py --route-grad       # a few steps of gradient descent on the actions through the simulator, with a route loss
     python examples/step_loop.py --ttc-grad         # one step: a time-to-collision penalty differentiated to the actions through the simulator
     python examples/step_loop.py --neighbors-grad   # one step: a keep-your-distance penalty on the neighbour features differentiated to the actions
+    python examples/step_loop.py --lanes 6 --lanes-grad     # one step: a lane-keeping penalty on the lane features differentiated to the actions
 """
 import argparse
 import os
@@ -100,6 +101,27 @@ def neighbors_grad_step(args, sim, dev):
           f'over the {int(involved.sum())} agents with such a neighbour, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
 
 
+def lanes_grad_step(args, sim, dev):
+    """--lanes-grad: the map half of a vector policy's observation with its gradient.  One step: the actions are applied, every agent pays
+    lateral^2 + sin_rel^2 of the nearest lane that runs its way (cos_rel > 0) -- "stay centred, face along the lane" -- and that penalty is
+    differentiated to the actions through the backward launch of the lane observations and the kinematic step.  The map is constant, so an
+    agent's penalty reaches its own action alone."""
+    k = args.lanes or 6
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    sim.kinematic_model.set_state(sim.get_state().detach())
+    sim.step(action)
+    lanes = sim.compute_lanes(k=k, differentiable=True)                   # features and points with the graph, n_valid and index without
+    lateral, sin_rel, cos_rel = lanes.features[..., 6], lanes.features[..., 2], lanes.features[..., 3]
+    along = lanes.mask & (cos_rel.detach() > 0)                           # an empty slot holds zeros: mask it, it is no lane at 0 m
+    first = along & (along.cumsum(-1) == 1)                               # the nearest such lane: the slots are nearest first
+    penalty = torch.where(first, lateral * lateral + sin_rel * sin_rel, torch.zeros_like(lateral)).sum()
+    grad, = torch.autograd.grad(penalty, action)
+    on_lane = first.any(-1)
+    print(f'{int(lanes.mask.sum())} of {lanes.mask.numel()} lane slots filled, {int(on_lane.sum())} of {on_lane.numel()} agents with a lane that runs their way, '
+          f'penalty {float(penalty.detach()):.2f}; |d penalty / d action| {float(grad.abs().sum(-1)[on_lane].mean()) if bool(on_lane.any()) else 0.0:.4f} on '
+          f'average over those agents, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -124,6 +146,8 @@ def main():
                     'actions through the simulator (compute_time_to_collision(differentiable=True))')
     ap.add_argument('--neighbors-grad', action='store_true', help='one step: differentiate a keep-your-distance penalty on the features of the --neighbors K '
                     '(default 8) nearest agents to the actions through the simulator (compute_neighbors(differentiable=True))')
+    ap.add_argument('--lanes-grad', action='store_true', help='one step: differentiate a lane-keeping penalty on lateral and sin_rel of the nearest of the '
+                    '--lanes K (default 6) lanes to the actions through the simulator (compute_lanes(differentiable=True))')
     args = ap.parse_args()
     if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) + (args.lanes > 0) > 1:
         ap.error('--scan, --neighbors, --stop-lines and --lanes are observations in place of the image: choose one')
@@ -173,6 +197,8 @@ def main():
         return ttc_grad_step(args, sim, dev)
     if args.neighbors_grad:
         return neighbors_grad_step(args, sim, dev)
+    if args.lanes_grad:
+        return lanes_grad_step(args, sim, dev)
     routed = bool(args.route) or args.route_to
     replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller

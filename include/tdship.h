@@ -952,6 +952,45 @@ int tds_lane_observations_multi(const tds_laneset_t *set, const int32_t *scene_m
                                 int64_t A, int K, int P, float spacing, float max_distance, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * K8b  differentiable lane observations: the backward of K8 (float64 torch-autograd model: tests/lane_obs_grad_model.py; the
+ * contributions of a slot and of a point are stated once, in csrc/tds_lane_obs_grad.h, and their numpy restatement in
+ * tests/test_lane_obs_grad_host.py equals them bit for bit).  The map is constant: the gradient goes to the observing agent's own pose alone.
+ * Inputs: agent_xy, agent_sc as K8 read them; index B x A x K int32 as K8 wrote it; g_features B x A x K x 8 and g_points B x A x K x P x 2
+ * float32, the incoming gradients -- either may be NULL, which reads as all zero.
+ * g_features must be 16-byte aligned and g_points 8-byte aligned (a slot's features are read as two 16-byte loads, a point as one of 8).
+ * Outputs: g_xy B x A x 2 and g_sc B x A x 2 float32.  Every element is written; the row of an observer with no contributing slot is exactly 0.
+ * s and c are independent inputs.  Constants of differentiation: which lanelet is in a slot and the order of the slots, the max_distance cut,
+ * the foot's segment sb, whether u was clamped, and for every point its validity, the lanelet its walk ends on and the segment k there.
+ * Slot (b, a, k) with l = index[b, a, k] is FILLED iff the scene has a lane table, 0 <= l < n of that table and l is a candidate in K8's sense
+ * (eligible, no excluded tag, a d2 below +inf for this pose) and none of x, y, s, c is a NaN.  Every other slot -- empty, an index that is
+ * garbage, a scene without a table, a NaN pose -- contributes exactly zero whatever its incoming gradients hold (a NaN, an infinity), and nothing is read at its index.  Whether a
+ * point is valid comes from redoing K8's walk with K8's arithmetic (n_valid is not an input); an invalid point contributes exactly zero.  A
+ * filled slot or valid point whose incoming gradient is not finite propagates what IEEE arithmetic gives.
+ * With K8's names, every operation binary64 on the widened float32 values and rounded once, in this order.  Per filled slot, with (dx, dy), l2,
+ * (fx, fy), d2 of segment sb, (tx, ty), W = cum[sb + 1] - cum[sb], and g0 .. g7 the incoming gradient of its features:
+ *   u0 = l2 > 0 ? ((x - ax)*dx + (y - ay)*dy) / l2 : 0;  m = l2 > 0 and 0 < u0 < 1                 (the unclamped u: a NaN gives m = 0)
+ *   a = m ? ((W*dx) / l2, (W*dy) / l2) : (0, 0)                                                      (d arc / d(x, y))
+ *   qx = g0*c - g1*s, qy = g0*s + g1*c;  tq = tx*qx + ty*qy;  G = g4 - g5;  dist = sqrt(d2)
+ *   x: ((m ? tq*tx - qx : -qx) + G*a.x) - g6*ty, then - g7*(fx / dist) iff dist > 0
+ *   y: ((m ? tq*ty - qy : -qy) + G*a.y) + g6*tx, then - g7*(fy / dist) iff dist > 0
+ *   sin: (g0*fy - g1*fx) + (g3*ty - g2*tx);   cos: (g0*fx + g1*fy) + (g2*ty + g3*tx)
+ * (d f / d(x, y) = m t t^T - I.  distance's term m*(f.t)*t / dist is left out: f is perpendicular to t wherever m = 1, so the term is zero in
+ * exact arithmetic.  An agent exactly on a centre line, dist == 0, gets nothing through feature 7 and no NaN.)
+ * Per valid point j of the slot on segment k of its final lanelet, w = cum[k + 1] - cum[k], with (gx, gy) its incoming gradient:
+ *   h = w > 0 ? ((px_(k+1) - px_k) / w, (py_(k+1) - py_k) / w) : (0, 0);  rx = gx*c - gy*s, ry = gx*s + gy*c;  hr = hx*rx + hy*ry
+ *   x: hr*a.x - rx;  y: hr*a.y - ry;  sin: gx*ey - gy*ex;  cos: gx*ex + gy*ey
+ * (hr * a is the polyline sliding along the lane as the agent moves; it vanishes where the foot is clamped.)
+ * Per observer each of its four gradients is the binary64 sum of these contributions, rounded to binary32 once, in a fixed order: 64 lanes;
+ * lane i first takes the features of slot i (i < K), then the pairs (slot, point) = i, i + 64, ... of the row-major K x P pairs in ascending
+ * order, each sum starting at 0; then a butterfly over the 64 lanes (xor 32, 16, 8, 4, 2, 1).  No atomics: two runs give the same bits.
+ * Argument rules, limits and codes are K8's (max_distance and present are not arguments: an absent observer's slots are empty); B * A == 0 is a
+ * successful no-op.  One launch; nothing is allocated and nothing synchronises; every loop of the kernel is bounded by the table's sizes, K, P
+ * or the hop limit whatever index holds. */
+int tds_lane_observations_bwd_multi(const tds_laneset_t *set, const int32_t *scene_map, const float *agent_xy, const float *agent_sc,
+                                    const int32_t *index, const float *g_features, const float *g_points, float *g_xy, float *g_sc, int64_t B,
+                                    int64_t A, int K, int P, float spacing, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K9  time to collision (no reference counterpart: the definition is this library's own; float64 model, equal bit for bit:
  * tests/ttc_model.py; the pair test is stated once, in csrc/tds_ttc.h).  For every exposed agent the K other entities it would touch first
  * within `horizon` seconds, soonest first, and when -- every entity keeping its velocity v * [cos psi, sin psi] and its heading.

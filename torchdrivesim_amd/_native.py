@@ -207,6 +207,8 @@ tds_stop_lines_f32(f32* agent_xy, f32* agent_sc, u8* agent_present, f32* lines, 
     i32* slot_state, int64 B, int64 A, int64 N, int K, float max_distance, int ahead_only, float min_cos, stream stream)
 tds_lane_observations_multi(handle set, i32* scene_map, f32* agent_xy, f32* agent_sc, u8* present, f32* features, f32* points, i32* n_valid, i32* index, int64 B, int64 A,
     int K, int P, float spacing, float max_distance, stream stream)
+tds_lane_observations_bwd_multi(handle set, i32* scene_map, f32* agent_xy, f32* agent_sc, i32* index, f32* g_features, f32* g_points, f32* g_xy, f32* g_sc, int64 B, int64 A,
+    int K, int P, float spacing, stream stream)
 tds_time_to_collision_f32(f32* boxes, f32* sc, f32* speed, u8* present, u8* visible, f32* ttc, i32* index, int64 B, int64 A, int64 E, int K, float horizon,
     float margin, stream stream)
 tds_time_to_collision_bwd_f32(f32* boxes, f32* sc, f32* speed, i32* index, f32* g_ttc, f32* g_boxes, f32* g_sc, f32* g_speed, int64 B, int64 A, int64 E, int K,

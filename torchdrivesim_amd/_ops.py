@@ -912,6 +912,53 @@ def lane_observations(lane_set, agent_xy, agent_sc, present, k, n_points, spacin
     return features, points, n_valid, index
 
 
+def _aligned(t):
+    """t, or a copy of it where its data does not start at a multiple of 16 bytes (a contiguous view at an odd storage offset): the backward kernel
+    reads a slot's incoming gradients as 16-byte loads"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _LaneObservationsGrad(torch.autograd.Function):
+    """K8 as an autograd node: forward = lane_observations, backward = tds_lane_observations_bwd_multi (csrc/lane_obs_bwd.hip), one launch"""
+
+    @staticmethod
+    def forward(ctx, agent_xy, agent_sc, lane_set, present, k, n_points, spacing, max_distance):
+        features, points, n_valid, index = lane_observations(lane_set, agent_xy, agent_sc, present, k, n_points, spacing, max_distance)
+        ctx.mark_non_differentiable(n_valid, index)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(agent_xy, agent_sc, index)
+        # holding the set keeps the device tables alive until the backward
+        ctx.lane_set, ctx.scene_map = lane_set, _scene_map(lane_set, index.shape[0], 'lane_observations')
+        ctx.n_points, ctx.spacing = int(n_points), float(spacing)
+        return features, points, n_valid, index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_features, g_points, _g_n_valid, _g_index):
+        if (g_features is None and g_points is None) or not any(ctx.needs_input_grad[:2]):
+            return (None,) * 8
+        agent_xy, agent_sc, index = ctx.saved_tensors
+        B, A, K = index.shape
+        dev = index.device
+        g_xy = torch.empty((B, A, 2), dtype=f32, device=dev)
+        g_sc = torch.empty((B, A, 2), dtype=f32, device=dev)
+        nat.call('tds_lane_observations_bwd_multi', dev, ctx.lane_set.handle, ctx.scene_map, _c(agent_xy.detach()), _c(agent_sc.detach()), index,
+                 None if g_features is None else _aligned(_c(g_features)), None if g_points is None else _aligned(_c(g_points)), g_xy, g_sc, B, A, K,
+                 ctx.n_points, ctx.spacing)
+        need = ctx.needs_input_grad
+        return (g_xy.to(agent_xy.dtype) if need[0] else None, g_sc.to(agent_sc.dtype) if need[1] else None) + (None,) * 6
+
+
+def lane_observations_grad(lane_set, agent_xy, agent_sc, present, k, n_points, spacing, max_distance):
+    """`lane_observations`, differentiable (include/tdship.h "K8b"): the same launch and the same bits; `features` and `points`
+    carry the graph to `agent_xy` and to `agent_sc` = [sin psi, cos psi] of the observing agent -- the map is constant --, `n_valid` and `index`
+    never do.  The backward is ONE launch (tds_lane_observations_bwd_multi).  Which lanelet is in a slot and the order of the slots, the
+    `max_distance` cut, the foot's segment, whether the foot was clamped to a segment's end and, for every point, its validity and the segment it
+    lies on are constants.  An empty slot and an invalid point contribute exactly zero whatever their incoming gradient holds.  No double
+    backward."""
+    return _LaneObservationsGrad.apply(agent_xy, agent_sc, lane_set, present, k, n_points, spacing, max_distance)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # K3 rasteriser
 # ---------------------------------------------------------------------------------------------------------------

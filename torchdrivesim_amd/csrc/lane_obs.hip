@@ -13,7 +13,7 @@
 //   points   the K x P (slot, point) pairs spread over the lanes, each pair walking from its slot's lanelet over at most TDS_LANE_OBS_MAX_HOPS
 //            unique successors to its own arc length; n_valid is counted from the wave's ballots of the valid pairs.
 // Lane-table arithmetic is binary64, every operation rounded once (-ffp-contract=off); every output float is the double rounded once.
-#include "tds_lanes.h"
+#include "tds_lane_obs.h"
 #include "tds_select.h"
 
 namespace {
@@ -21,6 +21,8 @@ namespace {
 using tds::LaneRec;
 using tds::LaneView;
 using tds::NO_KEY;
+using tds::usable;       // (tds_lane_obs.h: what K8 shares with its backward)
+using tds::wave_foot;
 
 constexpr int LO_BLOCK = 256;           // 4 waves = 4 observers
 constexpr int LO_WAVES = LO_BLOCK / 64;
@@ -40,29 +42,6 @@ struct LaneObsArgs {
     int A, K, P, key_stride;
     double spacing, reach, r2;          // reach = max_distance + LO_BOX_MARGIN, r2 = max_distance^2
 };
-
-// a lanelet K8 looks at: drivable and without an excluded tag (the rule of tds_lane_snap)
-__device__ __forceinline__ bool usable(const LaneView &v, int l, const LaneRec &r) { return !(r.flags & 1) && tds::drivable(v, l); }
-
-// the foot of (x, y) on the centre line of lanelet record r, found by the WHOLE WAVE (all 64 lanes call together; r, x, y are the same in every
-// lane): lane i takes the segments i, i + 64, ... in ascending order, then a wave-wide minimum of (d2, segment) -- the smallest d2, the earliest
-// segment on ties, what one pass over the segments in ascending order gives: every d2 is the same number whichever lane computes it.  The result
-// is the same in every lane; false if no d2 is below +inf.
-__device__ __forceinline__ bool wave_foot(const LaneView &v, const LaneRec &r, double x, double y, int lane, int &sb, double &d2) {
-    const double *cl = v.cl + 3 * (int64_t)r.cl_start;
-    d2 = INFINITY, sb = 0x7fffffff;
-    for (int i = lane; i + 1 < r.cl_n; i += 64) {
-        const double d = tds::segment_foot(cl, i, x, y).d2;
-        if (d < d2) d2 = d, sb = i;
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const double od = __shfl_xor(d2, m, 64);
-        const int oi = __shfl_xor(sb, m, 64);
-        if (od < d2 || (od == d2 && oi < sb)) d2 = od, sb = oi;
-    }
-    return sb != 0x7fffffff;
-}
 
 // whether lanelet l can be a candidate in range at all, before its centre line is touched: inside the record's box grown by `reach`, and usable
 __device__ __forceinline__ bool worth_a_look(const LaneView &v, int l, double x, double y, double reach) {
@@ -163,34 +142,11 @@ __global__ void __launch_bounds__(LO_BLOCK) lane_obs_kernel(LaneObsArgs g) {
         float2 pt = make_float2(0.0f, 0.0f);
         if (pair < pairs) {
             const int k = pair / P, j = pair - k * P;
-            int cur = item[k];
+            const int cur = item[k];
             if (cur >= 0) {
-                const double q = arcs[k] + (double)j * g.spacing;
-                LaneRec r = v.rec[cur];
-                double base = 0.0, len = v.cum[r.cl_start + r.cl_n - 1];
-                valid = true;
-                for (int hops = 0; q - base > len; ++hops) {         // at most TDS_LANE_OBS_MAX_HOPS hops
-                    int nxt = -1;
-                    if (hops < TDS_LANE_OBS_MAX_HOPS && v.succ_start) {
-                        const int s0 = v.succ_start[cur];
-                        if (v.succ_start[cur + 1] - s0 == 1) nxt = v.succ_items[s0];
-                    }
-                    if (nxt < 0 || nxt >= v.n) { valid = false; break; }
-                    const LaneRec rn = v.rec[nxt];
-                    if (!usable(v, nxt, rn)) { valid = false; break; }
-                    base += len, cur = nxt, r = rn, len = v.cum[r.cl_start + r.cl_n - 1];
-                }
-                if (valid) {
-                    const double *cum = v.cum + r.cl_start, *cl = v.cl + 3 * (int64_t)r.cl_start;
-                    const double pos = q - base;
-                    const int sg = tds::segment_of(cum, r.cl_n, pos);
-                    const double *a = cl + 3 * sg;
-                    const double w = cum[sg + 1] - cum[sg];
-                    const double t = w > 0.0 ? (pos - cum[sg]) / w : 0.0;
-                    const double wx = a[0] + t * (a[3] - a[0]), wy = a[1] + t * (a[4] - a[1]);
-                    const double ex = wx - x, ey = wy - y;
-                    pt = make_float2((float)(ex * c + ey * s), (float)(ey * c - ex * s));
-                }
+                tds::LanePoint p;
+                valid = tds::lane_point(v, cur, arcs[k] + (double)j * g.spacing, x, y, p);       // at most TDS_LANE_OBS_MAX_HOPS hops
+                if (valid) pt = make_float2((float)(p.ex * c + p.ey * s), (float)(p.ey * c - p.ex * s));
             }
             *(float2 *)(g.points + ((row * P) + pair) * 2) = pt;
         }

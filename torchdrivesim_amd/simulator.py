@@ -12,6 +12,7 @@
     compute_neighbors  -> K6 (csrc/neighbors.hip), the K nearest entities per agent   reference: -- (get_all_agents_relative, all pairs)
     compute_stop_lines -> K7 (csrc/lights.hip), the K nearest stop lines per agent    reference: --
     compute_lanes      -> K8 (csrc/lane_obs.hip), the K nearest lanes per agent as polylines  reference: --
+                          (differentiable=True: backward K8b, csrc/lane_obs_bwd.hip)
     compute_time_to_collision -> K9 (csrc/ttc.hip), when each agent would first touch another entity  reference: --
     compute_wrong_way  -> lane tables of `lanelet_map` (lanelet2.py), one launch  reference: simulator.py:607-630 (Python triple loop)
 
@@ -126,7 +127,9 @@ class StopLines(_Slots):
 class Lanes(_Slots):
     """What `Simulator.compute_lanes` returns: `features` BxAxKx8 float32 (the columns are `FEATURES`), `points` BxAxKxPx2 float32, the centre
     line ahead of the foot in the agent's frame, `n_valid` BxAxK int32, how many of a slot's points are valid (the others are 0), and `index`
-    BxAxK int32, the lanelet of every slot in its scene's `laneletLayer`, -1 for an empty one (its features and points are all 0)."""
+    BxAxK int32, the lanelet of every slot in its scene's `laneletLayer`, -1 for an empty one (its features and points are all 0).  From
+    `compute_lanes(differentiable=True)` `features` and `points` can carry an autograd graph to the observing agent's pose; `n_valid` and `index`
+    never do."""
     features: Tensor
     points: Tensor
     n_valid: Tensor
@@ -1432,7 +1435,7 @@ class Simulator:
         return StopLines(*out)
 
     # ------------------------------------------------------------------------------------------------- lane observations
-    def compute_lanes(self, k: int = 6, n_points: int = 8, spacing: float = 4.0, max_distance: float = 30.0) -> Lanes:
+    def compute_lanes(self, k: int = 6, n_points: int = 8, spacing: float = 4.0, max_distance: float = 30.0, differentiable: bool = False) -> Lanes:
         """The `k` nearest lanelets of `lanelet_map` of every exposed agent, by the distance to their centre lines, within `max_distance` metres
         (+inf: no limit), nearest first, equal float32 distances by the lower lanelet index.  The lanelets are those `snap_to_lanes` looks at:
         long enough to drive on and without an excluded tag.
@@ -1449,9 +1452,19 @@ class Simulator:
 
         Rows of agents that are not present, whose pose is NaN, or whose scene has no lanelet map (an entry `None`) are empty; without any lanelet
         map everything is empty and nothing is launched.  1 <= k <= 32, 1 <= n_points <= 32, at most 2048 lanelets per map.  One HIP kernel in
-        binary64 (csrc/lane_obs.hip; the definition is in include/tdship.h "K8", tests/lane_obs_model.py equals it bit for bit).  No gradient.
+        binary64 (csrc/lane_obs.hip; the definition is in include/tdship.h "K8", tests/lane_obs_model.py equals it bit for bit).
         Runs on the current stream and allocates its outputs only; the device lane tables are those of `compute_wrong_way`, built by the first
-        call of either -- which must happen outside a stream capture; after that the call can be captured into a graph."""
+        call of either -- which must happen outside a stream capture; after that the call can be captured into a graph.
+
+        `differentiable=True`, with grad mode on and a state that requires grad: the same launch and the same bits, and `features` and `points`
+        carry the graph to x, y and psi (through the shared [sin psi, cos psi] node) of the observing agent -- the map is constant, so nothing
+        goes to another entity; `n_valid` and `index` never do.  The backward is one HIP kernel (csrc/lane_obs_bwd.hip; include/tdship.h "K8b",
+        held to the float64 model tests/lane_obs_grad_model.py).  Constants of differentiation: which lanelet is in a slot and the order of the
+        slots, the `max_distance` cut, the segment the foot lies on, whether the foot was clamped to a segment's end, and for every point
+        whether it is valid and the lanelet and segment it lies on.  Where the foot is not clamped the polyline slides along the lane as the
+        agent moves, and the gradient of the points says so.  An empty slot and an invalid point contribute exactly zero whatever gradient
+        comes in, NaN and inf included; an agent exactly on a centre line gets no NaN from `distance`.  Otherwise -- the flag off, under
+        `no_grad`, nothing requiring grad, no lanelet map, no agents -- nothing is recorded and nothing is saved."""
         _ops.check_lanes_args(k, n_points, spacing, max_distance)
         state = self.get_state()
         if not state.is_cuda:
@@ -1459,6 +1472,9 @@ class Simulator:
         B, A = state.shape[0], self.agent_count
         if A == 0 or self.lanelet_map is None or all(m is None for m in self.lanelet_map):
             return Lanes(*_ops.empty_lane_observations(B, A, int(k), int(n_points), state.device))
+        if differentiable and torch.is_grad_enabled() and state.requires_grad:
+            return Lanes(*_ops.lane_observations_grad(self._lane_tables(state.device), state[..., :2], self._heading_sc()[:, :A], self.get_present_mask(),
+                                                      k, n_points, spacing, max_distance))
         with torch.no_grad():
             agent = state.detach()
             out = _ops.lane_observations(self._lane_tables(state.device), agent[..., :2], self._heading_sc().detach()[:, :A], self.get_present_mask(),
