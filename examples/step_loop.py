@@ -6,6 +6,7 @@ lane map); the "policy" is random.
 
     python examples/step_loop.py [--batch 64] [--agents 16] [--steps 50] [--res 128]
     python examples/step_loop.py --scan 64          # a non-visual loop: 64-ray range scans (other agents, road edge) instead of images
+    python examples/step_loop.py --scan 64 --scan-grad   # one step: a keep-clear-of-the-road-edge penalty on the scan, differentiated to the actions
     python examples/step_loop.py --neighbors 8      # a non-visual loop: the 8 nearest other agents in each agent's frame, with their relative velocity
     python examples/step_loop.py --ttc 5            # beside whatever is observed: when each agent would first hit another one within 5 s at constant velocity
     python examples/step_loop.py --lanes 6          # a non-visual loop: the 6 nearest lanes in each agent's frame, each a foot point and a polyline ahead
@@ -122,6 +123,25 @@ def lanes_grad_step(args, sim, dev):
           f'average over those agents, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
 
 
+def scan_grad_step(args, sim, dev):
+    """--scan-grad: the lidar-like observation with its gradient.  One step: the actions are applied, every agent pays (clear - road).clamp(min=0)
+    for each of its rays whose stretch of road ends less than `clear` metres away -- "keep clear of the road edge", a signal that is there long
+    before compute_offroad() is non-zero -- and that penalty is differentiated to the actions through the backward launch of the range scans
+    and the kinematic step.  The map is constant, so an agent's penalty reaches its own action alone."""
+    rays, clear = args.scan or 64, 4.0
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    sim.kinematic_model.set_state(sim.get_state().detach())
+    sim.step(action)
+    scan = sim.compute_range_scan(n_rays=rays, max_range=args.scan_range, agents=False, differentiable=True)      # road with the graph, hit without
+    near = (scan.road.detach() > 0) & (scan.road.detach() < clear)                          # 0: the agent is off the road already, the scan says nothing
+    penalty = torch.where(near, (clear - scan.road).clamp(min=0), torch.zeros_like(scan.road)).sum()
+    grad, = torch.autograd.grad(penalty, action)
+    involved = near.any(-1)
+    print(f'{int(near.sum())} of {near.numel()} rays leave the road within {clear:g} m, penalty {float(penalty.detach()):.2f} m; |d penalty / d action| '
+          f'{float(grad.abs().sum(-1)[involved].mean()) if bool(involved.any()) else 0.0:.4f} on average over the {int(involved.sum())} agents with such a '
+          f'ray, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -146,6 +166,8 @@ def main():
                     'actions through the simulator (compute_time_to_collision(differentiable=True))')
     ap.add_argument('--neighbors-grad', action='store_true', help='one step: differentiate a keep-your-distance penalty on the features of the --neighbors K '
                     '(default 8) nearest agents to the actions through the simulator (compute_neighbors(differentiable=True))')
+    ap.add_argument('--scan-grad', action='store_true', help='one step: differentiate a keep-clear-of-the-road-edge penalty on the road ranges of the --scan '
+                    'RAYS (default 64) rays to the actions through the simulator (compute_range_scan(differentiable=True))')
     ap.add_argument('--lanes-grad', action='store_true', help='one step: differentiate a lane-keeping penalty on lateral and sin_rel of the nearest of the '
                     '--lanes K (default 6) lanes to the actions through the simulator (compute_lanes(differentiable=True))')
     args = ap.parse_args()
@@ -199,6 +221,8 @@ def main():
         return neighbors_grad_step(args, sim, dev)
     if args.lanes_grad:
         return lanes_grad_step(args, sim, dev)
+    if args.scan_grad:
+        return scan_grad_step(args, sim, dev)
     routed = bool(args.route) or args.route_to
     replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller

@@ -785,6 +785,55 @@ int tds_range_scan_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, 
                              float max_range, float gap_tolerance, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * K5b  differentiable range scans: the backward of K5 (float64 torch-autograd model: tests/range_scan_grad_model.py; the
+ * per-ray derivatives and the edge rule are stated once, in csrc/tds_scan_grad.h, and their numpy restatement in tests/test_scan_grad_host.py
+ * equals them bit for bit).
+ * Inputs: map, boxes, sc, present, ray_sc, max_range, gap_tolerance as K5 read them ([sin, cos] are independent inputs; the map, max_range and
+ * gap_tolerance are constants); road_range B x A x R as K5 wrote it; g_agent, g_road B x A x R float32, the incoming gradients (either may be
+ * NULL: that part contributes nothing).
+ * Outputs, each optional (NULL):
+ *   g_boxes   B x E x 5      to [x, y, length, width, psi]; the psi column is 0: psi is not read, it gets its gradient through sc and ray_sc
+ *   g_sc      B x E x 2      to [sin, cos] of every entity
+ *   g_ray_sc  B x A x R x 2  to [sin, cos] of every ray
+ *   choice    B x A x R x 2  int32 witness: [the entity that defines agent_range or -1, the slab that binds: 0 none, 1 x (length), 2 y (width)]
+ *   road_edge B x A x R x 4  float32 witness: [x_i, y_i, x_j, y_j], the world end points of the edge road_range ends on, (x_i, y_i) <= (x_j, y_j)
+ *                            lexicographically; NaN where the road contributes nothing
+ * With every gradient output NULL the call only writes the witness ("which rectangle side and which road edge a ray ends on"), and g_agent,
+ * g_road may be NULL.
+ * Precision: every discrete choice is made again in binary32 with K5's own code on K5's own inputs; all derivative arithmetic and all sums are
+ * binary64 on the widened float32 inputs, summed in a fixed order and rounded to binary32 once, on the store.  No atomics: two runs give the
+ * same bits.
+ * Agent part, ray (a, k) of a present observer, with K5's names for entity j: (rx, ry) = origin - centre_j, lx = rx c + ry s, ly = ry c - rx s,
+ * ex = dx c + dy s, ey = dy c - dx s, hl, hw the half sizes.  Constants: the entity that defines agent_range (K5's: the lowest index on a tie,
+ * whether or not the road is nearer -- hit does not always name it), the slab that binds in K5's order 0, x, y (the y slab binds if its entry
+ * exceeds max(0, x entry), else the x slab if its entry exceeds 0, else nothing; a slab with e == 0 never binds), the entry side sigma = -sign(e).
+ * Differentiated: t = (sigma h - l) / e of the binding slab, to x, y of the observer, to x, y, length, width (h = size / 2), [sin, cos] of entity
+ * j and to [dx, dy] of the ray.  A ray without an entity below max_range, with t0 == 0 (origin inside a rectangle, the clamp binds) or of an
+ * absent observer contributes exactly zero whatever comes in, NaN and inf included.
+ * Road part: a ray contributes iff 0 < road_range < max_range.  road_range then equals, bit for bit, the far end `hi` of the line-triangle
+ * interval of a positive-area face listed in the cells around the end of the stretch r(road_range) (K5's cell rule and margin).  ONE pass over
+ * those lists: candidates are the (face, edge) pairs whose face has positive area and hi == road_range and whose edge crosses the line at
+ * u == road_range (binary32, K5's arithmetic); every edge is oriented so that its first end point is lexicographically (x, y) the smaller and
+ * the smallest 4-tuple (x_i, y_i, x_j, y_j) is taken -- a rule that does not depend on the grid.  Differentiated on that orientation:
+ * t = u_i + (u_j - u_i) w_i / (w_i - w_j), p = v - o, u = d . p, w = d x p, to x, y of the observer and to [dx, dy] of the ray; the edge is a
+ * constant.  road_range == 0 (origin off the road), road_range >= max_range (capped), no map and absent observers give exactly zero; so does a
+ * ray for which no candidate reproduces road_range, and its road_edge says so (NaN).
+ * Per entity j each gradient is the binary64 sum, chunk of 256 rays after chunk of the scene's A * R: the rays that end on j in ray order, then
+ * (j < A) the observer terms of j's own rays in ray order.  Every output is written in full; the row of an entity no ray touches is exactly 0.
+ * Argument rules, limits and codes are K5's, before any launch; the road part needs road_range; B * E == 0 or no output at all is a successful
+ * no-op.  One launch; nothing is allocated and nothing synchronises; every loop of the kernel is bounded whatever the inputs hold.  The
+ * launch asks for 80 bytes of LDS per entity + 17 KiB: 97 KiB at TDS_SCAN_MAX_ENTITIES. */
+int tds_range_scan_bwd_f32(const tds_map_t *map, const float *boxes, const float *sc, const uint8_t *present, const float *ray_sc,
+                           const float *road_range, const float *g_agent, const float *g_road, float *g_boxes, float *g_sc, float *g_ray_sc,
+                           int32_t *choice, float *road_edge, int64_t B, int64_t A, int64_t E, int R, float max_range, float gap_tolerance,
+                           void *stream);
+/* the same for scenes with different maps, as tds_range_scan_multi_f32 */
+int tds_range_scan_bwd_multi_f32(const tds_mapset_t *set, const int32_t *scene_map, const float *boxes, const float *sc, const uint8_t *present,
+                                 const float *ray_sc, const float *road_range, const float *g_agent, const float *g_road, float *g_boxes,
+                                 float *g_sc, float *g_ray_sc, int32_t *choice, float *road_edge, int64_t B, int64_t A, int64_t E, int R,
+                                 float max_range, float gap_tolerance, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K6  neighbour observations (no reference counterpart: the definition is this library's own; binary32 model, equal bit for
  * bit: tests/neighbors_model.py).  For every exposed agent the K nearest other entities within max_distance, nearest first, in its own frame.
  * Entities are those of tds_range_scan_f32: the A exposed agents followed by E - A NPCs.

@@ -198,6 +198,10 @@ tds_range_scan_f32(handle map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f3
     float gap_tolerance, stream stream)
 tds_range_scan_multi_f32(handle set, i32* scene_map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* agent_range, f32* road_range, i32* hit, int64 B, int64 A, int64 E,
     int R, float max_range, float gap_tolerance, stream stream)
+tds_range_scan_bwd_f32(handle map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* road_range, f32* g_agent, f32* g_road, f32* g_boxes, f32* g_sc, f32* g_ray_sc,
+    i32* choice, f32* road_edge, int64 B, int64 A, int64 E, int R, float max_range, float gap_tolerance, stream stream)
+tds_range_scan_bwd_multi_f32(handle set, i32* scene_map, f32* boxes, f32* sc, u8* present, f32* ray_sc, f32* road_range, f32* g_agent, f32* g_road, f32* g_boxes, f32* g_sc,
+    f32* g_ray_sc, i32* choice, f32* road_edge, int64 B, int64 A, int64 E, int R, float max_range, float gap_tolerance, stream stream)
 tds_neighbors_f32(f32* boxes, f32* sc, f32* speed, u8* present, u8* visible, f32* features, i32* index, int64 B, int64 A, int64 E, int K, float max_distance, stream stream)
 tds_neighbors_bwd_f32(f32* boxes, f32* sc, f32* speed, i32* index, f32* g_features, f32* g_boxes, f32* g_sc, f32* g_speed, int64 B, int64 A, int64 E, int K, stream stream)
 tds_lights_step(f64* duration, i32* next_phase, i32* n_phases, u8* colour, i32* phase, f64* remaining, i64* state, f32* time_to_change, u8* mask, int64 B, int64 M, int64 P,

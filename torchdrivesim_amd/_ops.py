@@ -648,6 +648,76 @@ def range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_toler
     return agents, road, hit
 
 
+def _range_scan_bwd(smap, boxes, sc, present, ray_sc, road, g_agent, g_road, want_grads, want_witness, max_range, gap_tolerance):
+    """one call of tds_range_scan_bwd_f32 / _multi (include/tdship.h "K5b") -> g_boxes, g_sc, g_ray_sc, choice, road_edge (None where not asked for;
+    want_witness = 'road': the road edge alone).  A part whose incoming gradient is None is skipped in the kernel; so is the road part without a map."""
+    B, A, R = (int(d) for d in ray_sc.shape[:3])
+    E = int(boxes.shape[1])
+    dev = boxes.device
+    g_boxes = torch.empty((B, E, 5), dtype=f32, device=dev) if want_grads else None
+    g_sc = torch.empty((B, E, 2), dtype=f32, device=dev) if want_grads else None
+    g_ray_sc = torch.empty((B, A, R, 2), dtype=f32, device=dev) if want_grads else None
+    choice = torch.empty((B, A, R, 2), dtype=i32, device=dev) if want_witness and want_witness != 'road' else None
+    road_edge = torch.empty((B, A, R, 4), dtype=f32, device=dev) if want_witness else None
+    nat.call(*_map_head('tds_range_scan_bwd', '_f32', smap, dev), boxes, sc, present, ray_sc, road if smap is not None else None,
+             None if g_agent is None else _c(g_agent), None if g_road is None or smap is None else _c(g_road), g_boxes, g_sc, g_ray_sc, choice, road_edge,
+             B, A, E, R, float(max_range), float(gap_tolerance))
+    return g_boxes, g_sc, g_ray_sc, choice, road_edge
+
+
+class _RangeScanGrad(torch.autograd.Function):
+    """K5 as an autograd node: forward = range_scan, backward = tds_range_scan_bwd_f32 / _multi (csrc/scan_bwd.hip), one launch"""
+
+    @staticmethod
+    def forward(ctx, smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents):
+        agents, road, hit = range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents=want_agents)
+        ctx.mark_non_differentiable(hit)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(boxes, sc, present, ray_sc, road)
+        ctx.cfg = (smap, float(max_range), float(gap_tolerance), bool(want_agents))
+        return agents, road, hit
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_agent, g_road, _g_hit):
+        smap, max_range, gap_tolerance, want_agents = ctx.cfg
+        need = ctx.needs_input_grad
+        if not want_agents:
+            g_agent = None                                   # agents = max_range everywhere: a constant
+        if smap is None:
+            g_road = None                                    # road = max_range everywhere
+        if (g_agent is None and g_road is None) or not (need[1] or need[2] or need[4]):
+            return (None,) * 9
+        boxes, sc, present, ray_sc, road = ctx.saved_tensors
+        g_boxes, g_sc, g_ray_sc, _, _ = _range_scan_bwd(smap, _c(boxes.detach()), _c(sc.detach()), _u8(present), _c(ray_sc.detach()), road, g_agent, g_road,
+                                                        True, False, max_range, gap_tolerance)
+        return (None, g_boxes.to(boxes.dtype) if need[1] else None, g_sc.to(sc.dtype) if need[2] else None, None,
+                g_ray_sc.to(ray_sc.dtype) if need[4] else None, None, None, None, None)
+
+
+def range_scan_grad(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents=True):
+    """`range_scan`, differentiable (include/tdship.h "K5b"): the same launch and the same bits; `agents` and `road` carry the graph
+    to `boxes` ([x, y, length, width]; the psi column gets zeros -- psi has its gradient through `sc` and `ray_sc`), to `sc` = [sin psi, cos psi] of
+    the entity a ray ends on and to `ray_sc`, `hit` never does.  The backward is ONE launch (tds_range_scan_bwd_f32 / _multi); a part that was not
+    computed (want_agents=False, no map) is skipped in the kernel.  Constants of differentiation: the entity and the rectangle side that define
+    `agents`, the road edge `road` ends on, the map, `max_range`, `gap_tolerance`.  A ray that is capped at `max_range`, starts inside a rectangle
+    or off the road, or belongs to an absent agent contributes exactly zero whatever its incoming gradient holds.  No double backward."""
+    return _RangeScanGrad.apply(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents)
+
+
+def range_scan_witness(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents=True):
+    """What the backward of `range_scan_grad` differentiates, from the same entry point with every gradient pointer NULL -> (choice (B,A,R,2) int32
+    [the entity that defines `agents` or -1, the side that binds: 0 none, 1 length, 2 width], road_edge (B,A,R,4) float32 [x_i, y_i, x_j, y_j] of
+    the road edge `road` ends on, NaN where the road contributes nothing)."""
+    _, road, _ = range_scan(smap, boxes, sc, present, ray_sc, n_exposed, max_range, gap_tolerance, want_agents=False)
+    B, A, R = road.shape
+    _, _, _, choice, road_edge = _range_scan_bwd(smap, _c(boxes.detach()), _c(sc.detach()), _u8(present), _c(ray_sc.detach()), road, None, None, False,
+                                                 True if want_agents else 'road', max_range, gap_tolerance)
+    if not want_agents:
+        choice = torch.stack([torch.full((B, A, R), -1, dtype=i32, device=road.device), torch.zeros((B, A, R), dtype=i32, device=road.device)], -1)
+    return choice, road_edge
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # K6 neighbour observations
 # ---------------------------------------------------------------------------------------------------------------

@@ -5,12 +5,14 @@
 // of 64 a wave holds rays of ONE agent: they share the origin, so the first look at the map grid is wave-uniform (scalar loads).
 // All arithmetic of the ranges is binary32 + - * / relative to the ray's origin; only the "positive area" test of a face is float64.
 #include "tds_common.h"
+#include "tds_scan.h"
 #include <algorithm>
 
 namespace {
 
 using tds::GridEntry;
 using tds::MapView;
+using tds::line_triangle;
 
 constexpr int SBLOCK = 256;             // 4 waves
 constexpr int SCAN_MAX_PASSES = 16384;  // hard cap of the fixed-point iteration (a pass that continues has retired at least one face)
@@ -31,26 +33,6 @@ struct ScanArgs {
     int A, E, R, agents_per_block;
     float max_range, gap;
 };
-
-// The parameter interval in which the line o + t d (|d| = 1) meets the closed triangle, from the vertices RELATIVE to o:
-// u = p . d (along the ray), w = d x p (signed distance from the line).  An edge whose end points lie on different sides (or on the line)
-// crosses at u_i + (u_j - u_i) * w_i / (w_i - w_j).  false: the line misses the triangle.
-__device__ __forceinline__ bool line_triangle(float dx, float dy, float p0x, float p0y, float p1x, float p1y, float p2x, float p2y, float &lo, float &hi) {
-    const float w0 = dx * p0y - dy * p0x, w1 = dx * p1y - dy * p1x, w2 = dx * p2y - dy * p2x;
-    if ((w0 > 0.0f && w1 > 0.0f && w2 > 0.0f) || (w0 < 0.0f && w1 < 0.0f && w2 < 0.0f)) return false;
-    const float u0 = dx * p0x + dy * p0y, u1 = dx * p1x + dy * p1y, u2 = dx * p2x + dy * p2y;
-    lo = __builtin_inff(); hi = -__builtin_inff();
-    auto edge = [&](float wi, float wj, float ui, float uj) {
-        if (wi != wj && fminf(wi, wj) <= 0.0f && fmaxf(wi, wj) >= 0.0f) {
-            const float u = ui + (uj - ui) * (wi / (wi - wj));
-            lo = fminf(lo, u); hi = fmaxf(hi, u);
-        }
-    };
-    edge(w0, w1, u0, u1);
-    edge(w1, w2, u1, u2);
-    edge(w2, w0, u2, u0);
-    return lo <= hi;
-}
 
 // The faces of a pass that lie AHEAD of F + gap wait in a per-lane list in LDS (the PEND nearest ones, entry k of lane t at pend[k * SBLOCK + t]:
 // consecutive lanes, consecutive words), so that a pass can chain through the faces of its cells instead of scanning them once per face.
@@ -98,9 +80,7 @@ __device__ __forceinline__ float road_pass(const MapView &m, float ox, float oy,
                 const float a = fmaxf(lo, 0.0f), b = fminf(hi, max_range);
                 if (!(a <= b) || !(b > F)) continue;
                 // faces without area are no road (padding faces [0,0,0], slivers): float64 on the float32 vertices, as the model evaluates it
-                const double area2 = ((double)v01.z - (double)v01.x) * ((double)v2.y - (double)v01.y) -
-                                     ((double)v2.x - (double)v01.x) * ((double)v01.w - (double)v01.y);
-                if (area2 == 0.0) continue;
+                if (!tds::positive_area(v01.x, v01.y, v01.z, v01.w, v2.x, v2.y)) continue;
                 if (a <= F + gap) F = b;
                 else pending_add(pq, a, b);
             }
@@ -117,20 +97,14 @@ __device__ __forceinline__ float road_pass(const MapView &m, float ox, float oy,
     return F;
 }
 
-// which cells can hold a face that meets the ray between the parameters F and F + gap: the bounding cells of the two end points, widened by
-// `marg` metres (binary32 rounding of the points; a point on a cell border is looked up in both neighbours).  tds::cell_coord is monotone, so
-// a face whose bounding box holds a point of that stretch is listed in one of these cells.  Coordinates are clamped to one cell around the
-// grid first (non-finite values included) and the cells to the grid: a superset of lists is harmless, every face is tested exactly.
+// which cells can hold a face that meets the ray between the parameters F and F + gap: tds::cells_of (tds_scan.h) on the map's grid
 __device__ __forceinline__ void cells_of(const MapView &m, float v0, float v1, float marg, float origin, int n, int &c0, int &c1) {
-    const float lo_lim = origin - m.cell, hi_lim = origin + (float)(n + 1) * m.cell;
-    const float lo = fminf(fmaxf(fminf(v0, v1) - marg, lo_lim), hi_lim), hi = fminf(fmaxf(fmaxf(v0, v1) + marg, lo_lim), hi_lim);
-    c0 = min(max(tds::cell_coord(lo, origin, m.inv_cell), 0), n - 1);
-    c1 = min(max(tds::cell_coord(hi, origin, m.inv_cell), c0), n - 1);
+    tds::cells_of(m.cell, m.inv_cell, v0, v1, marg, origin, n, c0, c1);
 }
 
 __device__ float road_range_of(const MapView &m, float ox, float oy, float dx, float dy, float gap, float max_range, bool uniform_origin, float2 *slot) {
     if (m.nx <= 0 || m.ny <= 0) return 0.0f;
-    const float marg = 0.004f + 1e-6f * (fabsf(ox) + fabsf(oy) + max_range);
+    const float marg = tds::scan_margin(ox, oy, max_range);
     float F = 0.0f;
     int moves = m.nx + m.ny + 2;                                 // the cell walk: a straight line changes its first cell at most nx + ny times
     int pcx0 = -1, pcx1 = -1, pcy0 = -1, pcy1 = -1;              // the cells of the last pass ...
@@ -223,13 +197,9 @@ __global__ void __launch_bounds__(SBLOCK) range_scan_kernel(ScanArgs g) {
                     const float rx = me.x - q.x, ry = me.y - q.y;
                     const float lx = rx * q2.y + ry * q2.x, ly = ry * q2.y - rx * q2.x;
                     const float ex = dx * q2.y + dy * q2.x, ey = dy * q2.y - dx * q2.x;
-                    float t0 = 0.0f, t1 = __builtin_inff();
-                    bool ok = true;
-                    if (ex == 0.0f) ok = ok && fabsf(lx) <= q.z;
-                    else { const float u = (-q.z - lx) / ex, v = (q.z - lx) / ex; t0 = fmaxf(t0, fminf(u, v)); t1 = fminf(t1, fmaxf(u, v)); }
-                    if (ey == 0.0f) ok = ok && fabsf(ly) <= q.w;
-                    else { const float u = (-q.w - ly) / ey, v = (q.w - ly) / ey; t0 = fmaxf(t0, fminf(u, v)); t1 = fminf(t1, fmaxf(u, v)); }
-                    if (ok && t0 <= t1 && t0 < ta) { ta = t0; who = j; }
+                    float t0;
+                    int slab;
+                    if (tds::slab_test(lx, ly, ex, ey, q.z, q.w, t0, slab) && t0 < ta) { ta = t0; who = j; }
                 }
             }
             if (has_map) tr = road_range_of(m, me.x, me.y, dx, dy, g.gap, g.max_range, wave_per_agent, (float2 *)(bx + BOX_WORDS * E) + tid);

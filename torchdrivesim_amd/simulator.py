@@ -61,7 +61,8 @@ class TorchDriveConfig:
 
 @dataclass
 class RangeScan:
-    """What `Simulator.compute_range_scan` returns: three BxAxR tensors (metres, metres, int32 -- see there)."""
+    """What `Simulator.compute_range_scan` returns: three BxAxR tensors (metres, metres, int32 -- see there).  With
+    `differentiable=True` `agents` and `road` carry the graph to the poses and sizes; `hit` never does."""
     agents: Tensor
     road: Tensor
     hit: Tensor
@@ -1275,7 +1276,7 @@ class Simulator:
         return (-fov / 2 + (fov * (k + 0.5)) / torch.full((), int(n_rays), dtype=torch.float64, device=device)).to(torch.float32)
 
     def compute_range_scan(self, n_rays: int = 64, max_range: float = 50.0, fov: float = 2 * np.pi, gap_tolerance: float = 0.02, road: bool = True,
-                           agents: bool = True) -> RangeScan:
+                           agents: bool = True, differentiable: bool = False) -> RangeScan:
         """A lidar-like observation of every exposed agent: `n_rays` rays from the agent's centre, ray k at the angle psi + off_k
         (`range_scan_angles`; counter-clockwise in world coordinates, as psi), each reporting in metres
 
@@ -1290,9 +1291,18 @@ class Simulator:
 
         Without a road mesh or with road=False every `road` is `max_range`; with agents=False every `agents` is.  Rows of exposed agents that are not
         present hold max_range, max_range, -1.  [sin, cos] of the rays come from torch.sin / torch.cos on the device; the rest is one HIP kernel in
-        binary32 (csrc/scan.hip; parity: tests/range_scan_model.py, a float64 model).  No gradient.  Runs on the current stream, allocates its
+        binary32 (csrc/scan.hip; parity: tests/range_scan_model.py, a float64 model).  Runs on the current stream, allocates its
         outputs only, and reuses the cached off-road map: once that map exists (one eager call, or `compute_offroad`, on this road mesh) the call
-        can be captured into a graph -- nothing crosses from the host, the ray offsets are built on the device."""
+        can be captured into a graph -- nothing crosses from the host, the ray offsets are built on the device.
+
+        `differentiable=True`, with grad mode on and a state or size that requires grad: the same launch and the same bits, and `agents` and
+        `road` carry the graph to x, y and psi of the observing agent (psi through the rays' [sin, cos] and the shared [sin psi, cos psi] node)
+        and to x, y, psi and the size of the entity a ray ends on; `hit` never does.  The backward is one HIP kernel (csrc/scan_bwd.hip;
+        include/tdship.h "K5b", held to the float64 model tests/range_scan_grad_model.py).  Constants of differentiation: the entity and the
+        side of its rectangle that define `agents`, the road edge `road` ends on, the map, `max_range`, `gap_tolerance` and `fov`.  A ray that is
+        capped at `max_range`, starts inside a rectangle or off the road, or belongs to an absent agent contributes exactly zero whatever
+        gradient comes in, NaN and inf included.  Otherwise -- the flag off, under `no_grad`, nothing requiring grad -- nothing is recorded
+        and nothing is saved."""
         _ops.check_range_scan_args(n_rays, max_range, gap_tolerance)
         if not (np.isfinite(fov) and fov > 0):
             raise ValueError(f'range scan: fov must be finite and positive (got {fov})')
@@ -1307,6 +1317,13 @@ class Simulator:
         if road and self.road_mesh.faces_count > 0:
             from torchdrivesim_amd.infractions import _static_maps_for
             smap = _static_maps_for(self.road_mesh, state.device)      # the geometry-only device map of compute_offroad, cached on the mesh
+        if differentiable and torch.is_grad_enabled():
+            all_state, size = self.get_all_agent_state(), self.get_all_agent_size()
+            if all_state.requires_grad or size.requires_grad:
+                boxes = _ops.state_boxes(all_state, size)
+                ray_sc = _ops.heading_sc(state[..., 2].unsqueeze(-1) + self.range_scan_angles(R, fov, device=state.device))
+                return RangeScan(*_ops.range_scan_grad(smap, boxes, self._heading_sc(), self.get_all_agent_present_mask(), ray_sc, A, max_range,
+                                                       gap_tolerance, want_agents=agents))
         with torch.no_grad():
             all_state = self.get_all_agent_state().detach()
             boxes = torch.cat([all_state[..., :2], self.get_all_agent_size().detach(), all_state[..., 2:3]], dim=-1)
