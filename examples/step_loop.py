@@ -20,6 +20,8 @@ lane map); the "policy" is random.
     python examples/step_loop.py --ttc-grad         # one step: a time-to-collision penalty differentiated to the actions through the simulator
     python examples/step_loop.py --neighbors-grad   # one step: a keep-your-distance penalty on the neighbour features differentiated to the actions
     python examples/step_loop.py --lanes 6 --lanes-grad     # one step: a lane-keeping penalty on the lane features differentiated to the actions
+    python examples/step_loop.py --lights device --stop-lines 4 --stop-lines-grad   # one step: a do-not-cross-the-red-line penalty differentiated to the actions
+    python examples/step_loop.py --wrong-way-grad   # one step: the wrong-way loss differentiated to the actions (it reaches them through psi alone)
 """
 import argparse
 import os
@@ -142,6 +144,42 @@ def scan_grad_step(args, sim, dev):
           f'ray, {int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
 
 
+def stop_lines_grad_step(args, sim, dev):
+    """--stop-lines-grad: the traffic-rule half of a vector policy's observation with its gradient.  One step: the actions are applied, every
+    agent whose nearest stop line ahead shows red pays (brake - distance).clamp(min=0) + (brake - x).clamp(min=0) for coming within `brake` metres
+    of it -- "do not cross the red line" -- and that penalty is differentiated to the actions through the backward launch of the stop-line
+    observations and the kinematic step.  The lines are constants, so an agent's penalty reaches its own action alone."""
+    k, brake = args.stop_lines or 4, 15.0
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    sim.kinematic_model.set_state(sim.get_state().detach())
+    sim.step(action)
+    lines = sim.compute_stop_lines(k=k, max_distance=args.scan_range, differentiable=True)      # features with the graph, index and state without
+    x, distance = lines.features[:, :, 0, 0], lines.features[:, :, 0, 7]                        # slot 0: the nearest line ahead
+    red = lines.mask[:, :, 0] & (lines.state[:, :, 0] == 0)                                     # an empty slot holds zeros: mask it, it is no line at 0 m
+    near = red & (distance.detach() < brake)
+    penalty = torch.where(near, (brake - distance).clamp(min=0) + (brake - x).clamp(min=0), torch.zeros_like(x)).sum()
+    grad, = torch.autograd.grad(penalty, action)
+    print(f'{int(lines.mask[:, :, 0].sum())} of {near.numel()} agents have a stop line ahead within {args.scan_range:g} m, {int(red.sum())} of them red, '
+          f'{int(near.sum())} within {brake:g} m, penalty {float(penalty.detach()):.2f} m; |d penalty / d action| '
+          f'{float(grad.abs().sum(-1)[near].mean()) if bool(near.any()) else 0.0:.4f} on average over those agents, '
+          f'{int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
+
+
+def wrong_way_grad_step(args, sim, dev):
+    """--wrong-way-grad: the wrong-way term of the reward with its gradient.  One step: the actions are applied and compute_wrong_way's loss is
+    differentiated to them.  As in the reference the position is a constant of this loss: the gradient reaches the actions through psi alone --
+    through the steering, which turns the car round."""
+    action = torch.zeros((args.batch, args.agents, 2), device=dev, requires_grad=True)
+    sim.kinematic_model.set_state(sim.get_state().detach())
+    sim.step(action)
+    loss = sim.compute_wrong_way(differentiable=True)                     # (B, A) with the graph to psi
+    grad, = torch.autograd.grad(loss.sum(), action)
+    wrong = loss.detach() > 0
+    print(f'{int(wrong.sum())} of {wrong.numel()} agents drive against their lane, loss {float(loss.detach().sum()):.2f}; |d loss / d steering| '
+          f'{float(grad[..., 1].abs()[wrong].mean()) if bool(wrong.any()) else 0.0:.4f} on average over those agents, '
+          f'{int((grad.abs().sum(-1) > 0).sum())} agents with a gradient')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
@@ -170,6 +208,10 @@ def main():
                     'RAYS (default 64) rays to the actions through the simulator (compute_range_scan(differentiable=True))')
     ap.add_argument('--lanes-grad', action='store_true', help='one step: differentiate a lane-keeping penalty on lateral and sin_rel of the nearest of the '
                     '--lanes K (default 6) lanes to the actions through the simulator (compute_lanes(differentiable=True))')
+    ap.add_argument('--stop-lines-grad', action='store_true', help='one step: differentiate a do-not-cross-the-red-line penalty on x and distance of the '
+                    'nearest of the --stop-lines K (default 4) lines to the actions through the simulator (compute_stop_lines(differentiable=True))')
+    ap.add_argument('--wrong-way-grad', action='store_true', help='one step: differentiate the wrong-way loss to the actions through the simulator '
+                    '(compute_wrong_way(differentiable=True)): it reaches them through psi alone')
     args = ap.parse_args()
     if (args.scan > 0) + (args.neighbors > 0) + (args.stop_lines > 0) + (args.lanes > 0) > 1:
         ap.error('--scan, --neighbors, --stop-lines and --lanes are observations in place of the image: choose one')
@@ -223,6 +265,10 @@ def main():
         return lanes_grad_step(args, sim, dev)
     if args.scan_grad:
         return scan_grad_step(args, sim, dev)
+    if args.stop_lines_grad:
+        return stop_lines_grad_step(args, sim, dev)
+    if args.wrong_way_grad:
+        return wrong_way_grad_step(args, sim, dev)
     routed = bool(args.route) or args.route_to
     replanned = torch.zeros((), device=dev)
     programme = cfg.traffic_light_controller

@@ -484,6 +484,15 @@ int tds_laneset_destroy(tds_laneset_t *set);
 int tds_wrong_way_f32(const tds_laneset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state,
                       const float *recenter_offset, const uint8_t *present, float *out, int64_t n_agents,
                       float direction_angle_threshold, float lanelet_dist_tolerance, void *stream);
+/* tds_wrong_way_f32 plus one more output, the same kernel with one more pointer: out has the bits of tds_wrong_way_f32, and
+ *   dloss_dpsi n = d out / d psi with the lanelet whose loss the minimum keeps held fixed: -sinf(d) where |d| > direction_angle_threshold, else 0
+ *   (normalize_angle has derivative 1).  Of equal losses the first in table order wins (the winner is tracked with a strict <; a NaN loss -- a NaN psi -- gives way to a
+ *   later one exactly as fminf drops it).  Exactly 0
+ *   wherever the loss is forced to 0: no lanelet, an excluded tag, a failed find_direction, an absent agent, a scene without a table.
+ *   The position is a constant, as in the reference (it passes through float() there, infractions.py:270-287): x and y get no gradient. */
+int tds_wrong_way_grad_f32(const tds_laneset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state,
+                           const float *recenter_offset, const uint8_t *present, float *out, float *dloss_dpsi, int64_t n_agents,
+                           float direction_angle_threshold, float lanelet_dist_tolerance, void *stream);
 /* find_lanelet_directions for a batch of points (xy n x 2 float64, as the reference passes host doubles): dirs / dists n x max_dirs
  * float64 (direction and distance of the first max_dirs lanelets found, in table order), count n (number found, may exceed max_dirs; 0 when excluded), status n uint8 (bit 0: find_direction
  * failed for some lanelet, bit 1: a lanelet with an excluded tag is within tolerance) */
@@ -948,6 +957,34 @@ int tds_stop_lines_f32(const float *agent_xy, const float *agent_sc, const uint8
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * K7b  differentiable stop-line observations: the backward of K7 (b) (float64 torch-autograd model:
+ * tests/stop_lines_grad_model.py; the slot gradient and the order of a row's sum are stated once, in csrc/tds_stop_lines_grad.h, and their numpy
+ * restatement in tests/test_stop_lines_grad_host.py equals them bit for bit).
+ * Inputs: agent_xy, agent_sc, lines, line_sc as K7 read them; index B x A x K int32 as K7 wrote it; g_features B x A x K x 8 float32, the
+ * incoming gradient, which must start at a multiple of 16 bytes (else TDS_EINVAL).
+ * Outputs: g_xy B x A x 2, g_sc B x A x 2: the gradients to the observing agent's own x, y and [sin, cos].  s and c are independent inputs.  The
+ * lines are constants and get nothing.  Constants of differentiation: which line is in a slot and the order of the slots, the max_distance
+ * cut, ahead_only, min_cos, mask.
+ * Slot (b, a, k) with n = index[b, a, k] is FILLED iff 0 <= n < N.  Every other slot -- empty, an index that is garbage -- contributes exactly
+ * zero whatever its g_features holds (a NaN, an infinity), and nothing is read at its index.  A filled slot whose inputs or incoming gradients
+ * are not finite propagates what IEEE arithmetic gives.
+ * With K7's names, and g0 .. g7 the incoming gradient of the slot's features, every operation binary64 on the widened float32 values and
+ * rounded once, in this order:
+ *   dx = x_n - x_a, dy = y_n - y_a;  r = sqrt(dx*dx + dy*dy)  (recomputed: not the forward's rounded distance)
+ *   q = g7 / r, and exactly 0 where r == 0  (an agent standing exactly on a line's centre gets no NaN from the distance)
+ *   to x_a:  -(g0*c - g1*s) - q*dx          to y_a:  -(g0*s + g1*c) - q*dy
+ *   to s:    ((g0*dy - g1*dx) - g2*cl) + g3*sl      to c:  ((g0*dx + g1*dy) + g2*sl) + g3*cl
+ * length, width and time_to_change are copies of constants: g4, g5 and g6 go nowhere and are not read.
+ * Per observer each of its four gradients is the binary64 sum over its K slots, rounded to binary32 once.  The order of the sum is fixed: 4
+ * lanes per observer; lane l starts from +0 and adds its filled slots l, l + 4, l + 8, ... in that order; then two rounds m = 2, 1 in which lane l
+ * takes (its sum) + (the sum of lane l ^ m); lane 0 has the result.  No atomics: two runs give the same bits.  Every output is written in full;
+ * the rows of an observer without a filled slot -- an absent agent's among them -- are exactly 0.
+ * Argument rules, limits and codes are K7's (max_distance, ahead_only and min_cos are not arguments); B * A == 0 is a successful no-op.  One
+ * launch; nothing is allocated and nothing synchronises; every loop of the kernel is bounded by A, N and K whatever index holds. */
+int tds_stop_lines_bwd_f32(const float *agent_xy, const float *agent_sc, const float *lines, const float *line_sc, const int32_t *index,
+                           const float *g_features, float *g_xy, float *g_sc, int64_t B, int64_t A, int64_t N, int K, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K8  lane observations (no reference counterpart: the definition is this library's own; float64 model, equal bit for bit:
  * tests/lane_obs_model.py).  For every exposed agent the K nearest lanelets of its scene's lane table within max_distance of their centre
  * lines, nearest first; each slot is the foot on the centre line in the agent's frame plus a polyline of P points ahead of the foot that
@@ -1191,6 +1228,9 @@ int tds_raster_plan_small_lane(int64_t n_img, int res, int out_mode, int n_keys,
                                int small_faces, int *small_lane);
 /* 0: maps created from now on carry no nearest-face candidate lists (K2b then walks grid rings) */
 int tds_testing_set_near_lists(int enabled);
+/* the lanes that share an observer in K7b's launch: 4 (the product's), 16 or 1 -- the shapes that were measured against each other; the order of
+ * a row's sum, and so the last bits, follow the choice */
+int tds_stop_lines_bwd_set_row_lanes(int lanes);
 #endif
 
 #ifdef __cplusplus

@@ -161,6 +161,8 @@ tds_laneset_create(host* lanes, int n, host* out)
 tds_laneset_destroy(handle set)
 tds_wrong_way_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* state, f32* recenter_offset, u8* present, f32* out, int64 n_agents, float direction_angle_threshold,
     float lanelet_dist_tolerance, stream stream)
+tds_wrong_way_grad_f32(handle set, i32* scene_map, int64 agents_per_scene, f32* state, f32* recenter_offset, u8* present, f32* out, f32* dloss_dpsi, int64 n_agents,
+    float direction_angle_threshold, float lanelet_dist_tolerance, stream stream)
 tds_lanelet_directions_f64(handle set, i32* scene_map, int64 points_per_scene, f64* xy, f64* dirs, f64* dists, i32* count, u8* status, int max_dirs, int64 n_points,
     float lanelet_dist_tolerance, stream stream)
 tds_spawn_on_lanes_f32(handle set, i32* scene_map, i64* scene_ids, int64 n_scenes, int agents_per_scene, f32* attributes, f32* occupied, f32* occupied_sc, u8* occupied_mask,
@@ -209,6 +211,8 @@ tds_lights_step(f64* duration, i32* next_phase, i32* n_phases, u8* colour, i32* 
 tds_lights_reset(i32* n_phases, f64* duration, i32* phase, f64* remaining, u8* mask, i64* scene_ids, int64 B, int64 M, int64 P, uint64 seed, stream stream)
 tds_stop_lines_f32(f32* agent_xy, f32* agent_sc, u8* agent_present, f32* lines, f32* line_sc, u8* mask, i64* state, f32* time_to_change, f32* features, i32* index,
     i32* slot_state, int64 B, int64 A, int64 N, int K, float max_distance, int ahead_only, float min_cos, stream stream)
+tds_stop_lines_bwd_f32(f32* agent_xy, f32* agent_sc, f32* lines, f32* line_sc, i32* index, f32* g_features, f32* g_xy, f32* g_sc, int64 B, int64 A, int64 N, int K,
+    stream stream)
 tds_lane_observations_multi(handle set, i32* scene_map, f32* agent_xy, f32* agent_sc, u8* present, f32* features, f32* points, i32* n_valid, i32* index, int64 B, int64 A,
     int K, int P, float spacing, float max_distance, stream stream)
 tds_lane_observations_bwd_multi(handle set, i32* scene_map, f32* agent_xy, f32* agent_sc, i32* index, f32* g_features, f32* g_points, f32* g_xy, f32* g_sc, int64 B, int64 A,
@@ -236,6 +240,7 @@ tds_raster_plan(int64 n_img, int res, int out_mode, int n_keys, int keys_listed,
 tds_raster_plan_small_lane(int64 n_img, int res, int out_mode, int n_keys, int keys_listed, int actors, int extra, int want_slices, int64 workspace_bytes, int cus,
     int force_tw, int bits_waves, int list_waves, int list_lds_kb, int debug, int small_faces, host* small_lane)
 tds_testing_set_near_lists(int enabled)
+tds_stop_lines_bwd_set_row_lanes(int lanes)
 '''
 
 ELEMENTS = {'f32*': torch.float32, 'f64*': torch.float64, 'u8*': torch.uint8, 'i32*': torch.int32, 'i64*': torch.int64, 'void*': None}

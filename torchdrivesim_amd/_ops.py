@@ -939,6 +939,50 @@ def stop_lines(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, t
     return features, index, slot_state
 
 
+def _aligned(t):
+    """t, or a copy of it where its data does not start at a multiple of 16 bytes (a contiguous view at an odd storage offset): the backward kernels
+    read a slot's incoming gradients as 16-byte loads"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _StopLinesGrad(torch.autograd.Function):
+    """K7's stop-line observations as an autograd node: forward = stop_lines, backward = tds_stop_lines_bwd_f32 (csrc/stop_lines_bwd.hip), one launch"""
+
+    @staticmethod
+    def forward(ctx, agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, time_to_change, k, max_distance, ahead_only, min_cos):
+        features, index, slot_state = stop_lines(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, time_to_change, k, max_distance,
+                                                 ahead_only=ahead_only, min_cos=min_cos)
+        ctx.mark_non_differentiable(index, slot_state)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(agent_xy, agent_sc, index, lines, line_sc)
+        return features, index, slot_state
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_features, _g_index, _g_state):
+        if g_features is None or not any(ctx.needs_input_grad[:2]):
+            return (None,) * 12
+        agent_xy, agent_sc, index, lines, line_sc = ctx.saved_tensors
+        B, A, K = index.shape
+        dev = index.device
+        g_xy = torch.empty((B, A, 2), dtype=f32, device=dev)
+        g_sc = torch.empty((B, A, 2), dtype=f32, device=dev)
+        nat.call('tds_stop_lines_bwd_f32', dev, _c(agent_xy.detach()), _c(agent_sc.detach()), _c(lines.detach()), _c(line_sc.detach()), index,
+                 _aligned(_c(g_features)), g_xy, g_sc, B, A, lines.shape[1], K)
+        need = ctx.needs_input_grad
+        return (g_xy.to(agent_xy.dtype) if need[0] else None, g_sc.to(agent_sc.dtype) if need[1] else None) + (None,) * 10
+
+
+def stop_lines_grad(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, time_to_change, k, max_distance, ahead_only=True, min_cos=None):
+    """`stop_lines`, differentiable (include/tdship.h "K7b"): the same launch and the same bits; `features` carries the graph to
+    `agent_xy` and to `agent_sc` = [sin psi, cos psi] of the observing agent -- the lines are constants, even where they require grad --, `index`
+    and `state` never do.  The backward is ONE launch (tds_stop_lines_bwd_f32).  Which line is in a slot and the order of the slots, the
+    `max_distance` cut, `ahead_only`, `min_cos` and `mask` are constants; `time_to_change`, length and width send no gradient anywhere.  An empty
+    slot contributes exactly zero whatever its incoming gradient holds; an agent exactly on a line's centre gets no NaN from `distance`.  No
+    double backward."""
+    return _StopLinesGrad.apply(agent_xy, agent_sc, agent_present, lines, line_sc, mask, state, time_to_change, k, max_distance, ahead_only, min_cos)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # K8 lane observations (csrc/lane_obs.hip; DESIGN.md 5.5i)
 # ---------------------------------------------------------------------------------------------------------------
@@ -980,12 +1024,6 @@ def lane_observations(lane_set, agent_xy, agent_sc, present, k, n_points, spacin
     nat.call('tds_lane_observations_multi', dev, lane_set.handle, scene_map, agent_xy, agent_sc, present, features, points, n_valid, index, B, A, K, P,
              float(spacing), float(max_distance))
     return features, points, n_valid, index
-
-
-def _aligned(t):
-    """t, or a copy of it where its data does not start at a multiple of 16 bytes (a contiguous view at an odd storage offset): the backward kernel
-    reads a slot's incoming gradients as 16-byte loads"""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 class _LaneObservationsGrad(torch.autograd.Function):
@@ -1817,21 +1855,59 @@ def _seed64(seed):
     return int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
-def wrong_way(lane_set, state, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance):
-    """lanelet_orientation_loss (infractions.py:232-304) [* present]: state (B,A,4) -> (B,A) float32.  No gradient, as in the
-    reference (the lane directions come from host floats there)."""
+def wrong_way(lane_set, state, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance, want_dpsi=False):
+    """lanelet_orientation_loss (infractions.py:232-304) [* present]: state (B,A,4) -> (B,A) float32.  No gradient from this call; `wrong_way_grad`
+    is the differentiable form.  (The reference's loss does have one, to psi alone: its position passes through float() and is a constant, and so
+    are the lane directions, which come from host floats, but `agent_state[2]` stays a tensor.)  With `want_dpsi` the same kernel also writes the
+    derivative of the loss to psi (tds_wrong_way_grad_f32) -> (out, dloss_dpsi (B,A) float32); `out` has the same bits either way."""
     state = _c(state.detach())
     if state.dim() != 3 or state.shape[-1] != 4:
         raise RuntimeError(f'wrong_way: state must be (B,A,4), got {tuple(state.shape)}')
     B, A = state.shape[:2]
     out = torch.empty((B, A), dtype=f32, device=state.device)
+    dpsi = torch.empty((B, A), dtype=f32, device=state.device) if want_dpsi else None
     if B * A == 0:
-        return out
+        return (out, dpsi) if want_dpsi else out
     off = None if recenter_offset is None else _c(recenter_offset.detach())
     pres = None if present is None else _u8(present)
+    if want_dpsi:
+        nat.call('tds_wrong_way_grad_f32', state.device, lane_set.handle, _scene_map(lane_set, B, 'wrong_way'), A, state, off, pres, out, dpsi, B * A,
+                 float(direction_angle_threshold), float(lanelet_dist_tolerance))
+        return out, dpsi
     nat.call('tds_wrong_way_f32', state.device, lane_set.handle, _scene_map(lane_set, B, 'wrong_way'), A, state, off, pres, out, B * A,
              float(direction_angle_threshold), float(lanelet_dist_tolerance))
     return out
+
+
+class _WrongWayGrad(torch.autograd.Function):
+    """the wrong-way loss as an autograd node: forward = tds_wrong_way_grad_f32, one launch; backward = g * dloss_dpsi into the psi column, in torch"""
+
+    @staticmethod
+    def forward(ctx, state, lane_set, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance):
+        out, dpsi = wrong_way(lane_set, state, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance, want_dpsi=True)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(dpsi)
+        ctx.state_dtype = state.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        dpsi, = ctx.saved_tensors
+        g_state = torch.zeros(tuple(dpsi.shape) + (4,), dtype=f32, device=dpsi.device)
+        g_state[..., 2] = g * dpsi
+        return (g_state.to(ctx.state_dtype),) + (None,) * 5
+
+
+def wrong_way_grad(lane_set, state, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance):
+    """`wrong_way`, differentiable: the bits of tds_wrong_way_f32, and the result carries the graph to `state[..., 2]` alone --
+    x, y and v get exactly zero, as in the reference, where the position passes through float().  d loss / d psi is -sin(delta) of the lanelet
+    whose loss the minimum keeps (the first in table order of equal ones) where |delta| exceeds the threshold, else 0, and exactly 0 wherever the
+    loss is forced to 0; it comes from the forward's own launch (tds_wrong_way_grad_f32), the backward is a product in torch.  Which lanelet
+    attains the minimum and the threshold test are constants of differentiation.  No double backward."""
+    return _WrongWayGrad.apply(state, lane_set, recenter_offset, present, direction_angle_threshold, lanelet_dist_tolerance)
 
 
 def lanelet_directions(tables, scene_map, points, lanelet_dist_tolerance, max_dirs=16):

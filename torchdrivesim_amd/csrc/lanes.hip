@@ -430,9 +430,10 @@ __device__ float normalize_angle_f32(float a) {
     return r - PI_F;
 }
 
-__global__ __launch_bounds__(256) void wrong_way_kernel(const LaneView *views, const int32_t *scene_map, int64_t agents_per_scene,
+// (four waves per SIMD, stated: the winner's delta is one more value alive across the walk, and without the bound the allocator goes past 128 VGPRs)
+__global__ __launch_bounds__(256, 4) void wrong_way_kernel(const LaneView *views, const int32_t *scene_map, int64_t agents_per_scene,
                                                         const float *xy, const double *xyd, const float *psi,
-                                                        const float *offset, const uint8_t *present, float *out, double *dirs,
+                                                        const float *offset, const uint8_t *present, float *out, float *dpsi, double *dirs,
                                                         double *dists, int32_t *count, uint8_t *status, int max_dirs, int64_t n,
                                                         float tol, float thr) {
     int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / GROUP;
@@ -441,6 +442,7 @@ __global__ __launch_bounds__(256) void wrong_way_kernel(const LaneView *views, c
     int64_t scene = a / agents_per_scene;
     int m = scene_map ? scene_map[scene] : 0;
     float loss = 0.f;
+    float dwin = 0.f;                                // with dpsi: delta of the first lanelet in table order that attains the minimum (strict <)
     int k = 0;
     bool excluded = false, failed = false;
     if (m >= 0) {
@@ -476,6 +478,8 @@ __global__ __launch_bounds__(256) void wrong_way_kernel(const LaneView *views, c
                 float df = (float)dir;
                 float delta = normalize_angle_f32(df - ps);
                 float l = -cosf(delta) * (fabsf(delta) > thr ? 1.f : 0.f);
+                // (`loss` is still the minimum of the lanelets before this one; where that is a NaN -- a NaN psi -- fminf drops it for l, and so does the winner)
+                if (dpsi && (k == 0 || l < loss || loss != loss)) dwin = delta;
                 loss = k == 0 ? l : fminf(loss, l);
                 if (dirs && k < max_dirs && g == 0) dirs[a * max_dirs + k] = dir, dists[a * max_dirs + k] = d;
                 k++;
@@ -483,11 +487,36 @@ __global__ __launch_bounds__(256) void wrong_way_kernel(const LaneView *views, c
         }
     }
     if (g != 0) return;
-    if (excluded || failed) loss = 0.f, k = excluded ? 0 : k;
-    if (present && !present[a]) loss = 0.f;       // `* self.get_present_mask()`, simulator.py:624 (loss is never NaN or infinite)
+    if (excluded || failed) loss = 0.f, dwin = 0.f, k = excluded ? 0 : k;
+    if (present && !present[a]) loss = 0.f, dwin = 0.f;       // `* self.get_present_mask()`, simulator.py:624 (loss is never NaN or infinite)
     if (out) out[a] = loss;
+    // d loss / d psi of the winner (normalize_angle has derivative 1); exactly 0 wherever the loss is forced to 0 or no lanelet was met (dwin = 0)
+    if (dpsi) dpsi[a] = fabsf(dwin) > thr ? -sinf(dwin) : 0.f;
     if (count) count[a] = k;
     if (status) status[a] = (excluded ? 2 : 0) | (failed ? 1 : 0);
+}
+
+}  // namespace
+
+namespace {
+
+// tds_wrong_way_f32 (dpsi null) and tds_wrong_way_grad_f32: the same launch with one more pointer
+int wrong_way_launch(const char *what, const tds_laneset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state,
+                     const float *recenter_offset, const uint8_t *present, float *out, float *dpsi, int64_t n_agents, float direction_angle_threshold,
+                     float lanelet_dist_tolerance, void *stream) {
+    TDS_CHECK_ARG(set && out, "%s: null argument", what);
+    TDS_CHECK_ARG(n_agents >= 0 && agents_per_scene > 0, "%s: bad sizes", what);
+    TDS_CHECK_ARG(lanelet_dist_tolerance >= 0.f && lanelet_dist_tolerance <= set->max_tol,
+                  "%s: lanelet_dist_tolerance %g exceeds the %g the lane tables were built for", what, lanelet_dist_tolerance, set->max_tol);
+    TDS_CHECK_SCENE_MAP(what, set, scene_map);
+    if (n_agents == 0) return TDS_OK;
+    TDS_CHECK_ARG(state, "%s: state is null", what);
+    unsigned blocks = (unsigned)((n_agents * GROUP + 255) / 256);
+    hipLaunchKernelGGL(wrong_way_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, set->d_views, scene_map, agents_per_scene, state,
+                       (const double *)nullptr, state + 2, recenter_offset, present, out, dpsi, (double *)nullptr, (double *)nullptr,
+                       (int32_t *)nullptr, (uint8_t *)nullptr, 0, n_agents, lanelet_dist_tolerance, direction_angle_threshold);
+    TDS_LAUNCH_CHECK("wrong_way_kernel");
+    return TDS_OK;
 }
 
 }  // namespace
@@ -495,20 +524,16 @@ __global__ __launch_bounds__(256) void wrong_way_kernel(const LaneView *views, c
 TDS_EXPORT int tds_wrong_way_f32(const tds_laneset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state,
                                  const float *recenter_offset, const uint8_t *present, float *out, int64_t n_agents,
                                  float direction_angle_threshold, float lanelet_dist_tolerance, void *stream) {
-    TDS_CHECK_ARG(set && out, "tds_wrong_way_f32: null argument");
-    TDS_CHECK_ARG(n_agents >= 0 && agents_per_scene > 0, "tds_wrong_way_f32: bad sizes");
-    TDS_CHECK_ARG(lanelet_dist_tolerance >= 0.f && lanelet_dist_tolerance <= set->max_tol,
-                  "tds_wrong_way_f32: lanelet_dist_tolerance %g exceeds the %g the lane tables were built for", lanelet_dist_tolerance,
-                  set->max_tol);
-    TDS_CHECK_SCENE_MAP("tds_wrong_way_f32", set, scene_map);
-    if (n_agents == 0) return TDS_OK;
-    TDS_CHECK_ARG(state, "tds_wrong_way_f32: state is null");
-    unsigned blocks = (unsigned)((n_agents * GROUP + 255) / 256);
-    hipLaunchKernelGGL(wrong_way_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, set->d_views, scene_map, agents_per_scene, state,
-                       (const double *)nullptr, state + 2, recenter_offset, present, out, (double *)nullptr, (double *)nullptr,
-                       (int32_t *)nullptr, (uint8_t *)nullptr, 0, n_agents, lanelet_dist_tolerance, direction_angle_threshold);
-    TDS_LAUNCH_CHECK("wrong_way_kernel");
-    return TDS_OK;
+    return wrong_way_launch("tds_wrong_way_f32", set, scene_map, agents_per_scene, state, recenter_offset, present, out, nullptr, n_agents,
+                            direction_angle_threshold, lanelet_dist_tolerance, stream);
+}
+
+TDS_EXPORT int tds_wrong_way_grad_f32(const tds_laneset_t *set, const int32_t *scene_map, int64_t agents_per_scene, const float *state,
+                                      const float *recenter_offset, const uint8_t *present, float *out, float *dloss_dpsi, int64_t n_agents,
+                                      float direction_angle_threshold, float lanelet_dist_tolerance, void *stream) {
+    TDS_CHECK_ARG(dloss_dpsi, "tds_wrong_way_grad_f32: null argument");
+    return wrong_way_launch("tds_wrong_way_grad_f32", set, scene_map, agents_per_scene, state, recenter_offset, present, out, dloss_dpsi, n_agents,
+                            direction_angle_threshold, lanelet_dist_tolerance, stream);
 }
 
 TDS_EXPORT int tds_lanelet_directions_f64(const tds_laneset_t *set, const int32_t *scene_map, int64_t points_per_scene, const double *xy,
@@ -525,7 +550,7 @@ TDS_EXPORT int tds_lanelet_directions_f64(const tds_laneset_t *set, const int32_
     unsigned blocks = (unsigned)((n_points * GROUP + 255) / 256);
     hipLaunchKernelGGL(wrong_way_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, set->d_views, scene_map, points_per_scene,
                        (const float *)nullptr, xy, (const float *)nullptr, (const float *)nullptr, (const uint8_t *)nullptr, (float *)nullptr,
-                       dirs, dists, count, status, max_dirs, n_points, lanelet_dist_tolerance, 4.f);
+                       (float *)nullptr, dirs, dists, count, status, max_dirs, n_points, lanelet_dist_tolerance, 4.f);
     TDS_LAUNCH_CHECK("wrong_way_kernel");
     return TDS_OK;
 }

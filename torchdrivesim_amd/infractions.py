@@ -102,7 +102,7 @@ def lane_table_set(lanelet_maps, device, lanelet_dist_tolerance: float = 1.0) ->
 
 def lanelet_orientation_loss(lanelet_maps, agents_state: Tensor, recenter_offset: Optional[Tensor] = None,
                              direction_angle_threshold: float = np.pi / 2, lanelet_dist_tolerance: float = 1.0,
-                             lane_set: Optional[_ops.LaneTableSet] = None) -> Tensor:
+                             lane_set: Optional[_ops.LaneTableSet] = None, differentiable: bool = False) -> Tensor:
     """
     Wrong-way loss (infractions.py:232-304): for every agent the lanelets within `lanelet_dist_tolerance` of its position, the
     local direction of each one's centre line, d = normalize_angle(direction - psi), loss = min over them of
@@ -110,6 +110,11 @@ def lanelet_orientation_loss(lanelet_maps, agents_state: Tensor, recenter_offset
     'parking', and where the reference's `find_direction` raises.  One kernel launch for the batch (csrc/lanes.hip) instead of the
     reference's Python loop over scenes, agents and lanelets.  `lanelet_maps`: a list of B `torchdrivesim_amd.lanelet2.LaneletMap`
     or None; `lane_set`: the prepared tables of these maps (callers that query every step keep it).
+
+    `differentiable=True`, with grad mode on and an `agents_state` that requires grad: the same values, bit for bit, and the result carries the
+    graph to `agents_state[..., 2]` alone, as the reference's does (its position passes through float() and is a constant; psi stays a tensor):
+    d loss / d psi = -sin(d) of the lanelet that attains the minimum where |d| exceeds the threshold, else 0 (`_ops.wrong_way_grad`, DESIGN.md
+    5.5r).  x, y and the speed get exactly zero.  Otherwise nothing is recorded and nothing is saved.
     """
     assert len(lanelet_maps) == agents_state.shape[0]
     if recenter_offset is not None:
@@ -119,4 +124,6 @@ def lanelet_orientation_loss(lanelet_maps, agents_state: Tensor, recenter_offset
         lane_set = lane_table_set(lanelet_maps, agents_state.device, lanelet_dist_tolerance)
     if lane_set is None or agents_state.shape[1] == 0:
         return torch.zeros(agents_state.shape[:2], dtype=torch.float, device=agents_state.device)
+    if differentiable and torch.is_grad_enabled() and agents_state.requires_grad:
+        return _ops.wrong_way_grad(lane_set, agents_state, recenter_offset, None, direction_angle_threshold, lanelet_dist_tolerance)
     return _ops.wrong_way(lane_set, agents_state, recenter_offset, None, direction_angle_threshold, lanelet_dist_tolerance)

@@ -1415,7 +1415,7 @@ class Simulator:
 
     # ------------------------------------------------------------------------------------------------- stop-line observations
     def compute_stop_lines(self, k: int = 4, max_distance: float = 60.0, ahead_only: bool = True, min_cos: Optional[float] = None,
-                           kind: str = 'traffic_light') -> StopLines:
+                           kind: str = 'traffic_light', differentiable: bool = False) -> StopLines:
         """The `k` nearest present stop lines of `traffic_controls[kind]` of every exposed agent within `max_distance` metres between centres
         (+inf: no limit), nearest first, equal distances by the lower index:
 
@@ -1427,8 +1427,17 @@ class Simulator:
 
         `ahead_only` keeps the lines with x >= 0; `min_cos` those whose relative orientation has at least that cosine.  Rows of agents that are not
         present are empty.  1 <= k <= 32, at most 1024 lines per scene.  One HIP kernel in binary32 (csrc/lights.hip; the definition is in
-        include/tdship.h "K7", tests/lights_model.py equals it bit for bit).  No gradient.  Runs on the current stream and allocates its outputs
-        only, so it can be captured into a graph."""
+        include/tdship.h "K7", tests/lights_model.py equals it bit for bit).  Runs on the current stream and allocates its outputs only, so it
+        can be captured into a graph.
+
+        `differentiable=True`, with grad mode on and a state that requires grad: the same launch and the same bits, and `features` carries the
+        graph to x, y and psi (through the shared [sin psi, cos psi] node) of the observing agent -- the stop lines are constants, even where
+        `control.pos` requires grad, so nothing goes to them or to another entity; `index` and `state` never carry a graph.  The backward is one
+        HIP kernel (csrc/stop_lines_bwd.hip; include/tdship.h "K7b", held to the float64 model tests/stop_lines_grad_model.py).  Constants of
+        differentiation: which line is in a slot and the order of the slots, the `max_distance` cut, `ahead_only`, `min_cos` and the control's
+        mask; `time_to_change`, length and width receive gradient from nowhere and send none.  An empty slot contributes exactly zero whatever
+        gradient comes in, NaN and inf included; an agent exactly on a line's centre gets no NaN from `distance`.  Otherwise -- the flag off,
+        under `no_grad`, nothing requiring grad, no agents -- nothing is recorded and nothing is saved."""
         _ops.check_stop_lines_args(k, max_distance, min_cos)
         controls = self.get_traffic_controls()
         if not controls or kind not in controls:
@@ -1446,6 +1455,11 @@ class Simulator:
                 lines = _ops._c(pos.detach()).to(state.device)
                 cached = (key, lines, _ops.heading_sc(lines[..., 4]))
                 control._line_sc_cache = cached
+        if differentiable and A > 0 and torch.is_grad_enabled() and state.requires_grad:
+            return StopLines(*_ops.stop_lines_grad(state[..., :2], self._heading_sc()[:, :A], self.get_present_mask(), cached[1], cached[2], control.mask,
+                                                   control.state, getattr(control, 'time_to_change', None), k, max_distance, ahead_only=ahead_only,
+                                                   min_cos=min_cos))
+        with torch.no_grad():
             agent = state.detach()
             out = _ops.stop_lines(agent[..., :2], self._heading_sc().detach()[:, :A], self.get_present_mask(), cached[1], cached[2], control.mask,
                                   control.state, getattr(control, 'time_to_change', None), k, max_distance, ahead_only=ahead_only, min_cos=min_cos)
@@ -1505,19 +1519,29 @@ class Simulator:
             self._lane_set = (lane_table_set(self.lanelet_map, device, tol), tol)
         return self._lane_set[0]
 
-    def compute_wrong_way(self) -> Tensor:
+    def compute_wrong_way(self, differentiable: bool = False) -> Tensor:
         """Wrong-way metric per agent, -cos of the angle between the agent and the lane it is on where that angle exceeds
         `cfg.wrong_way_angle_threshold` (simulator.py:607-630 -> infractions.lanelet_orientation_loss), times the present mask.
-        Zeros without a lanelet map, as the reference.  `lanelet_map`: a list of B `lanelet2.LaneletMap` or None."""
+        Zeros without a lanelet map, as the reference.  `lanelet_map`: a list of B `lanelet2.LaneletMap` or None.
+
+        `differentiable=True`, with grad mode on and a state that requires grad: the same bits, and the result carries the graph to psi alone,
+        as the reference's loss does (`_ops.wrong_way_grad`): -sin of that angle for the lanelet that attains the minimum
+        where the angle exceeds the threshold, else 0; x and y get exactly zero.  This call is computed in place on the current stream: it is
+        not foreseen beside a render, and a result prepared there is not used.  Otherwise -- the flag off, under `no_grad`, nothing requiring
+        grad, no lanelet map -- the path is the plain one and nothing is recorded."""
+        if differentiable and torch.is_grad_enabled() and self.get_state().requires_grad and \
+                not (self.lanelet_map is None or all(m is None for m in self.lanelet_map)):
+            return self._compute_wrong_way(differentiable=True)
         return self._beside_render(self._compute_wrong_way, ('wrong_way',))
 
-    def _compute_wrong_way(self) -> Tensor:
+    def _compute_wrong_way(self, differentiable: bool = False) -> Tensor:
         state = self.get_state()
         if self.lanelet_map is None or all(m is None for m in self.lanelet_map):
             return torch.zeros(state.shape[0], state.shape[1], device=state.device)
         tol = self.cfg.lanelet_inclusion_tolerance
         assert self.cfg.wrong_way_angle_threshold >= np.pi / 2, 'direction_angle_threshold smaller than pi / 2 will produce false positives'
-        return _ops.wrong_way(self._lane_tables(state.device), state, self.recenter_offset, self.get_present_mask(), self.cfg.wrong_way_angle_threshold, tol)
+        fn = _ops.wrong_way_grad if differentiable else _ops.wrong_way
+        return fn(self._lane_tables(state.device), state, self.recenter_offset, self.get_present_mask(), self.cfg.wrong_way_angle_threshold, tol)
 
     def compute_traffic_lights_violations(self) -> Tensor:
         """BxA: the agent is (mostly) past the stop line of a red light (simulator.py:1046-1062)."""
