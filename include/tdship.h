@@ -1178,6 +1178,10 @@ int tds_time_to_collision_bwd_f32(const float *boxes, const float *sc, const flo
                                                   pixels -- the difference is what that row's own expressions cost */
 #define TDS_RASTER_DBG_HELPER 67108864         /* never set by a caller: the testing build sets it in the arguments of the helper enqueue (tds_raster_aux_helper_t::
                                                   helper_stream), so that the work counters can tell its items (tds_raster_get_helper_stats) */
+#define TDS_RASTER_DBG_NO_ACTOR_WAVE 134217728 /* the persistent 4-wave bit-plane kernel leaves a work item's agents, and the masked agents' dot, to ONE wave
+                                                  of the workgroup (chosen by the item number: one lane per agent for the distance cull, faces for the
+                                                  visible agents only) while the others start on the map at once; with this flag every wave culls and
+                                                  projects its share of the agents, as the other launches do.  Same pixels. */
 #ifndef TDS_RASTER_SMALL_ROWS
 #define TDS_RASTER_SMALL_ROWS 7                /* rows (yb - yt + 1) of the largest face that is small: the persistent bit-plane kernel paints such faces
                                                   on the lane that scanned them; the flag above and the counters below go by the same test */
@@ -1199,6 +1203,9 @@ int tds_raster_set_helper_min_items(int items_per_workgroup);
 /* read and reset the counter of work items that workgroups of the helper enqueue rendered (TDS_RASTER_DBG_STATS); the two counters of
  * tds_raster_get_prep_stats count every item, whichever enqueue took it */
 int tds_raster_get_helper_stats(unsigned long long *out1);
+/* read and reset the counter of work items of the persistent 4-wave bit-plane launches whose agents were served by one wave of the workgroup
+ * (TDS_RASTER_DBG_STATS): every item of a launch with agents, 0 with TDS_RASTER_DBG_NO_ACTOR_WAVE */
+int tds_raster_get_actor_wave_stats(unsigned long long *out1);
 /* read and reset the 16 work counters of the bit-plane kernel */
 int tds_raster_get_stats(unsigned long long *out16);
 /* read and reset the two counters of the prepared scan set-ups (TDS_RASTER_DBG_STATS): work items of the persistent bit-plane launches that used

@@ -59,6 +59,7 @@ class RasterDebug(enum.IntFlag):
     SMALL_FREE_SLOPES = 16777216
     SMALL_NO_MIDDLE_ROW = 33554432
     HELPER = 67108864
+    NO_ACTOR_WAVE = 134217728
 
 _lib = None
 
@@ -232,6 +233,7 @@ tds_raster_set_list_waves(int waves)
 tds_raster_set_debug(int flags)
 tds_raster_set_helper_min_items(int items_per_workgroup)
 tds_raster_get_helper_stats(host* out1)
+tds_raster_get_actor_wave_stats(host* out1)
 tds_raster_get_stats(host* out16)
 tds_raster_get_prep_stats(host* out2)
 tds_raster_get_small_stats(host* out16)

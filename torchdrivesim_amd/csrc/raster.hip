@@ -17,6 +17,7 @@
 //     (every strip scans the grid) or binned (K3a bins faces per strip, K3b rasterises the lists) -- and the generic kernel for an
 //     explicit per-camera RGB mesh.
 // Roofline: HBM write, 3*H*W*4 B per camera (fp32) -- DESIGN.md.
+#include "tds_actor_lanes.h"
 #include "tds_common.h"
 #include "tds_face_rows.h"
 #include "tds_raster_plan.h"
@@ -840,13 +841,14 @@ __device__ __forceinline__ PrepWords *prep_words(const void *tab, int item) {
 // POLY: the walk is over the rendering grid with paired faces (MapView::qentries / qcell_start: the bit-plane kernels); the cells are the same
 template <typename SA, bool POLY = false>
 __device__ __forceinline__ void scan_init(ScanState &st, const SA &a, const CommonArgs &c, const Camera &cam, int64_t img, int lane, int wave, int X0,
-                                          int TWw, const PrepRecord *rec = nullptr) {   // wave = index among the cooperating waves; rec: the item's
-                                                                                        // prepared record (wave-uniform), nullptr: compute
+                                          int TWw, const PrepRecord *rec = nullptr, bool actors = true) {
+    // wave = index among the cooperating waves; rec: the item's prepared record (wave-uniform), nullptr: compute; actors (wave-uniform): this wave
+    // takes part in the actor phases (the persistent bit-plane kernel leaves them to one wave of the workgroup: scan_step, ACTW)
     st.map = a.map;
     if (a.views != nullptr) st.map = a.views[a.scene_map[img / a.Nc]];
     if constexpr (POLY) st.map.cell_start = st.map.qcell_start;
     const MapView &m = st.map;
-    st.phase = (a.N > 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_ACTORS)) ? 0 : 2;      // 0 actors, 1 masked-agent dot, 3 per-camera triangles, 2 static map
+    st.phase = (a.N > 0 && actors && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_ACTORS)) ? 0 : 2;      // 0 actors, 1 masked-agent dot, 3 per-camera triangles, 2 static map
     if constexpr (POLY) {
         // The scan kernel of the split form reads the first phase through the launch's (always zero, in the product) debug word: a phase the
         // compiler knows at compile time makes it restructure the phases so that scan_faces_kernel needs 368 instead of 112 bytes of scratch per
@@ -976,9 +978,15 @@ __device__ __forceinline__ void scan_candidate(const ScanState &st, const Common
 }
 
 // one producer step: at most one candidate face per lane; returns false when the producer is exhausted
-template <int NW = RWAVES, typename SA = SceneArgsEx>      // SceneArgsEx: the per-camera triangle phase is compiled in
+// ACTW (the persistent 4-wave bit-plane kernel; the testing build's TDS_RASTER_DBG_NO_ACTOR_WAVE gives the per-wave form back): the item's actors are ONE wave's -- the other waves of the workgroup
+// were started behind the actor phases (raster_scene_bits_kernel).  In rounds of 64 agents the wave culls one lane per agent -- mask byte,
+// state and first template vertex loaded once, the distance test of the per-wave form -- and gives the visible agents three lanes each, 21 per
+// step (tds_actor_lanes.h), for the loads and the arithmetic both forms share.  A 35 m view of 64 agents holds a handful: one step, and the
+// masked agents' dot once per item instead of once per wave that saw a masked agent.  `slots`: 64 words of LDS of the wave's own.
+template <int NW = RWAVES, typename SA = SceneArgsEx, bool ACTW = false>      // SceneArgsEx: the per-camera triangle phase is compiled in
 __device__ __forceinline__ bool scan_step(ScanState &st, const SA &a, const CommonArgs &c, const Camera &cam, int64_t img, int lane,
-                                          int wave, int X0, int TWw, bool &acc, uint32_t &key, int (&px)[3], int (&py)[3], unsigned &edges) {
+                                          int wave, int X0, int TWw, bool &acc, uint32_t &key, int (&px)[3], int (&py)[3], unsigned &edges,
+                                          uint32_t *slots = nullptr) {
     const MapView &m = st.map;
     unsigned ins = 0;
     edges = 7u;
@@ -986,6 +994,55 @@ __device__ __forceinline__ bool scan_step(ScanState &st, const SA &a, const Comm
     const int64_t b = img / a.Nc;
     acc = false;
     key = 0;
+    if constexpr (ACTW) if (st.phase == 0 && !(TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_ACTOR_WAVE)) {
+        // a0 = first agent of the round (a multiple of 64) + the step within it: lane j culls agent 64 r + j -- every step of the round anew,
+        // it is one load per lane and a view with more than 21 visible agents is rare --, a ballot gives the visible ones, and this step's 21
+        // of them get three lanes each through the wave's slots (tds_actor_lanes.h).  The lane numbers stay in the slots: they are below every
+        // marker of wave_owner, whose tags start at 64, and lose like stale markers.
+        const int step = st.a0 & (TDS_ACTOR_ROUND - 1), cand = st.a0 - step + lane;
+        bool off = false, seen = false;
+        if (cand < a.N) {
+            const int64_t ia = b * a.N + cand;
+            off = a.mask[img * a.N + cand] == 0;
+            if (!off) {
+                const float view_r = 1.05f * 1.41421356f / c.scale;
+                const float4 s = a.state[ia];
+                const float2 t0 = a.tmpl[ia * 7];
+                float reach = view_r + sqrtf(t0.x * t0.x + t0.y * t0.y);
+                reach = reach * 1.01f + 0.01f;
+                const float ddx = s.x - cam.cx, ddy = s.y - cam.cy;
+                seen = !(ddx * ddx + ddy * ddy > reach * reach);               // NaNs are kept
+            }
+        }
+        st.masked_seen = st.masked_seen || __ballot(off) != 0;
+        const uint64_t vis = __ballot(seen);
+        const int drop = actor_drop_position(vis, lane, step);
+        if (drop >= 0) slots[drop] = (uint32_t)lane;
+        wave_sync();
+        const int pos = actor_lane_position(vis, lane, step), f = actor_lane_face(lane);
+        if (pos >= 0) {
+            const int ag = st.a0 - step + (int)slots[pos];
+            const int64_t ia = b * a.N + ag;
+            const int64_t ik = a.key_per_cam ? img * a.N + ag : ia;
+            key = a.actor_key[2 * ik + (f == 2 ? 1 : 0)];
+            if (key != 0u) {                                                   // key 0: the part does not exist
+                const float4 s = a.state[ia];
+                const float2 sc = a.agent_sc[ia];
+                // (the transform of the per-wave form below, operation by operation)
+                const int v0 = f == 0 ? 0 : (f == 1 ? 1 : 4), v1 = f == 0 ? 1 : (f == 1 ? 3 : 5), v2 = f == 0 ? 3 : (f == 1 ? 2 : 6);
+                const float2 ta = a.tmpl[ia * 7 + v0], tb = a.tmpl[ia * 7 + v1], tc = a.tmpl[ia * 7 + v2];
+                const float fx[3] = {((sc.y * ta.x + (-sc.x) * ta.y) + s.x) + (-cam.cx), ((sc.y * tb.x + (-sc.x) * tb.y) + s.x) + (-cam.cx),
+                                     ((sc.y * tc.x + (-sc.x) * tc.y) + s.x) + (-cam.cx)};
+                const float fy[3] = {((sc.x * ta.x + sc.y * ta.y) + s.y) + (-cam.cy), ((sc.x * tb.x + sc.y * tb.y) + s.y) + (-cam.cy),
+                                     ((sc.x * tc.x + sc.y * tc.y) + s.y) + (-cam.cy)};
+                acc = trim_project(cam, c.scale, res, X0, TWw, fx, fy, px, py, ins, c.no_trim);
+                edges = edge_mask(f == 1 ? 2u : 0u, ins);
+            }
+        }
+        st.a0 = actor_more_steps(vis, step) ? st.a0 + 1 : st.a0 - step + TDS_ACTOR_ROUND;
+        if (st.a0 >= a.N) st.phase = 1;
+        return true;
+    }
     if (st.phase == 0) {
         // actors (mesh.py:1071-1103): 7 template vertices per agent, faces [0,1,3],[1,3,2] (body), [4,5,6] (direction).
         // One lane per (agent, face): 21 agents per wave and step (lane 63 idles), dealt round-robin to the cooperating waves;
@@ -1604,8 +1661,9 @@ __device__ inline bool clip_line_small(int W, int H, int &x1, int &y1, int &x2, 
 // (checked exhaustively against the iterative walk in tests/test_oracle_fill.py::test_line_rows_closed_form)
 // optional work counters (profiling hook tds_raster_get_stats of the testing build; active with debug flag TDS_RASTER_DBG_STATS)
 #ifdef TDS_TESTING
-__device__ unsigned long long g_stats[19];       // [16], [17]: work items that used their prepared record / computed their scan set-up (tds_raster_get_prep_stats)
+__device__ unsigned long long g_stats[20];       // [16], [17]: work items that used their prepared record / computed their scan set-up (tds_raster_get_prep_stats)
                                                  // [18]: work items taken by workgroups of the helper enqueue (tds_raster_get_helper_stats)
+                                                 // [19]: work items whose actors were served by the actor wave (tds_raster_get_actor_wave_stats)
 __device__ unsigned long long g_small_stats[16]; // small faces among the accepted ones (tds_raster_get_small_stats)
 #define TDS_STAT_LANES(W, I, V) do { if ((W).debug & TDS_RASTER_DBG_STATS) { const unsigned long long v_ = (unsigned long long)(V); if (v_) atomicAdd(&g_stats[I], v_); } } while (0)
 #define TDS_STAT(W, I, V) do { if (((W).debug & TDS_RASTER_DBG_STATS) && (W).lane == 0) atomicAdd(&g_stats[I], (unsigned long long)(V)); } while (0)
@@ -2583,6 +2641,7 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
     constexpr int BBLOCK = BWAVES * 64, P = 1 << (2 * NB);
     constexpr bool PERSIST = BWAVES == 4 && MINWG == 3;              // (the 8-wave instantiation as a persistent launch: 224 instead of 160 B of scratch, 6 % slower)
     constexpr int SROWS = PERSIST && !is_mask<OutT>::value ? SMALL_ROWS : 0;       // small faces painted on the scan lane (drain_bits)
+    constexpr bool ACTW = PERSIST;                                   // one wave serves an item's actors (scan_step)
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int res = c.res, H = res, W = res, wpr = TWp >> 5, K = kt.n;
@@ -2627,10 +2686,12 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         int64_t img;
         int X0;
         const PrepRecord *rec = nullptr;                                     // the item's prepared scan set-up, where the launch has a table
+        int item_no = 0;
         if constexpr (PERSIST) {
             __syncthreads();                                                 // the next item is known; every wave has left the planes of the previous one
             const int item = __builtin_amdgcn_readfirstlane((int)lkeys[16]);
             if (item < 0) break;
+            item_no = item;
             img = item / c.strips;
             X0 = (item - (int)img * c.strips) * TWp;
             if (c.prep != nullptr) {
@@ -2680,9 +2741,19 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
         __syncthreads();
         // (the fused kernel walks the grid of single triangles: the 48-byte entries of the grid with paired faces cost it four more registers for
         // the chunk in flight, which it does not have -- DESIGN_HISTORY.md, appendix R3; the split form's scan kernel takes the pairs)
+        // The item's actor wave is chosen by the item number, so that no SIMD carries the actors of every item (three workgroups share a CU and a wave
+        // stays on its SIMD); the other waves start on the map -- or the per-camera triangles, which stay on all waves -- and request their first
+        // chunk at once.  The chunk counter deals the actor wave fewer chunks.
+        bool actors = true;
+        if constexpr (ACTW) actors = (TDS_DBG(c.debug) & TDS_RASTER_DBG_NO_ACTOR_WAVE) != 0 || __builtin_amdgcn_readfirstlane(wave) == (item_no & 3);
         ScanState st;
-        scan_init(st, a, ci, cam, img, lane, wave, X0, TWp, rec);
+        scan_init(st, a, ci, cam, img, lane, wave, X0, TWp, rec, actors);
         st.dyn = lkeys + 15;
+#ifdef TDS_TESTING
+        if constexpr (ACTW) {
+            if ((c.debug & TDS_RASTER_DBG_STATS) && !(c.debug & TDS_RASTER_DBG_NO_ACTOR_WAVE) && st.phase == 0 && lane == 0) atomicAdd(&g_stats[19], 1ull);
+        }
+#endif
 #ifdef TDS_TESTING
         if (c.debug & TDS_RASTER_DBG_PROLOGUE_TWICE) {
             // the ablation that prices the prologue: the same computation once more on inputs the compiler cannot tell from new ones,
@@ -2712,7 +2783,7 @@ __global__ void __launch_bounds__(BWAVES * 64, BWAVES == 4 ? MINWG : 4) raster_s
             // (read by the testing build's counters only; sampled before the step, so the step that ends a phase -- the masked agents' dot, one
             // lane at the most -- is booked under the phase it belongs to)
             const bool map_phase = st.phase == 2;
-            const bool more = scan_step<BWAVES, SA>(st, a, ci, cam, img, lane, wave, X0, TWp, acc, key, px, py, edges);
+            const bool more = scan_step<BWAVES, SA, ACTW>(st, a, ci, cam, img, lane, wave, X0, TWp, acc, key, px, py, edges, w.slots);
             drain_bits<true, SROWS>(w, key_plane(lkeys, K, key), acc, edges, px, py, more, map_phase, c.small_lane != 0);
             if (!more) break;
         }
@@ -3467,6 +3538,15 @@ TDS_EXPORT int tds_raster_get_helper_stats(unsigned long long *out1) {
     unsigned long long zero[1] = {0};
     if (hipMemcpyFromSymbol(out1, HIP_SYMBOL(g_stats), sizeof(zero), 18 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_helper_stats: copy failed"); return TDS_EHIP; }
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 18 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_helper_stats: reset failed"); return TDS_EHIP; }
+    return TDS_OK;
+}
+
+// read and reset the counter of work items whose actors one wave of the workgroup served (debug flag TDS_RASTER_DBG_STATS; scan_step, ACTW)
+TDS_EXPORT int tds_raster_get_actor_wave_stats(unsigned long long *out1) {
+    TDS_CHECK_ARG(out1, "tds_raster_get_actor_wave_stats: null output");
+    unsigned long long zero[1] = {0};
+    if (hipMemcpyFromSymbol(out1, HIP_SYMBOL(g_stats), sizeof(zero), 19 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_actor_wave_stats: copy failed"); return TDS_EHIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), zero, sizeof(zero), 19 * sizeof(unsigned long long)) != hipSuccess) { tds::set_error("tds_raster_get_actor_wave_stats: reset failed"); return TDS_EHIP; }
     return TDS_OK;
 }
 
